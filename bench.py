@@ -22,6 +22,11 @@ What the line carries besides the contract's fields:
   cpu_baseline   the CPU oracle (a port: the reference has no CPU path) on this host, bounded samples
   bf16           (fp32 runs only) BASELINE configs[4] in the SAME record: K timed steps of a second trainer with bf16 activations
                  after the fp32 one is gone -- its own value / ms_per_step / roofline; `value`, `dtype`, `config` stay the fp32 line's
+
+--dump-outputs DIR writes what the last timed step handed its caller, per leg, as DIR/<dtype>_<name>.npy (f32_*, bf16_*), float32
+or float64, before any further step runs: loss, n_wrong, predictions (the host soft-max), and of the updated parameters and the
+Adam moments m (which carries the step's gradient: Adam clears the gradients) and v, every location's L2 norm plus a fixed seeded
+sample of DUMP_SAMPLE elements (positions in sample_index).  Inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import ctypes as C
@@ -47,6 +52,8 @@ FAMILIES_BF16 = {0: "7x7 stem fwd (st_pad + st_fwd_kernel, bf16 MFMA, bf16 outpu
                  5: "3x3 conv fwd+dgrad+wgrad incl. the 3x3-s2 projections (bgemm_kernel<*,3,*,*> on NCHW; the stride-2 layers on channel-last operands: cl_conv / cl_dgrad2 / cl_wgrad_kernel; implicit GEMM on bf16 MFMA)"}
 PMC_KEY = {0: "dconv", 1: "wgradC", 2: "gemm", 3: "bn", 5: "igemm3x3"}
 PMC_FILE_F32, PMC_FILE_BF16 = "r3_pmc_traffic.json", "r3_bf16_pmc_traffic.json"
+# --dump-outputs: at most 2 legs x (3 x 4 MB samples + 8 MB positions + predictions capped at 2 MB) = 44 MB, within 64 MB
+DUMP_SAMPLE, DUMP_PRED_CAP, DUMP_SEED = 1 << 20, 1 << 19, 20241015
 
 
 def _time_oracle(o, dims, batch, threads):
@@ -110,6 +117,41 @@ def source_sha16():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(tr, out_dir, bf16):
+    """--dump-outputs: what the last step handed its caller, as out_dir/<dtype>_<name>.npy (see the module docstring)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, ("bf16_" if bf16 else "f32_") + name + ".npy"), a)
+
+    def positions(n, k):  # a fixed seeded choice of about k of n flat positions, ascending
+        return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=k)) if n > k else np.arange(n)
+
+    loss, n_wrong = tr.loss()  # the host loss of the last step again: same predictions, same labels
+    save("loss", np.array([loss], np.float64))
+    save("n_wrong", np.array([n_wrong], np.float64))
+    pred = tr.pred()
+    if pred.size <= DUMP_PRED_CAP:
+        save("predictions", pred)
+    else:
+        rows = positions(pred.shape[0], DUMP_PRED_CAP // pred.shape[1])
+        save("predictions", pred[rows])
+        save("predictions_rows", rows.astype(np.float64))
+    offs = np.concatenate([[0], np.cumsum(tr.sizes)])
+    pos = positions(int(offs[-1]), DUMP_SAMPLE)
+    save("sample_index", pos.astype(np.float64))
+    for which, name in (("params", "params"), ("means", "adam_m"), ("vars", "adam_v")):
+        l2, sample = [], []
+        for i in range(tr.n_locations):
+            a = tr.get(which, i)
+            l2.append(np.linalg.norm(a.astype(np.float64)))
+            sel = pos[np.searchsorted(pos, offs[i]):np.searchsorted(pos, offs[i + 1])]
+            sample.append(a[sel - offs[i]])
+        save(name + "_l2", np.array(l2, np.float64))
+        save(name + "_sample", np.concatenate(sample))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -125,7 +167,11 @@ def parse_args(argv=None):
     ap.add_argument("--policy", choices=["fast", "recompute_bn"], default="fast", help="what backward keeps from forward (mi_trainer_set_store_policy)")
     ap.add_argument("--force-dist", action="store_true", help="run the torch.distributed + RCCL path even with one rank (self-test)")
     ap.add_argument("--launch-dry-run", action="store_true", help="with --gpus N and no WORLD_SIZE: print the N worker commands and environments, start nothing")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<dtype>_<name>.npy (rank 0)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -256,6 +302,8 @@ def run_leg(args, lib, dist, rank, local_rank, world, bf16, extras):
     losses += ls
     dom_stats = read_prof()[dom] if prof else None
     timings = tr.timings()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs, bf16)
 
     fam_stats, dt_fam, dt_h2d = {}, None, None
     fam_serial, dt_serial = {}, None
@@ -406,6 +454,7 @@ def main():
                    "--batch", str(args.batch), "--policy", args.policy, "--no-cpu-baseline", "--gpus", "1"]
             cmd += ["--no-prof"] if args.no_prof else []
             cmd += ["--no-extra"] if args.no_extra else []
+            cmd += ["--dump-outputs", args.dump_outputs] if args.dump_outputs else []
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
             try:
                 r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)

@@ -303,3 +303,25 @@ def test_bench_stdout_is_one_json_line_on_the_distributed_path():
     assert len(lines) == 1, r.stdout[:2000]
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 1 and rec["dtype"] == "bf16" and rec["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs: the fp32 line and its bf16 child leg both write their last timed step -- the fp32 loss is the record's final
+    loss, the predictions are the soft-max rows of the batch, parameters and Adam moments come back finite and non-zero"""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--no-extra", "--no-prof", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads(r.stdout.splitlines()[-1])
+    assert rec["steps"] == 2 and "error" not in rec["bf16"], rec.get("bf16")
+    assert abs(float(np.load(tmp_path / "f32_loss.npy")[0]) / 32 - rec["config"]["final_loss_per_image"]) <= 1e-4
+    for dt in ("f32", "bf16"):
+        pred = np.load(tmp_path / ("%s_predictions.npy" % dt))
+        assert pred.shape == (32, 1000) and np.allclose(pred.sum(axis=1), 1.0, atol=1e-3)
+        for name in ("params", "adam_m", "adam_v"):
+            l2 = np.load(tmp_path / ("%s_%s_l2.npy" % (dt, name)))
+            sample = np.load(tmp_path / ("%s_%s_sample.npy" % (dt, name)))
+            assert l2.shape == (160,) and np.all(np.isfinite(l2)) and l2.sum() > 0, (dt, name)
+            assert np.all(np.isfinite(sample)) and sample.shape == np.load(tmp_path / ("%s_sample_index.npy" % dt)).shape

@@ -221,6 +221,56 @@ def test_bench_traffic_is_stamped_with_the_sources_it_was_measured_on(tmp_path, 
     assert roof["traffic"] is None and "not present" in roof["traffic_note"]
 
 
+def test_bench_dump_outputs_is_seeded_sampled_and_bounded(tmp_path):
+    """--dump-outputs on a stand-in trainer with the benchmark network's 160 tensors: float32 / float64 files only, the same positions
+    every time, each sampled value from its place in the flat parameter order, and both legs together within 64 MB even when the
+    predictions have to be sampled too"""
+    import synth
+    sys.path.insert(0, ROOT)
+    import bench
+    sizes = [size for size, _, _ in synth.location_table(synth.R50_DIMS)]
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+
+    class Stand:  # every value is a function of its flat position in the parameter order
+        n_locations = len(sizes)
+
+        def __init__(self, batch):
+            self.batch, self.sizes = batch, sizes
+
+        def loss(self):
+            return 1234.5, 7
+
+        def pred(self):
+            return np.arange(self.batch * 1000, dtype=np.float32).reshape(self.batch, 1000)
+
+        def get(self, which, i):
+            return (np.arange(offs[i], offs[i + 1]) / 4 + {"params": 0, "means": 1, "vars": 2}[which]).astype(np.float32)
+
+    for batch in (256, 4096):
+        d1, d2 = tmp_path / ("a%d" % batch), tmp_path / ("b%d" % batch)
+        for d in (d1, d2):
+            bench.dump_outputs(Stand(batch), str(d), False)
+            bench.dump_outputs(Stand(batch), str(d), True)
+        names = sorted(os.listdir(d1))
+        assert names == sorted(os.listdir(d2)) and len(names) == 2 * (11 if batch > 524 else 10)
+        assert sum(os.path.getsize(d1 / n) for n in names) <= 64 << 20
+        for n in names:
+            a = np.load(d1 / n)
+            assert a.dtype in (np.float32, np.float64), n
+            assert np.array_equal(a, np.load(d2 / n)), n
+        pos = np.load(d1 / "f32_sample_index.npy")
+        assert len(pos) > bench.DUMP_SAMPLE * 0.98 and np.all(np.diff(pos) > 0) and pos[-1] < offs[-1]
+        for name, k in (("params", 0), ("adam_m", 1), ("adam_v", 2)):
+            assert np.array_equal(np.load(d1 / ("bf16_%s_sample.npy" % name)), (pos / 4 + k).astype(np.float32))
+        assert float(np.load(d1 / "f32_loss.npy")[0]) == 1234.5 and float(np.load(d1 / "f32_n_wrong.npy")[0]) == 7
+        pred = np.load(d1 / "f32_predictions.npy")
+        if batch > 524:
+            rows = np.load(d1 / "f32_predictions_rows.npy").astype(np.int64)
+            assert pred.size <= bench.DUMP_PRED_CAP and np.array_equal(pred, Stand(batch).pred()[rows])
+        else:
+            assert np.array_equal(pred, Stand(batch).pred())
+
+
 def test_bench_self_launch_dry_run():
     """`python bench.py --gpus N` with no launcher around it starts N fresh rank processes itself BEFORE anything touches a GPU
     (the library is not even loaded in the parent).  --launch-dry-run prints what it would start: N workers running this script

@@ -112,7 +112,7 @@ def test_shard_builder_matches_the_reference_binary(tmp_path):
 def test_error_paths(tmp_path):
     from resnet_amd import binding as B
     lib = B.load()
-    assert lib.mi_build_shard(b"/nonexistent.csv", b"/tmp", str(tmp_path).encode(), 0, 256, 224, 1) == -1
+    assert lib.mi_build_shard(str(tmp_path / "missing.csv").encode(), str(tmp_path).encode(), str(tmp_path).encode(), 0, 256, 224, 1) == -1
     csv = tmp_path / "000_images.csv"
     csv.write_text("005,0000,00,00\n")
     assert lib.mi_build_shard(str(csv).encode(), str(tmp_path).encode(), str(tmp_path).encode(), 0, 256, 224, 1) == -2  # no class file
