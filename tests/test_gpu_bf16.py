@@ -733,16 +733,18 @@ def test_bn_relu_written_twice_nchw_and_channel_last(ops, C, H, N, form):
 @pytest.mark.parametrize("switch", ["RESNET_MI_BF16_CL_S2=0", "RESNET_MI_BF16_CL_S1=0", "RESNET_MI_BF16_CL_DGRAD2=0", "RESNET_MI_BF16_STEM_TENSORS=f32"])
 def test_training_step_bf16_on_the_other_kernel_routes(switch):
     """every bf16 route switch (README) must leave a trainer that still passes the whole-step checks: the switches are read once per
-    process, so the 4-block / identity-block configuration and the two store policies are re-run in a child process per switch (the
-    NCHW kernels for the stride-2 / stride-1 3x3 layers, the NCHW stride-2 dgrad, fp32 stem tensors)"""
+    process, so the 4-block / identity-block configuration (one step pair, and 25 teacher-forced steps: test_gpu_trajectory.py) and
+    the two store policies are re-run in a child process per switch (the NCHW kernels for the stride-2 / stride-1 3x3 layers, the
+    NCHW stride-2 dgrad, fp32 stem tensors)"""
     import os
     import subprocess
     import sys
     k, v = switch.split("=")
     env = dict(os.environ, **{k: v})
     here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_bf16.py"), "-x", "-q", "-m", "gpu",
-                        "-k", "(test_training_step_bf16_vs_fp32_oracle and C4I) or test_recompute_policy", "-p", "no:cacheprovider"],
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_bf16.py"), os.path.join(here, "test_gpu_trajectory.py"),
+                        "-x", "-q", "-m", "gpu", "-k", "(test_training_step_bf16_vs_fp32_oracle and C4I) or test_recompute_policy"
+                        " or (test_bf16_teacher_forced and C4I)", "-p", "no:cacheprovider"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=os.path.dirname(here))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout

@@ -128,16 +128,38 @@ class _RoundBF16(torch.autograd.Function):
         return _rb(g)
 
 
+class _BNStoredStats(torch.autograd.Function):
+    """batch norm as the bf16 kernels do it: the statistics are taken from the fp32 convolution output BEFORE it is rounded (the
+    convolution's epilogue, kernels_igemm_bf16.hip), the normalisation is applied to the stored, rounded tensor, and the backward is
+    the textbook formula with x-hat of the stored tensor: dY = gamma / sigma (dZ - mean(dZ) - x-hat mean(dZ x-hat))"""
+
+    @staticmethod
+    def forward(ctx, y_stored, y_exact, g, b, eps):
+        m = y_exact.mean(dim=(0, 2, 3), keepdim=True)
+        inv = 1.0 / torch.sqrt(((y_exact - m) ** 2).mean(dim=(0, 2, 3), keepdim=True) + eps)
+        xh = (y_stored - m) * inv
+        ctx.save_for_backward(xh, inv, g)
+        return xh * g.view(1, -1, 1, 1) + b.view(1, -1, 1, 1)
+
+    @staticmethod
+    def backward(ctx, dz):
+        xh, inv, g = ctx.saved_tensors
+        dy = g.view(1, -1, 1, 1) * inv * (dz - dz.mean(dim=(0, 2, 3), keepdim=True) - xh * (dz * xh).mean(dim=(0, 2, 3), keepdim=True))
+        return dy, None, (dz * xh).sum(dim=(0, 2, 3)), dz.sum(dim=(0, 2, 3)), None
+
+
 class TorchNetBF16(TorchNet):
     """gates (optional): the DISCRETE decisions of another execution of the same step -- {name: bool NCHW array} for every ReLU
     ("stem", "b%d_red", "b%d_spa", "b%d_out": that execution's stored activation > 0) and "max_inds" (its per-plane arg-max
     positions).  With them the model takes those decisions instead of its own, so the two executions' gradients differ by
     rounding alone: a pre-activation within bf16 rounding of 0 no longer shows up as an O(1) difference of that element."""
 
-    def __init__(self, dims, params, eps=1e-7, dtype=torch.float64, gates=None, stem_bf16=False):
+    def __init__(self, dims, params, eps=1e-7, dtype=torch.float64, gates=None, stem_bf16=False, stats_before_rounding=False):
         super().__init__(dims, params, eps, dtype)
         self.gates = gates
         self.stem_bf16 = stem_bf16
+        # the product's rule: batch norm as _BNStoredStats instead of bn_train of the stored tensor
+        self.stats_before_rounding = stats_before_rounding
 
     def _relu(self, z, key):
         if self.gates is None:
@@ -150,15 +172,21 @@ class TorchNetBF16(TorchNet):
         w = w + (_rb(w.detach()) - w.detach())  # rounded value, gradient to the fp32 master copy
         if stem:  # the stem multiplies the bf16-rounded image (kernels_stem_bf16.hip).  (Its weight gradient rounds dY on the way in when
             x = _rb(x)  # that tensor is fp32: 2^-9 relative noise per element, averaged over 10^5..10^6 terms)
-        y = F.conv2d(x, w, stride=stride, padding=k // 2)
+        y = y_exact = F.conv2d(x, w, stride=stride, padding=k // 2)
         if not stem or self.stem_bf16:
             y = _RoundBF16.apply(y)
-        z = bn_train(y, self.p[i + 1], self.p[i + 2], self.eps)
+        if self.stats_before_rounding:
+            z = _BNStoredStats.apply(y, y_exact.detach(), self.p[i + 1], self.p[i + 2], self.eps)
+        else:
+            z = bn_train(y, self.p[i + 1], self.p[i + 2], self.eps)
         if residual is not None:
             z = self._relu(z + residual, key)  # BN + addVec + doActivation are one kernel: one rounding
         elif relu:
             z = self._relu(z, key)
-        return _RoundBF16.apply(z)
+        z = _RoundBF16.apply(z)
+        if key is not None:  # the stored tensors, under the keys of gates_of: "<key>_conv" the convolution output, "<key>" the unit's output
+            self.acts[key + "_conv"], self.acts[key] = y, z
+        return z
 
     def forward(self, images_nchw, labels):
         d = self.dims
@@ -169,6 +197,7 @@ class TorchNetBF16(TorchNet):
         li += 3
         given = None if self.gates is None else torch.tensor(np.asarray(self.gates["max_inds"]), dtype=torch.long)
         x = MaxPoolOverwrite.apply(x, d["init_maxpool_dim"], d["init_maxpool_stride"], given)
+        self.acts["pool"] = x
         inc, red, ex = f, f, 4 * f
         for b in range(d["n_conv_blocks"]):
             stride = 1
@@ -181,7 +210,6 @@ class TorchNetBF16(TorchNet):
             if inc != ex:
                 res = self._unit(x, li, ex, inc, 3 if stride == 2 else 1, stride, False, "proj"); li += 3
             x = self._unit(s, le, ex, red, 1, 1, False, "exp", residual=res, key="b%d_out" % b)
-            self.acts["b%d_out" % b] = x
             inc = ex
         pooled = x.mean(dim=(2, 3))
         logits = pooled @ self.p[li].view(inc, d["output"])
@@ -189,6 +217,19 @@ class TorchNetBF16(TorchNet):
         lab = torch.tensor(np.asarray(labels), dtype=torch.long)
         self.loss = -torch.log(self.pred[torch.arange(len(lab)), lab]).sum()
         return self.loss
+
+
+def adam(p, g, m, v, cur_b1, cur_b2, lr=1e-4, wd=0.0, b1=0.9, b2=0.999, eps=1e-7):
+    """update_parameters (resnet.cu:605-662, 2910-2987) in float64 numpy, as oracle/oracle.c's orc_adam states it: returns the new
+    (params, means, vars).  cur_b1 / cur_b2 are beta^t of THIS step -- the decays advance before use (resnet.cu:2920-2921), so the
+    first update divides by 1 - beta.  A non-finite gradient leaves m and v alone; a non-finite result keeps the old parameter."""
+    p, g, m, v = (np.asarray(a, np.float64) for a in (p, g, m, v))
+    ok = np.isfinite(g)
+    gd = np.where(ok, g, 0.0) + wd * p
+    m = np.where(ok, b1 * m + (1 - b1) * gd, m)
+    v = np.where(ok, b2 * v + (1 - b2) * gd * gd, v)
+    new = p - (lr * ((m / (1 - cur_b1)) / (np.sqrt(v / (1 - cur_b2)) + eps)) + wd * p)
+    return np.where(np.isfinite(new), new, p), m, v
 
 
 def gates_of(tr, dims):
