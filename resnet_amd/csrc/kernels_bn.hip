@@ -590,16 +590,11 @@ int mid_bn_debug_merge(mid_stream s, int R, int C, float *means, float *vars, fl
 /* (the bf16 kernels pad every image's columns to a multiple of 8) */
 size_t mid_bn_parts_floats(int N, int K, int Ho) { return (size_t)3 * (size_t)mi_cdiv((long)N * ((Ho * Ho + 7) / 8 * 8), 128) * 4 * K; }
 
-/* side output of the NEXT forward apply (one-shot: the caller sets it right before the call, the launcher consumes it): the activation
- * also as a zero-padded channel-last plane of H x H pixels (bn_apply_cl_kernel) */
-static struct { void *out; int H; } g_bn_cl = {nullptr, 0};
-/* H > 0: one plane with a halo of 1; H < 0: the four parity planes of a stride-2 3x3 over an |H| x |H| image */
-extern "C" void mid_bn_set_cl_out(void *ycl, int H) { g_bn_cl.out = ycl; g_bn_cl.H = H; }
-/* taken (and cleared) at the ENTRY of the public launchers, so that an early error return cannot leave it for some later layer */
-static void *bn_take_cl_out(int *H) { void *p = g_bn_cl.out; *H = g_bn_cl.H; g_bn_cl.out = nullptr; return p; }
+/* ycl != NULL: the activation also as a zero-padded channel-last plane of |Hcl| x |Hcl| pixels (bn_apply_cl_kernel): Hcl > 0 one plane
+ * with a halo of 1, Hcl < 0 the four parity planes of a stride-2 3x3 */
 static int bn_fwd_apply(hipStream_t st, const void *x, int x_dt, const float *gamma, const float *beta, const void *residual,
                         const float *means, const float *vars, void *y, int a_dt, float *xhat_out, float *norm_out, int N, int C,
-                        int P, float eps, int relu, void *ycl = nullptr, int Hcl = 0) {
+                        int P, float eps, int relu, void *ycl, int Hcl) {
     const int Hab = Hcl < 0 ? -Hcl : Hcl;
     if (ycl && x_dt == MID_BF16 && a_dt == MID_BF16 && (residual || relu) && !xhat_out && !norm_out && C % 64 == 0 && Hab * Hab == P && !(Hcl < 0 && (Hab & 1))) {
         hipLaunchKernelGGL(bn_apply_cl_kernel, dim3(C / 64, mi_cdiv(P, 64), N), dim3(256), 0, st, (const bf16_t *)x, gamma, beta, means, vars,
@@ -646,9 +641,7 @@ int mid_bn_stats_t(mid_stream s, float *ws, const void *x, int x_dt, float *mean
 
 /* y from x and GIVEN statistics (no reduction): forward's second half, and the backward-time recomputation of an activation */
 int mid_bn_apply_t(mid_stream s, const void *x, int x_dt, const float *gamma, const float *beta, const void *residual,
-                   const float *means, const float *vars, void *y, int a_dt, int N, int C, int P, float eps, int relu) {
-    int Hcl = 0;
-    void *ycl = bn_take_cl_out(&Hcl);
+                   const float *means, const float *vars, void *y, int a_dt, int N, int C, int P, float eps, int relu, void *ycl, int Hcl) {
     if (!bn_pair_ok(x_dt, a_dt)) { mi_record_error("mid_bn_apply_t", "unsupported storage types"); return -2; }
     hipStream_t st = (hipStream_t)s;
     mi_prof_begin(st, MI_FAM_BN, 0.0, (double)N * C * P * (dt_bytes(x_dt) + dt_bytes(a_dt) * (residual ? 2 : 1)));
@@ -659,9 +652,7 @@ int mid_bn_apply_t(mid_stream s, const void *x, int x_dt, const float *gamma, co
 
 int mid_bn_fwd_t(mid_stream s, float *ws, const mid_bn_parts *parts, const void *x, int x_dt, const float *gamma, const float *beta,
                  const void *residual, float *means, float *vars, void *y, int a_dt, float *xhat_out, float *norm_out, int N, int C,
-                 int P, float eps, int relu) {
-    int Hcl = 0;
-    void *ycl = bn_take_cl_out(&Hcl);
+                 int P, float eps, int relu, void *ycl, int Hcl) {
     if (!bn_pair_ok(x_dt, a_dt)) { mi_record_error("mid_bn_fwd_t", "unsupported storage types"); return -2; }
     if ((xhat_out || norm_out) && !(x_dt == MID_F32 && a_dt == MID_F32)) { mi_record_error("mid_bn_fwd_t", "full-store tensors exist in fp32 only"); return -2; }
     hipStream_t st = (hipStream_t)s;
@@ -704,13 +695,13 @@ int mid_bn_fwd_t(mid_stream s, float *ws, const mid_bn_parts *parts, const void 
 int mid_bn_fwd(mid_stream s, float *ws, const float *x, const float *gamma, const float *beta, const float *residual,
                float *means, float *vars, float *y, float *xhat_out, float *norm_out, int N, int C, int P, float eps,
                int relu) {
-    return mid_bn_fwd_t(s, ws, nullptr, x, MID_F32, gamma, beta, residual, means, vars, y, MID_F32, xhat_out, norm_out, N, C, P, eps, relu);
+    return mid_bn_fwd_t(s, ws, nullptr, x, MID_F32, gamma, beta, residual, means, vars, y, MID_F32, xhat_out, norm_out, N, C, P, eps, relu, nullptr, 0);
 }
 
 int mid_bn_fwd_parts(mid_stream s, float *ws, const mid_bn_parts *parts, const float *x, const float *gamma, const float *beta,
                      const float *residual, float *means, float *vars, float *y, float *xhat_out, float *norm_out, int N,
                      int C, int P, float eps, int relu) {
-    return mid_bn_fwd_t(s, ws, parts, x, MID_F32, gamma, beta, residual, means, vars, y, MID_F32, xhat_out, norm_out, N, C, P, eps, relu);
+    return mid_bn_fwd_t(s, ws, parts, x, MID_F32, gamma, beta, residual, means, vars, y, MID_F32, xhat_out, norm_out, N, C, P, eps, relu, nullptr, 0);
 }
 
 // bparts != NULL (nparts > 0): the reduction pass was done by the dgrad that produced dy (which is already gated: mask_mode 0)

@@ -150,7 +150,6 @@ int mid_cl_dgrad(mid_stream s, const void *dyp, const void *a_tiles, void *dx, c
 /* weight gradient from dY (NCHW) and the forward's re-laid input: transposed LDS reads on the pixel-major operand */
 int mid_cl_wgrad_supported(int N, int C, int H, int K, int stride);
 size_t mid_cl_wgrad_part_floats(int N, int C, int H, int K, int stride);
-void mid_bn_set_cl_out(void *ycl, int H); /* one-shot: the next mid_bn_fwd_t / mid_bn_apply_t also writes its (bf16; ReLU or + residual, ReLU) output channel-last: H > 0 one plane with a halo of 1, H < 0 the four parity planes of a stride-2 3x3 over |H| x |H| */
 int mid_cl_pw_supported(int N, int C, int H, int K);
 int mid_cl_relayout_dense(mid_stream s, const void *x, void *xp, int N, int C, int H);
 int mid_cl_pw_fwd(mid_stream s, const void *xc, const void *a_tiles, void *y, int N, int C, int H, int K, mid_bn_parts *parts);
@@ -220,17 +219,20 @@ int mid_bn_bwd_gate(mid_stream s, float *stats_ws, const float *x, const float *
                     float *dx, float *dgamma, float *dbeta, int N, int C, int P, float eps);
 
 /* the same operators over typed tensors: x_dt = storage type of the convolution output x (and of dx), a_dt = of the
- * activation-side tensors (y, residual, dy, mask_src, gated_out).  Pairs: (f32,f32), (bf16,bf16), (f32,bf16). */
+ * activation-side tensors (y, residual, dy, mask_src, gated_out).  Pairs: (f32,f32), (bf16,bf16), (f32,bf16).
+ * ycl != NULL (mid_bn_fwd_t, mid_bn_apply_t): the (bf16; ReLU or + residual, ReLU) output is also written channel-last for the
+ * 3x3 that reads it: Hcl > 0 one plane with a halo of 1, Hcl < 0 the four parity planes of a stride-2 3x3 over |Hcl| x |Hcl|;
+ * only the interior is written (the caller zeroes ycl once).  NULL, 0: no side output. */
 int mid_bn_fwd_t(mid_stream s, float *stats_ws, const mid_bn_parts *parts, const void *x, int x_dt, const float *gamma,
                  const float *beta, const void *residual, float *means, float *vars, void *y, int a_dt, float *xhat_out,
-                 float *norm_out, int N, int C, int P, float eps, int relu);
+                 float *norm_out, int N, int C, int P, float eps, int relu, void *ycl, int Hcl);
 /* cross-replica batch-norm statistics through `comm` (an RCCL communicator of its own); NULL = per-replica (the reference) */
 void mid_bn_set_sync(void *comm, int world, float *tmp, size_t tmp_floats, int force);
 /* test aid: the sync-BN merge kernels on R replicas held by one process (the all-reduce replaced by a sum kernel); see kernels_bn.hip */
 int mid_bn_debug_merge(mid_stream s, int R, int C, float *means, float *vars, float *dgamma, float *dbeta, float *sums_out, float *tmp);
 int mid_bn_stats_t(mid_stream s, float *stats_ws, const void *x, int x_dt, float *means, float *vars, int N, int C, int P);
 int mid_bn_apply_t(mid_stream s, const void *x, int x_dt, const float *gamma, const float *beta, const void *residual,
-                   const float *means, const float *vars, void *y, int a_dt, int N, int C, int P, float eps, int relu);
+                   const float *means, const float *vars, void *y, int a_dt, int N, int C, int P, float eps, int relu, void *ycl, int Hcl);
 /* mask_mode 0..2 as mid_bn_bwd; 3 = mid_bn_bwd_gate */
 int mid_bn_bwd_t(mid_stream s, float *stats_ws, const void *x, int x_dt, const float *gamma, const float *beta, const float *means,
                  const float *vars, const void *dy, const void *mask_src, void *gated_out, int a_dt, void *dx, float *dgamma,

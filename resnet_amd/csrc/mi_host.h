@@ -43,27 +43,55 @@ typedef struct BatchExt {
 BatchExt *mi_batch_ext(Batch *b);
 void mi_batch_ext_free(Batch *b);
 
-/* parity copies of a striding block's conv inputs; *_valid: the last forward pass wrote the planes (the weight gradient may read them) */
+/* the trainer's own switches (environment), read once per trainer by init_trainer; kernel-level switches stay in the .hip files */
 typedef struct {
-    void *spatial, *proj; size_t spatial_bytes, proj_bytes; int spatial_valid, proj_valid;
-    /* the stride-2 dgrads' output gradient re-laid channel-last with a zero row / column at the far end (kernels_cl_bf16.hip); the
-     * halo is zeroed once, when the buffers are made; NULL = that layer's dgrad stays on the NCHW kernel */
-    void *dye_spatial, *dye_proj;
-    void *dy1;                   /* stride-1 blocks: the 3x3's output gradient as a zero-padded channel-last plane (re-laid once per backward pass: dgrad and weight gradient read it) */
-    void *cl_s1;                 /* stride-1 blocks: the 3x3's input as ONE zero-padded channel-last plane, written by the reduction BN's apply itself */
-    void *cl_spatial, *cl_proj;  /* channel-last parity planes of the layer's input: forward + weight gradient (kernels_cl_bf16.hip) */
-} MiParity;
+    int cl_s1, cl_s1_dgrad;      /* RESNET_MI_BF16_CL_S1 / _CL_S1_DGRAD (0: stride-1 3x3 forward + wgrad / dgrad on the NCHW kernels) */
+    int cl_s2, cl_dgrad2;        /* RESNET_MI_BF16_CL_S2 / _CL_DGRAD2 (0: stride-2 forward + wgrad / dgrad on the NCHW kernels) */
+    int stem_mfma, bf16_stem;    /* RESNET_MI_STEM_MFMA / RESNET_MI_BF16_STEM (0: the stem on the VALU kernels) */
+    int stem_tensors_f32;        /* RESNET_MI_BF16_STEM_TENSORS=f32: the bf16 stem's output and its gradient stay fp32 tensors */
+    int bnfuse_bwd;              /* RESNET_MI_BF16_BNFUSE_BWD (0: no BN' reduction in any dgrad, either storage type) */
+    int bnfuse_bwd_f32;          /* RESNET_MI_F32_BNFUSE_BWD: fp32 site mask (see plan_layers) */
+    int overlap, overlap_given;  /* RESNET_MI_OVERLAP, and whether it was set at all */
+    int bnfuse;                  /* RESNET_MI_BNFUSE (0: fp32 forward BN statistics by a pass of their own) */
+    int prelayout;               /* RESNET_MI_PRELAYOUT (0: each fp32 convolution re-lays its own weights) */
+} MiOptions;
+
+/* One convolution of the network and how it runs, decided once per build of the buffers (plan_layers): the kernel routes follow
+ * from shape, storage type, store policy and options, and the buffers the layer owns follow from the routes. */
+enum { MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16 };
+enum { MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 };
+enum { MI_WG_F32, MI_WG_BF16, MI_WG_CL, MI_WG_CL2, MI_WG_STEM_F32, MI_WG_STEM_BF16 };
+typedef struct {
+    const float *w;
+    int C, H, K, k, stride;
+    const mid_wt_entry *we;      /* the weights re-laid once per forward pass (relayout_weights), or NULL */
+    int fwd, dgrad, wgrad;       /* MI_FWD_* / MI_DG_* / MI_WG_* */
+    int fz;                      /* the dgrad also does the reduction pass of the BN' its output feeds (mid_conv_dgrad_bn_*) */
+    /* bf16, channel-last input planes (kernels_cl_bf16.hip) read by the forward and the weight gradient: one zero-padded plane
+     * (stride 1) or four parity planes (stride 2); cl_by_bn: the producing BN apply writes them (the reduction BN for the 3x3,
+     * the expansion BN of the block above for a stride-2 projection), else a re-layout pass in front of the forward */
+    void *cl; int cl_by_bn;
+    void *dye;                   /* MI_DG_CL / MI_DG_CL2: the output gradient re-laid channel-last (unit_bwd), read by dgrad and wgrad */
+    /* bf16 stride 2: NCHW parity planes of the input; par_valid: the last forward left them there (the weight gradient reuses them) */
+    void *par; size_t par_bytes; int par_valid;
+    /* stem on the matrix cores: the batch as zero-padded parity planes + wave partials and re-laid weights (kernels_stem_bf16.hip) */
+    void *xp; size_t xp_bytes; float *scratch; size_t scratch_floats;
+} MiLayer;
+typedef struct { MiLayer red, spa, exp, proj; } MiBlockLayers; /* proj.w == NULL: no projection */
+
 typedef struct MiCtx {
     mid_workspace ws;
     float *bn_ws;
     mid_bn_parts bn_parts; /* statistics partials a forward convolution leaves for its batch norm */
-    /* weights re-laid for the implicit-GEMM kernel once per forward pass (one launch): host copy of the table for the
-     * per-call lookup by weight pointer, device copies for the kernel */
+    /* weights re-laid for the implicit-GEMM kernel once per forward pass (one launch): host table (MiLayer.we points into it),
+     * device copies for the kernel */
     mid_wt_entry *wt_tab;
     int wt_n, wt_tiles;
     mid_wt_entry *wt_tab_dev;
     int *wt_tile_entry_dev;
-    int fuse_bn_stats;
+    MiOptions opt;
+    MiLayer stem;
+    MiBlockLayers *blk;          /* per block */
     int *nan_flag_dev, *nan_flag_host;
     int nan_check_pending;       /* update_parameters queued a copy of the flag; read it at the next host sync point */
     mid_event ev_nan;            /* recorded behind that copy */
@@ -77,28 +105,12 @@ typedef struct MiCtx {
     size_t act_bytes, dev_bytes; /* forward activations kept for backward / every tracked allocation */
     size_t *alloc_bytes;
     float *rc_buf[2];            /* RECOMPUTE_BN: scratch for the BN(+ReLU) tensors (forward: consumed at once; backward: re-derived) */
-    /* bf16: the reduction pass of a unit's BN' done by the dgrad that produces its dy (mid_conv_dgrad_bn_bf16).  backwards_pass
-     * fills fz_req before the unit whose dgrad should do it; the unit's dgrad moves it to fz_done (nparts > 0) for the next unit_bwd */
-    mid_bn_bwd_parts fz_req, fz_done;
-    int cl_pre;                  /* bf16: the stride-2 layers' parity planes are written by the producing BN apply too (RESNET_MI_BF16_CL_PRE=0: by a re-layout pass) */
-    int cur_cl_ready;            /* forward: cur_cl already holds this step's planes (written by the producer) */
-    void *bn_cl_out; int bn_cl_H; /* forward: the next unit's BN apply also writes this channel-last plane (stride-1 3x3 input), or NULL */
     int stem_bf16;               /* bf16 mode: the stem convolution's output and its gradient are bf16 tensors too (RESNET_MI_BF16_STEM_TENSORS=f32: fp32 as in round 2) */
-    int cl_wgrad2;               /* bf16: stride-2 weight gradients with both operands channel-last where the plane does not fill 64-pixel tiles (RESNET_MI_BF16_CL_WGRAD2=0: off) */
-    int fz_bf16;                 /* bf16: which dgrads carry a BN' reduction (sites 1 | 2 | 4 as fz_f32; RESNET_MI_BF16_BNFUSE_SITES, default all) */
-    int fz_req_valid, fz_ready, fz_enable, fz_f32; /* fz_f32: the fp32 dgrads do it too (RESNET_MI_F32_BNFUSE_BWD, default on) */
     float *stem_dx;              /* bf16 mode: the stem convolution's output gradient stays fp32 */
-    void *stem_xp; size_t stem_xp_bytes;           /* bf16 mode: the batch as zero-padded bf16 parity planes (kernels_stem_bf16.hip) */
-    float *stem_scratch; size_t stem_scratch_floats; /*            its wave partials + re-laid weights; NULL = the fp32 stem kernels */
     int counting_act;
     int overlap_set;             /* mi_trainer_set_overlap was called: keep the caller's mode */
-    MiParity *par;               /* bf16: per block, NULL buffers for blocks that do not stride */
     int params_dirty;            /* update_parameters ran since the last weight re-layout */
     unsigned long host_epoch_seen; /* the process-wide host-write count (mi_copy_to_device) that re-layout was made at */
-    void *cur_par; size_t cur_par_bytes; int *cur_par_valid; /* parity buffer of the stride-2 convolution about to be launched */
-    void *cur_cl;                /* ... its channel-last parity planes (the forward pass fills them, the weight gradient reads them), or NULL */
-    int cur_dye_valid;           /* the stride-2 dgrad of this layer has filled cur_dye (this backward pass): the weight gradient may read it */
-    void *cur_dye;               /* ... and the channel-last buffer for its output gradient (stride-2 dgrad), or NULL */
     char *dump_root;
     /* every device allocation of this trainer (freed by destroy_trainer) */
     void **allocs;

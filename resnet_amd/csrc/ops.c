@@ -267,7 +267,7 @@ int mi_op_conv_bn_fwd_t(const void *x, const float *w, void *conv_out, int dt, c
         if (stride == 2) { ws.s2d_bytes = (size_t)N * C * H * H * 2; par = mi_malloc(ws.s2d_bytes); ws.s2d = par; }
         rc = mid_conv_fwd_bf16(mi_global()->compute, &ws, x, w, conv_out, N, C, H, K, k, stride, &parts);
     } else rc = mid_conv_fwd_stats(mi_global()->compute, &ws, (const float *)x, w, (float *)conv_out, N, C, H, K, k, stride, &parts);
-    if (!rc) rc = mid_bn_fwd_t(mi_global()->compute, bws, &parts, conv_out, dt, gamma, beta, NULL, means, vars, y, dt, NULL, NULL, N, K, Ho * Ho, eps, relu);
+    if (!rc) rc = mid_bn_fwd_t(mi_global()->compute, bws, &parts, conv_out, dt, gamma, beta, NULL, means, vars, y, dt, NULL, NULL, N, K, Ho * Ho, eps, relu, NULL, 0);
     rc = finish(rc);
     mi_free(par);
     mid_free(bws);
@@ -278,7 +278,7 @@ int mi_op_conv_bn_fwd_t(const void *x, const float *w, void *conv_out, int dt, c
 int mi_op_bn_fwd_t(const void *x, int x_dt, const float *gamma, const float *beta, const void *residual, float *means, float *vars,
                    void *y, int a_dt, int N, int C, int H, float eps, int relu) {
     float *ws = (float *)mid_malloc(mid_bn_ws_floats(C) * sizeof(float));
-    int rc = finish(mid_bn_fwd_t(mi_global()->compute, ws, NULL, x, x_dt, gamma, beta, residual, means, vars, y, a_dt, NULL, NULL, N, C, H * H, eps, relu));
+    int rc = finish(mid_bn_fwd_t(mi_global()->compute, ws, NULL, x, x_dt, gamma, beta, residual, means, vars, y, a_dt, NULL, NULL, N, C, H * H, eps, relu, NULL, 0));
     mid_free(ws);
     return rc;
 }
@@ -288,9 +288,8 @@ int mi_op_bn_fwd_t(const void *x, int x_dt, const float *gamma, const float *bet
 int mi_op_bn_fwd_cl_bf16(const void *x, const float *gamma, const float *beta, const void *residual, float *means, float *vars, void *y, void *ycl,
                          int N, int C, int H, float eps, int par) {
     float *ws = (float *)mid_malloc(mid_bn_ws_floats(C) * sizeof(float));
-    mid_bn_set_cl_out(ycl, par ? -H : H);
     int rc = finish(mid_bn_fwd_t(mi_global()->compute, ws, NULL, x, MID_BF16, gamma, beta, residual, means, vars, y, MID_BF16, NULL, NULL, N, C, H * H, eps,
-                                 residual ? 0 : 1));
+                                 residual ? 0 : 1, ycl, par ? -H : H));
     mid_free(ws);
     return rc;
 }
@@ -304,7 +303,7 @@ int mi_op_bn_bwd_t(const void *x, int x_dt, const float *gamma, const float *bet
 }
 int mi_op_bn_apply_t(const void *x, int x_dt, const float *gamma, const float *beta, const void *residual, const float *means,
                      const float *vars, void *y, int a_dt, int N, int C, int H, float eps, int relu) {
-    return finish(mid_bn_apply_t(mi_global()->compute, x, x_dt, gamma, beta, residual, means, vars, y, a_dt, N, C, H * H, eps, relu));
+    return finish(mid_bn_apply_t(mi_global()->compute, x, x_dt, gamma, beta, residual, means, vars, y, a_dt, N, C, H * H, eps, relu, NULL, 0));
 }
 int mi_op_maxpool_fwd_t(const void *x, void *y, int dt, int *max_inds, int N, int C, int H, int k, int stride) {
     return finish(mid_maxpool_fwd_t(mi_global()->compute, x, y, dt, max_inds, N, C, H, k, stride));

@@ -333,148 +333,185 @@ static size_t max_tensor_elems(const Dims *d, ConvBlock **blocks, int N) {
     return m;
 }
 
-static void size_workspaces(MiCtx *c, const Dims *d, ConvBlock **blocks, int N) {
-    size_t wt = 0, part = 0;
-    int maxc = d->init_conv_filters;
-#define LAYER(C_, H_, K_, k_, s_)                                                             \
-    do {                                                                                      \
-        size_t a_ = mid_conv_ws_wt_floats(C_, K_, k_), b_ = mid_conv_ws_part_floats(N, C_, H_, K_, k_, s_); \
-        if (c->dtype == MID_BF16 && (k_) <= 3) { size_t e_ = mid_bf16_part_floats(N, C_, H_, K_, k_, s_); if (e_ > b_) b_ = e_; } \
-        if (c->dtype == MID_BF16 && (k_) == 3 && mid_cl_wgrad_supported(N, C_, H_, K_, s_)) { size_t e_ = mid_cl_wgrad_part_floats(N, C_, H_, K_, s_); if (e_ > b_) b_ = e_; } \
-        if (c->dtype == MID_BF16 && (k_) == 3 && mid_cl_wgrad2_supported(N, C_, H_, K_, s_)) { size_t e_ = mid_cl_wgrad2_part_floats(N, C_, H_, K_, s_); if (e_ > b_) b_ = e_; } \
-        if (a_ > wt) wt = a_;                                                                 \
-        if (b_ > part) part = b_;                                                             \
-        if ((K_) > maxc) maxc = (K_);                                                         \
-    } while (0)
-    LAYER(3, d->input, d->init_conv_filters, d->init_kernel_dim, d->init_conv_stride);
-    for (int i = 0; i < d->n_conv_blocks; i++) {
-        const ConvBlock *b = blocks[i];
-        const int H = b->incoming_spatial_dim;
-        LAYER(b->incoming_filters, H, b->reduced_depth, 1, 1);
-        LAYER(b->reduced_depth, H, b->reduced_depth, 3, b->stride);
-        LAYER(b->reduced_depth, H / b->stride, b->expanded_depth, 1, 1);
-        if (b->projection) LAYER(b->incoming_filters, H, b->expanded_depth, b->stride == 2 ? 3 : 1, b->stride);
-    }
-#undef LAYER
-    c->ws.s2d = NULL; c->ws.s2d_bytes = 0; c->ws.s2d_valid = 0;
-    free(c->par); c->par = NULL;
+/* a device buffer that starts zeroed: the halos of the channel-last planes stay zero (their writers fill the interior only) */
+static void *zalloc(MiCtx *c, size_t bytes) {
+    void *p = mi_ctx_alloc(c, bytes);
+    mid_memset(p, 0, bytes, G.compute);
+    return p;
+}
+static void layer_init(MiLayer *L, const float *w, int C, int H, int K, int k, int stride) {
+    memset(L, 0, sizeof *L); /* MI_FWD_F32 / MI_DG_F32 / MI_WG_F32, no buffers */
+    L->w = w; L->C = C; L->H = H; L->K = K; L->k = k; L->stride = stride;
+}
+/* routes and buffers of one bottleneck convolution; site: its bit in the BN'-fusion site masks (0: not a site) */
+static void plan_conv(MiCtx *c, MiLayer *L, int N, int site) {
+    const MiOptions *o = &c->opt;
+    const int C = L->C, H = L->H, K = L->K, s = L->stride;
     if (c->dtype == MID_BF16) {
-        /* stride-2 layers read their input as four parity planes per channel (kernels_igemm_bf16.hip): one copy per such layer,
-         * written by the forward pass and read again by the weight gradient (1.1 GB in all at N = 256) */
-        c->par = (MiParity *)calloc((size_t)(d->n_conv_blocks > 0 ? d->n_conv_blocks : 1), sizeof(MiParity));
-        for (int i = 0; i < d->n_conv_blocks; i++) {
-            const ConvBlock *b = blocks[i];
-            if (b->stride != 2) {
-                /* stride-1 3x3: forward and weight gradient on the channel-last plane the reduction BN writes beside its NCHW output
-                 * (RESNET_MI_BF16_CL_S1=0: the NCHW kernels) */
-                const int Hs = b->incoming_spatial_dim;
-                if (!(getenv("RESNET_MI_BF16_CL_S1") && atoi(getenv("RESNET_MI_BF16_CL_S1")) == 0) && mid_cl_supported(0, N, b->reduced_depth, Hs, b->reduced_depth, 1)) {
-                    const size_t by = mid_cl_operand_bytes(0, N, b->reduced_depth, Hs, b->reduced_depth, 1);
-                    c->par[i].cl_s1 = mi_ctx_alloc(c, by);
-                    mid_memset(c->par[i].cl_s1, 0, by, G.compute);
-                    if (!(getenv("RESNET_MI_BF16_CL_S1_DGRAD") && atoi(getenv("RESNET_MI_BF16_CL_S1_DGRAD")) == 0) &&
-                        mid_cl_supported(1, N, b->reduced_depth, Hs, b->reduced_depth, 1)) {
-                        const size_t dyb = mid_cl_operand_bytes(1, N, b->reduced_depth, Hs, b->reduced_depth, 1);
-                        c->par[i].dy1 = mi_ctx_alloc(c, dyb);
-                        mid_memset(c->par[i].dy1, 0, dyb, G.compute);
-                    }
-                }
-                continue;
-            }
-            const size_t H = b->incoming_spatial_dim, e1 = (size_t)N * b->reduced_depth * H * H, e2 = (size_t)N * b->incoming_filters * H * H;
-            /* forward and weight gradient on channel-last parity planes (RESNET_MI_BF16_CL_S2=0: the NCHW kernels and their planes) */
-            int need_sp = 1, need_pr = b->projection != NULL;
-            if (!(getenv("RESNET_MI_BF16_CL_S2") && atoi(getenv("RESNET_MI_BF16_CL_S2")) == 0)) {
-                if (mid_cl_supported(0, N, b->reduced_depth, (int)H, b->reduced_depth, 2)) {
-                    const size_t by = mid_cl_operand_bytes(0, N, b->reduced_depth, (int)H, b->reduced_depth, 2);
-                    c->par[i].cl_spatial = mi_ctx_alloc(c, by);
-                    mid_memset(c->par[i].cl_spatial, 0, by, G.compute); /* the halo stays zero: the re-layout writes the interior only */
-                    need_sp = !mid_cl_wgrad_supported(N, b->reduced_depth, (int)H, b->reduced_depth, 2) && !mid_cl_wgrad2_supported(N, b->reduced_depth, (int)H, b->reduced_depth, 2);
-                }
-                if (b->projection && mid_cl_supported(0, N, b->incoming_filters, (int)H, b->expanded_depth, 2)) {
-                    const size_t by = mid_cl_operand_bytes(0, N, b->incoming_filters, (int)H, b->expanded_depth, 2);
-                    c->par[i].cl_proj = mi_ctx_alloc(c, by);
-                    mid_memset(c->par[i].cl_proj, 0, by, G.compute);
-                    need_pr = !mid_cl_wgrad_supported(N, b->incoming_filters, (int)H, b->expanded_depth, 2) && !mid_cl_wgrad2_supported(N, b->incoming_filters, (int)H, b->expanded_depth, 2);
-                }
-            }
-            if (need_sp) { c->par[i].spatial_bytes = e1 * 2; c->par[i].spatial = (char *)mi_ctx_alloc(c, e1 * 2 + 2 * MI_GUARD) + MI_GUARD; }
-            if (need_pr) { c->par[i].proj_bytes = e2 * 2; c->par[i].proj = (char *)mi_ctx_alloc(c, e2 * 2 + 2 * MI_GUARD) + MI_GUARD; }
-            /* the stride-2 dgrads on channel-last dY (RESNET_MI_BF16_CL_DGRAD2=0: the NCHW kernel's four parity classes) */
-            if (!(getenv("RESNET_MI_BF16_CL_DGRAD2") && atoi(getenv("RESNET_MI_BF16_CL_DGRAD2")) == 0)) {
-                if (mid_cl_dgrad2_supported(N, b->reduced_depth, (int)H, b->reduced_depth)) {
-                    const size_t by = mid_cl_dgrad2_operand_bytes(N, b->reduced_depth, (int)H / 2);
-                    c->par[i].dye_spatial = mi_ctx_alloc(c, by);
-                    mid_memset(c->par[i].dye_spatial, 0, by, G.compute);
-                }
-                if (b->projection && mid_cl_dgrad2_supported(N, b->incoming_filters, (int)H, b->expanded_depth)) {
-                    const size_t by = mid_cl_dgrad2_operand_bytes(N, b->expanded_depth, (int)H / 2);
-                    c->par[i].dye_proj = mi_ctx_alloc(c, by);
-                    mid_memset(c->par[i].dye_proj, 0, by, G.compute);
-                }
+        L->fwd = MI_FWD_BF16; L->dgrad = MI_DG_BF16; L->wgrad = MI_WG_BF16;
+        if (L->k == 3 && s == 1 && o->cl_s1 && mid_cl_supported(0, N, C, H, K, 1)) {
+            /* forward and weight gradient on one zero-padded channel-last plane */
+            L->cl = zalloc(c, mid_cl_operand_bytes(0, N, C, H, K, 1));
+            L->fwd = MI_FWD_CL;
+            if (o->cl_s1_dgrad && mid_cl_supported(1, N, C, H, K, 1)) { /* the dgrad on dY re-laid as one zero-padded plane */
+                L->dye = zalloc(c, mid_cl_operand_bytes(1, N, C, H, K, 1));
+                L->dgrad = MI_DG_CL;
             }
         }
+        if (s == 2) { /* (a 3x3: the striding convolutions are the spatial one and the projection) */
+            if (o->cl_s2 && mid_cl_supported(0, N, C, H, K, 2)) { /* forward and weight gradient on four channel-last parity planes */
+                L->cl = zalloc(c, mid_cl_operand_bytes(0, N, C, H, K, 2));
+                L->fwd = MI_FWD_CL;
+            }
+            if (o->cl_dgrad2 && mid_cl_dgrad2_supported(N, C, H, K)) { /* the dgrad on dY re-laid with a zero row / column at the far end */
+                L->dye = zalloc(c, mid_cl_dgrad2_operand_bytes(N, K, H / 2));
+                L->dgrad = MI_DG_CL2;
+            }
+        }
+        const int P = (H / s) * (H / s);
+        const int wg = L->cl && mid_cl_wgrad_supported(N, C, H, K, s), wg2 = L->cl && mid_cl_wgrad2_supported(N, C, H, K, s);
+        /* both operands channel-last (the dY planes of the dgrad) where the plane does not fill 64-pixel tiles (784, 196, 49 pixels: all
+         * of the benchmark network's stride-2 layers; -0.8 ms per step, most of it the two 7x7 layers the other kernel cannot take) */
+        if (L->dye && wg2 && (P % 64 != 0 || !wg)) L->wgrad = MI_WG_CL2;
+        else if (wg) L->wgrad = MI_WG_CL;
+        /* NCHW parity planes of a stride-2 input (kernels_igemm_bf16.hip): the NCHW forward writes them and the weight gradient reads
+         * them again (1.1 GB in all at N = 256 with every stride-2 layer on this route); behind a channel-last forward, only for
+         * shapes that no channel-last weight-gradient kernel takes (the NCHW one makes them itself) */
+        if (s == 2 && (L->fwd == MI_FWD_BF16 || (!wg && !wg2))) {
+            const size_t e = (size_t)N * C * H * H;
+            L->par_bytes = e * 2;
+            L->par = (char *)mi_ctx_alloc(c, e * 2 + 2 * MI_GUARD) + MI_GUARD;
+        }
     }
+    /* The dgrad also does the reduction pass of the BN' its output feeds (and gates that output): sites 1 expansion dgrad -> spatial
+     * BN', 2 spatial dgrad -> reduction BN', 4 reduction dgrad -> the expansion BN' of the identity block below.  bf16: every site
+     * whose dgrad is on the NCHW kernel (RECOMPUTE_BN too: the gating tensors have just been re-derived when the dgrad runs).
+     * fp32: the sites of RESNET_MI_F32_BNFUSE_BWD on the implicit-GEMM route, not with the FULL policy (its derivative mirror keeps
+     * the ungated gradients the dump tree names).  Measured at batch 256 (same box, ms/step): none 108.3-109.5, site 4 alone
+     * 108.3-108.9, site 1 alone 109.4-110.2, sites 1+2 111.6-112.8, all 111.7-112.2 -- the fp32 epilogue keeps lane = column, so
+     * the fused form reads x / mask / addend with 4-byte accesses (four times the memory instructions of the bf16 kernel's
+     * row-major drain) and pays for it wherever the separate reduction pass was only 2 tensors; site 4 replaces a 4-tensor pass
+     * and breaks even, so it is the default. */
+    const int f32_sites = mid_igemm_mode() >= 2 ? o->bnfuse_bwd_f32 : 0;
+    L->fz = site && o->bnfuse_bwd &&
+            (L->dgrad == MI_DG_BF16 || (L->dgrad == MI_DG_F32 && (f32_sites & site) && c->policy != MI_STORE_FULL));
+}
+/* the convolution table (MiCtx.stem, MiCtx.blk): routes, the buffers they need, and the weights re-laid once per forward pass */
+static void plan_layers(MiCtx *c, const Params *p, const Dims *d, int N) {
+    const MiOptions *o = &c->opt;
+    ConvBlock **blocks = p->conv_blocks;
+    const int f = d->init_conv_filters;
+    MiLayer *S = &c->stem;
+    layer_init(S, p->init_conv_layer, 3, d->input, f, d->init_kernel_dim, d->init_conv_stride);
+    c->stem_bf16 = 0;
+    const int stem_mc = mid_stem_bf16_supported(3, d->input, f, d->init_kernel_dim, d->init_conv_stride);
+    if (c->dtype == MID_F32 && mid_igemm_mode() > 0 && stem_mc && o->stem_mfma) {
+        /* fp32 storage: the stem in exact fp32 on the matrix cores (kernels_stem_bf16.hip, st32_*) */
+        S->xp_bytes = mid_stem_f32_xp_bytes(N, d->input);
+        S->scratch_floats = mid_stem_bf16_part_floats(N, d->input);
+        S->xp = falloc(c, (S->xp_bytes + 3) / 4);
+        S->scratch = falloc(c, S->scratch_floats);
+        S->fwd = MI_FWD_STEM_F32; S->wgrad = MI_WG_STEM_F32;
+    }
+    if (c->dtype == MID_BF16 && stem_mc && o->bf16_stem) {
+        /* the stem on the bf16 matrix cores (image and weights rounded to bf16 like every other convolution of this mode) */
+        S->xp_bytes = mid_stem_bf16_xp_bytes(N, d->input);
+        S->scratch_floats = mid_stem_bf16_part_floats(N, d->input);
+        S->xp = aalloc(c, (S->xp_bytes + 1) / 2);                 /* (aalloc counts 2-byte elements in bf16 mode) */
+        S->scratch = falloc(c, S->scratch_floats);
+        S->fwd = MI_FWD_STEM_BF16; S->wgrad = MI_WG_STEM_BF16;
+        /* its output and that tensor's gradient are stored as bf16 like every other convolution's (they stay in their fp32-sized buffers):
+         * 822 MB tensors at N = 256 that the stem BN reads twice forward and three times backward */
+        c->stem_bf16 = !o->stem_tensors_f32;
+    }
+    free(c->blk);
+    c->blk = (MiBlockLayers *)calloc((size_t)(d->n_conv_blocks > 0 ? d->n_conv_blocks : 1), sizeof(MiBlockLayers));
+    /* the weights re-laid once per forward pass (mid_conv_prelayout_all): every bf16 convolution (k-step tiles, forward and dgrad
+     * forms), the fp32 ones on the implicit-GEMM route (RESNET_MI_PRELAYOUT=0: each re-lays its own) */
+    free(c->wt_tab);
+    c->wt_tab = (mid_wt_entry *)calloc((size_t)(4 * d->n_conv_blocks + 1), sizeof(mid_wt_entry));
+    c->wt_n = 0; c->wt_tiles = 0;
+    for (int i = 0; i < d->n_conv_blocks; i++) {
+        const ConvBlock *b = blocks[i];
+        MiBlockLayers *B = &c->blk[i];
+        const int H = b->incoming_spatial_dim, s = b->stride;
+        layer_init(&B->red, b->depth_reduction, b->incoming_filters, H, b->reduced_depth, 1, 1);
+        layer_init(&B->spa, b->spatial, b->reduced_depth, H, b->reduced_depth, 3, s);
+        layer_init(&B->exp, b->depth_expansion, b->reduced_depth, H / s, b->expanded_depth, 1, 1);
+        plan_conv(c, &B->red, N, i > 0 && !blocks[i - 1]->projection ? 4 : 0);
+        plan_conv(c, &B->spa, N, 2);
+        plan_conv(c, &B->exp, N, 1);
+        /* the reduction BN writes the 3x3's planes beside its NCHW output (stride 2: a re-layout pass instead where the plane is odd) */
+        if (B->spa.cl) B->spa.cl_by_bn = s == 1 || !(H & 1);
+        if (b->projection) {
+            layer_init(&B->proj, b->projection, b->incoming_filters, H, b->expanded_depth, s == 2 ? 3 : 1, s);
+            plan_conv(c, &B->proj, N, 0);
+            /* this block's input is the output of the block above: its BN + add + ReLU writes the planes too */
+            if (B->proj.cl) B->proj.cl_by_bn = i > 0 && !(H & 1);
+        }
+        MiLayer *Ls[4] = {&B->red, &B->spa, &B->exp, &B->proj};
+        for (int j = 0; j < 4; j++) {
+            MiLayer *L = Ls[j];
+            int nf = 0, nd = 0;
+            if (L->w && c->dtype == MID_BF16) nf = nd = 1;
+            else if (L->w && o->prelayout) mid_conv_prelayout_needs(N, L->C, L->H, L->K, L->k, L->stride, &nf, &nd);
+            if (!nf && !nd) continue;
+            mid_wt_entry *e = &c->wt_tab[c->wt_n++];
+            const size_t n = ((size_t)L->k * L->k * L->C * L->K) / (c->dtype == MID_BF16 ? 2 : 1);
+            e->w = L->w; e->K = L->K; e->C = L->C; e->T = L->k * L->k;
+            e->fwd = nf ? falloc(c, n) : NULL; e->dgrad = nd ? falloc(c, n) : NULL;
+            e->tile0 = c->wt_tiles; c->wt_tiles += (L->C / 32) * (L->K / 32);
+            L->we = e;
+        }
+    }
+    c->wt_tab_dev = NULL; c->wt_tile_entry_dev = NULL;
+    if (c->wt_n) {
+        int *te = (int *)malloc((size_t)c->wt_tiles * sizeof(int));
+        for (int e = 0; e < c->wt_n; e++) {
+            const int nt = (c->wt_tab[e].C / 32) * (c->wt_tab[e].K / 32);
+            for (int q = 0; q < nt; q++) te[c->wt_tab[e].tile0 + q] = e;
+        }
+        c->wt_tab_dev = (mid_wt_entry *)mi_ctx_alloc(c, (size_t)c->wt_n * sizeof(mid_wt_entry));
+        c->wt_tile_entry_dev = (int *)mi_ctx_alloc(c, (size_t)c->wt_tiles * sizeof(int));
+        mid_memcpy_h2d(c->wt_tab_dev, c->wt_tab, (size_t)c->wt_n * sizeof(mid_wt_entry), G.compute);
+        mid_memcpy_h2d(c->wt_tile_entry_dev, te, (size_t)c->wt_tiles * sizeof(int), G.compute);
+        mid_stream_sync(G.compute);
+        free(te);
+    }
+}
+/* the workspaces every convolution shares, sized for the largest layer of the table */
+static void size_layer_ws(const MiCtx *c, const MiLayer *L, int N, size_t *wt, size_t *part, int *maxc) {
+    const int C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
+    size_t a = mid_conv_ws_wt_floats(C, K, k), b = mid_conv_ws_part_floats(N, C, H, K, k, s);
+    if (c->dtype == MID_BF16 && k <= 3) { size_t e = mid_bf16_part_floats(N, C, H, K, k, s); if (e > b) b = e; }
+    if (c->dtype == MID_BF16 && k == 3 && mid_cl_wgrad_supported(N, C, H, K, s)) { size_t e = mid_cl_wgrad_part_floats(N, C, H, K, s); if (e > b) b = e; }
+    if (c->dtype == MID_BF16 && k == 3 && mid_cl_wgrad2_supported(N, C, H, K, s)) { size_t e = mid_cl_wgrad2_part_floats(N, C, H, K, s); if (e > b) b = e; }
+    if (a > *wt) *wt = a;
+    if (b > *part) *part = b;
+    if (K > *maxc) *maxc = K;
+}
+static void size_workspaces(MiCtx *c, const Dims *d, int N) {
+    size_t wt = 0, part = 0, pf = 0; /* pf: largest statistics-partials table of any conv + BN unit */
+    int maxc = d->init_conv_filters;
+    size_layer_ws(c, &c->stem, N, &wt, &part, &maxc);
+    for (int i = 0; i < d->n_conv_blocks; i++) {
+        const MiBlockLayers *B = &c->blk[i];
+        size_layer_ws(c, &B->red, N, &wt, &part, &maxc);
+        size_layer_ws(c, &B->spa, N, &wt, &part, &maxc);
+        size_layer_ws(c, &B->exp, N, &wt, &part, &maxc);
+        if (B->proj.w) size_layer_ws(c, &B->proj, N, &wt, &part, &maxc);
+        const size_t a = mid_bn_parts_floats(N, B->red.K, B->red.H), e = mid_bn_parts_floats(N, B->exp.K, B->exp.H);
+        if (a > pf) pf = a;
+        if (e > pf) pf = e;
+    }
+    c->ws.s2d = NULL; c->ws.s2d_bytes = 0; c->ws.s2d_valid = 0;
     c->ws.wt_floats = wt; c->ws.part_floats = part;
     c->ws.wt = wt ? falloc(c, wt) : NULL;
     c->ws.part = part ? falloc(c, part) : NULL;
     c->bn_ws = falloc(c, mid_bn_ws_floats(maxc));
-    {
-        size_t pf = 0; /* largest statistics-partials table of any conv + BN unit */
-        for (int i = 0; i < d->n_conv_blocks; i++) {
-            const ConvBlock *b = blocks[i];
-            const int H = b->incoming_spatial_dim, Ho = H / b->stride;
-            size_t a = mid_bn_parts_floats(N, b->reduced_depth, H), e = mid_bn_parts_floats(N, b->expanded_depth, Ho);
-            if (a > pf) pf = a;
-            if (e > pf) pf = e;
-        }
-        c->bn_parts.floats = pf;
-        c->bn_parts.buf = pf ? falloc(c, pf) : NULL;
-        c->bn_parts.nparts = 0;
-    }
-    { /* table of the convolutions whose weights are re-laid once per forward pass (mid_conv_prelayout_all) */
-        const int maxn = 4 * d->n_conv_blocks + 1;
-        const int prelayout = getenv("RESNET_MI_PRELAYOUT") ? atoi(getenv("RESNET_MI_PRELAYOUT")) : 1; /* 0: each conv re-lays its own */
-        free(c->wt_tab);
-        c->wt_tab = (mid_wt_entry *)calloc((size_t)maxn, sizeof(mid_wt_entry));
-        c->wt_n = 0; c->wt_tiles = 0;
-#define WT_LAYER(w_, C_, H_, K_, k_, s_)                                                       \
-        do {                                                                                       \
-            int nf_ = 0, nd_ = 0;                                                                  \
-            if ((w_) && c->dtype == MID_BF16) nf_ = nd_ = 1; /* bf16 k-step tiles, forward and dgrad forms */ \
-            else if ((w_) && prelayout) mid_conv_prelayout_needs(N, C_, H_, K_, k_, s_, &nf_, &nd_); \
-            if (nf_ || nd_) {                                                                      \
-                mid_wt_entry *e_ = &c->wt_tab[c->wt_n++];                                          \
-                const size_t n_ = ((size_t)(k_) * (k_) * (C_) * (K_)) / (c->dtype == MID_BF16 ? 2 : 1); \
-                e_->w = (w_); e_->K = (K_); e_->C = (C_); e_->T = (k_) * (k_);                     \
-                e_->fwd = nf_ ? falloc(c, n_) : NULL; e_->dgrad = nd_ ? falloc(c, n_) : NULL;      \
-                e_->tile0 = c->wt_tiles; c->wt_tiles += ((C_) / 32) * ((K_) / 32);                 \
-            }                                                                                      \
-        } while (0)
-        for (int i = 0; i < d->n_conv_blocks; i++) {
-            const ConvBlock *b = blocks[i];
-            const int H = b->incoming_spatial_dim;
-            WT_LAYER(b->depth_reduction, b->incoming_filters, H, b->reduced_depth, 1, 1);
-            WT_LAYER(b->spatial, b->reduced_depth, H, b->reduced_depth, 3, b->stride);
-            WT_LAYER(b->depth_expansion, b->reduced_depth, H / b->stride, b->expanded_depth, 1, 1);
-            WT_LAYER(b->projection, b->incoming_filters, H, b->expanded_depth, b->stride == 2 ? 3 : 1, b->stride);
-        }
-#undef WT_LAYER
-        c->wt_tab_dev = NULL; c->wt_tile_entry_dev = NULL;
-        if (c->wt_n) {
-            int *te = (int *)malloc((size_t)c->wt_tiles * sizeof(int));
-            for (int e = 0; e < c->wt_n; e++) {
-                const int nt = (c->wt_tab[e].C / 32) * (c->wt_tab[e].K / 32);
-                for (int q = 0; q < nt; q++) te[c->wt_tab[e].tile0 + q] = e;
-            }
-            c->wt_tab_dev = (mid_wt_entry *)mi_ctx_alloc(c, (size_t)c->wt_n * sizeof(mid_wt_entry));
-            c->wt_tile_entry_dev = (int *)mi_ctx_alloc(c, (size_t)c->wt_tiles * sizeof(int));
-            mid_memcpy_h2d(c->wt_tab_dev, c->wt_tab, (size_t)c->wt_n * sizeof(mid_wt_entry), G.compute);
-            mid_memcpy_h2d(c->wt_tile_entry_dev, te, (size_t)c->wt_tiles * sizeof(int), G.compute);
-            mid_stream_sync(G.compute);
-            free(te);
-        }
-    }
+    c->bn_parts.floats = pf;
+    c->bn_parts.buf = pf ? falloc(c, pf) : NULL;
+    c->bn_parts.nparts = 0;
 }
 
 static MiCtx *ctx_of(Train_ResNet *t) { return (MiCtx *)t->backend_ctx; }
@@ -498,26 +535,6 @@ static void build_buffers(Train_ResNet *t) {
     if (c->policy == MI_STORE_FULL) add_full_store_extras(t);
     const int f = d->init_conv_filters, Hs = d->input / d->init_conv_stride;
     c->stem_dx = c->dtype == MID_BF16 ? falloc(c, (size_t)N * f * Hs * Hs) : NULL;
-    c->stem_xp = NULL; c->stem_scratch = NULL; c->stem_xp_bytes = 0; c->stem_scratch_floats = 0; c->stem_bf16 = 0;
-    if (c->dtype == MID_F32 && mid_igemm_mode() > 0 && mid_stem_bf16_supported(3, d->input, f, d->init_kernel_dim, d->init_conv_stride) &&
-        !(getenv("RESNET_MI_STEM_MFMA") && atoi(getenv("RESNET_MI_STEM_MFMA")) == 0)) {
-        /* fp32 storage: the stem in exact fp32 on the matrix cores (kernels_stem_bf16.hip, st32_*) */
-        c->stem_xp_bytes = mid_stem_f32_xp_bytes(N, d->input);
-        c->stem_scratch_floats = mid_stem_bf16_part_floats(N, d->input);
-        c->stem_xp = falloc(c, (c->stem_xp_bytes + 3) / 4);
-        c->stem_scratch = falloc(c, c->stem_scratch_floats);
-    }
-    if (c->dtype == MID_BF16 && mid_stem_bf16_supported(3, d->input, f, d->init_kernel_dim, d->init_conv_stride) &&
-        !(getenv("RESNET_MI_BF16_STEM") && atoi(getenv("RESNET_MI_BF16_STEM")) == 0)) {
-        /* the stem on the bf16 matrix cores (image and weights rounded to bf16 like every other convolution of this mode) */
-        c->stem_xp_bytes = mid_stem_bf16_xp_bytes(N, d->input);
-        c->stem_scratch_floats = mid_stem_bf16_part_floats(N, d->input);
-        c->stem_xp = aalloc(c, (c->stem_xp_bytes + 1) / 2);                 /* (aalloc counts 2-byte elements in bf16 mode) */
-        c->stem_scratch = falloc(c, c->stem_scratch_floats);
-        /* its output and that tensor's gradient are stored as bf16 like every other convolution's (they stay in their fp32-sized buffers):
-         * 822 MB tensors at N = 256 that the stem BN reads twice forward and three times backward */
-        c->stem_bf16 = !(getenv("RESNET_MI_BF16_STEM_TENSORS") && !strcmp(getenv("RESNET_MI_BF16_STEM_TENSORS"), "f32"));
-    }
     float *pool[6];
     for (int i = 0; i < 6; i++) pool[i] = aalloc(c, maxe);
     for (int i = 0; i < 6; i++) c->dpool[i] = pool[i];
@@ -529,8 +546,9 @@ static void build_buffers(Train_ResNet *t) {
     if ((c->policy != MI_STORE_FAST || c->dtype != MID_F32) && c->overlap_wgrad > 1) c->overlap_wgrad = 1;
     /* bf16: the weight gradients are no longer bound by the matrix pipe but by memory, like the batch norm they would run
      * next to -- measured 6028 img/s serial against 5973 overlapped; an explicit RESNET_MI_OVERLAP still wins */
-    if (c->dtype == MID_BF16 && !getenv("RESNET_MI_OVERLAP") && !c->overlap_set) c->overlap_wgrad = 0;
-    size_workspaces(c, d, blocks, N);
+    if (c->dtype == MID_BF16 && !c->opt.overlap_given && !c->overlap_set) c->overlap_wgrad = 0;
+    plan_layers(c, t->model->params, d, N);
+    size_workspaces(c, d, N);
     mid_stream_sync(G.compute);
 }
 static void drop_buffers(Train_ResNet *t) {
@@ -544,6 +562,24 @@ static void drop_buffers(Train_ResNet *t) {
     c->wgrad_pending = 0;
 }
 
+/* the trainer's switches (MiOptions), read once per trainer: a trainer made after a change of the environment sees the change */
+static void read_options(MiOptions *o) {
+#define ENV_INT(name_, default_) (getenv(name_) ? atoi(getenv(name_)) : (default_))
+    o->cl_s1 = ENV_INT("RESNET_MI_BF16_CL_S1", 1) != 0;
+    o->cl_s1_dgrad = ENV_INT("RESNET_MI_BF16_CL_S1_DGRAD", 1) != 0;
+    o->cl_s2 = ENV_INT("RESNET_MI_BF16_CL_S2", 1) != 0;
+    o->cl_dgrad2 = ENV_INT("RESNET_MI_BF16_CL_DGRAD2", 1) != 0;
+    o->stem_mfma = ENV_INT("RESNET_MI_STEM_MFMA", 1) != 0;
+    o->bf16_stem = ENV_INT("RESNET_MI_BF16_STEM", 1) != 0;
+    o->stem_tensors_f32 = getenv("RESNET_MI_BF16_STEM_TENSORS") && !strcmp(getenv("RESNET_MI_BF16_STEM_TENSORS"), "f32");
+    o->bnfuse_bwd = ENV_INT("RESNET_MI_BF16_BNFUSE_BWD", 1) != 0;
+    o->bnfuse_bwd_f32 = ENV_INT("RESNET_MI_F32_BNFUSE_BWD", 4);
+    o->overlap = ENV_INT("RESNET_MI_OVERLAP", 1);
+    o->overlap_given = getenv("RESNET_MI_OVERLAP") != NULL;
+    o->bnfuse = ENV_INT("RESNET_MI_BNFUSE", 1);
+    o->prelayout = ENV_INT("RESNET_MI_PRELAYOUT", 1);
+#undef ENV_INT
+}
 /* resnet.cu:1157-1194 */
 Train_ResNet *init_trainer(ResNet *model, Batch *cur_batch, int batch_size, float learning_rate, float weight_decay,
                            float mean_decay, float var_decay, float eps, int n_epochs, const char *dump_dir) {
@@ -557,18 +593,8 @@ Train_ResNet *init_trainer(ResNet *model, Batch *cur_batch, int batch_size, floa
     c->input_reset = 1;   /* resnet.cu:2981-2982 */
     c->world = 1; c->bucket_bytes = (size_t)32 << 20;
     c->dtype = MID_F32; c->policy = MI_STORE_FAST;
-    c->fz_enable = !(getenv("RESNET_MI_BF16_BNFUSE_BWD") && atoi(getenv("RESNET_MI_BF16_BNFUSE_BWD")) == 0);
-    /* fp32 storage: which dgrads do it (bits: 1 expansion dgrad -> spatial BN', 2 spatial dgrad -> reduction BN', 4 reduction dgrad -> the
-     * expansion BN' of the identity block below); RESNET_MI_F32_BNFUSE_BWD overrides.  Measured at batch 256 (same box, ms/step):
-     * none 108.3-109.5, site 4 alone 108.3-108.9, site 1 alone 109.4-110.2, sites 1+2 111.6-112.8, all 111.7-112.2 -- the fp32 epilogue
-     * keeps lane = column, so the fused form reads x / mask / addend with 4-byte accesses (four times the memory instructions of the
-     * bf16 kernel's row-major drain) and pays for it wherever the separate reduction pass was only 2 tensors; site 4 replaces a
-     * 4-tensor pass and breaks even, so it is the default */
-    c->fz_bf16 = getenv("RESNET_MI_BF16_BNFUSE_SITES") ? atoi(getenv("RESNET_MI_BF16_BNFUSE_SITES")) : 7;
-    c->cl_pre = !(getenv("RESNET_MI_BF16_CL_PRE") && atoi(getenv("RESNET_MI_BF16_CL_PRE")) == 0);
-    c->cl_wgrad2 = !(getenv("RESNET_MI_BF16_CL_WGRAD2") && atoi(getenv("RESNET_MI_BF16_CL_WGRAD2")) == 0);
-    c->fz_f32 = mid_igemm_mode() >= 2 ? (getenv("RESNET_MI_F32_BNFUSE_BWD") ? atoi(getenv("RESNET_MI_F32_BNFUSE_BWD")) : 4) : 0;
-    c->overlap_wgrad = getenv("RESNET_MI_OVERLAP") ? atoi(getenv("RESNET_MI_OVERLAP")) : 1;
+    read_options(&c->opt);
+    c->overlap_wgrad = c->opt.overlap;
     c->ev_bn_done = mid_event_create(); c->ev_wgrad_done = mid_event_create();
 
     /* persistent device state: survives a change of storage type / store policy */
@@ -609,7 +635,6 @@ Train_ResNet *init_trainer(ResNet *model, Batch *cur_batch, int batch_size, floa
     c->ev_grads = mid_event_create(); c->ev_reduced = mid_event_create();
     for (int i = 0; i < 6; i++) c->ev_t[i] = mid_event_create();
     for (int i = 0; i < MI_MAX_BUCKETS; i++) c->bk_ev[i] = mid_event_create();
-    c->fuse_bn_stats = getenv("RESNET_MI_BNFUSE") ? atoi(getenv("RESNET_MI_BNFUSE")) : 1;
 
     build_buffers(t);
 
@@ -743,12 +768,6 @@ void mi_trainer_last_timings(Train_ResNet *t, float out_ms[5]) {
 }
 
 /* ---------------------------------------------------------------------------------------------- */
-static const mid_wt_entry *wt_lookup(const MiCtx *c, const float *w) {
-    for (int i = 0; i < c->wt_n; i++)
-        if (c->wt_tab[i].w == w) return &c->wt_tab[i];
-    return NULL;
-}
-
 /* every implicit-GEMM layer's weights in the layouts forward and dgrad want, one launch (they hold until the parameters
  * change: update_parameters, or a host write -- mi_copy_to_device / overwrite_model_params set the dirty flag) */
 static void relayout_weights(MiCtx *c) {
@@ -796,43 +815,45 @@ void mi_trainer_poll_errors(Train_ResNet *t) {
 
 /* conv + BN (+ReLU | +residual+ReLU): prepareAndDoConvolution + prepareAndDoBatchNormAndActivate.
  * stem: the 7x7 convolution keeps fp32 input / output in every storage type; only its BN output is an activation tensor */
-/* c->cur_par: parity copy of the NEXT stride-2 convolution's input (set by the caller); c->cur_par_valid: where the forward pass
- * records whether it really wrote the planes (it does only on the 16-byte staging route), read back by the weight gradient */
-static void set_cur_par(MiCtx *c, void *buf, size_t bytes, int *valid) { c->cur_par = buf; c->cur_par_bytes = bytes; c->cur_par_valid = valid; c->cur_dye = NULL; c->cur_cl = NULL; c->cur_dye_valid = 0; c->cur_cl_ready = 0; }
-static void unit_fwd(Train_ResNet *t, const float *in, const float *w, const BatchNorm *bn, Cache_BatchNorm *cache,
-                     float *conv_out, float *act_out, const float *residual, int C, int H, int K, int k, int stride,
-                     int relu, int stem) {
+/* storage type of a convolution's output (the BN's x) and of that tensor's gradient */
+static int conv_out_dt(const MiCtx *c, const MiLayer *L) { return L == &c->stem ? (c->stem_bf16 ? MID_BF16 : MID_F32) : c->dtype; }
+/* cl_reader: a convolution this unit's output feeds; where its channel-last input planes are this BN's to write (cl_by_bn), the
+ * BN apply writes them beside its NCHW output */
+static void unit_fwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNorm *bn, Cache_BatchNorm *cache, float *conv_out,
+                     float *act_out, const float *residual, int relu, const MiLayer *cl_reader) {
     MiCtx *c = ctx_of(t);
-    c->ws.s2d = stride == 2 ? c->cur_par : NULL; c->ws.s2d_bytes = stride == 2 ? c->cur_par_bytes : 0; c->ws.s2d_valid = 0;
-    const int N = t->batch_size, Ho = H / stride;
-    const int bf = c->dtype == MID_BF16 && !stem;
-    /* the convolution leaves per-tile (count, mean, M2) partials of its output: BN reads the tensor twice, not three times */
-    const mid_wt_entry *we = wt_lookup(c, w);
-    mid_bn_parts *parts = (c->fuse_bn_stats || bf) ? &c->bn_parts : NULL;
-    c->ws.pre_fwd = we ? we->fwd : NULL; /* re-laid at the start of this forward pass */
-    if (stem && c->stem_scratch && c->dtype == MID_F32) {
-        ck(mid_stem_fwd_f32(G.compute, in, w, conv_out, c->stem_xp, c->stem_xp_bytes, c->stem_scratch, c->stem_scratch_floats, N, H, parts),
+    const int N = t->batch_size, C = L->C, H = L->H, K = L->K, Ho = H / L->stride;
+    /* the convolution leaves per-tile (count, mean, M2) partials of its output: BN reads the tensor twice, not three times (the
+     * kernels with bf16 operands always do) */
+    const int bf_ops = L->fwd == MI_FWD_BF16 || L->fwd == MI_FWD_CL || L->fwd == MI_FWD_STEM_BF16;
+    mid_bn_parts *parts = (c->opt.bnfuse || bf_ops) ? &c->bn_parts : NULL;
+    c->ws.s2d = L->par; c->ws.s2d_bytes = L->par_bytes; c->ws.s2d_valid = 0;
+    c->ws.pre_fwd = L->we ? L->we->fwd : NULL; /* re-laid at the start of this forward pass */
+    switch (L->fwd) {
+    case MI_FWD_STEM_F32:
+        ck(mid_stem_fwd_f32(G.compute, in, L->w, conv_out, L->xp, L->xp_bytes, L->scratch, L->scratch_floats, N, H, parts),
            "stem convolution forward (fp32 matrix cores)");
-    } else if (stem && c->stem_scratch) {
-        parts = &c->bn_parts; /* (the stem's tensors are fp32 here, but its statistics still come from the kernel's accumulators) */
-        ck(mid_stem_fwd_bf16(G.compute, in, w, conv_out, c->stem_bf16 ? MID_BF16 : MID_F32, c->stem_xp, c->stem_xp_bytes, c->stem_scratch, c->stem_scratch_floats, N, H, parts),
+        break;
+    case MI_FWD_STEM_BF16: /* (the stem's tensors may be fp32 here, but its statistics still come from the kernel's accumulators) */
+        ck(mid_stem_fwd_bf16(G.compute, in, L->w, conv_out, conv_out_dt(c, L), L->xp, L->xp_bytes, L->scratch, L->scratch_floats, N, H, parts),
            "stem convolution forward (bf16 operands)");
-    } else if (bf && k == 3 && stride == 1 && c->cur_cl && we && we->fwd) {
-        /* the reduction BN wrote this input as a zero-padded channel-last plane beside its NCHW output: no re-layout pass */
-        ck(mid_cl_fwd(G.compute, c->cur_cl, we->fwd, conv_out, N, C, H, K, 1, parts), "convolution forward (bf16, channel-last)");
-    } else if (bf && k == 3 && stride == 2 && c->cur_cl && we && we->fwd) {
-        /* channel-last route: the input re-laid once as four zero-padded parity planes, which the weight gradient reads again */
-        if (!c->cur_cl_ready) ck(mid_cl_relayout(G.compute, in, c->cur_cl, N, C, H, 1), "input re-layout (channel-last parity planes)");
-        ck(mid_cl_fwd(G.compute, c->cur_cl, we->fwd, conv_out, N, C, H, K, 2, parts), "convolution forward (bf16, channel-last)");
-        if (c->cur_par_valid) *c->cur_par_valid = 0;
-    } else if (bf) {
-        ck(mid_conv_fwd_bf16(G.compute, &c->ws, in, w, conv_out, N, C, H, K, k, stride, parts), "convolution forward (bf16)");
-        if (stride == 2 && c->cur_par_valid) *c->cur_par_valid = c->ws.s2d_valid; /* the launch says whether it left the parity planes */
-    } else ck(mid_conv_fwd_stats(G.compute, &c->ws, in, w, conv_out, N, C, H, K, k, stride, parts), "convolution forward");
+        break;
+    case MI_FWD_CL: /* planes written by the producing BN apply, else re-laid here; the weight gradient reads them again */
+        if (!L->cl_by_bn) ck(mid_cl_relayout(G.compute, in, L->cl, N, C, H, L->stride == 2), "input re-layout (channel-last parity planes)");
+        ck(mid_cl_fwd(G.compute, L->cl, L->we->fwd, conv_out, N, C, H, K, L->stride, parts), "convolution forward (bf16, channel-last)");
+        L->par_valid = 0;
+        break;
+    case MI_FWD_BF16:
+        ck(mid_conv_fwd_bf16(G.compute, &c->ws, in, L->w, conv_out, N, C, H, K, L->k, L->stride, parts), "convolution forward (bf16)");
+        L->par_valid = c->ws.s2d_valid; /* the launch says whether it left the parity planes */
+        break;
+    default: ck(mid_conv_fwd_stats(G.compute, &c->ws, in, L->w, conv_out, N, C, H, K, L->k, L->stride, parts), "convolution forward");
+    }
     c->ws.pre_fwd = NULL;
-    if (c->bn_cl_out) { mid_bn_set_cl_out(bf ? c->bn_cl_out : NULL, c->bn_cl_H); c->bn_cl_out = NULL; }
-    ck(mid_bn_fwd_t(G.compute, c->bn_ws, parts, conv_out, (bf || (stem && c->stem_bf16)) ? MID_BF16 : MID_F32, bn->gamma, bn->beta, residual, cache->means, cache->vars,
-                    act_out, c->dtype, cache->normalized_temp, cache->normalized, N, K, Ho * Ho, t->eps, relu), "batch norm forward");
+    void *ycl = cl_reader && cl_reader->cl_by_bn ? cl_reader->cl : NULL;
+    const int Hcl = ycl ? (cl_reader->stride == 2 ? -cl_reader->H : cl_reader->H) : 0;
+    ck(mid_bn_fwd_t(G.compute, c->bn_ws, parts, conv_out, conv_out_dt(c, L), bn->gamma, bn->beta, residual, cache->means, cache->vars,
+                    act_out, c->dtype, cache->normalized_temp, cache->normalized, N, K, Ho * Ho, t->eps, relu, ycl, Hcl), "batch norm forward");
 }
 
 /* the batch-norm launchers take their cross-replica setting from one process-wide slot (kernels_bn.hip): every pass binds ITS
@@ -852,49 +873,32 @@ void forward_pass(Train_ResNet *t) {
     mid_event_record(c->ev_t[0], G.compute);
     bind_sync_bn(c);
     relayout_weights(c);
-    set_cur_par(c, NULL, 0, NULL);
-    unit_fwd(t, t->cur_batch->images, p->init_conv_layer, p->norm_init_conv, a->norm_init_conv, a->init_conv_applied,
-             a->init_conv_activated, NULL, 3, d->input, f, d->init_kernel_dim, d->init_conv_stride, 1, 1);
+    unit_fwd(t, &c->stem, t->cur_batch->images, p->norm_init_conv, a->norm_init_conv, a->init_conv_applied, a->init_conv_activated,
+             NULL, 1, NULL);
     const int Hs = d->input / d->init_conv_stride;
     ck(mid_maxpool_fwd_t(G.compute, a->init_conv_activated, a->init_convblock_input, c->dtype, a->max_inds, N, f, Hs, d->init_maxpool_dim,
                          d->init_maxpool_stride), "max-pool forward");
     const float *bin = a->init_convblock_input;
-    int pr_ready = 0; /* the producing BN apply of the block before has already written this block's projection planes */
     for (int i = 0; i < d->n_conv_blocks; i++) {
         const ConvBlock *b = p->conv_blocks[i];
+        MiBlockLayers *B = &c->blk[i];
         Activation_ConvBlock *k = a->activation_conv_blocks[i];
-        const int H = b->incoming_spatial_dim, Ho = H / b->stride;
-        int sp_ready = 0;
-        if (c->par && c->par[i].cl_s1) { c->bn_cl_out = c->par[i].cl_s1; c->bn_cl_H = H; }
-        else if (c->par && c->cl_pre && b->stride == 2 && c->par[i].cl_spatial && !(H & 1)) { c->bn_cl_out = c->par[i].cl_spatial; c->bn_cl_H = -H; sp_ready = 1; }
-        unit_fwd(t, bin, b->depth_reduction, b->norm_depth_reduction, k->norm_post_reduced, k->post_reduced,
-                 k->post_reduced_activated, NULL, b->incoming_filters, H, b->reduced_depth, 1, 1, 1, 0);
-        if (c->par) set_cur_par(c, c->par[i].spatial, c->par[i].spatial_bytes, &c->par[i].spatial_valid); else set_cur_par(c, NULL, 0, NULL);
-        c->cur_cl = c->par ? (b->stride == 2 ? c->par[i].cl_spatial : c->par[i].cl_s1) : NULL;
-        c->cur_cl_ready = sp_ready;
-        unit_fwd(t, k->post_reduced_activated, b->spatial, b->norm_spatial, k->norm_post_spatial, k->post_spatial,
-                 k->post_spatial_activated, NULL, b->reduced_depth, H, b->reduced_depth, 3, b->stride, 1, 0);
+        const int Ho = b->incoming_spatial_dim / b->stride;
+        unit_fwd(t, &B->red, bin, b->norm_depth_reduction, k->norm_post_reduced, k->post_reduced, k->post_reduced_activated, NULL, 1, &B->spa);
+        unit_fwd(t, &B->spa, k->post_reduced_activated, b->norm_spatial, k->norm_post_spatial, k->post_spatial, k->post_spatial_activated,
+                 NULL, 1, NULL);
         const float *res = bin;
         if (b->projection) { /* resnet.cu:1685-1704 */
-            if (c->par) set_cur_par(c, c->par[i].proj, c->par[i].proj_bytes, &c->par[i].proj_valid); else set_cur_par(c, NULL, 0, NULL);
-            c->cur_cl = c->par ? c->par[i].cl_proj : NULL;
-            c->cur_cl_ready = pr_ready;
-            unit_fwd(t, bin, b->projection, b->norm_projection, k->norm_post_projection, k->transformed_residual,
-                     k->post_projection_norm_vals, NULL, b->incoming_filters, H, b->expanded_depth, b->stride == 2 ? 3 : 1,
-                     b->stride, 0, 0);
+            unit_fwd(t, &B->proj, bin, b->norm_projection, k->norm_post_projection, k->transformed_residual, k->post_projection_norm_vals,
+                     NULL, 0, NULL);
             res = k->post_projection_norm_vals;
         }
-        pr_ready = 0;
         if (!c->full_store) { /* BN(expanded) + addVec + doActivation in one kernel (:1670, :1717, :1723) */
-            if (c->par && c->cl_pre && i + 1 < d->n_conv_blocks && p->conv_blocks[i + 1]->stride == 2 && p->conv_blocks[i + 1]->projection &&
-                c->par[i + 1].cl_proj && !(Ho & 1)) { /* this block's output is the next block's 3x3 stride-2 projection input */
-                c->bn_cl_out = c->par[i + 1].cl_proj; c->bn_cl_H = -Ho; pr_ready = 1;
-            }
-            unit_fwd(t, k->post_spatial_activated, b->depth_expansion, b->norm_expansion, k->norm_post_expanded,
-                     k->post_expanded, k->output_activated, res, b->reduced_depth, Ho, b->expanded_depth, 1, 1, 0, 0);
+            unit_fwd(t, &B->exp, k->post_spatial_activated, b->norm_expansion, k->norm_post_expanded, k->post_expanded, k->output_activated,
+                     res, 0, i + 1 < d->n_conv_blocks ? &c->blk[i + 1].proj : NULL); /* (the next block's projection input) */
         } else {
-            unit_fwd(t, k->post_spatial_activated, b->depth_expansion, b->norm_expansion, k->norm_post_expanded,
-                     k->post_expanded, k->post_expanded_norm_vals, NULL, b->reduced_depth, Ho, b->expanded_depth, 1, 1, 0, 0);
+            unit_fwd(t, &B->exp, k->post_spatial_activated, b->norm_expansion, k->norm_post_expanded, k->post_expanded,
+                     k->post_expanded_norm_vals, NULL, 0, NULL);
             ck(mid_add_relu(G.compute, k->post_expanded_norm_vals, res, k->output, k->output_activated,
                             (size_t)N * b->expanded_depth * Ho * Ho), "add + ReLU");
         }
@@ -942,116 +946,108 @@ static float *ring_take(MiCtx *c, int *slot) {
     if (slot) *slot = i;
     return c->ring_buf[i];
 }
-/* typed launch helpers: the bottleneck convolutions run on the bf16 kernels in bf16 mode, the stem always on the fp32 path */
-static void conv_dgrad_t(Train_ResNet *t, const float *w, const float *dy, float *dx, const float *addend, int C, int H, int K, int k,
-                         int stride) {
+/* typed launch helpers: the bottleneck convolutions run on the bf16 kernels in bf16 mode, the stem always on the fp32 path.
+ * req (L->fz): the dgrad also does the reduction pass of the BN' its output feeds; it hands that over in *fz (nparts > 0 when the
+ * launch could do it, dx then holds the gated gradient) */
+static void conv_dgrad_t(Train_ResNet *t, const MiLayer *L, const float *dy, float *dx, const float *addend, const mid_bn_bwd_parts *req,
+                         mid_bn_bwd_parts *fz) {
     MiCtx *c = ctx_of(t);
-    const mid_wt_entry *we = wt_lookup(c, w);
-    c->ws.pre_dgrad = we ? we->dgrad : NULL;
-    if (c->dtype == MID_BF16 && stride == 1 && k == 3 && c->cur_dye && c->cur_dye_valid && we && we->dgrad) {
-        /* stride-1 dgrad on the channel-last dY plane (the BN' below then runs its own reduction pass: measured neutral) */
-        ck(mid_cl_dgrad(G.compute, c->cur_dye, we->dgrad, dx, addend, t->batch_size, C, H, K), "convolution dgrad (bf16, channel-last)");
-        c->fz_req_valid = 0;
-        c->ws.pre_dgrad = NULL;
+    const int N = t->batch_size, C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
+    if (L->dgrad == MI_DG_CL) { /* stride 1 on the channel-last dY plane (the BN' below then runs its own reduction pass: measured neutral) */
+        ck(mid_cl_dgrad(G.compute, L->dye, L->we->dgrad, dx, addend, N, C, H, K), "convolution dgrad (bf16, channel-last)");
         return;
     }
-    if (c->dtype == MID_BF16 && stride == 2 && k == 3 && !addend && c->cur_dye && we && we->dgrad) {
-        /* stride-2 dgrad on channel-last dY: re-lay dY (K channels, H/2 x H/2) into the layer's zero-bordered buffer, then both column
-         * parities of dx per workgroup by LDS-DMA staged MFMAs (dense stores; 1.5-1.9x the NCHW kernel's four parity classes) */
-        if (!c->cur_dye_valid) ck(mid_cl_relayout_end(G.compute, dy, c->cur_dye, t->batch_size, K, H / 2), "dY re-layout (channel-last)");
-        c->cur_dye_valid = 1;
-        ck(mid_cl_dgrad2(G.compute, c->cur_dye, we->dgrad, dx, t->batch_size, C, H, K), "convolution dgrad (bf16, channel-last, stride 2)");
-        c->fz_req_valid = 0;
-        c->ws.pre_dgrad = NULL;
+    if (L->dgrad == MI_DG_CL2) {
+        /* stride 2 on the channel-last dY: both column parities of dx per workgroup by LDS-DMA staged MFMAs (dense stores; 1.5-1.9x
+         * the NCHW kernel's four parity classes).  It writes every element of dx: no addend (the stride-2 layers' dgrads have none) */
+        ck(mid_cl_dgrad2(G.compute, L->dye, L->we->dgrad, dx, N, C, H, K), "convolution dgrad (bf16, channel-last, stride 2)");
         return;
     }
-    {
-        static int minp = -1; /* diagnostic: RESNET_MI_BNFUSE_MINP = smallest plane (pixels) whose dgrad still carries the BN' reduction */
-        if (minp < 0) minp = getenv("RESNET_MI_BNFUSE_MINP") ? atoi(getenv("RESNET_MI_BNFUSE_MINP")) : 0;
-        if (c->fz_req_valid && H * H < minp) c->fz_req_valid = 0;
-    }
-    if (c->dtype == MID_BF16 && c->fz_req_valid) { /* ... and the reduction pass of the BN' its output feeds */
-        ck(mid_conv_dgrad_bn_bf16(G.compute, &c->ws, w, dy, dx, addend, t->batch_size, C, H, K, k, stride, &c->fz_req), "convolution dgrad + BN' reduction (bf16)");
-        if (c->fz_req.nparts > 0) { c->fz_done = c->fz_req; c->fz_ready = 1; }
-    } else if (c->fz_req_valid) { /* fp32 storage: the stride-1 layers on the implicit-GEMM route do the same */
-        ck(mid_conv_dgrad_bn_f32(G.compute, &c->ws, w, dy, dx, addend, t->batch_size, C, H, K, k, stride, &c->fz_req), "convolution dgrad + BN' reduction");
-        if (c->fz_req.nparts > 0) { c->fz_done = c->fz_req; c->fz_ready = 1; }
-    } else if (c->dtype == MID_BF16) ck(mid_conv_dgrad_bf16(G.compute, &c->ws, w, dy, dx, addend, t->batch_size, C, H, K, k, stride), "convolution dgrad (bf16)");
-    else ck(mid_conv_dgrad(G.compute, &c->ws, w, dy, dx, addend, t->batch_size, C, H, K, k, stride), "convolution dgrad");
-    c->fz_req_valid = 0;
+    c->ws.pre_dgrad = L->we ? L->we->dgrad : NULL;
+    if (req) *fz = *req;
+    if (L->dgrad == MI_DG_BF16 && req)
+        ck(mid_conv_dgrad_bn_bf16(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s, fz), "convolution dgrad + BN' reduction (bf16)");
+    else if (req) /* fp32 storage: the stride-1 layers on the implicit-GEMM route do the same */
+        ck(mid_conv_dgrad_bn_f32(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s, fz), "convolution dgrad + BN' reduction");
+    else if (L->dgrad == MI_DG_BF16) ck(mid_conv_dgrad_bf16(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s), "convolution dgrad (bf16)");
+    else ck(mid_conv_dgrad(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s), "convolution dgrad");
     c->ws.pre_dgrad = NULL;
 }
-static void conv_wgrad_t(Train_ResNet *t, mid_stream st, const float *x, const float *dy, float *dw, int C, int H, int K, int k, int stride,
-                         int stem) {
+static void conv_wgrad_t(Train_ResNet *t, const MiLayer *L, mid_stream st, const float *x, const float *dy, float *dw) {
     MiCtx *c = ctx_of(t);
+    const int N = t->batch_size, C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
     /* the forward pass left the parity planes of x in the layer's own buffer: the weight gradient reads them again */
-    c->ws.s2d = stride == 2 ? c->cur_par : NULL; c->ws.s2d_bytes = stride == 2 ? c->cur_par_bytes : 0;
-    c->ws.s2d_valid = stride == 2 && c->cur_par != NULL && c->cur_par_valid && *c->cur_par_valid;
-    if (stem && c->stem_scratch && c->dtype == MID_F32)
-        ck(mid_stem_wgrad_f32(st, c->stem_xp, dy, dw, c->stem_scratch, c->stem_scratch_floats, t->batch_size, H), "stem convolution wgrad (fp32 matrix cores)");
-    else if (stem && c->stem_scratch) /* the forward pass left the batch as padded bf16 parity planes */
-        ck(mid_stem_wgrad_bf16(st, c->stem_xp, dy, c->stem_bf16 ? MID_BF16 : MID_F32, dw, c->stem_scratch, c->stem_scratch_floats, t->batch_size, H), "stem convolution wgrad (bf16 operands)");
-    else if (c->dtype == MID_BF16 && !stem && k == 3 && c->cur_cl && c->cur_dye && c->cur_dye_valid && c->cl_wgrad2 &&
-             mid_cl_wgrad2_supported(t->batch_size, C, H, K, stride) && (((H / stride) * (H / stride)) % 64 != 0 || !mid_cl_wgrad_supported(t->batch_size, C, H, K, stride)))
-        /* both operands channel-last (the dY planes the dgrad has just made): planes that do not fill 64-pixel tiles (784, 196, 49 pixels:
-         * all of the benchmark network's stride-2 layers; -0.8 ms per step, most of it the two 7x7 layers the other kernel cannot take) */
-        ck(mid_cl_wgrad2(st, c->cur_cl, c->cur_dye, dw, c->ws.part, c->ws.part_floats, t->batch_size, C, H, K, stride), "convolution wgrad (bf16, both operands channel-last)");
-    else if (c->dtype == MID_BF16 && !stem && k == 3 && stride == 1 && c->cur_cl && mid_cl_wgrad_supported(t->batch_size, C, H, K, 1))
-        ck(mid_cl_wgrad(st, c->cur_cl, dy, dw, c->ws.part, c->ws.part_floats, t->batch_size, C, H, K, 1), "convolution wgrad (bf16, channel-last input)");
-    else if (c->dtype == MID_BF16 && !stem && k == 3 && stride == 2 && c->cur_cl && mid_cl_wgrad_supported(t->batch_size, C, H, K, 2))
-        ck(mid_cl_wgrad(st, c->cur_cl, dy, dw, c->ws.part, c->ws.part_floats, t->batch_size, C, H, K, 2), "convolution wgrad (bf16, channel-last)");
-    else if (c->dtype == MID_BF16 && !stem) ck(mid_conv_wgrad_bf16(st, &c->ws, x, dy, dw, t->batch_size, C, H, K, k, stride), "convolution wgrad (bf16)");
-    else ck(mid_conv_wgrad(st, &c->ws, x, dy, dw, t->batch_size, C, H, K, k, stride), "convolution wgrad");
+    c->ws.s2d = L->par; c->ws.s2d_bytes = L->par_bytes; c->ws.s2d_valid = L->par && L->par_valid;
+    switch (L->wgrad) {
+    case MI_WG_STEM_F32:
+        ck(mid_stem_wgrad_f32(st, L->xp, dy, dw, L->scratch, L->scratch_floats, N, H), "stem convolution wgrad (fp32 matrix cores)");
+        break;
+    case MI_WG_STEM_BF16: /* the forward pass left the batch as padded bf16 parity planes */
+        ck(mid_stem_wgrad_bf16(st, L->xp, dy, conv_out_dt(c, L), dw, L->scratch, L->scratch_floats, N, H), "stem convolution wgrad (bf16 operands)");
+        break;
+    case MI_WG_CL2: /* both operands channel-last: the forward's input planes and the dY planes unit_bwd has made */
+        ck(mid_cl_wgrad2(st, L->cl, L->dye, dw, c->ws.part, c->ws.part_floats, N, C, H, K, s), "convolution wgrad (bf16, both operands channel-last)");
+        break;
+    case MI_WG_CL:
+        ck(mid_cl_wgrad(st, L->cl, dy, dw, c->ws.part, c->ws.part_floats, N, C, H, K, s), "convolution wgrad (bf16, channel-last input)");
+        break;
+    case MI_WG_BF16: ck(mid_conv_wgrad_bf16(st, &c->ws, x, dy, dw, N, C, H, K, k, s), "convolution wgrad (bf16)"); break;
+    default: ck(mid_conv_wgrad(st, &c->ws, x, dy, dw, N, C, H, K, k, s), "convolution wgrad");
+    }
 }
-/* d_slot: ring slot holding d_conv_out (mode 2), -1 otherwise */
-static void unit_bwd(Train_ResNet *t, const float *in, const float *w, const BatchNorm *bn, const Cache_BatchNorm *cache,
+/* d_slot: ring slot holding d_conv_out (mode 2), -1 otherwise.  fz: the BN'-partials hand-off between a fusing dgrad and the next
+ * unit (nparts > 0: this unit's BN' reduction is done); fz_req: what this unit's dgrad is to fill it with, or NULL (fz_request) */
+static void unit_bwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNorm *bn, const Cache_BatchNorm *cache,
                      const BatchNorm *dbn, const float *conv_out, const float *dy, const float *mask_src, int mask_mode,
-                     float *gated_out, float *d_conv_out, int d_slot, float *dx, const float *addend, float *dw, int C, int H, int K, int k,
-                     int stride, int stem) {
+                     float *gated_out, float *d_conv_out, int d_slot, float *dx, const float *addend, float *dw, mid_bn_bwd_parts *fz,
+                     const mid_bn_bwd_parts *fz_req) {
     MiCtx *c = ctx_of(t);
-    const int N = t->batch_size, Ho = H / stride;
-    const int x_dt = (c->dtype == MID_BF16 && (!stem || c->stem_bf16)) ? MID_BF16 : MID_F32;
+    const int N = t->batch_size, K = L->K, Ho = L->H / L->stride;
+    const int x_dt = conv_out_dt(c, L);
     /* BN' of this unit (HBM-bound) runs next to earlier units' weight gradients (FMA-bound, low-priority aux stream);
      * mask_mode 3: ReLU' of the block output fused in, and its product with the upstream gradient kept (gated_out) */
-    if (c->fz_ready) { /* the dgrad that produced dy gated it and left the sums: merge, finalize, apply */
-        c->fz_ready = 0;
-        ck(mid_bn_bwd_parts_t(G.compute, c->bn_ws, &c->fz_done, conv_out, x_dt, bn->gamma, bn->beta, cache->means, cache->vars, dy, c->dtype,
+    if (fz->nparts > 0) { /* the dgrad that produced dy gated it and left the sums: merge, finalize, apply */
+        ck(mid_bn_bwd_parts_t(G.compute, c->bn_ws, fz, conv_out, x_dt, bn->gamma, bn->beta, cache->means, cache->vars, dy, c->dtype,
                               d_conv_out, dbn->gamma, dbn->beta, N, K, Ho * Ho, t->eps), "batch norm backward (reduction done by the dgrad)");
+        fz->nparts = 0;
     } else
     ck(mid_bn_bwd_t(G.compute, c->bn_ws, conv_out, x_dt, bn->gamma, bn->beta, cache->means, cache->vars, dy, mask_src, gated_out, c->dtype,
                     d_conv_out, dbn->gamma, dbn->beta, N, K, Ho * Ho, t->eps, mask_mode), "batch norm backward");
-    if (c->dtype == MID_BF16 && !stem && stride == 1 && k == 3 && c->cur_dye && !c->cur_dye_valid) {
-        /* stride 1: the same, one plane with a halo of 1 */
-        ck(mid_cl_relayout(G.compute, d_conv_out, c->cur_dye, N, K, Ho, 0), "dY re-layout (channel-last)");
-        c->cur_dye_valid = 1;
-    }
-    if (c->dtype == MID_BF16 && !stem && stride == 2 && k == 3 && c->cur_dye && !c->cur_dye_valid) {
-        /* the channel-last copy of d_conv_out that the stride-2 dgrad AND the weight gradient read: made here, before either is
-         * launched, so that every weight-gradient schedule (the free-running one starts before the dgrad) runs the same kernels */
-        ck(mid_cl_relayout_end(G.compute, d_conv_out, c->cur_dye, N, K, Ho), "dY re-layout (channel-last)");
-        c->cur_dye_valid = 1;
-    }
+    /* the channel-last copy of d_conv_out that the channel-last dgrad AND the weight gradient read: made here, before either is
+     * launched, so that every weight-gradient schedule (the free-running one starts before the dgrad) runs the same kernels */
+    if (L->dgrad == MI_DG_CL) /* stride 1: one plane with a halo of 1 */
+        ck(mid_cl_relayout(G.compute, d_conv_out, L->dye, N, K, Ho, 0), "dY re-layout (channel-last)");
+    else if (L->dgrad == MI_DG_CL2) /* stride 2: a zero row / column at the far end */
+        ck(mid_cl_relayout_end(G.compute, d_conv_out, L->dye, N, K, Ho), "dY re-layout (channel-last)");
     if (c->overlap_wgrad == 2 && d_slot >= 0) {
         /* d_conv_out is final once BN' is: the weight gradient may start now and run for as long as the slot lives */
         mid_event_record(c->ev_bn_done, G.compute);
         mid_stream_wait_event(G.aux, c->ev_bn_done);
-        conv_wgrad_t(t, G.aux, in, d_conv_out, dw, C, H, K, k, stride, stem);
+        conv_wgrad_t(t, L, G.aux, in, d_conv_out, dw);
         mid_event_record(c->ring_ev[d_slot], G.aux);
         c->ring_busy[d_slot] = 1;
         mid_event_record(c->ev_wgrad_done, G.aux);
         c->wgrad_pending = 1;
-        if (dx) conv_dgrad_t(t, w, d_conv_out, dx, addend, C, H, K, k, stride);
+        if (dx) conv_dgrad_t(t, L, d_conv_out, dx, addend, fz_req, fz);
         return;
     }
     join_wgrad(c);
-    if (dx) conv_dgrad_t(t, w, d_conv_out, dx, addend, C, H, K, k, stride);
+    if (dx) conv_dgrad_t(t, L, d_conv_out, dx, addend, fz_req, fz);
     if (c->overlap_wgrad) {
         mid_event_record(c->ev_bn_done, G.compute);
         mid_stream_wait_event(G.aux, c->ev_bn_done);
-        conv_wgrad_t(t, G.aux, in, d_conv_out, dw, C, H, K, k, stride, stem);
+        conv_wgrad_t(t, L, G.aux, in, d_conv_out, dw);
         mid_event_record(c->ev_wgrad_done, G.aux);
         c->wgrad_pending = 1;
-    } else conv_wgrad_t(t, G.compute, in, d_conv_out, dw, C, H, K, k, stride, stem);
+    } else conv_wgrad_t(t, L, G.compute, in, d_conv_out, dw);
+}
+/* the request for a fusing dgrad (L->fz): the reduction over x / mask / means of the BN' its output feeds; NULL where L does not fuse */
+static const mid_bn_bwd_parts *fz_request(const MiCtx *c, mid_bn_bwd_parts *r, const MiLayer *L, const void *x, const void *mask,
+                                          const float *means) {
+    if (!L->fz) return NULL;
+    r->x = x; r->mask = mask; r->means = means;
+    r->buf = c->bn_parts.buf; r->floats = c->bn_parts.floats; r->nparts = 0;
+    return r;
 }
 
 /* resnet.cu:1777-2248 */
@@ -1081,12 +1077,15 @@ void backwards_pass(Train_ResNet *t) {
     ck(mid_avgpool_bwd_t(G.compute, da->final_conv_output_pooled, da->activation_conv_blocks[nb - 1]->output_activated, c->dtype, N, D, Hl * Hl),
        "average pool backward");
     const int ring = c->overlap_wgrad == 2;
+    mid_bn_bwd_parts fz = {NULL}, req; /* BN'-partials hand-off from a fusing dgrad to the next unit (unit_bwd) */
     for (int i = nb - 1; i >= 0; i--) {
         const ConvBlock *b = p->conv_blocks[i];
         const ConvBlock *db = dp->conv_blocks[i];
+        MiBlockLayers *B = &c->blk[i];
         const Activation_ConvBlock *k = a->activation_conv_blocks[i];
+        const Activation_ConvBlock *kb = i == 0 ? NULL : a->activation_conv_blocks[i - 1]; /* the block below */
         Activation_ConvBlock *dk = da->activation_conv_blocks[i];
-        const float *bin = i == 0 ? a->init_convblock_input : a->activation_conv_blocks[i - 1]->output_activated;
+        const float *bin = i == 0 ? a->init_convblock_input : kb->output_activated;
         float *dbin = i == 0 ? da->init_convblock_input : da->activation_conv_blocks[i - 1]->output_activated;
         const int H = b->incoming_spatial_dim, Ho = H / b->stride;
         const float *up = dk->output_activated; /* dL/d(block output) */
@@ -1096,22 +1095,12 @@ void backwards_pass(Train_ResNet *t) {
             dk->output = ring_take(c, NULL);
             if (b->projection) dk->transformed_residual = ring_take(c, &s_proj);
         }
-        /* bf16 + FAST: a dgrad may do the reduction pass of the BN' its output feeds (and gate that output) */
-        /* (RECOMPUTE_BN: the gating tensors have just been re-derived when the dgrad runs.)  fp32 storage: not with the FULL policy
-         * (its derivative mirror keeps the ungated gradients the dump tree names) */
-        const int fz = c->fz_enable && (c->dtype == MID_BF16 || (c->fz_f32 && c->policy != MI_STORE_FULL));
-#define FZ_REQ(site_, x_, mask_, means_) do { if (fz && (c->dtype == MID_BF16 ? (c->fz_bf16 & (site_)) : (c->fz_f32 & (site_)))) { c->fz_req.x = (x_); c->fz_req.mask = (mask_); c->fz_req.means = (means_); \
-        c->fz_req.buf = c->bn_parts.buf; c->fz_req.floats = c->bn_parts.floats; c->fz_req.nparts = 0; c->fz_req_valid = 1; } } while (0)
-        const int up_gated = c->fz_ready; /* the block above's reduction dgrad already gated `up` by this block's output and summed for the expansion BN' */
+        const int up_gated = fz.nparts > 0; /* the block above's reduction dgrad already gated `up` by this block's output and summed for the expansion BN' */
         if (b->projection) {
             /* ReLU' of the block output (doActivationDeriv, :1934) is fused into the projection BN' as an external mask; that
              * pass also leaves relu'(out) * up in dk->output, which the expansion BN' then reads instead of up + mask */
-            if (c->par) set_cur_par(c, c->par[i].proj, c->par[i].proj_bytes, &c->par[i].proj_valid); else set_cur_par(c, NULL, 0, NULL);
-            c->cur_dye = c->par ? c->par[i].dye_proj : NULL;
-            c->cur_cl = c->par ? c->par[i].cl_proj : NULL;
-            unit_bwd(t, bin, b->projection, b->norm_projection, k->norm_post_projection, db->norm_projection,
-                     k->transformed_residual, up, k->output_activated, 3, dk->output, dk->transformed_residual, s_proj, dbin, NULL,
-                     db->projection, b->incoming_filters, H, b->expanded_depth, b->stride == 2 ? 3 : 1, b->stride, 0);
+            unit_bwd(t, &B->proj, bin, b->norm_projection, k->norm_post_projection, db->norm_projection, k->transformed_residual, up,
+                     k->output_activated, 3, dk->output, dk->transformed_residual, s_proj, dbin, NULL, db->projection, &fz, NULL);
             exp_dy = dk->output; exp_mask = NULL; exp_mode = 0;
             red_addend = dbin; /* reduce-conv dgrad accumulates onto the projection path (toAdd, :2157) */
         } else {
@@ -1123,45 +1112,33 @@ void backwards_pass(Train_ResNet *t) {
         if (ring) { dk->post_expanded = ring_take(c, &s_exp); dk->post_spatial_activated = ring_take(c, NULL); }
         if (recompute) /* the expansion's input, re-derived: relu(BN(post_spatial)) (resnet_clean.cu:2753) */
             ck(mid_bn_apply_t(G.compute, k->post_spatial, c->dtype, b->norm_spatial->gamma, b->norm_spatial->beta, NULL, k->norm_post_spatial->means,
-                              k->norm_post_spatial->vars, k->post_spatial_activated, c->dtype, N, b->reduced_depth, Ho * Ho, t->eps, 1), "BN recompute");
-        FZ_REQ(1, k->post_spatial, k->post_spatial_activated, k->norm_post_spatial->means); /* expansion dgrad -> spatial BN' */
-        unit_bwd(t, k->post_spatial_activated, b->depth_expansion, b->norm_expansion, k->norm_post_expanded,
-                 db->norm_expansion, k->post_expanded, exp_dy, exp_mask, exp_mode, dk->output, dk->post_expanded, s_exp,
-                 dk->post_spatial_activated, NULL, db->depth_expansion, b->reduced_depth, Ho, b->expanded_depth, 1, 1, 0);
+                              k->norm_post_spatial->vars, k->post_spatial_activated, c->dtype, N, b->reduced_depth, Ho * Ho, t->eps, 1, NULL, 0),
+               "BN recompute");
+        unit_bwd(t, &B->exp, k->post_spatial_activated, b->norm_expansion, k->norm_post_expanded, db->norm_expansion, k->post_expanded, exp_dy,
+                 exp_mask, exp_mode, dk->output, dk->post_expanded, s_exp, dk->post_spatial_activated, NULL, db->depth_expansion, &fz,
+                 fz_request(c, &req, &B->exp, k->post_spatial, k->post_spatial_activated, k->norm_post_spatial->means));
         /* the call resnet.cu:2060-2083 forgot; present in resnet_cudnn.cu:2365-2366 */
         if (ring) { dk->post_spatial = ring_take(c, &s_spa); dk->post_reduced_activated = ring_take(c, NULL); }
         if (recompute) /* the 3x3's input, re-derived: relu(BN(post_reduced)) (resnet_clean.cu:2714) */
             ck(mid_bn_apply_t(G.compute, k->post_reduced, c->dtype, b->norm_depth_reduction->gamma, b->norm_depth_reduction->beta, NULL,
                               k->norm_post_reduced->means, k->norm_post_reduced->vars, k->post_reduced_activated, c->dtype, N, b->reduced_depth,
-                              H * H, t->eps, 1), "BN recompute");
-        if (c->par) set_cur_par(c, c->par[i].spatial, c->par[i].spatial_bytes, &c->par[i].spatial_valid); else set_cur_par(c, NULL, 0, NULL);
-        c->cur_dye = c->par ? (b->stride == 2 ? c->par[i].dye_spatial : c->par[i].dy1) : NULL;
-        c->cur_cl = c->par ? (b->stride == 2 ? c->par[i].cl_spatial : c->par[i].cl_s1) : NULL;
-        FZ_REQ(2, k->post_reduced, k->post_reduced_activated, k->norm_post_reduced->means); /* spatial dgrad -> reduction BN' */
-        unit_bwd(t, k->post_reduced_activated, b->spatial, b->norm_spatial, k->norm_post_spatial, db->norm_spatial,
-                 k->post_spatial, dk->post_spatial_activated, NULL, 1, NULL, dk->post_spatial, s_spa, dk->post_reduced_activated, NULL,
-                 db->spatial, b->reduced_depth, H, b->reduced_depth, 3, b->stride, 0);
+                              H * H, t->eps, 1, NULL, 0), "BN recompute");
+        unit_bwd(t, &B->spa, k->post_reduced_activated, b->norm_spatial, k->norm_post_spatial, db->norm_spatial, k->post_spatial,
+                 dk->post_spatial_activated, NULL, 1, NULL, dk->post_spatial, s_spa, dk->post_reduced_activated, NULL, db->spatial, &fz,
+                 fz_request(c, &req, &B->spa, k->post_reduced, k->post_reduced_activated, k->norm_post_reduced->means));
         if (ring) dk->post_reduced = ring_take(c, &s_red);
-        if (i > 0 && !p->conv_blocks[i - 1]->projection) { /* reduction dgrad -> the expansion BN' of the identity block below */
-            const Activation_ConvBlock *kb = a->activation_conv_blocks[i - 1];
-            FZ_REQ(4, kb->post_expanded, kb->output_activated, kb->norm_post_expanded->means);
-        }
-        unit_bwd(t, bin, b->depth_reduction, b->norm_depth_reduction, k->norm_post_reduced, db->norm_depth_reduction,
-                 k->post_reduced, dk->post_reduced_activated, NULL, 1, NULL, dk->post_reduced, s_red, dbin, red_addend,
-                 db->depth_reduction, b->incoming_filters, H, b->reduced_depth, 1, 1, 0);
+        unit_bwd(t, &B->red, bin, b->norm_depth_reduction, k->norm_post_reduced, db->norm_depth_reduction, k->post_reduced,
+                 dk->post_reduced_activated, NULL, 1, NULL, dk->post_reduced, s_red, dbin, red_addend, db->depth_reduction, &fz,
+                 kb ? fz_request(c, &req, &B->red, kb->post_expanded, kb->output_activated, kb->norm_post_expanded->means) : NULL);
         mi_dp_reduce_ready(t, (size_t)(db->depth_reduction - c->g_arena), 0);
-#undef FZ_REQ
     }
-    c->fz_ready = 0; c->fz_req_valid = 0;
     const int Hs = d->input / d->init_conv_stride;
     int s_stem = -1;
     if (ring) { da->init_conv_activated = ring_take(c, NULL); da->init_conv_applied = ring_take(c, &s_stem); }
     ck(mid_maxpool_bwd_t(G.compute, a->max_inds, da->init_convblock_input, da->init_conv_activated, c->dtype, N, d->init_conv_filters, Hs,
                          d->init_maxpool_dim, d->init_maxpool_stride), "max-pool backward");
-    set_cur_par(c, NULL, 0, NULL); /* the stem strides too, but has its own padded planes (stem_xp) */
-    unit_bwd(t, t->cur_batch->images, p->init_conv_layer, p->norm_init_conv, a->norm_init_conv, dp->norm_init_conv,
-             a->init_conv_applied, da->init_conv_activated, NULL, 1, NULL, da->init_conv_applied, s_stem, NULL, NULL,
-             dp->init_conv_layer, 3, d->input, d->init_conv_filters, d->init_kernel_dim, d->init_conv_stride, 1);
+    unit_bwd(t, &c->stem, t->cur_batch->images, p->norm_init_conv, a->norm_init_conv, dp->norm_init_conv, a->init_conv_applied,
+             da->init_conv_activated, NULL, 1, NULL, da->init_conv_applied, s_stem, NULL, NULL, dp->init_conv_layer, &fz, NULL);
     mi_dp_reduce_ready(t, 0, 1);
     mid_event_record(c->ev_t[3], G.compute);
 }
@@ -1347,7 +1324,7 @@ void destroy_trainer(Train_ResNet *t) {
     mi_batch_ext_free(t->cur_batch);
     free(t->model->dims); free(t->model);
     free(t->loss_per_epoch); free(t->accuracy_per_epoch);
-    free(c->dump_root); free(c->par); free(c);
+    free(c->dump_root); free(c->blk); free(c);
     free(t);
 }
 
