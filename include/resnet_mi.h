@@ -324,6 +324,18 @@ int mi_debug_poison_lds(void);
  * slices per tail tile, [5] k-steps per slice, [6] wgrad splits, [7] workgroups per class or split, [8] k-steps */
 int mi_debug_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]);
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi);
+/* host-only (no GPU needed): the plan a convolution operator launches with, from the same planner functions the launchers call.
+ * dtype MI_DTYPE_F32 (route DEFAULT: the implicit GEMM of mi_op_conv_*) or MI_DTYPE_BF16 (DEFAULT: the NCHW kernels of mi_op_conv_*_bf16;
+ * CL: the channel-last 3x3 kernels of mi_op_conv_{fwd,dgrad,wgrad}_bf16_cl; CL2: mi_op_conv_wgrad_bf16_cl2; PW: mi_op_conv1x1_fwd_bf16_cl
+ * and the LDS-DMA 1x1 weight gradient).  op 0 fwd, 1 dgrad, 2 wgrad; fwd / dgrad without a fused BN' reduction.
+ * The plan is the one of a launch with the workspace the mi_op_* operators give it: the partial-tile buffer of the fp32 sliced tail
+ * round, and for a bf16 NCHW stride-2 input its parity planes.  A launch without them plans differently (fp32: every tile whole; bf16
+ * stride 2: element-wise staging, no padded columns), and so does an fp32 dgrad that fuses the BN' reduction (every tile whole).
+ * out[0] rows per tile, [1] columns per tile, [2] tiles (a stride-2 dgrad: per parity class or row parity), [3] first tile of the sliced
+ * tail round (= tiles: none), [4] reduction slices per tail tile, [5] weight-gradient splits launched (1: fwd / dgrad), [6] 1 = the split
+ * reduce runs grouped.  Returns 0, or -2 where the route refuses the shape (out all 0). */
+enum { MI_ROUTE_DEFAULT = 0, MI_ROUTE_CL = 1, MI_ROUTE_CL2 = 2, MI_ROUTE_PW = 3 };
+int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]);
 
 
 /* ---------------- bf16-activation path (BASELINE configs[4]) ----------------

@@ -98,6 +98,7 @@ MI_SRC_SHARDS, MI_SRC_BUFFER, MI_SRC_SYNTHETIC, MI_SRC_HOST = 0, 1, 2, 3
 MI_LAYOUT_NHWC, MI_LAYOUT_NCHW = 0, 1
 MI_DTYPE_F32, MI_DTYPE_BF16 = 0, 1
 MI_STORE_FAST, MI_STORE_RECOMPUTE_BN, MI_STORE_FULL = 0, 1, 2
+MI_ROUTE_DEFAULT, MI_ROUTE_CL, MI_ROUTE_CL2, MI_ROUTE_PW = 0, 1, 2, 3
 
 # every symbol include/resnet_mi.h declares: name -> (restype, argtypes)
 _i, _f, _vp, _sz, _u64, _cp = C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p
@@ -172,6 +173,7 @@ PROTOTYPES = {
     "mi_op_fill_uniform": (_i, [_vp, _sz, _u64, _f, _f]),
     "mi_debug_poison_lds": (_i, []),
     "mi_debug_conv_plan": (_i, [_i] * 7 + [_vp]),
+    "mi_conv_plan": (_i, [_i] * 9 + [_vp]),
     "mi_trainer_set_dtype": (_i, [_T, _i]),
     "mi_trainer_get_dtype": (_i, [_T]),
     "mi_trainer_set_store_policy": (_i, [_T, _i]),

@@ -967,17 +967,24 @@ pw_wgrad_kernel(const u16 *__restrict__ dY, const u16 *__restrict__ X, float *__
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-static int cl_launch(hipStream_t st, const u16 *A, const u16 *In, u16 *Out, ClArgs &g, int N, double flops, double bytes) {
+// output tiling of cl_conv_kernel (g.M rows, g.P pixels per image): 128 x 128 tiles where the rows allow, else 64 x 256; returns the
+// rows per tile, *bn = the columns
+static int cl_plan_tiles(ClArgs &g, int N, int *bn) {
     g.ncols = N * g.P;
+    const int bm = g.M % 128 == 0 ? 128 : 64;
+    *bn = 16384 / bm;
+    g.mtiles = g.M / bm; g.tiles = g.mtiles * mi_cdiv(g.ncols, *bn); g.fdM = make_fastdiv(g.mtiles);
+    return bm;
+}
+static int cl_launch(hipStream_t st, const u16 *A, const u16 *In, u16 *Out, ClArgs &g, int N, double flops, double bytes) {
+    int bn;
+    const int bm = cl_plan_tiles(g, N, &bn), wmv = bm / 64;
     g.fdP = make_fastdiv(g.P); g.fdGW = make_fastdiv(g.GW);
     g.vw = g.P % 8 == 0 ? 8 : g.P % 4 == 0 ? 4 : 1;
     static int force = -1;
     if (force < 0) { const char *e = getenv("RESNET_MI_CL_NBUF"); force = e ? atoi(e) : 0; }
     const int nbuf = force == 1 ? 1 : 2;
-    const int wmv = g.M % 128 == 0 ? 2 : 1;
-    const int bm = 64 * wmv, bn = 256 / wmv;
     const int ctl = mi_cdiv(g.ncols, bn);
-    g.mtiles = g.M / bm; g.tiles = g.mtiles * ctl; g.fdM = make_fastdiv(g.mtiles);
     if (g.bn_part) g.bn_np = ctl * (bn / 64);
     size_t lds = (size_t)nbuf * (bm * 128 + bn * 128);
     const size_t img = (size_t)4 * 64 * 144;       // the epilogue's four wave images (fp32 form: 4 x 32 x 272, smaller)
@@ -1064,14 +1071,18 @@ int mid_cl_dgrad2_supported(int N, int C, int H, int K) {
 }
 /* dx (bf16 NCHW, C channels, H x H) = the 3x3 stride-2 dgrad of dyp (mid_cl_relayout_end of dY, K channels, H/2 x H/2) with
  * a_tiles = the dgrad k-step tiles [t][k/64][C][64].  Every element of dx is written (no addend). */
-int mid_cl_dgrad2(mid_stream s, const void *dyp, const void *a_tiles, void *dx, int N, int C, int H, int K) {
-    hipStream_t st = (hipStream_t)s;
-    if (!mid_cl_dgrad2_supported(N, C, H, K)) { mi_record_error("mid_cl_dgrad2", "shape not covered"); return -2; }
-    ClD2Args g = {};
+// geometry and tiling of cl_dgrad2_kernel: 128 x 128 tiles of dx per row parity (grid.y = 2)
+static void cl_dgrad2_plan(ClD2Args &g, int N, int C, int H, int K) {
     g.K = K; g.C = C; g.Ho = H / 2; g.Wo = H / 2; g.P = g.Ho * g.Wo; g.ncols = N * g.P; g.Wp = g.Wo + 1;
     g.fdP = make_fastdiv(g.P); g.fdWo = make_fastdiv(g.Wo);
     g.cpx = g.Wo % 4 == 0 ? 4 : g.Wo % 2 == 0 ? 2 : 1;
     g.mtiles = C / 128; g.tiles = g.mtiles * mi_cdiv(g.ncols, 128); g.fdM = make_fastdiv(g.mtiles);
+}
+int mid_cl_dgrad2(mid_stream s, const void *dyp, const void *a_tiles, void *dx, int N, int C, int H, int K) {
+    hipStream_t st = (hipStream_t)s;
+    if (!mid_cl_dgrad2_supported(N, C, H, K)) { mi_record_error("mid_cl_dgrad2", "shape not covered"); return -2; }
+    ClD2Args g = {};
+    cl_dgrad2_plan(g, N, C, H, K);
     static int attr_set = 0;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void *)cl_dgrad2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess) { mi_record_error("cl_dgrad2_kernel", "cannot raise the dynamic LDS limit"); return -1; }
@@ -1094,6 +1105,14 @@ static int cl_wgrad_splits(int N, int C, int K, int P) {
         if (eff > best_eff + 0.02) { best_eff = eff; best = sp; }
     }
     return best;
+}
+// reduction split of cl_wgrad_kernel (g.P set): tiles of CLW_KPX pixels per image, `splits` asked for, the number launched returned
+static int cl_wgrad_plan(ClWgArgs &g, int N, int C, int K, int *splits) {
+    g.ptiles = (g.P + CLW_KPX - 1) / CLW_KPX; g.rtiles = N * g.ptiles;
+    *splits = cl_wgrad_splits(N, C, K, g.P);
+    g.rlen = mi_cdiv(g.rtiles, *splits);
+    g.ctiles = C / 128; g.mtiles = K / 128;
+    return mi_cdiv(g.rtiles, g.rlen);
 }
 /* weight gradient on the channel-last input: 3x3, stride 1 or 2; C % 128, K % 128, output planes a multiple of 4 pixels */
 int mid_cl_wgrad_supported(int N, int C, int H, int K, int stride) {
@@ -1123,12 +1142,9 @@ int mid_cl_wgrad(mid_stream s, const void *xp, const void *dy, float *dw, float 
         g.img_rows = H + 2; g.Wp = H + 2;
         for (int t = 0; t < 9; t++) g.tap_delta[t] = (uint32_t)(((t / 3) * g.Wp + (t % 3)) * C) * 2u;
     }
-    g.ptiles = (g.P + CLW_KPX - 1) / CLW_KPX; g.rtiles = N * g.ptiles;
-    const int splits = cl_wgrad_splits(N, C, K, g.P);
+    int splits;
+    const int used = cl_wgrad_plan(g, N, C, K, &splits);
     if (part_floats < (size_t)splits * 9 * K * C) { mi_record_error("mid_cl_wgrad", "workspace too small"); return -3; }
-    g.rlen = mi_cdiv(g.rtiles, splits);
-    const int used = mi_cdiv(g.rtiles, g.rlen);
-    g.ctiles = C / 128; g.mtiles = K / 128;
     g.fdGW = make_fastdiv(g.GW); g.fdPt = make_fastdiv(g.ptiles); g.fdM = make_fastdiv(g.mtiles); g.fdT = make_fastdiv(g.mtiles * g.ctiles * 9); g.fd9 = make_fastdiv(9);
     g.tiles = (uint32_t)(g.mtiles * g.ctiles * 9); g.total8 = (uint32_t)(g.mtiles * g.ctiles * 9 * used) & ~7u;
     g.a_bytes = (uint32_t)((size_t)N * K * g.P * 2); g.b_bytes = (uint32_t)mid_cl_operand_bytes(0, N, C, H, K, stride);
@@ -1156,6 +1172,14 @@ static int cl_wgrad2_splits(int N, int C, int K, int P) {
         if (eff > best_eff + 0.02) { best_eff = eff; best = sp; }
     }
     return best;
+}
+// reduction split of cl_wgrad2_kernel (g.R, g.GH, g.GW set): one flat list of 64-pixel tiles; the number of splits launched returned
+static int cl_wgrad2_plan(ClWg2Args &g, int N, int C, int K, int *splits) {
+    g.rtiles = mi_cdiv(g.R, 64);
+    *splits = cl_wgrad2_splits(N, C, K, g.GH * g.GW);
+    g.rlen = mi_cdiv(g.rtiles, *splits);
+    g.ctiles = C / 128; g.mtiles = K / 128;
+    return mi_cdiv(g.rtiles, g.rlen);
 }
 /* weight gradient of a 3x3 layer from the channel-last planes of BOTH operands.  stride 2: xp = mid_cl_relayout(parity) of the input,
  * dyp = mid_cl_relayout_end of dY (what mid_cl_dgrad2 reads); stride 1: xp = the input with a halo of 1, dyp = dY with a halo of 1 (what
@@ -1187,12 +1211,9 @@ int mid_cl_wgrad2(mid_stream s, const void *xp, const void *dyp, float *dw, floa
         for (int t = 0; t < 9; t++) g.tap_delta[t] = (uint32_t)(((t / 3) * Hp + (t % 3)) * C) * 2u;
         g.a_rowb = (uint32_t)Hp * K * 2u; g.a_imgb = (uint32_t)Hp * g.a_rowb; g.a_off = g.a_rowb + (uint32_t)K * 2u;
     }
-    g.rtiles = mi_cdiv(g.R, 64);
-    const int splits = cl_wgrad2_splits(N, C, K, g.GH * g.GW);
+    int splits;
+    const int used = cl_wgrad2_plan(g, N, C, K, &splits);
     if (part_floats < (size_t)splits * 9 * K * C) { mi_record_error("mid_cl_wgrad2", "workspace too small"); return -3; }
-    g.rlen = mi_cdiv(g.rtiles, splits);
-    const int used = mi_cdiv(g.rtiles, g.rlen);
-    g.ctiles = C / 128; g.mtiles = K / 128;
     g.fdGW = make_fastdiv(g.GW); g.fdP = make_fastdiv(g.GH * g.GW); g.fdM = make_fastdiv(g.mtiles); g.fdT = make_fastdiv(g.mtiles * g.ctiles * 9); g.fd9 = make_fastdiv(9);
     g.tiles = (uint32_t)(g.mtiles * g.ctiles * 9); g.total8 = (uint32_t)(g.mtiles * g.ctiles * 9 * used) & ~7u;
     g.a_bytes = (uint32_t)((size_t)N * g.a_imgb); g.b_bytes = (uint32_t)mid_cl_operand_bytes(0, N, C, H, K, stride);
@@ -1221,6 +1242,14 @@ static int pw_wgrad_splits(int N, int C, int K, int P) {
     }
     return best;
 }
+// reduction split of pw_wgrad_kernel (g.P set): 64-pixel tiles per image; the number of splits launched returned
+static int pw_wgrad_plan(PwWgArgs &g, int N, int C, int K, int *splits) {
+    g.ptiles = (g.P + 63) / 64; g.rtiles = N * g.ptiles;
+    *splits = pw_wgrad_splits(N, C, K, g.P);
+    g.rlen = mi_cdiv(g.rtiles, *splits);
+    g.mtiles = K / 128;
+    return mi_cdiv(g.rtiles, g.rlen);
+}
 /* weight gradient of a 1x1 stride-1 convolution from the NCHW bf16 tensors: C % 128, K % 128, planes a multiple of 4 pixels */
 int mid_pw_wgrad_supported(int N, int C, int H, int K) {
     const long P = (long)H * H;
@@ -1235,12 +1264,9 @@ int mid_pw_wgrad(mid_stream s, const void *x, const void *dy, float *dw, float *
     if (!mid_pw_wgrad_supported(N, C, H, K)) { mi_record_error("mid_pw_wgrad", "shape not covered"); return -2; }
     PwWgArgs g = {};
     g.K = K; g.C = C; g.P = H * H;
-    g.ptiles = (g.P + 63) / 64; g.rtiles = N * g.ptiles;
-    const int splits = pw_wgrad_splits(N, C, K, g.P);
+    int splits;
+    const int used = pw_wgrad_plan(g, N, C, K, &splits);
     if (part_floats < (size_t)splits * K * C) { mi_record_error("mid_pw_wgrad", "workspace too small"); return -3; }
-    g.rlen = mi_cdiv(g.rtiles, splits);
-    const int used = mi_cdiv(g.rtiles, g.rlen);
-    g.mtiles = K / 128;
     const int tiles = g.mtiles * (C / 128);
     g.fdPt = make_fastdiv(g.ptiles); g.fdM = make_fastdiv(g.mtiles); g.fdT = make_fastdiv(tiles);
     g.tiles = (uint32_t)tiles; g.total8 = (uint32_t)(tiles * used) & ~7u;
@@ -1323,5 +1349,68 @@ int mid_cl_dgrad(mid_stream s, const void *dyp, const void *a_tiles, void *dx, c
     g.addend = (const u16 *)addend;
     return cl_launch((hipStream_t)s, (const u16 *)a_tiles, (const u16 *)dyp, (u16 *)dx, g, N, 2.0 * 9 * (double)N * g.P * C * K,
                      2.0 * ((double)N * K * g.P + (double)N * C * g.P * (addend ? 2 : 1)) + 4.0 * 9 * C * K);
+}
+/* mi_conv_plan for the channel-last / LDS-DMA kernels (resnet_mi.h): route 1 = channel-last 3x3 (forward, stride-1 dgrad, stride-2 dgrad
+ * on the dY planes, weight gradient from the channel-last input), 2 = the 3x3 weight gradient from both operands channel-last, 3 = the
+ * 1x1 kernels (forward on a dense channel-last input, LDS-DMA weight gradient).  0 where the kernel refuses the shape */
+int mid_cl_conv_plan(int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]) {
+    const int Ho = H / stride;
+    out[1] = 128; out[4] = 1; out[5] = 1; out[6] = 0;
+    if (route == 3 && k == 1 && stride == 1 && op == 0 && mid_cl_pw_supported(N, C, H, K)) {
+        ClArgs g = {};
+        g.M = K; g.P = H * H;
+        out[0] = cl_plan_tiles(g, N, &out[1]);
+        out[2] = out[3] = (int)g.tiles;
+        return 1;
+    }
+    if (route == 3 && k == 1 && stride == 1 && op == 2 && mid_pw_wgrad_supported(N, C, H, K)) {
+        PwWgArgs g = {};
+        g.P = H * H;
+        int splits;
+        out[5] = pw_wgrad_plan(g, N, C, K, &splits);
+        out[0] = 128; out[2] = out[3] = (int)g.mtiles * (C / 128);
+        out[6] = mid_wgrad_reduce_grouped(K, C, out[5]);
+        return 1;
+    }
+    if (route == 2 && k == 3 && op == 2 && mid_cl_wgrad2_supported(N, C, H, K, stride)) {
+        ClWg2Args g = {};
+        g.GH = g.GW = Ho; g.R = N * Ho * Ho;
+        int splits;
+        out[5] = cl_wgrad2_plan(g, N, C, K, &splits);
+        out[0] = 128; out[2] = out[3] = (int)(g.mtiles * g.ctiles * 9);
+        out[6] = mid_wgrad_reduce_grouped(K, C, out[5]);
+        return 1;
+    }
+    if (route != 1 || k != 3) return 0;
+    if (op == 0 && mid_cl_supported(0, N, C, H, K, stride)) {
+        ClArgs g = {};
+        g.M = K; g.P = Ho * Ho;
+        out[0] = cl_plan_tiles(g, N, &out[1]);
+        out[2] = out[3] = (int)g.tiles;
+        return 1;
+    }
+    if (op == 1 && stride == 1 && mid_cl_supported(1, N, C, H, K, 1)) {
+        ClArgs g = {};
+        g.M = C; g.P = H * H;
+        out[0] = cl_plan_tiles(g, N, &out[1]);
+        out[2] = out[3] = (int)g.tiles;
+        return 1;
+    }
+    if (op == 1 && stride == 2 && mid_cl_dgrad2_supported(N, C, H, K)) {
+        ClD2Args g = {};
+        cl_dgrad2_plan(g, N, C, H, K);
+        out[0] = 128; out[2] = out[3] = (int)g.tiles; // per row parity
+        return 1;
+    }
+    if (op == 2 && mid_cl_wgrad_supported(N, C, H, K, stride)) {
+        ClWgArgs g = {};
+        g.P = Ho * Ho;
+        int splits;
+        out[5] = cl_wgrad_plan(g, N, C, K, &splits);
+        out[0] = 128; out[2] = out[3] = (int)(g.mtiles * g.ctiles * 9);
+        out[6] = mid_wgrad_reduce_grouped(K, C, out[5]);
+        return 1;
+    }
+    return 0;
 }
 }

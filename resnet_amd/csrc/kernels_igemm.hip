@@ -851,11 +851,14 @@ igemm_wgrad_reduce_g_kernel(const float *__restrict__ part, float *__restrict__ 
         }
     }
 }
-static void igemm_wgrad_reduce_launch(hipStream_t st, const float *part, float *dw, long KC, int k, int splits) {
-    // groups of splits per output when one thread per output would leave most CUs without a workgroup
+// groups of splits per output when one thread per output would leave most CUs without a workgroup
+static bool igemm_wgrad_reduce_grouped(long KC, int splits) {
     static int on = -1;
     if (on < 0) { const char *e = getenv("RESNET_MI_WGRAD_REDUCE_G"); on = e ? atoi(e) : 1; }
-    const bool grouped = on && splits >= 16 && mi_cdiv(KC, 256) < 1024;
+    return on && splits >= 16 && mi_cdiv(KC, 256) < 1024;
+}
+static void igemm_wgrad_reduce_launch(hipStream_t st, const float *part, float *dw, long KC, int k, int splits) {
+    const bool grouped = igemm_wgrad_reduce_grouped(KC, splits);
     if (k == 1) {
         if (grouped) hipLaunchKernelGGL((igemm_wgrad_reduce_g_kernel<1, 8>), dim3(mi_cdiv(KC, 32)), dim3(256), 0, st, part, dw, KC, splits);
         else hipLaunchKernelGGL(igemm_wgrad_reduce_kernel<1>, dim3(mi_cdiv(KC, 256)), dim3(256), 0, st, part, dw, KC, splits);
@@ -1006,6 +1009,45 @@ static void igemm_geometry(IgArgs &g, int N, int C, int H, int K, int stride) {
     g.ncols = N * g.P;
     g.fdP = make_fastdiv(g.P); g.fdWo = make_fastdiv(g.Wo);
 }
+// geometry and output tiling of a forward (op IGOP_FWD: rows = K, reduction over C) or dgrad (rows = C, reduction over K); returns the
+// rows per tile.  The sliced tail round (igemm_tail_plan) is planned on top of it by the caller.
+static int igemm_plan_tiles(IgArgs &g, int op, int N, int C, int H, int K, int k, int stride) {
+    igemm_geometry(g, N, C, H, K, stride);
+    const int M = op == IGOP_FWD ? K : C, red = op == IGOP_FWD ? C : K;
+    const int bm = (op == IGOP_FWD || stride == 1) ? igemm_pick_bm(M, mi_cdiv(g.ncols, 128), k * k * (red / IG_BK), k) : (M % 128 == 0 ? 128 : 64);
+    g.mtiles = M / bm;
+    g.tiles = g.mtiles * mi_cdiv(g.ncols, 128);
+    g.fdM = make_fastdiv(g.mtiles);
+    g.cpt = red / IG_BK; g.fdCpt = make_fastdiv(g.cpt);
+    return bm;
+}
+// geometry, tiling and reduction split of a weight gradient (swapped: the 1x1 transposed product); returns the rows per tile, *used =
+// the splits launched (grid.y)
+static int igemm_plan_wgrad(IgArgs &g, int N, int C, int H, int K, int k, int stride, bool swapped, int *used) {
+    int bm;
+    if (swapped) {
+        const int splits = igemm_wgrad_splits(N, K, H, C, 1, 1);
+        igemm_geometry(g, N, /*columns:*/ K, H, /*rows:*/ C, 1);
+        bm = C % 128 == 0 ? 128 : 64;
+        g.mtiles = C / bm;
+        g.ctiles = K / 128;
+        g.tiles = g.mtiles * g.ctiles;
+        g.klen = mi_cdiv(mi_cdiv(N * g.P, splits), IG_BK) * IG_BK;
+    } else {
+        const int T = k * k;
+        const int splits = igemm_wgrad_splits(N, C, H, K, k, stride);
+        igemm_geometry(g, N, C, H, K, stride);
+        bm = K % 128 == 0 ? 128 : 64;
+        g.mtiles = K / bm;
+        g.ctiles = C / 128;
+        g.tiles = C == 64 ? g.mtiles * ((T + 1) / 2) : g.mtiles * T * g.ctiles; // C == 64: two taps per column tile
+        g.klen = mi_cdiv(mi_cdiv(N * g.P, splits), IG_BK) * IG_BK;
+    }
+    g.fdM = make_fastdiv(g.mtiles);
+    g.full = g.tiles; g.tsplit = 1; g.fdTs = make_fastdiv(1); g.cpt = 1; g.fdCpt = make_fastdiv(1);
+    *used = mi_cdiv(N * g.P, g.klen);
+    return bm;
+}
 template <int MODE, int KS, int S, int WMW, bool VB = false>
 static int igemm_launch_t(hipStream_t st, dim3 grid, const float *A, const float *B, float *out, const float *addend, const IgArgs &g) {
     constexpr int BM = 64 * WMW;
@@ -1055,12 +1097,7 @@ int mi_igemm_fwd(hipStream_t st, mid_workspace *ws, const float *x, const float 
         A = ws->wt;
     }
     IgArgs g = {};
-    igemm_geometry(g, N, C, H, K, stride);
-    const int bm = igemm_pick_bm(K, mi_cdiv(g.ncols, 128), T * (C / IG_BK), k);
-    g.mtiles = K / bm;
-    g.tiles = g.mtiles * mi_cdiv(g.ncols, 128);
-    g.fdM = make_fastdiv(g.mtiles);
-    g.cpt = C / IG_BK; g.fdCpt = make_fastdiv(g.cpt);
+    const int bm = igemm_plan_tiles(g, IGOP_FWD, N, C, H, K, k, stride);
     igemm_tail_plan(g, T * g.cpt, ws->wt_floats >= (size_t)T * C * K + IG_TAIL_FLOATS ? ws->wt + (size_t)T * C * K : nullptr, bm);
     if (parts) {
         parts->nparts = 0;
@@ -1097,12 +1134,7 @@ int mi_igemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const floa
         }
     }
     IgArgs g = {};
-    igemm_geometry(g, N, C, H, K, stride);
-    const int bm = stride == 1 ? igemm_pick_bm(C, mi_cdiv(g.ncols, 128), T * (K / IG_BK), k) : (C % 128 == 0 ? 128 : 64);
-    g.mtiles = C / bm;
-    g.tiles = g.mtiles * mi_cdiv(g.ncols, 128);
-    g.fdM = make_fastdiv(g.mtiles);
-    g.cpt = K / IG_BK; g.fdCpt = make_fastdiv(g.cpt);
+    const int bm = igemm_plan_tiles(g, IGOP_DGRAD, N, C, H, K, k, stride);
     bool fused = false;
     if (fz && fz->buf && stride == 1) {
         const int np = mi_cdiv(g.ncols, 128) * (bm == 128 ? 2 : 4);
@@ -1134,16 +1166,9 @@ int mi_igemm_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const floa
         const int splits = igemm_wgrad_splits(N, K, H, C, 1, 1);
         if (!ws || ws->part_floats < (size_t)splits * K * C) { mi_record_error("mi_igemm_wgrad", "workspace too small"); return -3; }
         IgArgs g = {};
-        igemm_geometry(g, N, /*columns:*/ K, H, /*rows:*/ C, 1);
-        const int bm = C % 128 == 0 ? 128 : 64;
-        g.mtiles = C / bm;
-        g.ctiles = K / 128;
-        g.tiles = g.mtiles * g.ctiles;
-        g.fdM = make_fastdiv(g.mtiles);
+        int used;
+        const int bm = igemm_plan_wgrad(g, N, C, H, K, k, stride, true, &used);
         const int kd = N * g.P;
-        g.full = g.tiles; g.tsplit = 1; g.fdTs = make_fastdiv(1); g.cpt = 1; g.fdCpt = make_fastdiv(1);
-        g.klen = mi_cdiv(mi_cdiv(kd, splits), IG_BK) * IG_BK;
-        const int used = mi_cdiv(kd, g.klen);
         mi_prof_begin(st, igemm_fam(1), 2.0 * (double)kd * C * K, 4.0 * ((double)N * C * g.HW + (double)kd * K + (double)C * K));
         const int rc = igemm_launch<IG_WGRAD>(st, dim3(g.tiles, used), /*rows from*/ x, /*columns from*/ dy, ws->part, nullptr, g, 1, 1, bm);
         mi_prof_end(st);
@@ -1157,16 +1182,9 @@ int mi_igemm_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const floa
     const int splits = igemm_wgrad_splits(N, C, H, K, k, stride);
     if (!ws || ws->part_floats < (size_t)splits * T * K * C) { mi_record_error("mi_igemm_wgrad", "workspace too small"); return -3; }
     IgArgs g = {};
-    igemm_geometry(g, N, C, H, K, stride);
-    const int bm = K % 128 == 0 ? 128 : 64;
-    g.mtiles = K / bm;
-    g.ctiles = C / 128;
-    g.tiles = C == 64 ? g.mtiles * ((T + 1) / 2) : g.mtiles * T * g.ctiles; // C == 64: two taps per column tile
-    g.fdM = make_fastdiv(g.mtiles);
+    int used;
+    const int bm = igemm_plan_wgrad(g, N, C, H, K, k, stride, false, &used);
     const int kd = N * g.P;
-    g.full = g.tiles; g.tsplit = 1; g.fdTs = make_fastdiv(1); g.cpt = 1; g.fdCpt = make_fastdiv(1);
-    g.klen = mi_cdiv(mi_cdiv(kd, splits), IG_BK) * IG_BK;
-    const int used = mi_cdiv(kd, g.klen);
     mi_prof_begin(st, igemm_fam(k), 2.0 * T * (double)kd * C * K,
                   4.0 * ((double)N * C * g.HW + (double)kd * K + (double)T * C * K));
     const int rc = igemm_launch<IG_WGRAD>(st, dim3(g.tiles, used), dy, x, ws->part, nullptr, g, k, stride, bm);
@@ -1200,29 +1218,29 @@ extern "C" int mid_igemm_plan(int op, int N, int C, int H, int K, int k, int str
     for (int i = 0; i < 9; i++) out[i] = 0;
     if (!mi_igemm_supported(op, N, C, H, K, k, stride)) return 0;
     out[0] = 1;
-    const int T = k * k;
     IgArgs g = {};
     if (op == IGOP_WGRAD) {
-        const bool sw = igemm_wgrad_swapped(C, K, k);
-        const int rows = sw ? C : K, cols = sw ? K : C;
-        igemm_geometry(g, N, cols, H, rows, stride);
-        const int bm = rows % 128 == 0 ? 128 : 64;
-        const int splits = sw ? igemm_wgrad_splits(N, K, H, C, 1, 1) : igemm_wgrad_splits(N, C, H, K, k, stride);
-        const int tiles = sw ? (rows / bm) * (cols / 128) : (C == 64 && k == 3 ? (rows / bm) * ((T + 1) / 2) : (rows / bm) * T * (C / 128));
-        const int kd = N * g.P, klen = mi_cdiv(mi_cdiv(kd, splits), IG_BK) * IG_BK;
-        out[1] = bm; out[2] = tiles; out[3] = tiles; out[4] = 1; out[5] = klen / IG_BK; out[6] = mi_cdiv(kd, klen); out[7] = tiles; out[8] = mi_cdiv(kd, IG_BK);
+        int used;
+        out[1] = igemm_plan_wgrad(g, N, C, H, K, k, stride, igemm_wgrad_swapped(C, K, k), &used);
+        out[2] = g.tiles; out[3] = g.tiles; out[4] = 1; out[5] = g.klen / IG_BK; out[6] = used; out[7] = g.tiles; out[8] = mi_cdiv(N * g.P, IG_BK);
         return 1;
     }
-    igemm_geometry(g, N, C, H, K, stride);
-    const int M = op == IGOP_FWD ? K : C, red = op == IGOP_FWD ? C : K;
-    const int ksteps = T * (red / IG_BK);
-    const int bm = (op == IGOP_FWD || stride == 1) ? igemm_pick_bm(M, mi_cdiv(g.ncols, 128), ksteps, k) : (M % 128 == 0 ? 128 : 64);
-    g.mtiles = M / bm;
-    g.tiles = g.mtiles * mi_cdiv(g.ncols, 128);
-    float dummy;
-    igemm_tail_plan(g, ksteps, (op == IGOP_FWD || stride == 1) ? &dummy : nullptr, bm);
+    const int bm = igemm_plan_tiles(g, op, N, C, H, K, k, stride);
+    float dummy; // the operator's workspace always holds the partial-tile buffer; stride-2 dgrads are never sliced
+    igemm_tail_plan(g, k * k * g.cpt, (op == IGOP_FWD || stride == 1) ? &dummy : nullptr, bm);
     out[1] = bm; out[2] = g.tiles; out[3] = g.full; out[4] = g.tsplit; out[5] = g.tklen; out[6] = 1;
-    out[7] = g.full + (g.tiles - g.full) * g.tsplit; out[8] = ksteps;
+    out[7] = g.full + (g.tiles - g.full) * g.tsplit; out[8] = k * k * g.cpt;
+    return 1;
+}
+// whether the second stage of a weight gradient with `splits` partial planes of K x C runs grouped (igemm_wgrad_reduce_launch)
+extern "C" int mid_wgrad_reduce_grouped(int K, int C, int splits) { return igemm_wgrad_reduce_grouped((long)K * C, splits) ? 1 : 0; }
+// The plan mi_conv_plan reports for the fp32 route (see resnet_mi.h): out[0] rows per tile, [1] columns per tile, [2] tiles, [3] first
+// sliced tile, [4] slices per tail tile, [5] wgrad splits launched, [6] grouped split reduce.  0 where the route refuses the shape.
+extern "C" int mid_igemm_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[7]) {
+    int o[9];
+    if (!mid_igemm_plan(op, N, C, H, K, k, stride, o)) return 0;
+    out[0] = o[1]; out[1] = 128; out[2] = o[2]; out[3] = o[3]; out[4] = o[4]; out[5] = o[6];
+    out[6] = op == IGOP_WGRAD && !igemm_wgrad_swapped(C, K, k) ? mid_wgrad_reduce_grouped(K, C, o[6]) : 0; // (the transposed 1x1 form has a reduce of its own)
     return 1;
 }
 

@@ -1190,6 +1190,17 @@ static int bgemm_pick_bm(int M, long coltiles) {
     return (long)(M / 128) * coltiles < 256 ? 64 : 128;
 }
 static int bgemm_vw(int P) { return P % 8 == 0 ? 8 : P % 4 == 0 ? 4 : 1; }
+// output tiling of a forward (M = K) or dgrad (M = C) once the staging width svw is known (8: the column space padded to groups of 8
+// pixels per image); returns the rows per tile
+static int bgemm_plan_tiles(BgArgs &g, int M, int svw) {
+    if (svw == 8) { g.Pc = (g.P + 7) / 8 * 8; g.ncols = g.N * g.Pc; g.fdPc = make_fastdiv(g.Pc); }
+    const int ctl = mi_cdiv(g.ncols, 128);
+    const int bm = bgemm_pick_bm(M, ctl);
+    g.mtiles = M / bm;
+    g.tiles = g.mtiles * ctl;
+    g.fdM = make_fastdiv(g.mtiles);
+    return bm;
+}
 
 static int bg_prelayout_one(hipStream_t st, const float *w, u16 *fw, u16 *dg, int K, int C, int k) {
     if (k == 1) hipLaunchKernelGGL(bg_wt_kernel<1>, dim3(C / 32, K / 32), dim3(256), 0, st, w, fw, dg, K, C);
@@ -1218,12 +1229,8 @@ int mi_bgemm_fwd(hipStream_t st, mid_workspace *ws, const u16 *x, const float *w
             ws->s2d_valid = 1;
         } else svw = 1;
     }
-    if (svw == 8) { g.Pc = (g.P + 7) / 8 * 8; g.ncols = N * g.Pc; g.fdPc = make_fastdiv(g.Pc); }
+    const int bm = bgemm_plan_tiles(g, K, svw);
     const int ctl = mi_cdiv(g.ncols, 128);
-    const int bm = bgemm_pick_bm(K, ctl);
-    g.mtiles = K / bm;
-    g.tiles = g.mtiles * ctl;
-    g.fdM = make_fastdiv(g.mtiles);
     g.vw = bgemm_vw(g.P);
     if (parts) {
         parts->nparts = 0;
@@ -1253,12 +1260,8 @@ int mi_bgemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const u16 
     BgArgs g = {};
     bgemm_geometry(g, N, C, H, K, stride);
     const int svw = bgemm_stage_vw(BGOP_DGRAD, g.P, g.Wo, stride);
-    if (svw == 8) { g.Pc = (g.P + 7) / 8 * 8; g.ncols = N * g.Pc; g.fdPc = make_fastdiv(g.Pc); }
+    const int bm = bgemm_plan_tiles(g, C, svw);
     const int ctl = mi_cdiv(g.ncols, 128);
-    const int bm = bgemm_pick_bm(C, ctl);
-    g.mtiles = C / bm;
-    g.tiles = g.mtiles * ctl;
-    g.fdM = make_fastdiv(g.mtiles);
     g.vw = bgemm_vw(g.HW);
     if (fz && fz->buf && stride == 1 && svw == 8 && g.vw > 1 && bgemm_swp_enabled()) {
         const int np = ctl * (bm == 128 ? 2 : 4);
@@ -1302,20 +1305,15 @@ static int bgemm_wgrad_splits_p(long kd, int C, int K, int k) {
     }
     return best;
 }
-int mi_bgemm_wgrad(hipStream_t st, mid_workspace *ws, const u16 *x, const u16 *dy, float *dw, int N, int C, int H, int K, int k, int stride) {
+// geometry, tiling and reduction split of a weight gradient (parity_ok: x may be read as parity planes); returns the rows per tile,
+// *vw = pixels per staged load, *splits = what the split heuristic asked for, *used = the splits launched (grid.y)
+static int bgemm_plan_wgrad(BgArgs &g, int N, int C, int H, int K, int k, int stride, bool parity_ok, int *vw, int *splits, int *used) {
     const int T = k * k;
-    BgArgs g = {};
     bgemm_geometry(g, N, C, H, K, stride);
-    const bool parity_ok = stride == 2 && ws && ws->s2d && ws->s2d_bytes >= (size_t)N * C * g.HW * 2;
-    const int vw = bgemm_wgrad_vw(g.Wo, stride, parity_ok);
-    if (vw > 1) { g.Pc = (g.P + vw - 1) / vw * vw; g.fdPc = make_fastdiv(g.Pc); }
+    *vw = bgemm_wgrad_vw(g.Wo, stride, parity_ok);
+    if (*vw > 1) { g.Pc = (g.P + *vw - 1) / *vw * *vw; g.fdPc = make_fastdiv(g.Pc); }
     const long kd = (long)N * g.Pc;
-    const int splits = bgemm_wgrad_splits_p(kd, C, K, k);
-    if (!ws || ws->part_floats < (size_t)splits * T * K * C) { mi_record_error("mi_bgemm_wgrad", "workspace too small"); return -3; }
-    if (stride == 2 && vw > 1) { // x as parity planes: every tap becomes a unit-stride read
-        if (!ws->s2d_valid && bg_s2d(st, x, (u16 *)ws->s2d, (long)N * C, H, H)) return -1;
-        x = (const u16 *)ws->s2d;
-    }
+    *splits = bgemm_wgrad_splits_p(kd, C, K, k);
     const int bm = K % 128 == 0 ? 128 : 64;
     g.mtiles = K / bm;
     g.cb64 = C / 64;
@@ -1323,8 +1321,21 @@ int mi_bgemm_wgrad(hipStream_t st, mid_workspace *ws, const u16 *x, const u16 *d
     g.fdCb = make_fastdiv(g.cb64);
     g.tiles = g.mtiles * ((g.nhalf + 1) / 2);
     g.fdM = make_fastdiv(g.mtiles);
-    g.klen = mi_cdiv(mi_cdiv(kd, splits), BG_BK) * BG_BK;
-    const int used = mi_cdiv(kd, g.klen);
+    g.klen = mi_cdiv(mi_cdiv(kd, *splits), BG_BK) * BG_BK;
+    *used = mi_cdiv(kd, g.klen);
+    return bm;
+}
+int mi_bgemm_wgrad(hipStream_t st, mid_workspace *ws, const u16 *x, const u16 *dy, float *dw, int N, int C, int H, int K, int k, int stride) {
+    const int T = k * k;
+    BgArgs g = {};
+    const bool parity_ok = stride == 2 && ws && ws->s2d && ws->s2d_bytes >= (size_t)N * C * H * H * 2;
+    int vw, splits, used;
+    const int bm = bgemm_plan_wgrad(g, N, C, H, K, k, stride, parity_ok, &vw, &splits, &used);
+    if (!ws || ws->part_floats < (size_t)splits * T * K * C) { mi_record_error("mi_bgemm_wgrad", "workspace too small"); return -3; }
+    if (stride == 2 && vw > 1) { // x as parity planes: every tap becomes a unit-stride read
+        if (!ws->s2d_valid && bg_s2d(st, x, (u16 *)ws->s2d, (long)N * C, H, H)) return -1;
+        x = (const u16 *)ws->s2d;
+    }
     mi_prof_begin(st, bgemm_fam(k), 2.0 * T * (double)N * g.P * C * K, 2.0 * ((double)N * C * g.HW + (double)N * g.P * K) + 4.0 * T * C * K);
     const int rc = bgemm_launch<BG_WGRAD>(st, dim3(g.tiles, used), dy, x, ws->part, nullptr, g, k, stride, bm, vw);
     if (rc) { mi_prof_end(st); return rc; }
@@ -1380,6 +1391,22 @@ int mid_conv_wgrad_bf16(mid_stream s, mid_workspace *ws, const void *x, const vo
         return mid_pw_wgrad(s, x, dy, dw, ws->part, ws->part_floats, N, C, H, K);
     if (!mi_bgemm_supported(BGOP_WGRAD, N, C, H, K, k, stride)) { mi_record_error("mid_conv_wgrad_bf16", "shape not supported by the bf16 kernels"); return -2; }
     return mi_bgemm_wgrad((hipStream_t)s, ws, (const u16 *)x, (const u16 *)dy, dw, N, C, H, K, k, stride);
+}
+/* mi_conv_plan for the NCHW route (resnet_mi.h): the planners of mi_bgemm_fwd / _dgrad / _wgrad with the operator's workspace (parity
+ * planes for a stride-2 input).  0 where the route refuses the shape */
+int mid_bf16_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[7]) {
+    if (!mi_bgemm_supported(op, N, C, H, K, k, stride)) return 0;
+    BgArgs g = {};
+    if (op == BGOP_WGRAD) {
+        int vw, splits, used;
+        out[0] = bgemm_plan_wgrad(g, N, C, H, K, k, stride, stride == 2, &vw, &splits, &used);
+        out[1] = 128; out[2] = g.tiles; out[3] = g.tiles; out[4] = 1; out[5] = used; out[6] = mid_wgrad_reduce_grouped(K, C, used);
+        return 1;
+    }
+    bgemm_geometry(g, N, C, H, K, stride);
+    out[0] = bgemm_plan_tiles(g, op == BGOP_FWD ? K : C, bgemm_stage_vw(op, g.P, g.Wo, stride));
+    out[1] = 128; out[2] = g.tiles; out[3] = g.tiles; out[4] = 1; out[5] = 1; out[6] = 0;
+    return 1;
 }
 int mid_f32_to_bf16(mid_stream s, const float *in, void *out, size_t n) {
     size_t b = (n + 255) / 256; if (b > 65536) b = 65536; if (b < 1) b = 1;

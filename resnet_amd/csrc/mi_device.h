@@ -186,6 +186,12 @@ int mid_bf16_to_f32(mid_stream s, const void *in, float *out, size_t n);
 
 /* host-only: route and grid the launch planners choose for a convolution (kernels_igemm.hip); op 0 fwd, 1 dgrad, 2 wgrad */
 int mid_igemm_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]);
+/* mi_conv_plan's pieces (resnet_mi.h): the launch planners of the fp32 implicit GEMM, the bf16 NCHW kernels and the channel-last / LDS-DMA
+ * kernels; 1 = planned, 0 = the route refuses the shape */
+int mid_igemm_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[7]);
+int mid_bf16_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[7]);
+int mid_cl_conv_plan(int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]);
+int mid_wgrad_reduce_grouped(int K, int C, int splits); /* 1: the split reduce of a weight gradient runs grouped */
 
 /* ---- plain GEMMs for the FC layer (row-major) ---- */
 /* out[m x n] = A[m x k] B[k x n] */

@@ -104,6 +104,16 @@ int mi_op_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C) 
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_poison_lds(void) { return finish(mid_lds_poison(mi_global()->compute)); }
 int mi_debug_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]) { return mid_igemm_plan(op, N, C, H, K, k, stride, out); }
+int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]) {
+    for (int i = 0; i < 7; i++) out[i] = 0;
+    int ok = 0;
+    if (op < 0 || op > 2) ok = 0;
+    else if (dtype == MI_DTYPE_F32 && route == MI_ROUTE_DEFAULT) ok = mid_igemm_conv_plan(op, N, C, H, K, k, stride, out);
+    else if (dtype == MI_DTYPE_BF16 && route == MI_ROUTE_DEFAULT) ok = mid_bf16_conv_plan(op, N, C, H, K, k, stride, out);
+    else if (dtype == MI_DTYPE_BF16 && route >= MI_ROUTE_CL && route <= MI_ROUTE_PW) ok = mid_cl_conv_plan(route, op, N, C, H, K, k, stride, out);
+    if (!ok) { for (int i = 0; i < 7; i++) out[i] = 0; return -2; }
+    return 0;
+}
 
 /* ---- typed operators: activation tensors as bf16 (MI_DTYPE_BF16), arithmetic in fp32 ---- */
 int mi_op_convert(const void *in, int in_dt, void *out, int out_dt, size_t n) {
