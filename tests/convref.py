@@ -13,6 +13,7 @@ terms is typically off by ~2^-24 A; one missing term costs ~A / n (n <= 18432 te
   * fp32 outputs: |got - ref| <= delta
   * bf16 outputs: RNE(ref - delta) <= got <= RNE(ref + delta), RNE = round to the nearest bf16, ties to even
   * A == 0: got must be exactly 0
+  * NaN is out of every bound
 """
 import numpy as np
 import torch
@@ -211,9 +212,9 @@ def dist_f32(got, ref, A):
     got = np.asarray(got, np.float64)
     err = np.abs(got - ref)
     pos = A > 0
-    bad = int(np.count_nonzero(err[pos] > C_FACTOR * U24 * A[pos])) + int(np.count_nonzero(got[~pos] != 0))
+    bad = int(np.count_nonzero(~(err[pos] <= C_FACTOR * U24 * A[pos]))) + int(np.count_nonzero(got[~pos] != 0))  # (NaN is out of bounds)
     worst = float(np.max(err[pos] / (U24 * A[pos]))) if pos.any() else 0.0
-    if np.any(got[~pos] != 0):
+    if np.any(got[~pos] != 0) or np.isnan(worst):
         worst = float("inf")
     return worst, bad
 
@@ -226,11 +227,11 @@ def dist_bf16(got, ref, A):
     d = C_FACTOR * U24 * A
     lo, hi = rne_bf16(ref - d), rne_bf16(ref + d)
     pos = A > 0
-    bad = int(np.count_nonzero(((got < lo) | (got > hi))[pos])) + int(np.count_nonzero(got[~pos] != 0))
+    bad = int(np.count_nonzero(~((got >= lo) & (got <= hi))[pos])) + int(np.count_nonzero(got[~pos] != 0))
     ulp = bf16_ulp(ref)
     tight = pos & (d < 0.5 * ulp)
     worst = float(np.max(np.abs(got - ref)[tight] / ulp[tight])) if tight.any() else 0.0
-    if np.any(got[~pos] != 0):
+    if np.any(got[~pos] != 0) or np.isnan(got[pos]).any():
         worst = float("inf")
     return worst, bad
 

@@ -1,0 +1,395 @@
+"""Float64 references and per-element bounds for the element-wise half of the training step (CPU only): batch norm forward and
+backward, max-pool, average pool, soft-max, Adam.  The checks are convref's (dist_f32 / dist_bf16 / check_slabs: |got - ref| <=
+C_FACTOR 2^-24 A, bf16 outputs between RNE(ref -/+ that bound)); what this module adds is each operation's reference and its A.
+
+Batch norm (kernels_bn.hip), per channel c over M = N * P samples, statistics (mean, biased var) given or produced:
+  * statistics: mean and var in float64 over every sample of the slab's channels; A = mean |x|, mean x^2 (sum of |terms| / M)
+  * apply: ref = g (x - mean) / sqrt(var + eps) + b (+ r), ReLU; A = APPLY_TERMS |g x_hat| + |b| (+ |r|) -- the kernel's own statistics
+    are the contract (backward reuses them), so the reference takes the statistics the kernel was given or produced
+  * dbeta = sum g_i, dgamma = sum g_i x_hat_i with g_i the gated gradient; A = sum of |terms| (convref.bn_grad_sums)
+  * dx = (gamma / sd) (g_i - k1 - x_hat k2), k1 = dbeta / M, k2 = dgamma / M from the float64 sums;
+    A = |gamma / sd| (DX_TERMS (|g_i| + |k1| + |x_hat k2|) + (sum |g|) / M + |x_hat| (sum |g x_hat|) / M): the second half is what the
+    bounds of the two sums carry into dx
+Max-pool (3x3, stride 2, pad 1, kernels_misc.hip) is restated exactly: strict '>' from -1024 in (r, c) scan order (the first maximum
+wins), backward "last writer in (oh, ow) scan order".  Soft-max: A = out (t_j + sum_k out_k t_k + 1), t = |x - max| + 1 (expf of an
+argument carries that argument's absolute rounding error), plus an absolute 2^-126 / (C_FACTOR 2^-24) for results that underflow.  Adam: the reference kernels' formula in float64 from the same float32
+inputs, with the error of each intermediate carried through (adam_ref).
+"""
+import numpy as np
+
+import convref as R
+
+C_FACTOR, U24 = R.C_FACTOR, R.U24
+APPLY_TERMS = 4   # x - mean, / sd, sd itself, the fma: roundings relative to |g x_hat|
+DX_TERMS = 4
+EPS = 1e-7        # the trainer's batch-norm eps (resnet_amd/trainer.py)
+TINY32 = 2.0 ** -126
+STEP = 16         # images per float64 block of the whole-tensor sums
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# batch norm
+def _c(v):
+    return np.asarray(v, np.float64)[None, :, None, None]
+
+
+def stats_ref(x):
+    """float64 mean / biased var per channel of x [n, c, H, W] (every image of those channels) and their bounds"""
+    n = x.shape[0]
+    Cn = x.shape[1]
+    s, s2, sa = np.zeros(Cn), np.zeros(Cn), np.zeros(Cn)
+    step = STEP
+    M = n * x.shape[2] * x.shape[3]
+    for i in range(0, n, step):
+        xc = x[i:i + step].astype(np.float64)
+        s += xc.sum((0, 2, 3)); sa += np.abs(xc).sum((0, 2, 3)); s2 += (xc * xc).sum((0, 2, 3))
+    mu = s / M
+    var = np.zeros(Cn)
+    for i in range(0, n, step):
+        d = x[i:i + step].astype(np.float64) - mu[None, :, None, None]
+        var += (d * d).sum((0, 2, 3))
+    return mu, var / M, C_FACTOR * U24 * sa / M, C_FACTOR * U24 * s2 / M
+
+
+def grad_sums(g, x, means, vars_, eps):
+    """convref.bn_grad_sums over blocks of STEP images (host memory)"""
+    tot = None
+    for i in range(0, g.shape[0], STEP):
+        part = R.bn_grad_sums(g[i:i + STEP], x[i:i + STEP], means, vars_, eps)
+        tot = part if tot is None else tuple(a + b for a, b in zip(tot, part))
+    return tot
+
+
+def stats_violations(gm, gv, x):
+    """channels of (gm, gv) outside the bounds of stats_ref(x), and the worst distance in 2^-24 (bound scale) units"""
+    mu, var, bm, bv = stats_ref(x)
+    em, ev = np.abs(np.asarray(gm, np.float64) - mu), np.abs(np.asarray(gv, np.float64) - var)
+    bad = int(np.count_nonzero(~(em <= bm))) + int(np.count_nonzero(~(ev <= bv)))
+    return bad, float(max(np.max(em / bm), np.max(ev / bv))) * C_FACTOR
+
+
+def apply_ref(x, gamma, beta, means, vars_, eps, relu, residual=None):
+    """ref, A of the BN apply on x [n, c, H, W] with the per-channel vectors of those channels"""
+    sd = np.sqrt(np.asarray(vars_, np.float64) + eps)
+    xh = (x.astype(np.float64) - _c(means)) / _c(sd)
+    gx = _c(gamma) * xh
+    ref = gx + _c(beta)
+    A = APPLY_TERMS * np.abs(gx) + np.abs(_c(beta))
+    if residual is not None:
+        ref += residual
+        A += np.abs(residual)
+    if relu or residual is not None:
+        ref = np.maximum(ref, 0.0)
+    return ref, A
+
+
+def bn_gate_y(x, gamma, beta, means, vars_, eps):
+    """float64 y = g x_hat + b (the mode-1 gate's argument) and its bound"""
+    ref, A = apply_ref(x, gamma, beta, means, vars_, eps, False)
+    return ref, C_FACTOR * U24 * A
+
+
+def dx_ref(g, x, gamma, means, vars_, eps, sums, M):
+    """ref, A of the BN backward dx on a slab (g: gated gradient, x: the BN input, per-channel vectors of the slab's channels; sums =
+    (dbeta, dgamma, sum|g|, sum|g x_hat|) of those channels in float64)"""
+    db, dg, adb, adg = (np.asarray(a, np.float64) for a in sums)
+    sd = np.sqrt(np.asarray(vars_, np.float64) + eps)
+    xh = (x.astype(np.float64) - _c(means)) / _c(sd)
+    s = _c(gamma / sd)
+    k1, k2 = _c(db / M), _c(dg / M)
+    g64 = g.astype(np.float64)
+    ref = s * (g64 - k1 - xh * k2)
+    A = np.abs(s) * (DX_TERMS * (np.abs(g64) + np.abs(k1) + np.abs(xh * k2)) + _c(adb / M) + np.abs(xh) * _c(adg / M))
+    return ref, A
+
+
+def bn_dx_slabs(g, x, gamma, means, vars_, eps, sums, S, Rc):
+    """dx_ref on convref's two slabs: every channel of the images S, every image of the channels Rc"""
+    M = x.shape[0] * x.shape[2] * x.shape[3]
+    out = []
+    ref, A = dx_ref(g[S], x[S], gamma, means, vars_, eps, sums, M)
+    out.append(R.Slab("images %s" % (S,), ref, A, lambda a, S=S: a[S]))
+    sub = [np.asarray(v)[Rc] for v in sums]
+    ref, A = dx_ref(g[:, Rc], x[:, Rc], gamma[Rc], means[Rc], vars_[Rc], eps, sub, M)
+    out.append(R.Slab("channels %d of %d" % (len(Rc), x.shape[1]), ref, A, lambda a, Rc=Rc: a[:, Rc]))
+    return out
+
+
+def bn_apply_slabs(x, gamma, beta, means, vars_, eps, relu, residual, S, Rc):
+    out = []
+    ref, A = apply_ref(x[S], gamma, beta, means, vars_, eps, relu, None if residual is None else residual[S])
+    out.append(R.Slab("images %s" % (S,), ref, A, lambda a, S=S: a[S]))
+    ref, A = apply_ref(x[:, Rc], gamma[Rc], beta[Rc], means[Rc], vars_[Rc], eps, relu, None if residual is None else residual[:, Rc])
+    out.append(R.Slab("channels %d of %d" % (len(Rc), x.shape[1]), ref, A, lambda a, Rc=Rc: a[:, Rc]))
+    return out
+
+
+def sums_violations(db, dg, ref_sums):
+    """channels of the kernel's dbeta / dgamma outside C_FACTOR 2^-24 sum|terms|, and the worst distance in 2^-24 sum|terms|"""
+    rdb, rdg, adb, adg = ref_sums
+    eb, eg = np.abs(np.asarray(db, np.float64) - rdb), np.abs(np.asarray(dg, np.float64) - rdg)
+    bb, bg = C_FACTOR * U24 * adb, C_FACTOR * U24 * adg
+    bad = int(np.count_nonzero(~((eb <= bb) | ((adb == 0) & (db == 0))))) + int(np.count_nonzero(~((eg <= bg) | ((adg == 0) & (dg == 0)))))
+    w = float(max(np.max(eb / np.maximum(adb * U24, 1e-300)), np.max(eg / np.maximum(adg * U24, 1e-300))))
+    return bad, w
+
+
+def channel_last(y, par):
+    """the channel-last copy bn_apply_cl_kernel writes of y [N, C, H, H], halos zero: one plane [N][H+2][H+2][C] with a halo of 1, or
+    (par) the four parity planes [N][4][H/2+1][H/2+1][C] of a stride-2 3x3 (plane 2 (y & 1) + (x & 1), a leading zero row / column)"""
+    N, Cn, H, _ = y.shape
+    if not par:
+        out = np.zeros((N, H + 2, H + 2, Cn), y.dtype)
+        out[:, 1:H + 1, 1:H + 1] = y.transpose(0, 2, 3, 1)
+        return out
+    Hp = H // 2 + 1
+    out = np.zeros((N, 4, Hp, Hp, Cn), y.dtype)
+    for py in (0, 1):
+        for px in (0, 1):
+            out[:, 2 * py + px, 1:, 1:] = y[:, :, py::2, px::2].transpose(0, 2, 3, 1)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# max-pool 3x3 / stride 2 / pad 1 (even H), restated from its documented rule
+def maxpool_fwd_ref(x, last_max=False):
+    """values and flat arg-max indices: strict '>' from -1024 in (r, c) scan order (last_max: '>=', a mutant)"""
+    N, Cn, H, _ = x.shape
+    Ho = H // 2
+    xp = np.full((N, Cn, H + 2, H + 2), -np.inf, np.float32)
+    xp[:, :, 1:H + 1, 1:H + 1] = x
+    mv = np.full((N, Cn, Ho, Ho), -1024.0, np.float32)
+    mi = np.full((N, Cn, Ho, Ho), -1024, np.int32)
+    base = (np.arange(N * Cn, dtype=np.int32) * np.int32(H * H)).reshape(N, Cn, 1, 1)
+    o = np.arange(Ho, dtype=np.int32)
+    for r in (-1, 0, 1):
+        for c in (-1, 0, 1):
+            cand = xp[:, :, r + 1:r + 1 + 2 * Ho:2, c + 1:c + 1 + 2 * Ho:2]
+            upd = (cand >= mv) if last_max else (cand > mv)
+            mv = np.where(upd, cand, mv)
+            mi = np.where(upd, base + ((2 * o[:, None] + r) * H + 2 * o[None, :] + c), mi)
+    return mv, mi
+
+
+def maxpool_bwd_ref(idx, dy, H, first_writer=False):
+    """dx[e] = dy of the LAST window in (oh, ow) scan order whose arg-max is e (first_writer: the first, a mutant).  The output index o
+    grows in scan order, so the writer is the window with the largest (smallest) o among those naming e; windows of one parity class
+    (oh & 1, ow & 1) are disjoint, so each class names every element at most once"""
+    N, Cn, Ho, _ = dy.shape
+    total = N * Cn * H * H
+    pick = np.full(total, -1 if not first_writer else np.iinfo(np.int32).max, np.int32)
+    o = np.arange(N * Cn * Ho * Ho, dtype=np.int32).reshape(N, Cn, Ho, Ho)
+    for a in (0, 1):
+        for b in (0, 1):
+            cls = np.full(total, -1, np.int32)
+            cls[idx[:, :, a::2, b::2].ravel()] = o[:, :, a::2, b::2].ravel()
+            if first_writer:
+                pick = np.where(cls >= 0, np.minimum(pick, cls), pick)
+            else:
+                pick = np.maximum(pick, cls)
+            del cls
+    if first_writer:
+        pick[pick == np.iinfo(np.int32).max] = -1
+    dyf = dy.ravel()
+    dx = np.where(pick >= 0, dyf[np.maximum(pick, 0)], np.float32(0))
+    return dx.reshape(N, Cn, H, H).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# soft-max, average pool
+def softmax_ref(x):
+    """float64 soft-max of the rows of x and A = out (t + sum_k out_k t_k + 1), t = |x - max| + 1"""
+    x64 = x.astype(np.float64)
+    mx = x64.max(1, keepdims=True)
+    e = np.exp(x64 - mx)
+    out = e / e.sum(1, keepdims=True)
+    t = np.abs(x64 - mx) + 1.0
+    # + an absolute floor: results below float32's normal range (expf of x - max < -87) may flush to 0
+    return out, out * (t + (out * t).sum(1, keepdims=True) + 1.0) + TINY32 / (C_FACTOR * U24)
+
+
+def softmax_f32(x, subtract_max=True):
+    """a float32 execution (numpy): the valid form, or (subtract_max=False) the mutant that overflows on large logits"""
+    x = x.astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.exp(x - x.max(1, keepdims=True)) if subtract_max else np.exp(x)
+        return (e / e.sum(1, keepdims=True, dtype=np.float32)).astype(np.float32)
+
+
+def softmax_rows(N, L, seed):
+    """logits of the benchmark's scale, plus rows with |x| ~ 80-100 (where a soft-max without the max subtraction overflows or flushes to
+    0 / 0) and rows with many equal maxima"""
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal((N, L)) * 3.0).astype(np.float32)
+    x[1] += np.float32(95.0)
+    x[2] -= np.float32(110.0)
+    x[3] = np.float32(88.0)                                     # every entry the maximum
+    x[4, rng.choice(L, 37, replace=False)] = x[4].max() + np.float32(1.0)
+    x[5] = np.round(x[5])                                      # many ties, including at the maximum
+    x[6, ::2] = np.float32(80.0); x[6, 1::2] = np.float32(-80.0)
+    return x
+
+
+def avgpool_ref(x):
+    """float64 mean of every plane of x [N, C, H, W] and A = mean |x|"""
+    x64 = x.reshape(x.shape[0], x.shape[1], -1).astype(np.float64)
+    return x64.mean(2), np.abs(x64).mean(2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Adam (kernels_misc.hip adam_kernel = the reference's updateMeans / updateVars / updateParams)
+def adam_ref(p, g, m, v, lr, wd, b1, b2, cb1, cb2, eps, bias_b=False):
+    """float64 (p', m', v') of the update from float32 inputs (hyper-parameters as float32), each with A such that C_FACTOR 2^-24 A bounds
+    the float32 execution: m' and v' carry |terms| (the gradient g + wd p included); p' carries |p|, |wd p|, lr |r| and what the bounds of
+    m', v' carry through r = (m' / (1 - cb1)) / (sqrt(v' / (1 - cb2)) + eps).  bias_b: the mutant that corrects by b instead of b^t.
+    Where g is NaN / Inf the moments stay and p' is formed from them (the reference's kernels)."""
+    f = lambda a: np.float64(np.float32(a))
+    lr, wd, b1, b2, cb1, cb2, eps = (f(a) for a in (lr, wd, b1, b2, cb1, cb2, eps))
+    if bias_b:
+        cb1, cb2 = b1, b2
+    p64, g64, m64, v64 = (a.astype(np.float64) for a in (p, g, m, v))
+    ok = np.isfinite(g64)
+    gs = np.where(ok, g64, 0.0)
+    gd = gs + wd * p64
+    agd = np.abs(gs) + np.abs(wd * p64)
+    m1 = np.where(ok, b1 * m64 + (1 - b1) * gd, m64)
+    v1 = np.where(ok, b2 * v64 + (1 - b2) * gd * gd, v64)
+    Am = np.where(ok, np.abs(b1 * m64) + (1 - b1) * agd, np.abs(m64))   # (kept moments: the tests ask for them bit for bit)
+    Av = np.where(ok, b2 * v64 + (1 - b2) * agd * agd * 3, v64)
+    ma, va = m1 / (1 - cb1), v1 / (1 - cb2)
+    s = np.sqrt(va)
+    den = s + eps
+    r = ma / den
+    # absolute error bounds of ma and s (2 roundings of their own each, plus the carried bounds)
+    Ema = (C_FACTOR * U24 * Am + 2 * U24 * np.abs(m1)) / (1 - cb1) + 2 * U24 * np.abs(ma)
+    Eva = (C_FACTOR * U24 * Av + 2 * U24 * v1) / (1 - cb2) + 2 * U24 * va
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Es = np.where(s > 0, np.minimum(Eva / (2 * s), np.sqrt(Eva)), np.sqrt(Eva)) + U24 * s
+    Er = Ema / den + np.abs(ma) * Es / (den * den) + 2 * U24 * np.abs(r)
+    p1 = p64 - (lr * r + wd * p64)
+    Ap = np.abs(p64) + np.abs(wd * p64) + lr * np.abs(r) + lr * Er / (C_FACTOR * U24)
+    return (p1, Ap), (m1, Am), (v1, Av)
+
+
+def adam_f32(p, g, m, v, lr, wd, b1, b2, cb1, cb2, eps):
+    """a float32 execution (numpy) of the kernel's arithmetic, in its order"""
+    f = np.float32
+    lr, wd, b1, b2, cb1, cb2, eps = (f(a) for a in (lr, wd, b1, b2, cb1, cb2, eps))
+    ok = np.isfinite(g)
+    gd = np.where(ok, g, f(0)) + wd * p
+    m1 = np.where(ok, b1 * m + (f(1) - b1) * gd, m)
+    v1 = np.where(ok, b2 * v + (f(1) - b2) * gd * gd, v)
+    ma, va = m1 / (f(1) - cb1), v1 / (f(1) - cb2)
+    p1 = p - (lr * (ma / (np.sqrt(va) + eps)) + wd * p)
+    return p1.astype(np.float32), m1.astype(np.float32), v1.astype(np.float32)
+
+
+def arena_floats(dims):
+    """the trainer's parameter arena: every tensor of synth.location_table padded to 64 floats (trainer.c align_up)"""
+    import synth
+    return sum((size + 63) // 64 * 64 for size, _, _ in synth.location_table(dims))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the batch-norm sites of ResNet-50 at N = 256.  Forward forms: "relu" (stem, reduction, spatial), "none" (projection), "add_relu"
+# (expansion: + shortcut, ReLU), and in bf16 the dual writes of bn_apply_cl_kernel: "cl plane" / "cl par" (the reduction BN writes its 3x3's
+# channel-last input), "cl par add_relu" (the expansion BN writes the next block's projection input as parity planes).  Backward modes
+# (mid_bn_bwd_t): 1 = gate recomputed from y > 0, 3 = external mask + gated dy written, 0 = dy already gated.
+# (C, H, forward forms, backward modes); storage pairs: "f32" = (f32, f32), "bf16" = (bf16, bf16), "f32>bf16" = fp32 convolution output,
+# bf16 activation (the bf16 stem under RESNET_MI_BF16_STEM_TENSORS=f32)
+STEM_SHAPE = (64, 112)
+BN_SHAPES = [
+    (64, 112, ("relu",), (1,)),
+    (64, 56, ("relu", "cl plane"), (1,)),
+    (256, 56, ("none", "add_relu", "cl par add_relu"), (3, 0)),
+    (128, 56, ("relu", "cl par"), (1,)),
+    (128, 28, ("relu", "cl plane"), (1,)),
+    (512, 28, ("none", "add_relu", "cl par add_relu"), (3, 0)),
+    (256, 28, ("relu", "cl par"), (1,)),
+    (256, 14, ("relu", "cl plane"), (1,)),
+    (1024, 14, ("none", "add_relu", "cl par add_relu"), (3, 0)),
+    (512, 14, ("relu", "cl par"), (1,)),
+    (512, 7, ("relu", "cl plane"), (1,)),
+    (2048, 7, ("none", "add_relu"), (3, 0)),
+]
+
+
+def _pairs(Cn, H):
+    return ("f32", "bf16", "f32>bf16") if (Cn, H) == STEM_SHAPE else ("f32", "bf16")
+
+
+def bn_fwd_cases():
+    """(pair, C, H, forms): the channel-last forms in bf16 storage only"""
+    out = []
+    for Cn, H, forms, _ in BN_SHAPES:
+        for pr in _pairs(Cn, H):
+            out.append((pr, Cn, H, tuple(f for f in forms if pr == "bf16" or not f.startswith("cl"))))
+    return out
+
+
+def bn_bwd_cases():
+    """(pair, C, H, mode)"""
+    return [(pr, Cn, H, mode) for Cn, H, _, modes in BN_SHAPES for pr in _pairs(Cn, H) for mode in modes]
+
+
+def trainer_bn_sites(L, dims=None):
+    """every (pair, C, H, "fwd", form) and (pair, C, H, "bwd", mode) that forward_pass / backwards_pass (resnet_amd/csrc/trainer.c) produce
+    for ResNet-50 at N = 256 with default switches, restated from plan_layers, unit_fwd and unit_bwd; mode "parts" = the BN' whose reduction
+    a fusing dgrad did (mid_bn_bwd_parts_t, test_gpu_batch256.py's dgrad cases).  L: the library (mi_conv_plan answers the route queries)"""
+    import synth
+    d = dims or synth.R50_DIMS
+    N = R.N256
+    f, Hs = d["init_conv_filters"], d["input"] // d["init_conv_stride"]
+    blocks = []
+    inc, red, ex, H = f, f, 4 * f, Hs // d["init_maxpool_stride"]
+    for i in range(d["n_conv_blocks"]):
+        s = 1
+        if d["is_block_spatial_reduction"][i]:
+            s, red, ex = 2, red * 2, ex * 2
+        blocks.append(dict(inc=inc, red=red, ex=ex, H=H, s=s, proj=inc != ex))
+        inc, H = ex, H // s
+    out = set()
+    for dt in ("f32", "bf16"):
+        bf = dt == "bf16"
+        route = (lambda op, Cn, H, K, k, s: R.bf16_route(L, op, N, Cn, H, K, k, s)) if bf else (lambda *a: "default")
+        # the stem: conv_out_dt keeps fp32 for the fp32 trainer; the bf16 trainer stores bf16, or fp32 under STEM_TENSORS=f32
+        for pr in (("bf16", "f32>bf16") if bf else ("f32",)):
+            out.add((pr, f, Hs, "fwd", "relu"))
+            out.add((pr, f, Hs, "bwd", 1))
+
+        def fuses(site, Cn, H, K, k, s):
+            """plan_conv's L->fz and whether the launch fuses: fp32 site 4 only (RESNET_MI_F32_BNFUSE_BWD = 4); bf16 every site whose dgrad
+            runs on the NCHW kernels, which fuse where the plane is a multiple of 4"""
+            if not bf:
+                return site == 4
+            return route("dgrad", Cn, H, K, k, s) == "default" and (H * H) % 4 == 0
+
+        for i, b in enumerate(blocks):
+            H, s, Ho = b["H"], b["s"], b["H"] // b["s"]
+            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+            # forward: reduction (+ the 3x3's planes where B->spa.cl_by_bn), spatial, projection, expansion (+ the next projection's planes)
+            form = "relu"
+            if bf and route("fwd", b["red"], H, b["red"], 3, s) == "cl" and (s == 1 or H % 2 == 0):
+                form = "cl plane" if s == 1 else "cl par"
+            out.add((dt, b["red"], H, "fwd", form))
+            out.add((dt, b["red"], Ho, "fwd", "relu"))
+            if b["proj"]:
+                out.add((dt, b["ex"], Ho, "fwd", "none"))
+            form = "add_relu"
+            if bf and nxt and nxt["proj"]:
+                pk = 3 if nxt["s"] == 2 else 1
+                if pk == 3 and route("fwd", nxt["inc"], nxt["H"], nxt["ex"], pk, nxt["s"]) == "cl" and nxt["H"] % 2 == 0:
+                    form = "cl par add_relu"
+            out.add((dt, b["ex"], Ho, "fwd", form))
+            # backward: projection mode 3; expansion mode 0 after a projection, else mode 3 unless the block above's reduction dgrad
+            # (site 4) did its reduction; spatial fed by the expansion dgrad (site 1), reduction by the spatial dgrad (site 2)
+            if b["proj"]:
+                out.add((dt, b["ex"], Ho, "bwd", 3))
+                out.add((dt, b["ex"], Ho, "bwd", 0))
+            elif nxt is not None and fuses(4, nxt["inc"], nxt["H"], nxt["red"], 1, 1):
+                out.add((dt, b["ex"], Ho, "bwd", "parts"))
+            else:
+                out.add((dt, b["ex"], Ho, "bwd", 3))
+            out.add((dt, b["red"], Ho, "bwd", "parts" if fuses(1, b["red"], Ho, b["ex"], 1, 1) else 1))
+            out.add((dt, b["red"], H, "bwd", "parts" if fuses(2, b["red"], H, b["red"], 3, s) else 1))
+    return out

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import convref as R
+import ewref as E
 
 pytestmark = pytest.mark.gpu
 
@@ -172,13 +173,13 @@ def test_conv_bn_fwd_at_batch_256(ops, case):
     x = rnd(_normal((N, Cn, H, H), seed + 2))
     w = rnd(_normal((K, Cn, k, k), seed + 1, (2.0 / (k * k * (Cn + K))) ** 0.5))
     gamma, beta = _bn_params(K, seed + 3)
-    conv, gm, gv, _, fused = ops.conv_bn_fwd_t(x, w, gamma, beta, s, 1e-7, 1, 1 if bf else 0)
+    conv, gm, gv, y, fused = ops.conv_bn_fwd_t(x, w, gamma, beta, s, 1e-7, 1, 1 if bf else 0)
     assert fused, "every layer tiles: the statistics must come from the convolution's epilogue"
     plan = R.conv_plan(ops.L, 1 if bf else 0, "default", "fwd", N, Cn, H, K, k, s)
     Ho = H // s
     Pc = (Ho * Ho + 7) // 8 * 8 if bf else Ho * Ho
-    Rk = R.slab_channels(K, seed)
-    slabs = R.fwd_slabs(x, w, s, R.slab_images(N, plan, K, Pc, seed), Rk)
+    Rk, S = R.slab_channels(K, seed), R.slab_images(N, plan, K, Pc, seed)
+    slabs = R.fwd_slabs(x, w, s, S, Rk)
     worst = R.check_slabs(conv, slabs, bf, "conv_bn %s %s" % (dt, (Cn, H, K, k, s)))
     _record((dt, "default", "fwd+bn"), worst)
     mu, var, bm, bv = R.bn_stats_ref(slabs[1].ref, slabs[1].A)
@@ -187,7 +188,12 @@ def test_conv_bn_fwd_at_batch_256(ops, case):
     assert np.all(ev <= bv), "vars: %d of %d channels out of bounds, worst %.3g of the bound" % (np.sum(ev > bv), len(Rk), np.max(ev / bv))
     ws = float(max(np.max(em / bm), np.max(ev / bv))) * R.C_FACTOR
     _record((dt, "bn stats", "fwd"), ws)
-    print("%s plan %s: conv worst %.3g %s, statistics worst %.3g x 2^-24 (bound scale)" % (case, plan, worst, "bf16 ulp" if bf else "x 2^-24 A", ws))
+    # the BN + ReLU output: the float64 apply of the stored convolution output with the statistics the epilogue produced (ewref)
+    wy = R.check_slabs(y, E.bn_apply_slabs(conv, gamma, beta, gm, gv, 1e-7, True, None, S, Rk), bf,
+                       "conv_bn y %s %s" % (dt, (Cn, H, K, k, s)))
+    _record((dt, "bn apply", "fwd+bn"), wy)
+    print("%s plan %s: conv worst %.3g %s, statistics worst %.3g x 2^-24 (bound scale), y worst %.3g"
+          % (case, plan, worst, "bf16 ulp" if bf else "x 2^-24 A", ws, wy))
 
 
 DGRAD_BN = R.dgrad_bn_cases()
@@ -213,11 +219,12 @@ def test_dgrad_bn_bwd_at_fused_sites(ops, case):
     sd = np.sqrt(vars_ + np.float32(eps))
     mask = rnd(np.maximum(gamma[None, :, None, None] * ((bn_x - means[None, :, None, None]) / sd[None, :, None, None]) + beta[None, :, None, None], 0))
     fn = ops.conv_dgrad_bn_bwd_bf16 if bf else ops.conv_dgrad_bn_bwd_f32
-    gated, _, dg, db, fused = fn(w, dy, H, s, bn_x, mask, gamma, beta, means, vars_, eps, addend=addend)
+    gated, bdx, dg, db, fused = fn(w, dy, H, s, bn_x, mask, gamma, beta, means, vars_, eps, addend=addend)
     assert fused == (not bf or (H * H) % 4 == 0), "which launches fuse the BN' reduction"
     plan = R.conv_plan(ops.L, 1 if bf else 0, "default", "dgrad", N, Cn, H, K, k, s)
     Pc = (H * H + 7) // 8 * 8 if bf else H * H
-    slabs = R.gate_slabs(R.dgrad_slabs(w, dy, H, s, R.slab_images(N, plan, Cn, Pc, seed), R.slab_channels(Cn, seed), addend), mask)
+    S, Rc = R.slab_images(N, plan, Cn, Pc, seed), R.slab_channels(Cn, seed)
+    slabs = R.gate_slabs(R.dgrad_slabs(w, dy, H, s, S, Rc, addend), mask)
     worst = R.check_slabs(gated, slabs, bf, "gated dgrad %s %s" % (dt, (Cn, H, K, k, s)))
     _record((dt, "default", "dgrad+bn'"), worst)
     rdb, rdg, adb, adg = R.bn_grad_sums(gated, bn_x, means, vars_, eps)
@@ -227,5 +234,8 @@ def test_dgrad_bn_bwd_at_fused_sites(ops, case):
     assert np.all((eg <= bg) | ((adg == 0) & (dg == 0))), "dgamma: %d of %d channels out of bounds" % (np.sum(eg > bg), Cn)
     ws = float(max(np.max(eb / np.maximum(adb * R.U24, 1e-300)), np.max(eg / np.maximum(adg * R.U24, 1e-300))))
     _record((dt, "bn' sums", "bwd"), ws)
-    print("%s plan %s fused %s: gated worst %.3g %s, dbeta / dgamma worst %.3g x 2^-24 sum|terms|"
-          % (case, plan, fused, worst, "bf16 ulp" if bf else "x 2^-24 A", ws))
+    # BN' dx (mid_bn_bwd_parts_t where fused: the merged partials, then bn_bwd_apply_kernel) against the float64 formula from the sums
+    wx = R.check_slabs(bdx, E.bn_dx_slabs(gated, bn_x, gamma, means, vars_, eps, (rdb, rdg, adb, adg), S, Rc), bf, "BN' dx %s %s" % (dt, (Cn, H, K, k, s)))
+    _record((dt, "bn' dx", "bwd"), wx)
+    print("%s plan %s fused %s: gated worst %.3g %s, dbeta / dgamma worst %.3g x 2^-24 sum|terms|, dx worst %.3g"
+          % (case, plan, fused, worst, "bf16 ulp" if bf else "x 2^-24 A", ws, wx))
