@@ -375,6 +375,25 @@ void mi_trainer_set_nan_exit(Train_ResNet *t, int on);
  * Device pointers [R][C]: means / vars (per-replica in, merged out), dgamma / dbeta (per-replica sums in, gradient-arena values
  * out = sum / R), sums_out [R][2C] (the sums each replica's dx formula sees) or NULL.  Either pair may be NULL. */
 int mi_debug_bn_merge(int R, int C, float *means, float *vars, float *dgamma, float *dbeta, float *sums_out);
+/* The update rule of update_parameters.  MI_OPT_ADAM (default): the reference's Adam.  MI_OPT_SGD: torch.optim.SGD with momentum,
+ * dampening 0, no Nesterov, weight decay on every tensor: d = g + wd w; b = mu b + d; w -= lr b.  MI_OPT_LARS (You et al. 2017, the
+ * MLPerf ResNet-50 form): convolution and FC weights b = mu b + lr trust (g + wd w); w -= b with trust = tau |w| / (|g| + wd |w|)
+ * (1 where |w| or |g| is 0), the norms per tensor before any update; BN gamma / beta b = mu b + lr g; w -= b.  lr, wd = the trainer's
+ * learning_rate / weight_decay, read at every update (a schedule writes learning_rate between steps).  b = the prev_means arena
+ * (starts at zero, dumped as means/); prev_vars is not touched.  Guards as Adam's: a NaN / Inf gradient element keeps its w and b
+ * and stays in the arena, finite gradients are cleared; LARS leaves a whole tensor as it is when a norm is not finite; the NaN flag
+ * names the highest offending locations[] index.  Call before the first update_parameters (later: -1, mi_last_error says why); the
+ * choice is not dumped, a resumed run sets it again. */
+enum { MI_OPT_ADAM = 0, MI_OPT_SGD = 1, MI_OPT_LARS = 2 };
+int mi_trainer_set_optimizer(Train_ResNet *t, int kind, float momentum, float trust_coef);
+int mi_trainer_get_optimizer(const Train_ResNet *t);
+/* the SGD / LARS kernels on their own: p, g, b device arrays of n floats; tensor i starts at offsets_host[i] (n_tensors + 1 entries,
+ * multiples of 4, the last <= n) and runs to the next offset; tensor_is_weight_host[i] 1: trust ratio and weight decay (LARS).
+ * nan_flag_dev: device int or NULL.  sq_norms_out_host (optional, 2 n_tensors doubles): (|w|^2, |g|^2) per tensor before the update,
+ * for SGD too.  Returns 0, or -1 (mi_last_error says why). */
+int mi_op_momentum_update(int kind, float *p, float *g, float *b, size_t n, const size_t *offsets_host, int n_tensors,
+                          const int *tensor_is_weight_host, float lr, float wd, float momentum, float trust_coef, int *nan_flag_dev,
+                          double *sq_norms_out_host);
 /* the end-of-epoch bookkeeping of the reference's main() (resnet.cu:3410-3421) */
 void mi_trainer_end_epoch(Train_ResNet *t, float epoch_loss, float epoch_n_wrong, float total_images_per_epoch);
 /* host-only (no GPU needed): the gradient buckets the data-parallel path cuts for a network -- float offsets [from, to) into

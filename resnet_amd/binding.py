@@ -99,6 +99,7 @@ MI_LAYOUT_NHWC, MI_LAYOUT_NCHW = 0, 1
 MI_DTYPE_F32, MI_DTYPE_BF16 = 0, 1
 MI_STORE_FAST, MI_STORE_RECOMPUTE_BN, MI_STORE_FULL = 0, 1, 2
 MI_ROUTE_DEFAULT, MI_ROUTE_CL, MI_ROUTE_CL2, MI_ROUTE_PW = 0, 1, 2, 3
+MI_OPT_ADAM, MI_OPT_SGD, MI_OPT_LARS = 0, 1, 2
 
 # every symbol include/resnet_mi.h declares: name -> (restype, argtypes)
 _i, _f, _vp, _sz, _u64, _cp = C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p
@@ -182,6 +183,9 @@ PROTOTYPES = {
     "mi_clear_error": (None, []),
     "mi_trainer_check_errors": (_i, [_T]),
     "mi_trainer_end_epoch": (None, [_T, _f, _f, _f]),
+    "mi_trainer_set_optimizer": (_i, [_T, _i, _f, _f]),
+    "mi_trainer_get_optimizer": (_i, [_T]),
+    "mi_op_momentum_update": (_i, [_i, _vp, _vp, _vp, _sz, _vp, _i, _vp, _f, _f, _f, _f, _vp, _vp]),
     "mi_trainer_nan_location": (_i, [_T]),
     "mi_trainer_stem_dtype": (_i, [_T]),
     "mi_trainer_set_nan_exit": (None, [_T, _i]),

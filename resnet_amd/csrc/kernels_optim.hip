@@ -1,0 +1,195 @@
+// kernels_optim.hip -- momentum SGD and LARS (You et al. 2017) over the parameter arena, beside the reference's Adam
+// (kernels_misc.hip).  The arena is cut into chunks of at most MID_OPT_CHUNK floats that never cross a tensor boundary
+// (mid_chunk table, built once per trainer on the host); every pass runs one workgroup per chunk over a chunk range, so a
+// data-parallel bucket (cut at block boundaries) runs exactly its own chunks.  Tensor offsets are multiples of 4 floats:
+// every chunk starts 16-B aligned and is read with float4 loads, a length that is not a multiple of 4 ends in scalar code.
+//
+//   norms   one workgroup per chunk: (sum w^2, sum g^2) of the chunk in double, fixed-order wave + workgroup reduction,
+//           one double2 partial per chunk (no atomics: the same inputs give the same bits)
+//   trust   one wave per tensor: its partials summed in a fixed order -> squared norms and the LARS trust ratio
+//           (NaN: a norm is not finite, the tensor is left as it is)
+//   update  one workgroup per chunk (tensor id wave-uniform): the rule, the guards, gradient clearing, the NaN flag
+//
+// Guards (the contract of adam_kernel): a non-finite gradient element keeps its w and b and stays in the arena, finite
+// gradients are cleared; a non-finite result keeps w and b; LARS leaves a whole tensor untouched when its trust ratio is not
+// finite.  *nan_flag becomes the highest offending tensor index + 1 (atomicMax on an int).
+#include "mi_common.hpp"
+#include "mi_device.h"
+
+#define OPT_THREADS 256
+
+__device__ __forceinline__ bool fin(float x) { return !(isnan(x) || isinf(x)); }
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(OPT_THREADS)
+optim_norm_kernel(const float *__restrict__ p, const float *__restrict__ g, const mid_chunk *__restrict__ chunks, int c0,
+                  double2 *__restrict__ part) {
+    const mid_chunk ch = chunks[c0 + blockIdx.x];
+    const float *pw = p + ch.start, *pg = g + ch.start;
+    const int n4 = ch.len >> 2;
+    double sw = 0.0, sg = 0.0;
+    if (n4 == MID_OPT_CHUNK / 4) { // a whole chunk: every load in flight before the first product
+        float4 w[MID_OPT_CHUNK / 4 / OPT_THREADS], q[MID_OPT_CHUNK / 4 / OPT_THREADS];
+#pragma unroll
+        for (int k = 0; k < MID_OPT_CHUNK / 4 / OPT_THREADS; k++) {
+            w[k] = ((const float4 *)pw)[threadIdx.x + k * OPT_THREADS];
+            q[k] = ((const float4 *)pg)[threadIdx.x + k * OPT_THREADS];
+        }
+#pragma unroll
+        for (int k = 0; k < MID_OPT_CHUNK / 4 / OPT_THREADS; k++) {
+            sw = fma((double)w[k].x, (double)w[k].x, sw); sw = fma((double)w[k].y, (double)w[k].y, sw);
+            sw = fma((double)w[k].z, (double)w[k].z, sw); sw = fma((double)w[k].w, (double)w[k].w, sw);
+            sg = fma((double)q[k].x, (double)q[k].x, sg); sg = fma((double)q[k].y, (double)q[k].y, sg);
+            sg = fma((double)q[k].z, (double)q[k].z, sg); sg = fma((double)q[k].w, (double)q[k].w, sg);
+        }
+    } else {
+        for (int i = threadIdx.x; i < n4; i += OPT_THREADS) {
+            const float4 w = ((const float4 *)pw)[i], q = ((const float4 *)pg)[i];
+            sw = fma((double)w.x, (double)w.x, sw); sw = fma((double)w.y, (double)w.y, sw);
+            sw = fma((double)w.z, (double)w.z, sw); sw = fma((double)w.w, (double)w.w, sw);
+            sg = fma((double)q.x, (double)q.x, sg); sg = fma((double)q.y, (double)q.y, sg);
+            sg = fma((double)q.z, (double)q.z, sg); sg = fma((double)q.w, (double)q.w, sg);
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < ch.len; i += OPT_THREADS) {
+            sw = fma((double)pw[i], (double)pw[i], sw);
+            sg = fma((double)pg[i], (double)pg[i], sg);
+        }
+    }
+    // float squares are exact in double; the sums of a chunk are exact to ~1e-16 relative
+    sw = wave_sum_d(sw);
+    sg = wave_sum_d(sg);
+    __shared__ double red[2][OPT_THREADS / 64];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][wave] = sw; red[1][wave] = sg; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0, b = 0.0;
+        for (int k = 0; k < OPT_THREADS / 64; k++) { a += red[0][k]; b += red[1][k]; }
+        part[c0 + blockIdx.x] = make_double2(a, b);
+    }
+}
+
+// one wave per tensor: lane l sums partials l, l + 64, ... in order, then a butterfly (every lane ends with the same bits).  A
+// tensor has up to ~300 chunks; one thread walking them would wait on each load in turn
+__global__ void __launch_bounds__(64)
+optim_trust_kernel(const double2 *__restrict__ part, const int *__restrict__ first_chunk, const int *__restrict__ is_weight, int t0,
+                   float trust_coef, float wd, double2 *__restrict__ sq, float *__restrict__ trust) {
+    const int t = t0 + blockIdx.x;
+    double sw = 0.0, sg = 0.0;
+    for (int c = first_chunk[t] + threadIdx.x; c < first_chunk[t + 1]; c += 64) { sw += part[c].x; sg += part[c].y; }
+    sw = wave_sum_d(sw);
+    sg = wave_sum_d(sg);
+    if (threadIdx.x) return;
+    sq[t] = make_double2(sw, sg);
+    float tr = 1.f;
+    if (isnan(sw) || isinf(sw) || isnan(sg) || isinf(sg)) tr = NAN;
+    else if (is_weight[t]) {
+        const float wn = (float)sqrt(sw), gn = (float)sqrt(sg);
+        if (wn > 0.f && gn > 0.f) tr = trust_coef * wn / (gn + wd * wn);
+    }
+    trust[t] = tr;
+}
+
+// KIND MID_OPT_SGD:  d = g + wd w;  b = mu b + d;  w = w - lr b                (torch.optim.SGD, dampening 0, no Nesterov)
+// KIND MID_OPT_LARS: b = mu b + (lr trust) (g + wd w);  w = w - b             (BN gamma / beta: trust 1, no weight decay)
+template <int KIND>
+__device__ __forceinline__ void opt_elem(float &w, float &gr, float &b, float s, float wdt, float lr, float mu, bool skip, bool &bad) {
+    if (!fin(gr)) { bad = true; return; } // w, b kept; the gradient stays for the diagnostic dump
+    if (!skip) {
+        const float d = gr + wdt * w;
+        float nb, nw;
+        if (KIND == MID_OPT_SGD) { nb = mu * b + d; nw = w - lr * nb; }
+        else { nb = mu * b + s * d; nw = w - nb; }
+        if (fin(nb) && fin(nw)) { b = nb; w = nw; }
+        else bad = true;
+    }
+    gr = 0.f;
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(OPT_THREADS)
+optim_update_kernel(float *__restrict__ p, float *__restrict__ g, float *__restrict__ bm, const mid_chunk *__restrict__ chunks,
+                    int c0, const int *__restrict__ is_weight, const float *__restrict__ trust, float lr, float wd, float mu,
+                    int *__restrict__ nan_flag) {
+    const mid_chunk ch = chunks[c0 + blockIdx.x];
+    const int t = ch.tensor;
+    float s = lr, wdt = wd;
+    bool skip = false;
+    if (KIND == MID_OPT_LARS) {
+        const float tr = trust[t];
+        skip = !fin(tr);
+        if (is_weight[t]) s = lr * tr;
+        else wdt = 0.f;
+    }
+    bool bad = skip;
+    float *pw = p + ch.start, *pg = g + ch.start, *pb = bm + ch.start;
+    const int n4 = ch.len >> 2;
+    if (n4 == MID_OPT_CHUNK / 4) { // a whole chunk: every load in flight before the first update
+        constexpr int K = MID_OPT_CHUNK / 4 / OPT_THREADS;
+        float4 w[K], q[K], b[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const int i = threadIdx.x + k * OPT_THREADS;
+            w[k] = ((float4 *)pw)[i]; q[k] = ((float4 *)pg)[i]; b[k] = ((float4 *)pb)[i];
+        }
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            opt_elem<KIND>(w[k].x, q[k].x, b[k].x, s, wdt, lr, mu, skip, bad);
+            opt_elem<KIND>(w[k].y, q[k].y, b[k].y, s, wdt, lr, mu, skip, bad);
+            opt_elem<KIND>(w[k].z, q[k].z, b[k].z, s, wdt, lr, mu, skip, bad);
+            opt_elem<KIND>(w[k].w, q[k].w, b[k].w, s, wdt, lr, mu, skip, bad);
+            const int i = threadIdx.x + k * OPT_THREADS;
+            ((float4 *)pw)[i] = w[k]; ((float4 *)pg)[i] = q[k]; ((float4 *)pb)[i] = b[k];
+        }
+    } else {
+        for (int i = threadIdx.x; i < n4; i += OPT_THREADS) {
+            float4 w = ((float4 *)pw)[i], q = ((float4 *)pg)[i], b = ((float4 *)pb)[i];
+            opt_elem<KIND>(w.x, q.x, b.x, s, wdt, lr, mu, skip, bad);
+            opt_elem<KIND>(w.y, q.y, b.y, s, wdt, lr, mu, skip, bad);
+            opt_elem<KIND>(w.z, q.z, b.z, s, wdt, lr, mu, skip, bad);
+            opt_elem<KIND>(w.w, q.w, b.w, s, wdt, lr, mu, skip, bad);
+            ((float4 *)pw)[i] = w; ((float4 *)pg)[i] = q; ((float4 *)pb)[i] = b;
+        }
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < ch.len; i += OPT_THREADS) {
+        float w = pw[i], q = pg[i], b = pb[i];
+        opt_elem<KIND>(w, q, b, s, wdt, lr, mu, skip, bad);
+        pw[i] = w; pg[i] = q; pb[i] = b;
+    }
+    if (bad && nan_flag) atomicMax(nan_flag, t + 1);
+}
+
+extern "C" {
+int mid_optim_norms(mid_stream s, const float *p, const float *g, const mid_chunk *chunks, int c0, int c1, double *part) {
+    if (c1 <= c0) return 0;
+    hipLaunchKernelGGL(optim_norm_kernel, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, chunks, c0, (double2 *)part);
+    MI_LAUNCH_CHECK("optim_norm_kernel");
+    return 0;
+}
+int mid_optim_trust(mid_stream s, const double *part, const int *first_chunk, const int *is_weight, int t0, int t1, float trust_coef,
+                    float wd, double *sq, float *trust) {
+    if (t1 <= t0) return 0;
+    hipLaunchKernelGGL(optim_trust_kernel, dim3(t1 - t0), dim3(64), 0, (hipStream_t)s, (const double2 *)part, first_chunk, is_weight, t0,
+                       trust_coef, wd, (double2 *)sq, trust);
+    MI_LAUNCH_CHECK("optim_trust_kernel");
+    return 0;
+}
+int mid_optim_update(mid_stream s, int kind, float *p, float *g, float *b, const mid_chunk *chunks, int c0, int c1, const int *is_weight,
+                     const float *trust, float lr, float wd, float momentum, int *nan_flag) {
+    if (c1 <= c0) return 0;
+    if (kind == MID_OPT_SGD)
+        hipLaunchKernelGGL(optim_update_kernel<MID_OPT_SGD>, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, b, chunks, c0,
+                           is_weight, trust, lr, wd, momentum, nan_flag);
+    else if (kind == MID_OPT_LARS)
+        hipLaunchKernelGGL(optim_update_kernel<MID_OPT_LARS>, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, b, chunks, c0,
+                           is_weight, trust, lr, wd, momentum, nan_flag);
+    else { mi_record_error("mid_optim_update", "unknown optimizer kind"); return -1; }
+    MI_LAUNCH_CHECK("optim_update_kernel");
+    return 0;
+}
+}

@@ -264,6 +264,19 @@ int mid_ce_deriv(mid_stream s, const float *pred, const int *labels, float *d, i
 int mid_adam(mid_stream s, float *p, float *g, float *m, float *v, size_t n, float lr, float wd, float b1,
              float b2, float cur_b1, float cur_b2, float eps, int *nan_flag, int zero_grads, const size_t *loc_off_dev, int n_loc,
              size_t base);
+/* momentum SGD / LARS (kernels_optim.hip).  The parameter-shaped arenas are cut into chunks of at most MID_OPT_CHUNK floats that
+ * never cross a tensor (start: float offset into the arena, a multiple of 4); every pass runs one workgroup per chunk of
+ * [c0, c1).  norms: double2 (sum w^2, sum g^2) per chunk into part[2 * chunk].  trust: for tensors [t0, t1) (first_chunk:
+ * n_tensors + 1 entries) the partials summed in a fixed order into sq[2 * t] and the LARS trust ratio into trust[t] (NaN: a norm
+ * is not finite).  update: the rule of `kind` (MID_OPT_SGD ignores is_weight / trust); *nan_flag = highest offending tensor + 1 */
+enum { MID_OPT_ADAM = 0, MID_OPT_SGD = 1, MID_OPT_LARS = 2 };
+#define MID_OPT_CHUNK 8192
+typedef struct { int tensor, start, len, pad; } mid_chunk;
+int mid_optim_norms(mid_stream s, const float *p, const float *g, const mid_chunk *chunks, int c0, int c1, double *part);
+int mid_optim_trust(mid_stream s, const double *part, const int *first_chunk, const int *is_weight, int t0, int t1, float trust_coef,
+                    float wd, double *sq, float *trust);
+int mid_optim_update(mid_stream s, int kind, float *p, float *g, float *b, const mid_chunk *chunks, int c0, int c1, const int *is_weight,
+                     const float *trust, float lr, float wd, float momentum, int *nan_flag);
 int mid_nhwc_to_nchw(mid_stream s, const float *in, float *out, int N, int H, int W, int C);
 int mid_nchw_to_nhwc(mid_stream s, const float *in, float *out, int N, int C, int H, int W);
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */

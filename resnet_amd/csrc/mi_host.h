@@ -79,6 +79,29 @@ typedef struct {
 } MiLayer;
 typedef struct { MiLayer red, spa, exp, proj; } MiBlockLayers; /* proj.w == NULL: no projection */
 
+/* momentum SGD / LARS over a parameter-shaped arena (kernels_optim.hip): the chunk table and the per-chunk / per-tensor scratch,
+ * built once per arena geometry */
+typedef struct {
+    int kind;                    /* MI_OPT_ADAM (nothing built) | MI_OPT_SGD | MI_OPT_LARS */
+    float momentum, trust_coef;
+    int n_tensors, n_chunks;
+    size_t *off;                 /* host: n_tensors + 1 float offsets (tensor starts, then the arena's end) */
+    int *first_chunk;            /* host: n_tensors + 1 */
+    mid_chunk *chunks_dev;
+    int *first_chunk_dev, *is_weight_dev;
+    double *part_dev;            /* 2 per chunk: (sum w^2, sum g^2) */
+    double *sq_dev;              /* 2 per tensor: the squared norms of the last LARS pass */
+    float *trust_dev;            /* 1 per tensor */
+} MiOptim;
+/* off: n + 1 float offsets (multiples of 4), sizes: n tensor lengths (<= the offset gap), is_weight: n flags (1: LARS trust ratio
+ * and weight decay; 0: BN gamma / beta).  Returns 0, or -1 with mi_last_error set. */
+int mi_optim_init(MiOptim *o, int kind, float momentum, float trust_coef, const size_t *off, const int *sizes, const int *is_weight, int n);
+void mi_optim_free(MiOptim *o);
+/* one update of the tensors whose start lies in [from, to) (floats into the arena), stream-ordered; want_norms: SGD too runs the
+ * norm pass (sq_dev filled) */
+int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, size_t from, size_t to, float lr, float wd,
+                  int *nan_flag, int want_norms);
+
 typedef struct MiCtx {
     mid_workspace ws;
     float *bn_ws;
@@ -96,6 +119,7 @@ typedef struct MiCtx {
     int nan_check_pending;       /* update_parameters queued a copy of the flag; read it at the next host sync point */
     mid_event ev_nan;            /* recorded behind that copy */
     size_t *loc_off_dev; int n_loc; /* arena offsets of locations[] (+ the arena's end) for the Adam kernel's report */
+    size_t *loc_off;             /* the same offsets on the host */
     int nan_location, nan_no_exit;  /* last reported locations[] index (-1 none); test hook: report without exit(1) */
     struct MiCtx *next_live;     /* registry of live contexts (communicator teardown on a fatal error) */
     int full_store, dump_every, input_reset;
@@ -110,6 +134,8 @@ typedef struct MiCtx {
     int counting_act;
     int overlap_set;             /* mi_trainer_set_overlap was called: keep the caller's mode */
     int params_dirty;            /* update_parameters ran since the last weight re-layout */
+    MiOptim optim;               /* mi_trainer_set_optimizer: SGD / LARS instead of Adam (kind MI_OPT_ADAM: nothing built) */
+    int n_updates;               /* update_parameters calls so far (the optimizer is chosen before the first) */
     unsigned long host_epoch_seen; /* the process-wide host-write count (mi_copy_to_device) that re-layout was made at */
     char *dump_root;
     /* every device allocation of this trainer (freed by destroy_trainer) */
@@ -159,5 +185,6 @@ size_t mi_params_arena_floats(const Params *p);
 float *mi_params_arena_base(const Params *p);
 void mi_dp_reduce_ready(Train_ResNet *t, size_t from_float_offset, int force);
 void mi_trainer_poll_errors(Train_ResNet *t); /* load_new_batch: wait for and read the NaN / Inf flag of the last update */
+void mi_record_host_error(const char *what, const char *detail); /* sets mi_last_error (runtime.hip) */
 
 #endif

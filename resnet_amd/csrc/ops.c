@@ -100,6 +100,29 @@ int mi_op_adam(float *p, const float *g, float *m, float *v, size_t n, float lr,
                float cur_b2, float eps, int *nan_flag_dev) {
     return finish(mid_adam(mi_global()->compute, p, (float *)g, m, v, n, lr, wd, b1, b2, cur_b1, cur_b2, eps, nan_flag_dev, 0, NULL, 0, 0));
 }
+int mi_op_momentum_update(int kind, float *p, float *g, float *b, size_t n, const size_t *offsets_host, int n_tensors,
+                          const int *tensor_is_weight_host, float lr, float wd, float momentum, float trust_coef, int *nan_flag_dev,
+                          double *sq_norms_out_host) {
+    if (kind != MI_OPT_SGD && kind != MI_OPT_LARS) { mi_record_host_error("mi_op_momentum_update", "kind is MI_OPT_SGD or MI_OPT_LARS"); return -1; }
+    if (n_tensors < 1 || offsets_host[n_tensors] > n) { mi_record_host_error("mi_op_momentum_update", "tensors beyond the n floats"); return -1; }
+    int *sizes = (int *)malloc(sizeof(int) * (size_t)n_tensors);
+    for (int i = 0; i < n_tensors; i++) {
+        const size_t len = offsets_host[i + 1] >= offsets_host[i] ? offsets_host[i + 1] - offsets_host[i] : 0;
+        sizes[i] = len > (size_t)INT32_MAX ? -1 : (int)len; /* descending or oversized: refused by mi_optim_init */
+    }
+    MiOptim o;
+    int rc = mi_optim_init(&o, kind, momentum, trust_coef, offsets_host, sizes, tensor_is_weight_host, n_tensors);
+    free(sizes);
+    if (rc) return -1;
+    mid_stream s = mi_global()->compute;
+    rc = finish(mi_optim_step(&o, s, p, g, b, 0, offsets_host[n_tensors], lr, wd, nan_flag_dev, sq_norms_out_host != NULL));
+    if (!rc && sq_norms_out_host) {
+        mid_memcpy_d2h(sq_norms_out_host, o.sq_dev, 2 * sizeof(double) * (size_t)n_tensors, s);
+        rc = finish(0);
+    }
+    mi_optim_free(&o);
+    return rc;
+}
 int mi_op_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C) { return finish(mid_nhwc_to_nchw(mi_global()->compute, in, out, N, H, W, C)); }
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_poison_lds(void) { return finish(mid_lds_poison(mi_global()->compute)); }

@@ -620,7 +620,7 @@ Train_ResNet *init_trainer(ResNet *model, Batch *cur_batch, int batch_size, floa
         c->loc_off_dev = (size_t *)mi_ctx_alloc(c, sizeof(size_t) * (size_t)(mp->n_locations + 1));
         mid_memcpy_h2d(c->loc_off_dev, lo, sizeof(size_t) * (size_t)(mp->n_locations + 1), G.compute);
         mid_stream_sync(G.compute);
-        free(lo);
+        c->loc_off = lo;
         c->n_loc = mp->n_locations;
     }
     c->ev_nan = mid_event_create();
@@ -1206,6 +1206,112 @@ void mi_dp_reduce_ready(Train_ResNet *t, size_t from, int force) {
     c->dp_pending = 1;
 }
 
+/* ---- momentum SGD / LARS (kernels_optim.hip) ---- */
+int mi_optim_init(MiOptim *o, int kind, float momentum, float trust_coef, const size_t *off, const int *sizes, const int *is_weight, int n) {
+    memset(o, 0, sizeof *o);
+    o->kind = kind; o->momentum = momentum; o->trust_coef = trust_coef;
+    if (kind == MI_OPT_ADAM) return 0;
+    if (kind != MI_OPT_SGD && kind != MI_OPT_LARS) { mi_record_host_error("mi_optim_init", "unknown optimizer kind"); return -1; }
+    if (n < 1) { mi_record_host_error("mi_optim_init", "no tensors"); return -1; }
+    size_t n_chunks = 0;
+    for (int i = 0; i < n; i++) {
+        if (off[i] % 4 || off[i + 1] < off[i] + (size_t)sizes[i] || sizes[i] < 0 || off[i] + (size_t)sizes[i] > (size_t)INT32_MAX) {
+            mi_record_host_error("mi_optim_init", "tensor offsets must ascend in multiples of 4 floats below 2^31, each tensor within its gap");
+            return -1;
+        }
+        n_chunks += ((size_t)sizes[i] + MID_OPT_CHUNK - 1) / MID_OPT_CHUNK;
+    }
+    mid_chunk *ch = (mid_chunk *)malloc(sizeof(mid_chunk) * (n_chunks ? n_chunks : 1));
+    int *isw = (int *)malloc(sizeof(int) * (size_t)n);
+    o->off = (size_t *)malloc(sizeof(size_t) * (size_t)(n + 1));
+    o->first_chunk = (int *)malloc(sizeof(int) * (size_t)(n + 1));
+    int k = 0;
+    for (int i = 0; i < n; i++) {
+        o->off[i] = off[i];
+        o->first_chunk[i] = k;
+        isw[i] = is_weight[i] != 0;
+        for (int s0 = 0; s0 < sizes[i]; s0 += MID_OPT_CHUNK) {
+            ch[k].tensor = i; ch[k].start = (int)(off[i] + (size_t)s0);
+            ch[k].len = sizes[i] - s0 < MID_OPT_CHUNK ? sizes[i] - s0 : MID_OPT_CHUNK;
+            ch[k].pad = 0;
+            k++;
+        }
+    }
+    o->off[n] = off[n];
+    o->first_chunk[n] = k;
+    o->n_tensors = n; o->n_chunks = k;
+    o->chunks_dev = (mid_chunk *)mid_malloc(sizeof(mid_chunk) * (size_t)(k ? k : 1));
+    o->first_chunk_dev = (int *)mid_malloc(sizeof(int) * (size_t)(n + 1));
+    o->is_weight_dev = (int *)mid_malloc(sizeof(int) * (size_t)n);
+    o->part_dev = (double *)mid_malloc(2 * sizeof(double) * (size_t)(k ? k : 1));
+    o->sq_dev = (double *)mid_malloc(2 * sizeof(double) * (size_t)n);
+    o->trust_dev = (float *)mid_malloc(sizeof(float) * (size_t)n);
+    int rc = 0;
+    if (!o->chunks_dev || !o->first_chunk_dev || !o->is_weight_dev || !o->part_dev || !o->sq_dev || !o->trust_dev) rc = -1;
+    else {
+        MiGlobal *g = mi_global();
+        if (k) mid_memcpy_h2d(o->chunks_dev, ch, sizeof(mid_chunk) * (size_t)k, g->compute);
+        mid_memcpy_h2d(o->first_chunk_dev, o->first_chunk, sizeof(int) * (size_t)(n + 1), g->compute);
+        mid_memcpy_h2d(o->is_weight_dev, isw, sizeof(int) * (size_t)n, g->compute);
+        mid_memset(o->sq_dev, 0, 2 * sizeof(double) * (size_t)n, g->compute);
+        mid_stream_sync(g->compute);
+    }
+    free(ch); free(isw);
+    if (rc) mi_optim_free(o);
+    return rc;
+}
+void mi_optim_free(MiOptim *o) {
+    mid_free(o->chunks_dev); mid_free(o->first_chunk_dev); mid_free(o->is_weight_dev);
+    mid_free(o->part_dev); mid_free(o->sq_dev); mid_free(o->trust_dev);
+    free(o->off); free(o->first_chunk);
+    memset(o, 0, sizeof *o);
+}
+/* first tensor whose start is >= pos */
+static int optim_tensor_at(const MiOptim *o, size_t pos) {
+    int lo = 0, hi = o->n_tensors;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (o->off[mid] < pos) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, size_t from, size_t to, float lr, float wd,
+                  int *nan_flag, int want_norms) {
+    const int t0 = optim_tensor_at(o, from), t1 = optim_tensor_at(o, to);
+    const int c0 = o->first_chunk[t0], c1 = o->first_chunk[t1];
+    if (o->kind == MI_OPT_LARS || want_norms) {
+        if (mid_optim_norms(s, p, g, o->chunks_dev, c0, c1, o->part_dev)) return -1;
+        if (mid_optim_trust(s, o->part_dev, o->first_chunk_dev, o->is_weight_dev, t0, t1, o->trust_coef, wd, o->sq_dev, o->trust_dev)) return -1;
+    }
+    return mid_optim_update(s, o->kind, p, g, b, o->chunks_dev, c0, c1, o->is_weight_dev, o->trust_dev, lr, wd, o->momentum, nan_flag);
+}
+
+/* momentum SGD or LARS instead of Adam; before the first update_parameters (later, the momentum arena would hold Adam moments) */
+int mi_trainer_set_optimizer(Train_ResNet *t, int kind, float momentum, float trust_coef) {
+    MiCtx *c = ctx_of(t);
+    if (c->n_updates > 0) {
+        mi_record_host_error("mi_trainer_set_optimizer", "the optimizer is chosen before the first update_parameters");
+        return -1;
+    }
+    if (kind != MI_OPT_ADAM && kind != MI_OPT_SGD && kind != MI_OPT_LARS) {
+        mi_record_host_error("mi_trainer_set_optimizer", "unknown optimizer kind");
+        return -1;
+    }
+    const Params *p = t->model->params;
+    const int n = p->n_locations;
+    int *isw = (int *)malloc(sizeof(int) * (size_t)n);
+    /* locations[] holds (weight, gamma, beta) triples -- the stem, every convolution of every block -- then the FC weight */
+    for (int i = 0; i < n; i++) isw[i] = i % 3 == 0;
+    MiOptim o;
+    const int rc = mi_optim_init(&o, kind, momentum, trust_coef, c->loc_off, p->sizes, isw, n);
+    free(isw);
+    if (rc) return -1;
+    mi_optim_free(&c->optim);
+    c->optim = o;
+    return 0;
+}
+int mi_trainer_get_optimizer(const Train_ResNet *t) { return ((const MiCtx *)t->backend_ctx)->optim.kind; }
+
 /* resnet.cu:2910-2987.  No host synchronisation in here: the NaN / Inf flag is copied back asynchronously and read at the
  * next synchronisation point (forward_pass's pred copy), and with a communicator Adam runs bucket by bucket, each launch
  * waiting only for its own bucket's all-reduce -- the FC ... stage-3 updates run while the stem-side buckets are still on
@@ -1225,13 +1331,20 @@ void update_parameters(Train_ResNet *t) {
         for (int b = 0; b < c->n_buckets; b++) {
             mid_stream_wait_event(G.compute, c->bk_ev[b]);
             const size_t o = c->bk_from[b], n = c->bk_to[b] - c->bk_from[b];
-            ck(mid_adam(G.compute, p_arena + o, c->g_arena + o, c->m_arena + o, c->v_arena + o, n, t->learning_rate, t->weight_decay,
-                        t->base_mean_decay, t->base_var_decay, cur_b1, cur_b2, t->eps, c->nan_flag_dev, 1, c->loc_off_dev, c->n_loc, o), "Adam");
+            if (c->optim.kind != MI_OPT_ADAM)
+                ck(mi_optim_step(&c->optim, G.compute, p_arena, c->g_arena, c->m_arena, o, o + n, t->learning_rate, t->weight_decay,
+                                 c->nan_flag_dev, 0), c->optim.kind == MI_OPT_SGD ? "SGD" : "LARS");
+            else
+                ck(mid_adam(G.compute, p_arena + o, c->g_arena + o, c->m_arena + o, c->v_arena + o, n, t->learning_rate, t->weight_decay,
+                            t->base_mean_decay, t->base_var_decay, cur_b1, cur_b2, t->eps, c->nan_flag_dev, 1, c->loc_off_dev, c->n_loc, o), "Adam");
         }
         c->dp_pending = 0; c->n_buckets = 0;
     } else {
-        /* one launch over the whole arena; it also clears the gradients (:2972-2978) */
-        ck(mid_adam(G.compute, p_arena, c->g_arena, c->m_arena, c->v_arena, c->arena_floats, t->learning_rate, t->weight_decay,
+        /* one launch over the whole arena (LARS: norm pass, trust ratios, update); it also clears the gradients (:2972-2978) */
+        if (c->optim.kind != MI_OPT_ADAM)
+            ck(mi_optim_step(&c->optim, G.compute, p_arena, c->g_arena, c->m_arena, 0, c->arena_floats, t->learning_rate, t->weight_decay,
+                             c->nan_flag_dev, 0), c->optim.kind == MI_OPT_SGD ? "SGD" : "LARS");
+        else ck(mid_adam(G.compute, p_arena, c->g_arena, c->m_arena, c->v_arena, c->arena_floats, t->learning_rate, t->weight_decay,
                     t->base_mean_decay, t->base_var_decay, cur_b1, cur_b2, t->eps, c->nan_flag_dev, 1, c->loc_off_dev, c->n_loc, 0), "Adam");
     }
     if (c->input_reset) { /* :2981-2982 */
@@ -1243,6 +1356,7 @@ void update_parameters(Train_ResNet *t) {
     mid_event_record(c->ev_nan, G.compute);
     c->nan_check_pending = 1;
     c->params_dirty = 1; /* the re-laid weight copies are stale until the next forward_pass */
+    c->n_updates++;
     t->cur_mean_decay = cur_b1;
     t->cur_var_decay = cur_b2;
 }
@@ -1324,6 +1438,8 @@ void destroy_trainer(Train_ResNet *t) {
     mi_batch_ext_free(t->cur_batch);
     free(t->model->dims); free(t->model);
     free(t->loss_per_epoch); free(t->accuracy_per_epoch);
+    mi_optim_free(&c->optim);
+    free(c->loc_off);
     free(c->dump_root); free(c->blk); free(c);
     free(t);
 }

@@ -167,6 +167,20 @@ class Ops:
         self._chk(self.L.mi_op_adam(dp.ptr, dg.ptr, dm.ptr, dv.ptr, p.size, lr, wd, b1, b2, cur_b1, cur_b2, eps, flag.ptr), "adam")
         return dp.get(), dm.get(), dv.get(), int(flag.get()[0])
 
+    def momentum_update(self, kind, p, g, b, offsets, is_weight, lr, wd, momentum, trust=0.001):
+        """mi_op_momentum_update over one arena: p, g, b float32 arrays of the same length, tensor i = [offsets[i], offsets[i + 1]).
+        Returns (p, g, b, NaN flag, squared norms [n_tensors, 2] as (|w|^2, |g|^2) before the update)"""
+        dp, dg, db = (self.dev(np.ascontiguousarray(a, np.float32)) for a in (p, g, b))
+        flag = self.dev(np.zeros(1, np.int32))
+        off = np.ascontiguousarray(offsets, np.uint64)
+        isw = np.ascontiguousarray(is_weight, np.int32)
+        n_t = len(off) - 1
+        assert isw.size == n_t and C.sizeof(C.c_size_t) == 8
+        sq = np.zeros((n_t, 2), np.float64)
+        self._chk(self.L.mi_op_momentum_update(int(kind), dp.ptr, dg.ptr, db.ptr, p.size, off.ctypes.data, n_t, isw.ctypes.data, lr, wd,
+                                               momentum, trust, flag.ptr, sq.ctypes.data), "momentum_update")
+        return dp.get(), dg.get(), db.get(), int(flag.get()[0]), sq
+
     def nhwc_to_nchw(self, x):
         N, H, W, Cc = x.shape
         dx, do = self.dev(x), self.dev(shape=(N, Cc, H, W))

@@ -53,6 +53,22 @@ class Trainer:
             raise RuntimeError("mi_trainer_set_dtype: " + e)
         self.dtype = int(dtype)
 
+    OPTIMIZERS = {"adam": B.MI_OPT_ADAM, "sgd": B.MI_OPT_SGD, "lars": B.MI_OPT_LARS}
+
+    def set_optimizer(self, kind, momentum=0.9, trust=0.001):
+        """"adam" (the reference's, default), "sgd" (momentum SGD) or "lars"; before the first update (include/resnet_mi.h)"""
+        if self.L.mi_trainer_set_optimizer(self.t, self.OPTIMIZERS[kind], momentum, trust) != 0:
+            e = self.error()
+            self.L.mi_clear_error()
+            raise RuntimeError("mi_trainer_set_optimizer: " + e)
+
+    def optimizer(self):
+        return {v: k for k, v in self.OPTIMIZERS.items()}[self.L.mi_trainer_get_optimizer(self.t)]
+
+    def set_lr(self, lr):
+        """learning_rate for the next update_parameters and on (read at every update)"""
+        self.t.contents.learning_rate = lr
+
     def set_store_policy(self, policy):
         if self.L.mi_trainer_set_store_policy(self.t, int(policy)) != 0:
             e = self.error()
