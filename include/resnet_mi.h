@@ -455,6 +455,16 @@ int mi_op_stem_wgrad_f32(const float *x, const float *w_kcrs, const float *dy, f
  * Returns < 0 on error, else the number of statistics partial rows the convolution left (0 = separate statistics pass). */
 int mi_op_conv_bn_fwd_t(const void *x, const float *w_kcrs, void *conv_out, int dt, const float *gamma, const float *beta,
                         float *means, float *vars, void *y, int N, int C, int H, int K, int k, int stride, float eps, int relu);
+/* the same pair on the channel-last 3x3 forward (the bf16 trainer's route for 3x3 layers with channels % 64): x, conv_out, y bf16.
+ * -2: shape not covered; else < 0 on error, or the number of statistics partial rows the convolution left */
+int mi_op_conv_bn_fwd_bf16_cl(const void *x_bf16, const float *w_kcrs, void *conv_out_bf16, const float *gamma, const float *beta,
+                              float *means, float *vars, void *y_bf16, int N, int C, int H, int K, int stride, float eps, int relu);
+/* the stem (7x7 stride 2, 3 -> 64) and its BN + ReLU on the matrix cores: exact = 1 the fp32 trainer's (conv_dt fp32), exact = 0 the bf16
+ * trainer's with conv_out stored as conv_dt (fp32 or bf16); y stored as a_dt.  Returns as mi_op_conv_bn_fwd_t. */
+int mi_op_stem_bn_fwd_t(const float *x, const float *w_kcrs, void *conv_out, int conv_dt, const float *gamma, const float *beta,
+                        float *means, float *vars, void *y, int a_dt, int N, int H, float eps, int exact);
+/* the bf16 stem's weight gradient from dy stored as dy_dt (fp32 or bf16) */
+int mi_op_stem_wgrad_bf16_t(const float *x, const float *w_kcrs, const void *dy, int dy_dt, float *dw_kcrs, int N, int H);
 int mi_op_bn_fwd_t(const void *x, int x_dt, const float *gamma, const float *beta, const void *residual, float *means, float *vars,
                    void *y, int a_dt, int N, int C, int H, float eps, int relu);
 int mi_op_bn_apply_t(const void *x, int x_dt, const float *gamma, const float *beta, const void *residual, const float *means,

@@ -214,6 +214,9 @@ PROTOTYPES = {
     "mi_op_stem_fwd_bf16": (_i, [_vp, _vp, _vp, _i, _i]),
     "mi_op_stem_wgrad_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
     "mi_op_conv_bn_fwd_t": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i]),
+    "mi_op_conv_bn_fwd_bf16_cl": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i]),
+    "mi_op_stem_bn_fwd_t": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i]),
+    "mi_op_stem_wgrad_bf16_t": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
     "mi_op_bn_fwd_t": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i]),
     "mi_op_bn_apply_t": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i]),
     "mi_op_bn_bwd_t": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i]),

@@ -308,6 +308,67 @@ int mi_op_conv_bn_fwd_t(const void *x, const float *w, void *conv_out, int dt, c
     ws_free(&ws);
     return rc < 0 ? rc : parts.nparts; /* > 0: the statistics were fused (number of partial rows), 0: separate pass */
 }
+/* the same pair on a bf16 3x3 layer whose forward takes the channel-last kernel (unit_fwd, MI_FWD_CL): weights re-laid, input re-laid
+ * into a zeroed operand, the channel-last forward leaving the statistics partials, the BN behind it.  All image tensors bf16. */
+int mi_op_conv_bn_fwd_bf16_cl(const void *x, const float *w, void *conv_out, const float *gamma, const float *beta, float *means,
+                              float *vars, void *y, int N, int C, int H, int K, int stride, float eps, int relu) {
+    if (!mid_cl_supported(0, N, C, H, K, stride)) return -2;
+    mid_stream st = mi_global()->compute;
+    const int Ho = H / stride;
+    const size_t xb = mid_cl_operand_bytes(0, N, C, H, K, stride);
+    mid_bn_parts parts = {NULL, mid_bn_parts_floats(N, K, Ho), 0}; /* (what size_workspaces gives every unit of the layer's block, or more) */
+    void *xp = mid_malloc(xb), *at = mid_malloc((size_t)9 * C * K * 2);
+    parts.buf = (float *)mid_malloc(parts.floats * sizeof(float));
+    float *bws = (float *)mid_malloc(mid_bn_ws_floats(K) * sizeof(float));
+    int rc = (!xp || !at || !parts.buf || !bws) ? -3 : 0;
+    if (!rc) { mid_memset(xp, 0, xb, st); rc = mid_bf16_prelayout_fwd(st, w, at, K, C, 3); }
+    if (!rc) rc = mid_cl_relayout(st, x, xp, N, C, H, stride == 2);
+    if (!rc) rc = mid_cl_fwd(st, xp, at, conv_out, N, C, H, K, stride, &parts);
+    if (!rc) rc = mid_bn_fwd_t(st, bws, &parts, conv_out, MID_BF16, gamma, beta, NULL, means, vars, y, MID_BF16, NULL, NULL, N, K, Ho * Ho, eps, relu, NULL, 0);
+    rc = finish(rc);
+    mid_free(bws); mid_free(parts.buf);
+    mid_free(xp); mid_free(at);
+    return rc < 0 ? rc : parts.nparts;
+}
+/* the stem and its BN + ReLU as forward_pass runs them on the matrix cores: exact = 1 MI_FWD_STEM_F32 (conv_out fp32), exact = 0
+ * MI_FWD_STEM_BF16 with conv_out fp32 or bf16 (mi_trainer_stem_dtype); a_dt = storage type of y.  The statistics come from the stem
+ * kernel's partials.  Returns < 0 on error, else the number of partial rows (0 = separate statistics pass). */
+int mi_op_stem_bn_fwd_t(const float *x, const float *w, void *conv_out, int conv_dt, const float *gamma, const float *beta, float *means,
+                        float *vars, void *y, int a_dt, int N, int H, float eps, int exact) {
+    if (!mid_stem_bf16_supported(3, H, 64, 7, 2) || (exact && conv_dt != MID_F32)) return -2;
+    mid_stream st = mi_global()->compute;
+    const int Ho = H / 2;
+    const size_t xb = exact ? mid_stem_f32_xp_bytes(N, H) : mid_stem_bf16_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
+    /* the trainer's partials table is sized for its largest block unit, the first expansion (4 x 64 channels over a quarter of the
+     * stem's pixels): at least this */
+    mid_bn_parts parts = {NULL, mid_bn_parts_floats(N, 64, Ho), 0};
+    void *xp = mi_malloc(xb);
+    float *sc = (float *)mid_malloc(sf * sizeof(float)), *bws = (float *)mid_malloc(mid_bn_ws_floats(64) * sizeof(float));
+    parts.buf = (float *)mid_malloc(parts.floats * sizeof(float));
+    int rc = (!xp || !sc || !bws || !parts.buf) ? -3 : 0;
+    if (!rc) rc = exact ? mid_stem_fwd_f32(st, x, w, (float *)conv_out, xp, xb, sc, sf, N, H, &parts)
+                        : mid_stem_fwd_bf16(st, x, w, conv_out, conv_dt, xp, xb, sc, sf, N, H, &parts);
+    if (!rc) rc = mid_bn_fwd_t(st, bws, &parts, conv_out, conv_dt, gamma, beta, NULL, means, vars, y, a_dt, NULL, NULL, N, 64, Ho * Ho, eps, 1, NULL, 0);
+    rc = finish(rc);
+    mid_free(parts.buf); mid_free(bws); mid_free(sc);
+    mi_free(xp);
+    return rc < 0 ? rc : parts.nparts;
+}
+/* the bf16 stem's weight gradient from dy stored as dy_dt (bf16: the stem tensors of the bf16 trainer, mi_trainer_stem_dtype) */
+int mi_op_stem_wgrad_bf16_t(const float *x, const float *w, const void *dy, int dy_dt, float *dw, int N, int H) {
+    if (!mid_stem_bf16_supported(3, H, 64, 7, 2)) return -2;
+    const size_t xb = mid_stem_bf16_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
+    void *xp = mi_malloc(xb);
+    float *sc = (float *)mid_malloc(sf * sizeof(float));
+    void *y = mi_malloc((size_t)N * 64 * (H / 2) * (H / 2) * (dy_dt == MID_BF16 ? 2 : 4));
+    int rc = (!xp || !sc || !y) ? -3 : mid_stem_fwd_bf16(mi_global()->compute, x, w, y, dy_dt, xp, xb, sc, sf, N, H, NULL); /* leaves the padded planes in xp */
+    if (!rc) rc = mid_stem_wgrad_bf16(mi_global()->compute, xp, dy, dy_dt, dw, sc, sf, N, H);
+    rc = finish(rc);
+    mi_free(y);
+    mid_free(sc);
+    mi_free(xp);
+    return rc;
+}
 int mi_op_bn_fwd_t(const void *x, int x_dt, const float *gamma, const float *beta, const void *residual, float *means, float *vars,
                    void *y, int a_dt, int N, int C, int H, float eps, int relu) {
     float *ws = (float *)mid_malloc(mid_bn_ws_floats(C) * sizeof(float));

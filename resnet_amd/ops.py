@@ -367,6 +367,40 @@ class Ops:
             self._chk(rc, "conv_bn_fwd_t")
         return self.get_t(dc, dt), dm.get(), dv.get(), self.get_t(dy, dt), rc > 0
 
+    def conv_bn_fwd_bf16_cl(self, x, w, gamma, beta, stride, eps, relu):
+        """conv + BN on the channel-last 3x3 forward (the bf16 trainer's MI_FWD_CL); returns as conv_bn_fwd_t"""
+        N, Cc, H, _ = x.shape
+        K = w.shape[0]
+        Ho = H // stride
+        BF = B.MI_DTYPE_BF16
+        dx, dw, dg, db = self.dev_t(x, BF), self.dev(w), self.dev(gamma), self.dev(beta)
+        dc, dy = self.new_t((N, K, Ho, Ho), BF), self.new_t((N, K, Ho, Ho), BF)
+        dm, dv = self.dev(shape=(K,)), self.dev(shape=(K,))
+        rc = self.L.mi_op_conv_bn_fwd_bf16_cl(dx.ptr, dw.ptr, dc.ptr, dg.ptr, db.ptr, dm.ptr, dv.ptr, dy.ptr, N, Cc, H, K, stride, eps, int(relu))
+        if rc < 0:
+            self._chk(rc, "conv_bn_fwd_bf16_cl")
+        return self.get_t(dc, BF), dm.get(), dv.get(), self.get_t(dy, BF), rc > 0
+
+    def stem_bn_fwd_t(self, x, w, gamma, beta, eps, conv_dt, a_dt, exact):
+        """the matrix-core stem + BN + ReLU (MI_FWD_STEM_F32 with exact, else MI_FWD_STEM_BF16); conv_out stored as conv_dt, y as a_dt;
+        returns as conv_bn_fwd_t"""
+        N, _, H, _ = x.shape
+        Ho = H // 2
+        dx, dw, dg, db = self.dev(x), self.dev(w), self.dev(gamma), self.dev(beta)
+        dc, dy = self.new_t((N, 64, Ho, Ho), conv_dt), self.new_t((N, 64, Ho, Ho), a_dt)
+        dm, dv = self.dev(shape=(64,)), self.dev(shape=(64,))
+        rc = self.L.mi_op_stem_bn_fwd_t(dx.ptr, dw.ptr, dc.ptr, conv_dt, dg.ptr, db.ptr, dm.ptr, dv.ptr, dy.ptr, a_dt, N, H, eps, int(exact))
+        if rc < 0:
+            self._chk(rc, "stem_bn_fwd_t")
+        return self.get_t(dc, conv_dt), dm.get(), dv.get(), self.get_t(dy, a_dt), rc > 0
+
+    def stem_wgrad_bf16_t(self, x, w, dy, dy_dt):
+        """the bf16 stem's weight gradient from dy stored as dy_dt"""
+        N, _, H, _ = x.shape
+        dx, dw, ddy, out = self.dev(x), self.dev(w), self.dev_t(dy, dy_dt), self.dev(shape=w.shape)
+        self._chk(self.L.mi_op_stem_wgrad_bf16_t(dx.ptr, dw.ptr, ddy.ptr, dy_dt, out.ptr, N, H), "stem_wgrad_bf16_t")
+        return out.get()
+
     def bn_apply_t(self, x, gamma, beta, means, vars_, eps, relu, x_dt, a_dt, residual=None):
         N, Cc, H, _ = x.shape
         dx, dg, db, dm, dv = self.dev_t(x, x_dt), self.dev(gamma), self.dev(beta), self.dev(means), self.dev(vars_)

@@ -190,6 +190,15 @@ def bn_stats_ref(ref, A):
     return mu, var, bm, bv
 
 
+def conv_stats_violations(gm, gv, ref, A):
+    """channels of the kernel's (means, vars) [of the R slab's channels] outside the bounds of bn_stats_ref(ref, A), and the worst distance in
+    2^-24 (bound scale) units"""
+    mu, var, bm, bv = bn_stats_ref(ref, A)
+    em, ev = np.abs(np.asarray(gm, np.float64) - mu), np.abs(np.asarray(gv, np.float64) - var)
+    bad = int(np.count_nonzero(~(em <= bm))) + int(np.count_nonzero(~(ev <= bv)))
+    return bad, float(max(np.max(em / bm), np.max(ev / bv))) * C_FACTOR
+
+
 def bn_grad_sums(g, bn_x, means, vars_, eps):
     """float64 dbeta = sum g, dgamma = sum g (x - mean) / sqrt(var + eps) per channel of the product's own gated gradient g, with
     sum |terms| of each"""
@@ -303,17 +312,86 @@ def bf16_route(L, op, N, Cn, H, K, k, s):
     return "pw" if k == 1 and ok("pw", "wgrad") else "default"
 
 
-def batch256_cases(L):
-    """(dtype, route, op, C, H, K, k, stride, where): every (layer, route) pair of the trainer at N = 256 in both storage types, and
-    the 1x1 forward on a channel-last input (mi_op_conv1x1_fwd_bf16_cl) at every 1x1 layer"""
+def blocks(dims):
+    """the bottleneck blocks of a net (plan_layers' walk of init_dimensions' table): incoming / reduced / expanded channels, incoming plane,
+    stride, and whether the block has a projection; with the stem's output plane Hs and filters f"""
+    f, Hs = dims["init_conv_filters"], dims["input"] // dims["init_conv_stride"]
+    out = []
+    inc, red, ex, H = f, f, 4 * f, Hs // dims["init_maxpool_stride"]
+    for i in range(dims["n_conv_blocks"]):
+        s = 1
+        if dims["is_block_spatial_reduction"][i]:
+            s, red, ex = 2, red * 2, ex * 2
+        out.append(dict(inc=inc, red=red, ex=ex, H=H, s=s, proj=inc != ex))
+        inc, H = ex, H // s
+    return out
+
+
+def trainer_units(dims):
+    """(block, role, (C, H, K, k, stride), site) of every bottleneck convolution in plan_layers order (per block: reduction, spatial,
+    expansion, projection); site = its bit in plan_conv's BN'-fusion masks: 4 the reduction of block i > 0 whose block below (i - 1) has no
+    projection (its dgrad feeds that block's expansion BN'), 2 every spatial layer, 1 every expansion, 0 the projections"""
+    bl = blocks(dims)
+    out = []
+    for i, b in enumerate(bl):
+        H, s = b["H"], b["s"]
+        out.append((i, "red", (b["inc"], H, b["red"], 1, 1), 4 if i > 0 and not bl[i - 1]["proj"] else 0))
+        out.append((i, "spa", (b["red"], H, b["red"], 3, s), 2))
+        out.append((i, "exp", (b["red"], H // s, b["ex"], 1, 1), 1))
+        if b["proj"]:
+            out.append((i, "proj", (b["inc"], H, b["ex"], 3 if s == 2 else 1, s), 0))
+    return out
+
+
+def trainer_layers(dims):
+    """the distinct convolution shapes of a net in order of first appearance, (C, H, K, k, stride, where): where names each role the
+    shape plays, "b<i> <role>" where one block has it, "stage <j> <role>" where several blocks of stage j do (stages 1, 2, ... begin at
+    block 0 and at every striding block).  "red" in where: the dgrad takes the shortcut gradient as its addend (backwards_pass,
+    red_addend, every block)"""
+    bl = blocks(dims)
+    stage, st = [], 0
+    for b in bl:
+        st += b["s"] == 2 or not stage
+        stage.append(st)
+    occ = {}
+    for i, role, shape, _ in trainer_units(dims):
+        occ.setdefault(shape, {}).setdefault(role, []).append(i)
+    out = []
+    for shape, roles in occ.items():
+        tags = []
+        for role, idx in roles.items():
+            idx = sorted(set(idx))
+            tags.append("b%d %s" % (idx[0], role) if len(idx) == 1 else "stage %d %s" % (stage[idx[0]], role))
+        out.append(shape + (", ".join(tags),))
+    return out
+
+
+def trainer_sites(dims):
+    """shape -> the set of BN'-fusion sites (trainer_units) its occurrences have"""
+    out = {}
+    for _, _, shape, site in trainer_units(dims):
+        out.setdefault(shape, set()).add(site)
+    return out
+
+
+def trainer_conv_cases(L, dims, N):
+    """(dtype, route, op, C, H, K, k, stride, where): every (layer, route) pair the trainer of this net at batch N gives in both storage
+    types (bf16: plan_conv's routes with default switches, bf16_route), and the 1x1 forward on a channel-last input
+    (mi_op_conv1x1_fwd_bf16_cl) at every 1x1 layer"""
     cases = []
-    for (Cn, H, K, k, s, where) in LAYERS:
+    for (Cn, H, K, k, s, where) in trainer_layers(dims):
         for op in OPS:
             cases.append(("f32", "default", op, Cn, H, K, k, s, where))
-            cases.append(("bf16", bf16_route(L, op, N256, Cn, H, K, k, s), op, Cn, H, K, k, s, where))
+            cases.append(("bf16", bf16_route(L, op, N, Cn, H, K, k, s), op, Cn, H, K, k, s, where))
         if k == 1:
             cases.append(("bf16", "pw", "fwd", Cn, H, K, k, s, where))
     return cases
+
+
+def batch256_cases(L):
+    """trainer_conv_cases of ResNet-50 at the benchmark's batch"""
+    import synth
+    return trainer_conv_cases(L, synth.R50_DIMS, N256)
 
 
 # the stem (plan_layers: 7x7 stride 2, 3 -> 64 filters, 224 x 224): the fp32 trainer runs it exactly on the fp32 matrix cores
@@ -321,23 +399,52 @@ def batch256_cases(L):
 STEM = (3, 224, 64, 7, 2)
 
 
-def conv_bn_cases():
+def trainer_conv_bn_cases(dims):
     """(dtype, C, H, K, k, stride, where): forward_pass pairs every convolution with its BN (mi_op_conv_bn_fwd_t: statistics from the
-    convolution's epilogue)"""
-    return [(dt,) + layer for layer in LAYERS for dt in ("f32", "bf16")]
+    convolution's epilogue; the bf16 layers on the NCHW kernels -- the channel-last ones are trainer_conv_bn_cl_cases)"""
+    return [(dt,) + layer for layer in trainer_layers(dims) for dt in ("f32", "bf16")]
 
 
-def dgrad_bn_cases():
-    """(dtype, C, H, K, k, stride, where) of the dgrads that also do the BN' reduction (plan_conv's L->fz, trainer.c): site 4 = the
-    reduction dgrad of block i > 0 whose block above has no projection (every "red" shape but b0's; it takes the shortcut addend),
-    site 1 = every expansion dgrad, site 2 = the spatial dgrad -- fp32: site 4 only (RESNET_MI_F32_BNFUSE_BWD = 4); bf16: every site
-    whose dgrad is on the NCHW kernels (the spatial dgrads of ResNet-50 all take the channel-last kernels)"""
+def trainer_conv_bn_cl_cases(L, dims, N):
+    """(C, H, K, k, stride, where) of the bf16 layers whose forward takes the channel-last kernel at batch N (unit_fwd's MI_FWD_CL:
+    mi_op_conv_bn_fwd_bf16_cl, statistics from that kernel's epilogue)"""
+    return [layer for layer in trainer_layers(dims) if bf16_route(L, "fwd", N, *layer[:5]) == "cl"]
+
+
+def trainer_dgrad_bn_cases(L, dims, N):
+    """(dtype, C, H, K, k, stride, where) of the dgrads that also do the BN' reduction (plan_conv's L->fz, trainer.c) at batch N: fp32 the
+    site-4 layers only (RESNET_MI_F32_BNFUSE_BWD = 4); bf16 every site (trainer_units) whose dgrad is on the NCHW kernels (bf16_route)"""
+    sites = trainer_sites(dims)
     out = []
-    for layer in LAYERS:
-        Cn, H, K, k, s, where = layer
-        red = "red" in where and where != "b0 red"
-        if red:
+    for layer in trainer_layers(dims):
+        st = sites[layer[:5]]
+        if 4 in st:
             out.append(("f32",) + layer)
-        if red or " exp" in where:
+        if st & {1, 2, 4} and bf16_route(L, "dgrad", N, *layer[:5]) == "default":
             out.append(("bf16",) + layer)
     return out
+
+
+def conv_bn_cases():
+    """trainer_conv_bn_cases of ResNet-50"""
+    import synth
+    return trainer_conv_bn_cases(synth.R50_DIMS)
+
+
+def dgrad_bn_cases(L):
+    """trainer_dgrad_bn_cases of ResNet-50 at N = 256: site 4 = every "red" shape but b0's (it takes the shortcut addend), site 1 = every
+    expansion dgrad; the spatial dgrads (site 2) of ResNet-50 all take the channel-last kernels there"""
+    import synth
+    return trainer_dgrad_bn_cases(L, synth.R50_DIMS, N256)
+
+
+# the nets the per-element files check: (name, dims, N) -- ResNet-50 at the benchmark's batch and at a batch whose column counts are no
+# multiple of any tile (33: every fwd / dgrad plan of the list has a partial last tile), the trajectory tests' nets at their batches
+def nets():
+    import synth
+    return {"r50": synth.R50_DIMS, "c1s": synth.C1S_DIMS, "c4i": synth.C4I_DIMS}
+
+
+def stem_shape(dims):
+    """(C, H, K, k, stride) of the stem"""
+    return (3, dims["input"], dims["init_conv_filters"], dims["init_kernel_dim"], dims["init_conv_stride"])

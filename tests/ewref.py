@@ -220,14 +220,14 @@ def softmax_rows(N, L, seed):
     """logits of the benchmark's scale, plus rows with |x| ~ 80-100 (where a soft-max without the max subtraction overflows or flushes to
     0 / 0) and rows with many equal maxima"""
     rng = np.random.default_rng(seed)
-    x = (rng.standard_normal((N, L)) * 3.0).astype(np.float32)
+    x = (rng.standard_normal((max(N, 7), L)) * 3.0).astype(np.float32)
     x[1] += np.float32(95.0)
     x[2] -= np.float32(110.0)
     x[3] = np.float32(88.0)                                     # every entry the maximum
     x[4, rng.choice(L, 37, replace=False)] = x[4].max() + np.float32(1.0)
     x[5] = np.round(x[5])                                      # many ties, including at the maximum
     x[6, ::2] = np.float32(80.0); x[6, 1::2] = np.float32(-80.0)
-    return x
+    return x if N >= 7 else x[np.arange(N) * 6 // max(1, N - 1) if N > 1 else [0]].copy()  # (small N: rows spread over the planted ones)
 
 
 def avgpool_ref(x):
@@ -291,7 +291,7 @@ def arena_floats(dims):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the batch-norm sites of ResNet-50 at N = 256.  Forward forms: "relu" (stem, reduction, spatial), "none" (projection), "add_relu"
+# the batch-norm sites of ResNet-50 (any N: the plane sizes do not depend on it).  Forward forms: "relu" (stem, reduction, spatial), "none" (projection), "add_relu"
 # (expansion: + shortcut, ReLU), and in bf16 the dual writes of bn_apply_cl_kernel: "cl plane" / "cl par" (the reduction BN writes its 3x3's
 # channel-last input), "cl par add_relu" (the expansion BN writes the next block's projection input as parity planes).  Backward modes
 # (mid_bn_bwd_t): 1 = gate recomputed from y > 0, 3 = external mask + gated dy written, 0 = dy already gated.
@@ -314,12 +314,61 @@ BN_SHAPES = [
 ]
 
 
-def _pairs(Cn, H):
-    return ("f32", "bf16", "f32>bf16") if (Cn, H) == STEM_SHAPE else ("f32", "bf16")
+FORM_ORDER = ("relu", "cl plane", "cl par", "none", "add_relu", "cl par add_relu")
+MODE_ORDER = (1, 3, 0)
+
+
+def bn_shapes(dims):
+    """BN_SHAPES of any net: every (C, H) a batch norm of forward_pass normalises, in order of first appearance, with every forward form and
+    backward mode the net's structure allows there -- the channel-last dual writes wherever a 3x3 reads the output (the reduction BN in front
+    of a stride-1 / stride-2 spatial convolution, the expansion BN in front of the next block's stride-2 projection; parity planes only over
+    even planes), whichever route the trainer then takes"""
+    f, Hs = dims["init_conv_filters"], dims["input"] // dims["init_conv_stride"]
+    forms, modes = {(f, Hs): {"relu"}}, {(f, Hs): {1}}
+    bl = R.blocks(dims)
+
+    def add(Cn, H, form, mode=None):
+        forms.setdefault((Cn, H), set()).add(form)
+        modes.setdefault((Cn, H), set()).update(() if mode is None else (mode,))
+
+    for i, b in enumerate(bl):
+        H, s, Ho = b["H"], b["s"], b["H"] // b["s"]
+        nxt = bl[i + 1] if i + 1 < len(bl) else None
+        add(b["red"], H, "relu", 1)
+        if s == 1 or H % 2 == 0:
+            add(b["red"], H, "cl plane" if s == 1 else "cl par")
+        add(b["red"], Ho, "relu", 1)
+        if b["proj"]:
+            add(b["ex"], Ho, "none", 3)
+        add(b["ex"], Ho, "add_relu", 0 if b["proj"] else 3)
+        if nxt and nxt["proj"] and nxt["s"] == 2 and nxt["H"] % 2 == 0:
+            add(b["ex"], Ho, "cl par add_relu")
+    return [(Cn, H, tuple(x for x in FORM_ORDER if x in forms[(Cn, H)]), tuple(m for m in MODE_ORDER if m in modes[(Cn, H)]))
+            for (Cn, H) in forms]
+
+
+def _pairs(Cn, H, stem=STEM_SHAPE):
+    return ("f32", "bf16", "f32>bf16") if (Cn, H) == stem else ("f32", "bf16")
+
+
+def trainer_bn_fwd_cases(dims):
+    """(pair, C, H, forms) over bn_shapes(dims): the channel-last forms in bf16 storage only; the stem also as "f32>bf16" """
+    stem = (dims["init_conv_filters"], dims["input"] // dims["init_conv_stride"])
+    out = []
+    for Cn, H, forms, _ in bn_shapes(dims):
+        for pr in _pairs(Cn, H, stem):
+            out.append((pr, Cn, H, tuple(f for f in forms if pr == "bf16" or not f.startswith("cl"))))
+    return out
+
+
+def trainer_bn_bwd_cases(dims):
+    """(pair, C, H, mode) over bn_shapes(dims)"""
+    stem = (dims["init_conv_filters"], dims["input"] // dims["init_conv_stride"])
+    return [(pr, Cn, H, mode) for Cn, H, _, modes in bn_shapes(dims) for pr in _pairs(Cn, H, stem) for mode in modes]
 
 
 def bn_fwd_cases():
-    """(pair, C, H, forms): the channel-last forms in bf16 storage only"""
+    """(pair, C, H, forms) of BN_SHAPES (ResNet-50): the channel-last forms in bf16 storage only"""
     out = []
     for Cn, H, forms, _ in BN_SHAPES:
         for pr in _pairs(Cn, H):
@@ -332,22 +381,16 @@ def bn_bwd_cases():
     return [(pr, Cn, H, mode) for Cn, H, _, modes in BN_SHAPES for pr in _pairs(Cn, H) for mode in modes]
 
 
-def trainer_bn_sites(L, dims=None):
+def trainer_bn_sites(L, dims=None, N=None):
     """every (pair, C, H, "fwd", form) and (pair, C, H, "bwd", mode) that forward_pass / backwards_pass (resnet_amd/csrc/trainer.c) produce
-    for ResNet-50 at N = 256 with default switches, restated from plan_layers, unit_fwd and unit_bwd; mode "parts" = the BN' whose reduction
-    a fusing dgrad did (mid_bn_bwd_parts_t, test_gpu_batch256.py's dgrad cases).  L: the library (mi_conv_plan answers the route queries)"""
+    for the net (default ResNet-50) at batch N (default 256) with default switches, restated from plan_layers, unit_fwd and unit_bwd; mode
+    "parts" = the BN' whose reduction a fusing dgrad did (mid_bn_bwd_parts_t, the dgrad cases of convref.trainer_dgrad_bn_cases).  L: the
+    library (mi_conv_plan answers the route queries)"""
     import synth
     d = dims or synth.R50_DIMS
-    N = R.N256
+    N = N or R.N256
     f, Hs = d["init_conv_filters"], d["input"] // d["init_conv_stride"]
-    blocks = []
-    inc, red, ex, H = f, f, 4 * f, Hs // d["init_maxpool_stride"]
-    for i in range(d["n_conv_blocks"]):
-        s = 1
-        if d["is_block_spatial_reduction"][i]:
-            s, red, ex = 2, red * 2, ex * 2
-        blocks.append(dict(inc=inc, red=red, ex=ex, H=H, s=s, proj=inc != ex))
-        inc, H = ex, H // s
+    blocks = R.blocks(d)
     out = set()
     for dt in ("f32", "bf16"):
         bf = dt == "bf16"
@@ -358,10 +401,10 @@ def trainer_bn_sites(L, dims=None):
             out.add((pr, f, Hs, "bwd", 1))
 
         def fuses(site, Cn, H, K, k, s):
-            """plan_conv's L->fz and whether the launch fuses: fp32 site 4 only (RESNET_MI_F32_BNFUSE_BWD = 4); bf16 every site whose dgrad
-            runs on the NCHW kernels, which fuse where the plane is a multiple of 4"""
-            if not bf:
-                return site == 4
+            """plan_conv's L->fz and whether the launch fuses: fp32 site 4 only (RESNET_MI_F32_BNFUSE_BWD = 4) where the dgrad runs on the
+            implicit GEMM; bf16 every site whose dgrad runs on the NCHW kernels, which fuse where the plane is a multiple of 4"""
+            if not bf:  # (mi_op_conv_dgrad_bn_bwd_f32 fuses where the dgrad runs on the implicit GEMM)
+                return site == 4 and R.conv_plan(L, 0, "default", "dgrad", N, Cn, H, K, k, s) is not None
             return route("dgrad", Cn, H, K, k, s) == "default" and (H * H) % 4 == 0
 
         for i, b in enumerate(blocks):

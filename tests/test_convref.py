@@ -246,3 +246,215 @@ def test_conv_plan_refuses_and_matches_the_implicit_gemm_view():
                 continue
             assert L.mi_conv_plan(0, 0, op, 256, Cn, H, K, k, s, out) == 0
             assert (out[0], out[2], out[3], out[4], out[5]) == (d[1], d[2], d[3], d[4], d[6])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the case lists built from (dims, N)
+def _lib():
+    from resnet_amd import binding as B
+    return B.load()
+
+
+def test_generalized_lists_reproduce_the_batch256_lists():
+    """trainer_layers / trainer_conv_cases / trainer_conv_bn_cases / trainer_dgrad_bn_cases of ResNet-50 at N = 256 are the lists the
+    batch-256 file checked when they were written by hand: LAYERS, every (layer, op) in fp32 and on its bf16 route plus the 1x1 forward on a
+    channel-last input, conv + BN per layer and dtype, dgrad + BN' at every reduction but b0's (fp32 and bf16) and every expansion (bf16)"""
+    import synth
+    L = _lib()
+    assert R.trainer_layers(synth.R50_DIMS) == R.LAYERS
+    want = []
+    for (Cn, H, K, k, s, where) in R.LAYERS:
+        for op in R.OPS:
+            want.append(("f32", "default", op, Cn, H, K, k, s, where))
+            want.append(("bf16", R.bf16_route(L, op, R.N256, Cn, H, K, k, s), op, Cn, H, K, k, s, where))
+        if k == 1:
+            want.append(("bf16", "pw", "fwd", Cn, H, K, k, s, where))
+    assert R.batch256_cases(L) == want
+    assert R.conv_bn_cases() == [(dt,) + layer for layer in R.LAYERS for dt in ("f32", "bf16")]
+    want = []
+    for layer in R.LAYERS:
+        red = "red" in layer[5] and layer[5] != "b0 red"
+        if red:
+            want.append(("f32",) + layer)
+        if red or " exp" in layer[5]:
+            want.append(("bf16",) + layer)
+    assert R.dgrad_bn_cases(L) == want
+    # every fp32 site fuses (its dgrad runs on the implicit GEMM), every bf16 3x3 forward runs channel-last
+    assert all(R.conv_plan(L, 0, "default", "dgrad", R.N256, *c[1:6]) is not None for c in want if c[0] == "f32")
+    assert R.trainer_conv_bn_cl_cases(L, synth.R50_DIMS, R.N256) == [layer for layer in R.LAYERS if layer[3] == 3]
+
+
+def _kinds(L, cases, N, table=None):
+    """the plan kinds of test_batch256_cases_reach_every_plan_kind, plus the partial last column tile per route family and the partial tile
+    inside a sliced round (fp32 fwd / dgrad); prints the table"""
+    kinds, sliced_partial = set(), 0
+    for (dt, route, op, Cn, H, K, k, s, where) in cases:
+        p = R.conv_plan(L, 0 if dt == "f32" else 1, route, op, N, Cn, H, K, k, s)
+        if table is not None:
+            table.append("%-5s %-7s %-5s %-22s %-24s %s" % (dt, route, op, (Cn, H, K, k, s), where, p if p else "other kernels"))
+        if p is None:
+            assert dt == "f32" and op == "wgrad", "a bf16 route the trainer takes refuses its shape: %s" % ((dt, route, op, Cn, H, K, k, s),)
+            continue
+        bm, bn, tiles, full, slices, splits, grouped = p
+        if dt == "f32" and op != "wgrad" and 0 < full < tiles and slices > 1:
+            kinds.add("mixed " + op)
+        if dt == "f32":
+            kinds.add("bm%d" % bm)
+        if op == "wgrad" and splits >= 16 and grouped:
+            kinds.add("splits>=16 grouped")
+        if op == "wgrad" and 2 <= splits < 16:
+            kinds.add("2<=splits<16")
+        if route in ("cl", "cl2", "pw") and op == "wgrad" and splits > 1:
+            kinds.add(route + " wgrad split")
+        if dt == "bf16" and route == "default":
+            kinds.add("bf16 nchw bm%d" % bm)
+        if op != "wgrad":
+            P = (H // s) ** 2 if op == "fwd" else H * H
+            cols = N * ((P + 7) // 8 * 8 if dt == "bf16" and route == "default" else P)
+            if cols % bn:
+                fam = {"f32": "f32 igemm"}.get(dt, {"default": "bf16 nchw", "cl": "channel-last", "pw": "channel-last"}[route])
+                kinds.add("partial tile " + fam)
+                if dt == "f32" and 0 < full < tiles and slices > 1:  # (the sliced tail round behind the whole ones holds the last tiles)
+                    kinds.add("partial tile in a sliced round")
+                    sliced_partial += 1
+    return kinds, sliced_partial
+
+
+PLAN_KINDS = {"mixed fwd", "mixed dgrad", "bm64", "bm128", "splits>=16 grouped", "2<=splits<16", "cl2 wgrad split", "pw wgrad split",
+              "bf16 nchw bm64", "bf16 nchw bm128"}
+
+
+def test_batch33_cases_reach_every_plan_kind_and_partial_tiles():
+    """ResNet-50 at N = 33 (test_gpu_ragged.py): every plan kind of the batch-256 list, a partial last column tile on every fwd / dgrad
+    case (the fp32 implicit GEMM, the bf16 NCHW and the channel-last kernels), and partial tiles inside sliced rounds -- none of which N = 256
+    has"""
+    import synth
+    L = _lib()
+    table = []
+    kinds, nsp = _kinds(L, R.trainer_conv_cases(L, synth.R50_DIMS, 33), 33, table)
+    print("\nResNet-50 at N = 33\n%-5s %-7s %-5s %-22s %-24s %s" % ("dtype", "route", "op", "(C, H, K, k, s)", "where",
+                                                                 "bm bn tiles full slices splits grouped"))
+    print("\n".join(table))
+    print("kinds: %s; fp32 fwd / dgrad cases with the partial tile inside a sliced tail round: %d" % (sorted(kinds), nsp))
+    want = PLAN_KINDS | {"partial tile f32 igemm", "partial tile bf16 nchw", "partial tile channel-last", "partial tile in a sliced round"}
+    assert want <= kinds, want - kinds
+    k256, n256 = _kinds(L, R.batch256_cases(L), R.N256)
+    assert not any(k.startswith("partial") for k in k256) and n256 == 0, "N = 256 fills every column tile"
+    # every fp32 / bf16 fwd and dgrad of the 256 list ends in a partial tile at N = 33
+    for (dt, route, op, Cn, H, K, k, s, where) in R.trainer_conv_cases(L, synth.R50_DIMS, 33):
+        if op == "wgrad" or route == "pw" or dt == "f32" and R.conv_plan(L, 0, route, op, 33, Cn, H, K, k, s) is None:
+            continue
+        p = R.conv_plan(L, 0 if dt == "f32" else 1, route, op, 33, Cn, H, K, k, s)
+        P = (H // s) ** 2 if op == "fwd" else H * H
+        assert 33 * ((P + 7) // 8 * 8 if dt == "bf16" and route == "default" else P) % p[1], (dt, route, op, Cn, H, K, k, s)
+
+
+def test_trajectory_nets_hold_their_trainers_routes():
+    """C1S and C4I at N = 4, ResNet-50 at N = 8 (test_gpu_trajectory.py's nets and batches): every convolution of plan_layers is in the
+    list in fp32 and on the bf16 route plan_conv gives it, every route the list names plans the shape, and the 3x3 layers run channel-last
+    on the 8 x 8 and 4 x 4 planes"""
+    L = _lib()
+    for net, N in (("c1s", 4), ("c4i", 4), ("r50", 8)):
+        d = R.nets()[net]
+        cases = R.trainer_conv_cases(L, d, N)
+        shapes = {u[2] for u in R.trainer_units(d)}
+        assert {c[3:8] for c in cases} == shapes
+        for (Cn, H, K, k, s) in shapes:
+            for op in R.OPS:
+                assert ("f32", "default", op) in {c[:3] for c in cases if c[3:8] == (Cn, H, K, k, s)}
+                assert ("bf16", R.bf16_route(L, op, N, Cn, H, K, k, s), op) in {c[:3] for c in cases if c[3:8] == (Cn, H, K, k, s)}
+        for c in cases:
+            if c[0] == "bf16":
+                assert R.conv_plan(L, 1, c[1], c[2], N, *c[3:8]) is not None, (net, c)
+        cl = R.trainer_conv_bn_cl_cases(L, d, N)
+        assert cl == [layer for layer in R.trainer_layers(d) if layer[3] == 3], (net, cl)
+        if net != "r50":
+            assert {layer[1] // layer[4] for layer in cl} == {8, 4}, (net, cl)
+        _kinds(L, cases, N)   # (a bf16 route the trainer takes plans the shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# mutants at N = 33: the partial last column tile
+N33 = 33
+TAIL_SHAPES = [(512, 7, 2048, 1, 1), (128, 28, 128, 3, 1)]
+
+
+def _data33(shape):
+    Cn, H, K, k, s = shape
+    rng = np.random.default_rng(Cn + H + K + k)
+    x = rng.standard_normal((N33, Cn, H, H), dtype=np.float32)
+    w = (rng.standard_normal((K, Cn, k, k), dtype=np.float32) * np.float32((2.0 / (k * k * (Cn + K))) ** 0.5))
+    return x, w
+
+
+def _tail(L, shape):
+    """the fp32 forward's plan at N = 33 and the columns [c0, cols) of its partial last tile"""
+    Cn, H, K, k, s = shape
+    p = R.conv_plan(L, 0, "default", "fwd", N33, Cn, H, K, k, s)
+    bn = p[1]
+    cols = N33 * (H // s) ** 2
+    assert cols % bn, "a partial last tile"
+    return p, cols - cols % bn, cols
+
+
+@pytest.mark.parametrize("shape", TAIL_SHAPES, ids=["C%d_H%d_K%d_k%d_s%d" % s for s in TAIL_SHAPES])
+def test_mutant_partial_tile_misses_a_reduction_slice(shape):
+    """6: the columns of the partial last tile miss one 32-channel reduction slice (rows of one 64-row tile): the checker of
+    test_gpu_ragged.py, on its slabs at N = 33, rejects it; the correct result passes"""
+    Cn, H, K, k, s = shape
+    L = _lib()
+    x, w = _data33(shape)
+    Ho = H // s
+    P = Ho * Ho
+    plan, c0, cols = _tail(L, shape)
+    seed = 3
+    slabs = R.fwd_slabs(x, w, s, R.slab_images(N33, plan, K, P, seed), R.slab_channels(K, seed))
+    got = _f32("fwd", x, w, None, shape)
+    R.check_slabs(got, slabs, False, "valid fwd at N = 33")
+    mat = got.transpose(1, 0, 2, 3).reshape(K, N33 * P).copy()
+    part = _f32("fwd", x[:, 32:64], w[:, 32:64], None, (32, H, K, k, s)).transpose(1, 0, 2, 3).reshape(K, N33 * P)
+    r0 = 64
+    mat[r0:r0 + 64, c0:cols] -= part[r0:r0 + 64, c0:cols]
+    bad = np.ascontiguousarray(mat.reshape(K, N33, Ho, Ho).transpose(1, 0, 2, 3))
+    assert R.violations(bad, slabs, False) > 0
+
+
+def _stats_tiles_f32(y, bn, pad_zeros=False):
+    """per-channel (mean, biased var) of y [N, K, P] the way the epilogue partials merge: per column tile of bn columns a float32 two-pass,
+    tiles merged in float32 (Chan).  pad_zeros: the mutant that counts the partial tile's masked columns as zeros"""
+    K = y.shape[1]
+    mat = y.transpose(1, 0, 2, 3).reshape(K, -1)
+    cols = mat.shape[1]
+    n, mean, m2 = np.zeros(K, np.float32), np.zeros(K, np.float32), np.zeros(K, np.float32)
+    for c in range(0, cols, bn):
+        t = mat[:, c:c + bn]
+        if pad_zeros and t.shape[1] < bn:
+            t = np.concatenate([t, np.zeros((K, bn - t.shape[1]), np.float32)], 1)
+        cnt = np.float32(t.shape[1])
+        mu = t.sum(1, dtype=np.float32) / cnt
+        d = t - mu[:, None]
+        q = (d * d).sum(1, dtype=np.float32)
+        tot = n + cnt
+        dd = mu - mean
+        fr = cnt / tot
+        m2 = (m2 + q + dd * dd * n * fr).astype(np.float32)
+        mean = (mean + dd * fr).astype(np.float32)
+        n = tot
+    return mean, (m2 / n).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape", TAIL_SHAPES, ids=["C%d_H%d_K%d_k%d_s%d" % s for s in TAIL_SHAPES])
+def test_mutant_statistics_count_masked_columns(shape):
+    """7: BN statistics that count the partial last tile's masked columns as zeros fail the statistics check of the conv + BN cases at
+    N = 33; statistics merged from float32 tile partials pass"""
+    Cn, H, K, k, s = shape
+    L = _lib()
+    x, w = _data33(shape)
+    plan, c0, cols = _tail(L, shape)
+    Rk = R.slab_channels(K, 5)
+    slab = R.fwd_slabs(x, w, s, [0], Rk)[1]
+    y = _f32("fwd", x, w, None, shape)
+    gm, gv = _stats_tiles_f32(y, plan[1])
+    assert R.conv_stats_violations(gm[Rk], gv[Rk], slab.ref, slab.A)[0] == 0
+    gm, gv = _stats_tiles_f32(y, plan[1], pad_zeros=True)
+    assert R.conv_stats_violations(gm[Rk], gv[Rk], slab.ref, slab.A)[0] > 0

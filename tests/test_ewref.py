@@ -300,10 +300,36 @@ def test_case_list_covers_every_trainer_bn_site():
     sites = E.trainer_bn_sites(L)
     have = {(pr, Cn, H, "fwd", f) for pr, Cn, H, forms in E.bn_fwd_cases() for f in forms}
     have |= {(pr, Cn, H, "bwd", m) for pr, Cn, H, m in E.bn_bwd_cases()}
-    have |= {(dt, Cn, H, "bwd", "parts") for dt, Cn, H, K, k, s, where in R.dgrad_bn_cases()}
+    have |= {(dt, Cn, H, "bwd", "parts") for dt, Cn, H, K, k, s, where in R.dgrad_bn_cases(L)}
     missing = sorted(sites - have, key=str)
     assert not missing, missing
     kinds = {(k[3], k[4]) for k in sites}
     for want in (("fwd", "cl plane"), ("fwd", "cl par"), ("fwd", "cl par add_relu"), ("bwd", 0), ("bwd", 1), ("bwd", 3), ("bwd", "parts")):
         assert want in kinds, want
     print("\n%d trainer sites, %d forward and %d backward cases" % (len(sites), len(E.bn_fwd_cases()), len(E.bn_bwd_cases())))
+
+
+def test_bn_lists_from_dims_are_the_batch256_lists():
+    """bn_shapes / trainer_bn_fwd_cases / trainer_bn_bwd_cases of ResNet-50 are BN_SHAPES and the case lists of test_gpu_batch256_ew.py"""
+    import synth
+    assert E.bn_shapes(synth.R50_DIMS) == E.BN_SHAPES
+    assert E.trainer_bn_fwd_cases(synth.R50_DIMS) == E.bn_fwd_cases()
+    assert E.trainer_bn_bwd_cases(synth.R50_DIMS) == E.bn_bwd_cases()
+
+
+@pytest.mark.parametrize("net,n", [("r50", 33), ("c1s", 4), ("c4i", 4), ("r50", 8)])
+def test_ragged_lists_cover_every_trainer_bn_site(net, n):
+    """every batch-norm site of the net's trainer at batch n is a case of test_gpu_ragged.py: a forward form or backward mode of the BN
+    lists built from its dims, or (BN' with the reduction done by the dgrad) one of its dgrad + BN' cases"""
+    from resnet_amd import binding as B
+    L = B.load()
+    d = R.nets()[net]
+    sites = E.trainer_bn_sites(L, d, n)
+    have = {(pr, Cn, H, "fwd", f) for pr, Cn, H, forms in E.trainer_bn_fwd_cases(d) for f in forms}
+    have |= {(pr, Cn, H, "bwd", m) for pr, Cn, H, m in E.trainer_bn_bwd_cases(d)}
+    have |= {(dt, Cn, H, "bwd", "parts") for dt, Cn, H, K, k, s, where in R.trainer_dgrad_bn_cases(L, d, n)}
+    missing = sorted(sites - have, key=str)
+    assert not missing, missing
+    kinds = {(k[3], k[4]) for k in sites}
+    for want in (("fwd", "cl plane"), ("fwd", "cl par"), ("fwd", "cl par add_relu"), ("bwd", 0), ("bwd", 1), ("bwd", 3), ("bwd", "parts")):
+        assert want in kinds, want
