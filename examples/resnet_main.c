@@ -7,6 +7,9 @@
  *   gcc -O2 -Iinclude examples/resnet_main.c -Lresnet_amd -lresnet_mi -lm -Wl,-rpath,$PWD/resnet_amd -o ResNetMI
  *   ./ResNetMI --iters 20 --batch 64                       synthetic data, reference-defined ResNet-50
  *   ./ResNetMI --shards /data/train_data_shards/nchw --layout nchw --shard-images 32768 --batch 256
+ *   ./ResNetMI --shards-u8 /data/train_data_shards/u8 --dim-in 256 --augment random --aug-seed 7 --shard-images 32768 --batch 256
+ *              uint8 shards of whole 256^2 images (tools/build_shards --u8): crop, flip and float conversion on the device, a new
+ *              draw per epoch; --augment fixed (default: the shard's own crops, the reference's pixels) | center | random, --no-flip
  *   ./ResNetMI --labels-file id_to_label_mapping.txt --synsets-file id_to_synset_mapping.txt --counts-file id_to_img_count_mapping.txt
  *              the class metadata of resnet.cu:3236-3242: iterations per epoch = ceil(sum of the class counts / batch) (:3309)
  *              unless --iters says otherwise
@@ -35,6 +38,12 @@ int main(int argc, char **argv) {
     const int SHARD_N_IMAGES = atoi(opt(argc, argv, "--shard-images", "32768"));
     const char *shards = opt(argc, argv, "--shards", NULL);
     const char *layout = opt(argc, argv, "--layout", "nchw");
+    const char *shards_u8 = opt(argc, argv, "--shards-u8", NULL);
+    const int DIM_IN = atoi(opt(argc, argv, "--dim-in", "256"));
+    const char *augment = opt(argc, argv, "--augment", "fixed");
+    const unsigned long long aug_seed = strtoull(opt(argc, argv, "--aug-seed", "0"), NULL, 10);
+    int flip = 1;
+    for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--no-flip")) flip = 0;
     const char *dump_root = opt(argc, argv, "--dump-root", NULL);
     const char *loss_log = opt(argc, argv, "--loss-log", "avg_loss_log.txt");
     const int resume_id = atoi(opt(argc, argv, "--resume", "-1"));           /* LOAD_FROM_DUMP_ID, resnet.cu:3299 */
@@ -59,9 +68,13 @@ int main(int argc, char **argv) {
     MiRng *gen = mi_rng_create(1234ULL);                                      /* :3264-3267 */
     ResNet *model = init_resnet(dims, gen);
     Batch *batch = init_general_batch(BATCH_SIZE, INPUT_DIM * INPUT_DIM * 3, INPUT_DIM, SHARD_N_IMAGES);
-    if (shards) mi_batch_source_shards(batch, shards, !strcmp(layout, "nhwc") ? MI_LAYOUT_NHWC : MI_LAYOUT_NCHW);
+    if (shards_u8) {
+        mi_batch_source_shards_u8(batch, shards_u8, DIM_IN);
+        const int mode = !strcmp(augment, "random") ? MI_AUG_RANDOM : !strcmp(augment, "center") ? MI_AUG_CENTER : MI_AUG_FIXED;
+        if (mi_batch_set_augment(batch, mode, flip, aug_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    } else if (shards) mi_batch_source_shards(batch, shards, !strcmp(layout, "nhwc") ? MI_LAYOUT_NHWC : MI_LAYOUT_NCHW);
     else mi_batch_source_synthetic(batch, 1234, 1235, N_CLASSES, 4);
-    if (shards) mi_batch_set_prefetch(batch, 1);
+    if (shards || shards_u8) mi_batch_set_prefetch(batch, 1);
     Train_ResNet *trainer = init_trainer(model, batch, BATCH_SIZE, LEARNING_RATE, WEIGHT_DECAY, 0.9f, 0.999f, EPS, N_EPOCHS, "my_custom");
     if (dump_root) mi_trainer_set_dump_root(trainer, dump_root); else mi_trainer_set_dump_every(trainer, 0);
     if (resume_id != -1) { overwrite_trainer_hyperparams(trainer, resume_id, "my_custom"); overwrite_model_params(trainer, resume_id, "my_custom"); }

@@ -270,7 +270,7 @@ void mi_trainer_last_timings(Train_ResNet *t, float out_ms[5]);
 
 /* optional per-kernel-family timing with HIP events on the launch stream (used by bench.py's roofline):
  * family 0 direct (VALU) conv fwd/dgrad, 1 direct (VALU) conv wgrad, 2 1x1 conv / FC on MFMA, 3 batch norm,
- * 5 3x3 conv on the MFMA implicit GEMM (fwd, dgrad, wgrad; 4 is unused).
+ * 5 3x3 conv on the MFMA implicit GEMM (fwd, dgrad, wgrad), 4 the input-side passes (uint8 decode, NHWC -> NCHW).
  * flops/bytes are the ALGORITHMIC work of the timed launches. */
 void mi_prof_enable(int on); /* 0 off, 1 all families, otherwise a bit mask of (1 << family) */
 void mi_prof_reset(void);
@@ -411,6 +411,44 @@ int mi_build_shard(const char *partition_csv, const char *class_dir, const char 
 /* data parallel: this rank's slice of every global batch of a shard ("each rank reads its slice of the same
  * shard/batch"): global batch g of a shard = images [g*world*N, (g+1)*world*N), rank r takes [.. + r*N, .. + (r+1)*N) */
 void mi_batch_set_rank_slice(Batch *b, int rank, int world);
+
+/* ---------------- uint8 shards with on-device crop, flip and decode ----------------
+ * The fp32 shards above hold one crop per image, made once offline.  A uint8 shard keeps the class files' bytes as they are -- whole
+ * dim_in x dim_in images, a third of the bytes of the 224^2 fp32 crop -- and the crop (+ flip, B,G,R -> R,G,B planes, mean subtraction)
+ * is made on the device at every load (kernels_input.hip), so a new crop can be drawn every epoch.
+ *
+ * mi_build_shard_u8: same partition CSV and class files as mi_build_shard; writes <out_dir>/%03d.images_u8 ([n][dim_in][dim_in][3]
+ * bytes, every image whole and unchanged, B,G,R interleaved), %03d.labels (int32, as mi_build_shard) and %03d.crops (int32 [n][2]: the
+ * CSV's row and column offsets).  Returns the number of images, or -1 (no CSV), -2 (no class file), -4 (short class file). */
+int mi_build_shard_u8(const char *partition_csv, const char *class_dir, const char *out_dir, int shard_id, int image_dim_in);
+/* The augmentation plan of n consecutive images, host-only and deterministic: out[i] = (row_off, col_off, flip) of the image with global
+ * index g = first_global_index + i.  FIXED: the offsets of fixed_crops ([n][2], the shard's .crops), no flip -- the reference's
+ * behaviour.  CENTER: both offsets (dim_in - dim_out) / 2, no flip.  RANDOM: with R = dim_in - dim_out, s = splitmix64_at(seed, epoch),
+ * r = splitmix64_at(s, g) (the counter streams of synth.c): row_off = ((r & 0xFFFFF) (R + 1)) >> 20, col_off = (((r >> 20) & 0xFFFFF)
+ * (R + 1)) >> 20, flip = flip ? r >> 63 : 0.  Returns 0, or -1 (unknown mode, dim_out > dim_in, FIXED without fixed_crops or with an
+ * offset outside [0, R]; mi_last_error says which). */
+enum { MI_AUG_FIXED = 0, MI_AUG_CENTER = 1, MI_AUG_RANDOM = 2 };
+int mi_augment_plan(int mode, int flip, uint64_t seed, int epoch, int64_t first_global_index, int n, int dim_in, int dim_out,
+                    const int *fixed_crops, int *out);
+/* the decode kernel on its own: src_dev n whole images of bytes (16-byte aligned, else -1), plan_dev int [n][3] as mi_augment_plan
+ * writes it, out_nchw fp32 [n][3][dim_out][dim_out]: out[n][d][h][w] = (float)((double)(float)byte - mean) of the byte
+ * src[n][row_off + h][col_off + (flip ? dim_out - 1 - w : w)][2 - d], mean = 123.68 / 116.78 / 103.94 for byte position 0 / 1 / 2 --
+ * the bits mi_build_shard writes.  Offsets outside [0, dim_in - dim_out] are clamped; nothing outside the n images is read. */
+int mi_op_decode_u8(const uint8_t *src_dev, const int *plan_dev, float *out_nchw, int n, int dim_in, int dim_out);
+/* load_new_batch from <shard_dir>/%03d.images_u8 + .labels (+ .crops): the shard stays in host RAM as bytes; every load builds the plan
+ * of this rank's images (global index = cur_shard_id * shard_n_images + position in the shard, epoch = trainer->cur_epoch: the values
+ * dump_trainer saves, so prefetch, rank slices and a resumed run see the same pixels), copies the batch's bytes, labels and plan
+ * through pinned buffers and decodes into Batch.images (fp32 NCHW, image_dim = the crop's size) on the same stream -- the compute
+ * stream, or the copy stream for the prefetched next batch.  Shard rotation, ragged tail, rank slices, status -1 on a missing file and
+ * the cur_batch_in_shard / cur_dump_id bookkeeping are those of MI_SRC_SHARDS; FIXED without a .crops file is status -1 too.
+ * Batch.images_float_cpu and Batch.full_shard_images are NOT filled by this source (there is no host fp32 image). */
+enum { MI_SRC_SHARDS_U8 = 4 };
+void mi_batch_source_shards_u8(Batch *b, const char *shard_dir, int image_dim_in);
+/* mode MI_AUG_* (default FIXED), flip 0 / 1 (RANDOM only), seed; MI_SRC_SHARDS_U8 only (else -1, mi_last_error set).  Like the
+ * optimizer, mode and seed are not dumped: a resumed run sets them again. */
+int mi_batch_set_augment(Batch *b, int mode, int flip, uint64_t seed);
+/* the plan of the last load, int [n_images][3]; returns n_images, or -1 (another source, or nothing loaded yet) */
+int mi_batch_last_plan(const Batch *b, int *out);
 
 /* typed operator layer: x_dt = storage type of the convolution-side tensors (x, dx), a_dt = of the activation-side tensors
  * (y, residual, dy, mask_src, gated_out).  Supported pairs: (F32,F32), (BF16,BF16), (F32,BF16). */

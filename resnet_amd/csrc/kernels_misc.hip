@@ -407,7 +407,9 @@ int mid_adam(mid_stream s, float *p, float *g, float *m, float *v, size_t n, flo
     return 0;
 }
 int mid_nhwc_to_nchw(mid_stream s, const float *in, float *out, int N, int H, int W, int C) {
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 8.0 * N * H * W * C);
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ew_blocks((size_t)N * H * W * C)), dim3(256), 0, (hipStream_t)s, in, out, N, H * W, C);
+    mi_prof_end((hipStream_t)s);
     MI_LAUNCH_CHECK("nhwc_to_nchw_kernel");
     return 0;
 }

@@ -5,6 +5,8 @@
  * legacy directory and NCHW under nchw/.  Same behaviour here, with the data source selectable (shards,
  * a dumped images.buffer/labels.buffer pair, caller-filled host buffers, or a seeded synthetic pool that
  * stays resident in HBM) because the reference's /mnt/storage paths are literals.
+ * MI_SRC_SHARDS_U8 (new work, no counterpart in the reference): the shard holds whole uint8 images; the crop is drawn per load by
+ * mi_augment_plan and made, with the flip and the float conversion, by the decode kernel (kernels_input.hip).
  */
 #define _GNU_SOURCE
 #include <stdio.h>
@@ -34,6 +36,10 @@ void mi_batch_ext_free(Batch *b) {
         mid_free_host(e->pinned_next); mid_free_host(e->labels_next_host);
         if (e->ev_next) mid_event_destroy(e->ev_next);
         if (e->ev_compute) mid_event_destroy(e->ev_compute);
+        free(e->u8_shard); free(e->u8_crops);
+        for (int k = 0; k < 2; k++) {
+            mid_free_host(e->u8_pinned[k]); mid_free(e->u8_dev[k]); mid_free_host(e->plan_pinned[k]); mid_free(e->plan_dev[k]);
+        }
         free(e);
     }
     mid_free_host(b->images_float_cpu); mid_free_host(b->correct_classes_cpu);
@@ -60,21 +66,87 @@ void mi_batch_source_shards(Batch *b, const char *dir, int layout) {
     BatchExt *e = mi_batch_ext(b);
     e->source = MI_SRC_SHARDS; e->layout = layout; set_str(&e->shard_dir, dir);
     e->have_next = 0;
+    if (e->prefetch) mi_batch_set_prefetch(b, 1); /* the fp32 staging buffers, should the prefetch have been set up for uint8 shards */
+}
+/* staging of the uint8 source: set 0 for the blocking load, set 1 for the prefetched batch */
+static void u8_ensure(Batch *b, BatchExt *e) {
+    const size_t bytes = (size_t)b->n_images * e->u8_dim_in * e->u8_dim_in * 3, plan = (size_t)b->n_images * 3 * sizeof(int);
+    for (int k = 0; k < (e->prefetch ? 2 : 1); k++) {
+        if (e->u8_pinned[k]) continue;
+        e->u8_pinned[k] = (uint8_t *)mid_malloc_host(bytes);
+        e->u8_dev[k] = (uint8_t *)mid_malloc(bytes);
+        e->plan_pinned[k] = (int *)mid_malloc_host(plan);
+        e->plan_dev[k] = (int *)mid_malloc(plan);
+    }
+}
+void mi_batch_source_shards_u8(Batch *b, const char *dir, int image_dim_in) {
+    BatchExt *e = mi_batch_ext(b);
+    if (e->u8_dim_in != image_dim_in) { /* buffers of another image size */
+        free(e->u8_shard); free(e->u8_crops); e->u8_shard = NULL; e->u8_crops = NULL;
+        for (int k = 0; k < 2; k++) {
+            mid_free_host(e->u8_pinned[k]); mid_free(e->u8_dev[k]); mid_free_host(e->plan_pinned[k]); mid_free(e->plan_dev[k]);
+            e->u8_pinned[k] = NULL; e->u8_dev[k] = NULL; e->plan_pinned[k] = NULL; e->plan_dev[k] = NULL;
+        }
+    }
+    e->source = MI_SRC_SHARDS_U8; e->layout = MI_LAYOUT_NCHW; e->u8_dim_in = image_dim_in; set_str(&e->shard_dir, dir);
+    e->have_next = 0; e->have_plan = 0;
+    u8_ensure(b, e);
+}
+int mi_batch_set_augment(Batch *b, int mode, int flip, uint64_t seed) {
+    BatchExt *e = mi_batch_ext(b);
+    if (e->source != MI_SRC_SHARDS_U8) { mi_record_host_error("mi_batch_set_augment", "the data source is not MI_SRC_SHARDS_U8"); return -1; }
+    if (mode != MI_AUG_FIXED && mode != MI_AUG_CENTER && mode != MI_AUG_RANDOM) { mi_record_host_error("mi_batch_set_augment", "mode is MI_AUG_FIXED, _CENTER or _RANDOM"); return -1; }
+    e->aug_mode = mode; e->aug_flip = flip != 0; e->aug_seed = seed;
+    e->have_next = 0; /* a batch prefetched under the old choice */
+    return 0;
+}
+int mi_batch_last_plan(const Batch *b, int *out) {
+    BatchExt *e = mi_batch_ext((Batch *)b);
+    if (e->source != MI_SRC_SHARDS_U8 || !e->have_plan) return -1;
+    memcpy(out, e->plan_pinned[0], (size_t)b->n_images * 3 * sizeof(int));
+    return b->n_images;
+}
+int mi_augment_plan(int mode, int flip, uint64_t seed, int epoch, int64_t first_global_index, int n, int dim_in, int dim_out,
+                    const int *fixed_crops, int *out) {
+    const int R = dim_in - dim_out;
+    if (R < 0 || dim_out < 1 || n < 0) { mi_record_host_error("mi_augment_plan", "need 1 <= dim_out <= dim_in and n >= 0"); return -1; }
+    if (mode == MI_AUG_FIXED) {
+        if (!fixed_crops) { mi_record_host_error("mi_augment_plan", "MI_AUG_FIXED needs the shard's crop offsets"); return -1; }
+        for (int i = 0; i < n; i++) {
+            const int ro = fixed_crops[2 * i], co = fixed_crops[2 * i + 1];
+            if (ro < 0 || ro > R || co < 0 || co > R) { mi_record_host_error("mi_augment_plan", "a fixed crop does not fit into the image"); return -1; }
+            out[3 * i] = ro; out[3 * i + 1] = co; out[3 * i + 2] = 0;
+        }
+    } else if (mode == MI_AUG_CENTER) {
+        for (int i = 0; i < n; i++) { out[3 * i] = out[3 * i + 1] = R / 2; out[3 * i + 2] = 0; }
+    } else if (mode == MI_AUG_RANDOM) {
+        const uint64_t s = mi_splitmix64_at(seed, (uint64_t)(int64_t)epoch);
+        for (int i = 0; i < n; i++) {
+            const uint64_t r = mi_splitmix64_at(s, (uint64_t)(first_global_index + i));
+            out[3 * i] = (int)(((r & 0xFFFFF) * (uint64_t)(R + 1)) >> 20);
+            out[3 * i + 1] = (int)((((r >> 20) & 0xFFFFF) * (uint64_t)(R + 1)) >> 20);
+            out[3 * i + 2] = flip ? (int)(r >> 63) : 0;
+        }
+    } else { mi_record_host_error("mi_augment_plan", "mode is MI_AUG_FIXED, _CENTER or _RANDOM"); return -1; }
+    return 0;
 }
 /* double-buffered H2D: while step t runs, batch t+1 of the resident shard goes pinned -> device on the copy stream
  * (the reference copies synchronously at the top of every step, resnet.cu:1315-1316) */
 void mi_batch_set_prefetch(Batch *b, int on) {
     BatchExt *e = mi_batch_ext(b);
     e->prefetch = on; e->have_next = 0;
+    const size_t bytes = (size_t)b->n_images * b->image_size * sizeof(float);
     if (on && !e->images_next) {
-        const size_t bytes = (size_t)b->n_images * b->image_size * sizeof(float);
         e->images_next = (float *)mid_malloc(bytes);
-        e->stage_next = (float *)mid_malloc(bytes);
-        e->pinned_next = (float *)mid_malloc_host(bytes);
         e->labels_next = (int *)mid_malloc((size_t)b->n_images * sizeof(int));
         e->labels_next_host = (int *)mid_malloc_host((size_t)b->n_images * sizeof(int));
         e->ev_next = mid_event_create();
         e->ev_compute = mid_event_create();
+    }
+    if (on && e->source == MI_SRC_SHARDS_U8) u8_ensure(b, e); /* bytes are staged, not floats */
+    else if (on && !e->pinned_next) {
+        e->stage_next = (float *)mid_malloc(bytes);
+        e->pinned_next = (float *)mid_malloc_host(bytes);
     }
 }
 /* enqueue batch (shard resident in host RAM, index bi) on the copy stream into the *_next buffers */
@@ -97,6 +169,33 @@ static void prefetch_enqueue(Batch *b, BatchExt *e, int bi) {
     mid_memcpy_h2d(e->labels_next, e->labels_next_host, (size_t)N * sizeof(int), g->copy);
     mid_event_record(e->ev_next, g->copy);
     e->have_next = 1; e->next_shard_id = b->cur_shard_id; e->next_batch_in_shard = bi;
+}
+/* MI_SRC_SHARDS_U8: batch bi of the resident shard -> pinned set k -> device on stream s, decoded into `images`; the plan is in
+ * plan_pinned[k] already */
+static void u8_enqueue(Batch *b, BatchExt *e, int bi, int k, mid_stream s, float *images, int *labels_dev, int *labels_host) {
+    const int N = b->n_images;
+    const size_t bytes = (size_t)N * e->u8_dim_in * e->u8_dim_in * 3;
+    memcpy(e->u8_pinned[k], e->u8_shard + (size_t)bi * bytes, bytes);
+    memcpy(labels_host, b->full_shard_correct_classes + (size_t)bi * N, (size_t)N * sizeof(int));
+    mid_memcpy_h2d(e->u8_dev[k], e->u8_pinned[k], bytes, s);
+    mid_memcpy_h2d(labels_dev, labels_host, (size_t)N * sizeof(int), s);
+    mid_memcpy_h2d(e->plan_dev[k], e->plan_pinned[k], (size_t)N * 3 * sizeof(int), s);
+    mid_decode_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim);
+}
+/* the plan of this rank's batch bi of the resident shard at `epoch` into plan_pinned[k]; 0, or -1 with a message */
+static int u8_plan(Batch *b, BatchExt *e, int bi, int epoch, int k) {
+    const int N = b->n_images;
+    if (e->aug_mode == MI_AUG_FIXED && !e->u8_have_crops) {
+        fprintf(stderr, "resnet_mi: MI_AUG_FIXED needs %s/%03d.crops\n", e->shard_dir, b->cur_shard_id);
+        return -1;
+    }
+    const int64_t first = (int64_t)b->cur_shard_id * b->shard_n_images + (int64_t)bi * N;
+    if (mi_augment_plan(e->aug_mode, e->aug_flip, e->aug_seed, epoch, first, N, e->u8_dim_in, b->image_dim,
+                        e->u8_have_crops ? e->u8_crops + (size_t)bi * N * 2 : NULL, e->plan_pinned[k])) {
+        fprintf(stderr, "resnet_mi: no augmentation plan for shard %d batch %d: %s\n", b->cur_shard_id, bi, mi_last_error());
+        return -1;
+    }
+    return 0;
 }
 void mi_batch_source_buffer(Batch *b, const char *images_path, const char *labels_path, int layout) {
     BatchExt *e = mi_batch_ext(b);
@@ -209,6 +308,62 @@ void load_new_batch(Train_ResNet *trainer, Class_Metadata *class_metadata, Batch
                 /* the swapped-out buffer may still be read (stem weight gradient) and cleared (input_reset) by the step that
                  * just ended: prefetch_enqueue orders the copy stream behind the compute stream before writing into it */
                 prefetch_enqueue(b, e, (b->cur_batch_in_shard + 1) * W + R);
+            }
+        }
+    } else if (e->source == MI_SRC_SHARDS_U8) {
+        /* rotation, ragged tail, rank slices and bookkeeping as MI_SRC_SHARDS above */
+        const int W = e->world, R = e->rank, epoch = trainer->cur_epoch;
+        const size_t img_bytes = (size_t)e->u8_dim_in * e->u8_dim_in * 3;
+        if (trainer->init_loaded || b->cur_shard_id == -1 || (b->cur_batch_in_shard + 1) * W * N > b->shard_n_images) {
+            if (!trainer->init_loaded) b->cur_shard_id += 1;
+            if (!e->u8_shard) {
+                e->u8_shard = (uint8_t *)malloc((size_t)b->shard_n_images * img_bytes);
+                e->u8_crops = (int *)malloc((size_t)b->shard_n_images * 2 * sizeof(int));
+            }
+            if (!b->full_shard_correct_classes) b->full_shard_correct_classes = (int *)malloc((size_t)b->shard_n_images * sizeof(int));
+            char *pi = NULL, *pl = NULL, *pc = NULL;
+            if (asprintf(&pi, "%s/%03d.images_u8", e->shard_dir, b->cur_shard_id) < 0 || asprintf(&pl, "%s/%03d.labels", e->shard_dir, b->cur_shard_id) < 0 ||
+                asprintf(&pc, "%s/%03d.crops", e->shard_dir, b->cur_shard_id) < 0) exit(1);
+            const size_t ni = read_file(pi, e->u8_shard, 1, (size_t)b->shard_n_images * img_bytes);
+            const size_t nl = read_file(pl, b->full_shard_correct_classes, sizeof(int), b->shard_n_images);
+            e->u8_have_crops = read_file(pc, e->u8_crops, sizeof(int), (size_t)b->shard_n_images * 2) == (size_t)b->shard_n_images * 2;
+            if (ni != (size_t)b->shard_n_images * img_bytes || nl != (size_t)b->shard_n_images) {
+                fprintf(stderr, "resnet_mi: cannot read shard %s (%zu of %zu bytes)\n", pi, ni, (size_t)b->shard_n_images * img_bytes);
+                e->status = -1;
+            }
+            free(pi); free(pl); free(pc);
+            e->have_next = 0; /* cut from the shard this one replaced */
+            if (!trainer->init_loaded) b->cur_batch_in_shard = 0;
+            trainer->init_loaded = 0;
+        }
+        if (e->status == 0) {
+            const int bi = b->cur_batch_in_shard * W + R; /* this rank's batch of the shard */
+            u8_ensure(b, e);
+            /* the draw changes with the epoch and mi_trainer_end_epoch rewinds to shard 0: a prefetched batch counts only for its epoch */
+            if (e->prefetch && e->have_next && e->next_shard_id == b->cur_shard_id && e->next_batch_in_shard == bi && e->next_epoch == epoch) {
+                mid_stream_wait_event(g->compute, e->ev_next);
+                mid_event_sync(e->ev_next); /* the pinned staging buffers are rewritten below */
+                float *ti = b->images; b->images = e->images_next; e->images_next = ti;
+                int *tl = b->correct_classes; b->correct_classes = e->labels_next; e->labels_next = tl;
+                memcpy(b->correct_classes_cpu, e->labels_next_host, (size_t)N * sizeof(int));
+                memcpy(e->plan_pinned[0], e->plan_pinned[1], (size_t)N * 3 * sizeof(int));
+                e->have_next = 0; e->have_plan = 1;
+            } else if (u8_plan(b, e, bi, epoch, 0) == 0) {
+                u8_enqueue(b, e, bi, 0, g->compute, b->images, b->correct_classes, b->correct_classes_cpu);
+                mid_stream_sync(g->compute); /* blocking, as the fp32 sources: the pinned buffers are free again */
+                e->have_plan = 1;
+            } else e->status = -1;
+            if (e->status == 0 && e->prefetch && (b->cur_batch_in_shard + 2) * W * N <= b->shard_n_images) {
+                const int nb = (b->cur_batch_in_shard + 1) * W + R;
+                if (e->have_next) { mid_event_sync(e->ev_next); e->have_next = 0; } /* a prefetch nobody took still reads the pinned set */
+                if (u8_plan(b, e, nb, epoch, 1) == 0) {
+                    /* the copy stream waits for what the compute stream holds against images_next / labels_next (see prefetch_enqueue) */
+                    mid_event_record(e->ev_compute, g->compute);
+                    mid_stream_wait_event(g->copy, e->ev_compute);
+                    u8_enqueue(b, e, nb, 1, g->copy, e->images_next, e->labels_next, e->labels_next_host);
+                    mid_event_record(e->ev_next, g->copy);
+                    e->have_next = 1; e->next_shard_id = b->cur_shard_id; e->next_batch_in_shard = nb; e->next_epoch = epoch;
+                }
             }
         }
     } else if (e->source == MI_SRC_BUFFER) {

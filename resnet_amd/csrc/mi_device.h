@@ -279,6 +279,10 @@ int mid_optim_update(mid_stream s, int kind, float *p, float *g, float *b, const
                      const float *trust, float lr, float wd, float momentum, int *nan_flag);
 int mid_nhwc_to_nchw(mid_stream s, const float *in, float *out, int N, int H, int W, int C);
 int mid_nchw_to_nhwc(mid_stream s, const float *in, float *out, int N, int C, int H, int W);
+/* uint8 shards (kernels_input.hip): src = n whole images [dim_in][dim_in][3] bytes (B,G,R interleaved), 16-byte aligned; plan = int [n][3]
+ * (row_off, col_off, flip) in device memory; out = fp32 NCHW [n][3][dim_out][dim_out], R,G,B planes, means subtracted as mi_build_shard
+ * does.  Reads nothing outside [src, src + n dim_in^2 3).  Returns 0, -1 (alignment / sizes; mid_last_error says which), -2 (dim_out too large) */
+int mid_decode_u8(mid_stream s, const uint8_t *src, const int *plan, float *out, int n, int dim_in, int dim_out);
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */
 int mid_fill_uniform(mid_stream s, float *out, size_t n, uint64_t seed, uint64_t offset, float lo, float hi);
 int mid_lds_poison(mid_stream s); /* test aid: fills LDS of every CU with NaNs */

@@ -38,6 +38,15 @@ typedef struct BatchExt {
     int *labels_next, *labels_next_host;
     mid_event ev_next, ev_compute; /* copy done / compute stream's position when the target buffers were handed to the copy stream */
     uint64_t synth_step;
+    /* MI_SRC_SHARDS_U8: the resident shard as bytes (whole dim_in^2 images) with its crop offsets, the augmentation choice, and per
+     * buffer set (0: the blocking load / the batch in use, 1: the prefetched next batch; swapped with the images) a pinned and a
+     * device staging buffer for the batch's bytes and for its plan */
+    int u8_dim_in, aug_mode, aug_flip, u8_have_crops, have_plan, next_epoch;
+    uint64_t aug_seed;
+    uint8_t *u8_shard;           /* host, shard_n_images * dim_in^2 * 3 */
+    int *u8_crops;               /* host, [shard_n_images][2] */
+    uint8_t *u8_pinned[2], *u8_dev[2];
+    int *plan_pinned[2], *plan_dev[2]; /* [n_images][3]; plan_pinned[0] = the plan of the last load */
     struct BatchExt *next;
 } BatchExt;
 BatchExt *mi_batch_ext(Batch *b);

@@ -10,6 +10,8 @@
  *                   and rounded once, as the reference's `((float) byte) - 123.68` does)                 (:115-129)
  *   layout          NHWC -> NCHW                                                                         (:132-144)
  *   files           <out_dir>/%03d.images (fp32) and %03d.labels (int32)                                 (:150-160)
+ * mi_build_shard_u8 stops after the first step: whole images as bytes, with the CSV's crop offsets beside them, for the loader that
+ * crops and converts on the device (MI_SRC_SHARDS_U8).
  * Differences: every fopen is checked, the staging buffers are sized by the rows actually present (the reference mallocs a
  * full 32768-image shard of bytes up front, :20), and layout NHWC can be kept for the legacy loader directory.
  */
@@ -27,12 +29,10 @@ static int field(const char *line, int off, int len) {
     return atoi(tmp);
 }
 
-int mi_build_shard(const char *partition_csv, const char *class_dir, const char *out_dir, int shard_id, int image_dim_in,
-                   int image_dim_out, int layout) {
-    const long channels = 3;
-    const size_t size_in = (size_t)image_dim_in * image_dim_in * channels, size_out = (size_t)image_dim_out * image_dim_out * channels;
+/* the partition CSV: class, image number, row and column offset per line; returns the number of lines, or -1 (cannot open) */
+static int read_partition(const char *partition_csv, const char *who, int **cls_out, int **num_out, int **ro_out, int **co_out) {
     FILE *fp = fopen(partition_csv, "r");
-    if (!fp) { fprintf(stderr, "mi_build_shard: cannot open %s\n", partition_csv); return -1; }
+    if (!fp) { fprintf(stderr, "%s: cannot open %s\n", who, partition_csv); return -1; }
     int cap = 1024, cnt = 0;
     int *cls = (int *)malloc(sizeof(int) * cap), *num = (int *)malloc(sizeof(int) * cap), *ro = (int *)malloc(sizeof(int) * cap),
         *co = (int *)malloc(sizeof(int) * cap);
@@ -51,6 +51,17 @@ int mi_build_shard(const char *partition_csv, const char *class_dir, const char 
     }
     free(line);
     fclose(fp);
+    *cls_out = cls; *num_out = num; *ro_out = ro; *co_out = co;
+    return cnt;
+}
+
+int mi_build_shard(const char *partition_csv, const char *class_dir, const char *out_dir, int shard_id, int image_dim_in,
+                   int image_dim_out, int layout) {
+    const long channels = 3;
+    const size_t size_in = (size_t)image_dim_in * image_dim_in * channels, size_out = (size_t)image_dim_out * image_dim_out * channels;
+    int *cls, *num, *ro, *co;
+    const int cnt = read_partition(partition_csv, "mi_build_shard", &cls, &num, &ro, &co);
+    if (cnt < 0) return -1;
 
     int rc = 0;
     uint8_t *bytes = (uint8_t *)malloc(size_out * (size_t)(cnt > 0 ? cnt : 1));
@@ -92,5 +103,38 @@ int mi_build_shard(const char *partition_csv, const char *class_dir, const char 
         free(out);
     }
     free(bytes); free(cls); free(num); free(ro); free(co);
+    return rc ? rc : cnt;
+}
+
+/* the same images kept whole, as bytes (include/resnet_mi.h): %03d.images_u8, %03d.labels, %03d.crops */
+static int write_file(const char *out_dir, int shard_id, const char *ext, const void *data, size_t elem, size_t count) {
+    char path[4096];
+    snprintf(path, sizeof path, "%s/%03d.%s", out_dir, shard_id, ext);
+    FILE *f = fopen(path, "wb");
+    const int bad = !f || fwrite(data, elem, count, f) != count;
+    if (f) fclose(f);
+    return bad;
+}
+int mi_build_shard_u8(const char *partition_csv, const char *class_dir, const char *out_dir, int shard_id, int image_dim_in) {
+    const size_t size_in = (size_t)image_dim_in * image_dim_in * 3;
+    int *cls, *num, *ro, *co;
+    const int cnt = read_partition(partition_csv, "mi_build_shard_u8", &cls, &num, &ro, &co);
+    if (cnt < 0) return -1;
+    int rc = 0;
+    uint8_t *bytes = (uint8_t *)malloc(size_in * (size_t)(cnt > 0 ? cnt : 1));
+    int *crops = (int *)malloc(sizeof(int) * 2 * (size_t)(cnt > 0 ? cnt : 1));
+    for (int i = 0; i < cnt && !rc; i++) {
+        char path[4096];
+        snprintf(path, sizeof path, "%s/%08d.buffer", class_dir, cls[i]);
+        FILE *f = fopen(path, "rb");
+        if (!f) { fprintf(stderr, "mi_build_shard_u8: cannot open class file %s\n", path); rc = -2; break; }
+        if (fseek(f, (long)num[i] * (long)size_in, SEEK_SET) || fread(bytes + (size_t)i * size_in, 1, size_in, f) != size_in) rc = -4;
+        fclose(f);
+        crops[2 * i] = ro[i]; crops[2 * i + 1] = co[i];
+    }
+    if (!rc && (write_file(out_dir, shard_id, "images_u8", bytes, 1, size_in * (size_t)cnt) ||
+                write_file(out_dir, shard_id, "labels", cls, sizeof(int), (size_t)cnt) ||
+                write_file(out_dir, shard_id, "crops", crops, sizeof(int), 2 * (size_t)cnt))) rc = -5;
+    free(bytes); free(crops); free(cls); free(num); free(ro); free(co);
     return rc ? rc : cnt;
 }

@@ -103,6 +103,19 @@ class Ops:
                                            obet.ptr, N, Cc, H, eps), "bn_bwd_gate")
         return out.get(), ogam.get(), obet.get(), gated.get()
 
+    def decode_u8(self, src, plan, dim_out, pad_floats=0, fill=0.0):
+        """uint8 images (n, dim_in, dim_in, 3) B,G,R + int32 plan (n, 3) -> fp32 (n, 3, dim_out, dim_out) (mi_op_decode_u8).
+        pad_floats > 0: the output buffer is that much longer, pre-filled with `fill`; the padding comes back as a second array"""
+        src = np.ascontiguousarray(src, np.uint8)
+        n, dim_in = src.shape[0], src.shape[1]
+        total = n * 3 * dim_out * dim_out
+        dsrc, dplan = self.dev(src), self.dev(np.ascontiguousarray(plan, np.int32))
+        dout = self.dev(np.full(total + pad_floats, fill, np.float32))
+        self._chk(self.L.mi_op_decode_u8(dsrc.ptr, dplan.ptr, dout.ptr, n, dim_in, dim_out), "decode_u8")
+        out = dout.get()
+        img = out[:total].reshape(n, 3, dim_out, dim_out)
+        return (img, out[total:]) if pad_floats else img
+
     def maxpool_fwd(self, x, k, stride):
         N, Cc, H, _ = x.shape
         Ho = H // stride

@@ -151,6 +151,27 @@ class Trainer:
         if prefetch:
             self.L.mi_batch_set_prefetch(self.c_batch, 1)
 
+    AUGMENTS = {"fixed": B.MI_AUG_FIXED, "center": B.MI_AUG_CENTER, "random": B.MI_AUG_RANDOM}
+
+    def source_shards_u8(self, shard_dir, dim_in, augment="fixed", flip=True, seed=0, prefetch=False):
+        """uint8 shards of whole dim_in x dim_in images (mi_build_shard_u8); crop, flip and float conversion on the device at
+        every load.  augment: "fixed" (the shard's .crops, the reference's pixels), "center" or "random" (a new draw per epoch)"""
+        self.L.mi_batch_source_shards_u8(self.c_batch, shard_dir.encode(), int(dim_in))
+        if self.L.mi_batch_set_augment(self.c_batch, self.AUGMENTS[augment], int(bool(flip)), int(seed)) != 0:
+            e = self.error()
+            self.L.mi_clear_error()
+            raise RuntimeError("mi_batch_set_augment: " + e)
+        if prefetch:
+            self.L.mi_batch_set_prefetch(self.c_batch, 1)
+        self.check()
+
+    def last_plan(self):
+        """(row_off, col_off, flip) per image of the last load_new_batch (uint8 shards), int32 (batch, 3)"""
+        out = np.empty((self.batch, 3), np.int32)
+        if self.L.mi_batch_last_plan(self.c_batch, out.ctypes.data) != self.batch:
+            raise RuntimeError("no plan: the source is not uint8 shards, or nothing was loaded yet")
+        return out
+
     def fill_host_batch(self, images, labels):
         """write the caller-owned pinned staging buffers (images_float_cpu / correct_classes_cpu)"""
         b = self.c_batch.contents
