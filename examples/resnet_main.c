@@ -9,7 +9,10 @@
  *   ./ResNetMI --shards /data/train_data_shards/nchw --layout nchw --shard-images 32768 --batch 256
  *   ./ResNetMI --shards-u8 /data/train_data_shards/u8 --dim-in 256 --augment random --aug-seed 7 --shard-images 32768 --batch 256
  *              uint8 shards of whole 256^2 images (tools/build_shards --u8): crop, flip and float conversion on the device, a new
- *              draw per epoch; --augment fixed (default: the shard's own crops, the reference's pixels) | center | random, --no-flip
+ *              draw per epoch; --augment fixed (default: the shard's own crops, the reference's pixels) | center | random | rrc, --no-flip
+ *   ./ResNetMI --shards-u8 /data/train_data_shards/u8 --augment rrc --rrc-scale 0.08,1 --rrc-ratio 0.75,1.3333333333333333 --batch 256
+ *              random-resized crop: a box of LO .. HI of the image's area and of aspect ratio LO .. HI (the defaults shown), resampled
+ *              to the input size on the device
  *   ./ResNetMI --labels-file id_to_label_mapping.txt --synsets-file id_to_synset_mapping.txt --counts-file id_to_img_count_mapping.txt
  *              the class metadata of resnet.cu:3236-3242: iterations per epoch = ceil(sum of the class counts / batch) (:3309)
  *              unless --iters says otherwise
@@ -42,6 +45,9 @@ int main(int argc, char **argv) {
     const int DIM_IN = atoi(opt(argc, argv, "--dim-in", "256"));
     const char *augment = opt(argc, argv, "--augment", "fixed");
     const unsigned long long aug_seed = strtoull(opt(argc, argv, "--aug-seed", "0"), NULL, 10);
+    double rrc_scale[2] = {0.08, 1.0}, rrc_ratio[2] = {3.0 / 4.0, 4.0 / 3.0};
+    if (sscanf(opt(argc, argv, "--rrc-scale", "0.08,1"), "%lf,%lf", &rrc_scale[0], &rrc_scale[1]) != 2) { fprintf(stderr, "--rrc-scale LO,HI\n"); return 1; }
+    if (opt(argc, argv, "--rrc-ratio", NULL) && sscanf(opt(argc, argv, "--rrc-ratio", ""), "%lf,%lf", &rrc_ratio[0], &rrc_ratio[1]) != 2) { fprintf(stderr, "--rrc-ratio LO,HI\n"); return 1; }
     int flip = 1;
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--no-flip")) flip = 0;
     const char *dump_root = opt(argc, argv, "--dump-root", NULL);
@@ -71,7 +77,8 @@ int main(int argc, char **argv) {
     if (shards_u8) {
         mi_batch_source_shards_u8(batch, shards_u8, DIM_IN);
         const int mode = !strcmp(augment, "random") ? MI_AUG_RANDOM : !strcmp(augment, "center") ? MI_AUG_CENTER : MI_AUG_FIXED;
-        if (mi_batch_set_augment(batch, mode, flip, aug_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+        if (!strcmp(augment, "rrc") ? mi_batch_set_augment_rrc(batch, flip, aug_seed, rrc_scale[0], rrc_scale[1], rrc_ratio[0], rrc_ratio[1])
+                                    : mi_batch_set_augment(batch, mode, flip, aug_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     } else if (shards) mi_batch_source_shards(batch, shards, !strcmp(layout, "nhwc") ? MI_LAYOUT_NHWC : MI_LAYOUT_NCHW);
     else mi_batch_source_synthetic(batch, 1234, 1235, N_CLASSES, 4);
     if (shards || shards_u8) mi_batch_set_prefetch(batch, 1);

@@ -447,8 +447,43 @@ void mi_batch_source_shards_u8(Batch *b, const char *shard_dir, int image_dim_in
 /* mode MI_AUG_* (default FIXED), flip 0 / 1 (RANDOM only), seed; MI_SRC_SHARDS_U8 only (else -1, mi_last_error set).  Like the
  * optimizer, mode and seed are not dumped: a resumed run sets them again. */
 int mi_batch_set_augment(Batch *b, int mode, int flip, uint64_t seed);
-/* the plan of the last load, int [n_images][3]; returns n_images, or -1 (another source, or nothing loaded yet) */
+/* the plan of the last load, int [n_images][3]; returns n_images, or -1 (another source, nothing loaded yet, or MI_AUG_RRC, whose plan
+ * is mi_batch_last_boxes') */
 int mi_batch_last_plan(const Batch *b, int *out);
+
+/* ---------------- random-resized crop (RRC) from the uint8 shards ----------------
+ * The modes above cut a dim_out^2 window: every image is seen at one scale.  MI_AUG_RRC draws a box of random area and aspect ratio per
+ * image and epoch (torchvision's RandomResizedCrop.get_params on a square image) and the resample kernel (kernels_input.hip) scales it
+ * to dim_out^2 -- bilinear, + flip, planes and mean subtraction as the decode.
+ *
+ * mi_augment_plan_rrc: out[i] = (row0, col0, box_h, box_w, flip) of the image with global index g = first_global_index + i, host-only, a
+ * pure function of (seed, epoch, g).  s = splitmix64_at(seed, epoch), k = splitmix64_at(s, g), d(j) = splitmix64_at(k, j),
+ * U(x) = (x >> 11) 2^-53.  Try t = 0 .. 9: target = dim_in^2 (scale_lo + U(d(4t)) (scale_hi - scale_lo)), ratio = exp(log(ratio_lo) +
+ * U(d(4t + 1)) (log(ratio_hi) - log(ratio_lo))), w = lrint(sqrt(target ratio)), h = lrint(sqrt(target / ratio)) (half to even); the first
+ * try with 1 <= w, h <= dim_in is taken, row0 = ((d(4t + 2) >> 32) (dim_in - h + 1)) >> 32, col0 = ((d(4t + 3) >> 32) (dim_in - w + 1)) >> 32.
+ * No try taken: ratio_lo > 1: w = dim_in, h = lrint(dim_in / ratio_lo); ratio_hi < 1: h = dim_in, w = lrint(dim_in ratio_hi); else the
+ * whole image; h, w clamped to [1, dim_in], the box centred.  flip = flip ? d(40) >> 63 : 0.  Plain double arithmetic, every operation
+ * rounded on its own.  Returns 0, or -1 (n < 0, dim_in < 1, scale_lo or ratio_lo not positive, scale_hi < scale_lo, ratio_hi < ratio_lo). */
+enum { MI_AUG_RRC = 3 };
+int mi_augment_plan_rrc(int flip, uint64_t seed, int epoch, int64_t first_global_index, int n, int dim_in, double scale_lo, double scale_hi,
+                        double ratio_lo, double ratio_hi, int *out);
+/* the resample kernel on its own: src_dev as mi_op_decode_u8 (16-byte aligned, else -1), boxes_dev int [n][5] as mi_augment_plan_rrc
+ * writes it, out_nchw fp32 [n][3][dim_out][dim_out].  The box is clamped first (h, w into [1, dim_in], row0 into [0, dim_in - h], col0
+ * into [0, dim_in - w]): nothing outside the n images is read.  With D = dim_out, output row oy reads source rows y0 and
+ * y1 = min(y0 + 1, h - 1) of the box with weight wy / 256 on y1: num = clamp((2 oy + 1) h - D, 0, (h - 1) 2 D), fy = floor(256 num / (2 D)),
+ * y0 = fy >> 8, wy = fy & 255; columns likewise with w on ox' = flip ? D - 1 - ox : ox.  For byte position p (B, G, R) of the four
+ * neighbours b: top = b00 (256 - wx) + b01 wx, bot = b10 (256 - wx) + b11 wx, v = top (256 - wy) + bot wy (<= 255 * 65536, exact in int32
+ * and fp32), out[n][2 - p][oy][ox] = (float)((double)v 2^-16 - mean[p]), mean = 123.68 / 116.78 / 103.94.  A box with h = w = dim_out has
+ * wx = wy = 0 everywhere: the bits of mi_op_decode_u8 on the plan (row0, col0, flip).  The kernel stages source rows in LDS sized for a
+ * box as large as the image: with R output rows per workgroup (16, fewer where needed) it holds ceil((R - 1) dim_in / D) + 2 rows of
+ * 16 ceil((3 dim_in + 15) / 16) bytes + 4 (D + R, each rounded up to 4) bytes of tables in 64 KB.  Returns -2 where R = 1 does not fit. */
+int mi_op_resample_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_nchw, int n, int dim_in, int dim_out);
+/* MI_SRC_SHARDS_U8 only (else -1, mi_last_error set; -1 too for bounds mi_augment_plan_rrc refuses): load_new_batch builds the box plan
+ * at the same (epoch, global index) as the RANDOM mode and resamples on the same stream; rotation, ragged tail, rank slices, prefetch
+ * and resume are unchanged.  A later mi_batch_set_augment switches back.  Like the other modes it is not dumped. */
+int mi_batch_set_augment_rrc(Batch *b, int flip, uint64_t seed, double scale_lo, double scale_hi, double ratio_lo, double ratio_hi);
+/* the boxes of the last load, int [n_images][5]; returns n_images, or -1 (another source or mode, or nothing loaded yet) */
+int mi_batch_last_boxes(const Batch *b, int *out);
 
 /* typed operator layer: x_dt = storage type of the convolution-side tensors (x, dx), a_dt = of the activation-side tensors
  * (y, residual, dy, mask_src, gated_out).  Supported pairs: (F32,F32), (BF16,BF16), (F32,BF16). */

@@ -96,7 +96,7 @@ class Train_ResNet(C.Structure):
 
 MI_SRC_SHARDS, MI_SRC_BUFFER, MI_SRC_SYNTHETIC, MI_SRC_HOST = 0, 1, 2, 3
 MI_SRC_SHARDS_U8 = 4
-MI_AUG_FIXED, MI_AUG_CENTER, MI_AUG_RANDOM = 0, 1, 2
+MI_AUG_FIXED, MI_AUG_CENTER, MI_AUG_RANDOM, MI_AUG_RRC = 0, 1, 2, 3
 MI_LAYOUT_NHWC, MI_LAYOUT_NCHW = 0, 1
 MI_DTYPE_F32, MI_DTYPE_BF16 = 0, 1
 MI_STORE_FAST, MI_STORE_RECOMPUTE_BN, MI_STORE_FULL = 0, 1, 2
@@ -203,6 +203,10 @@ PROTOTYPES = {
     "mi_batch_source_shards_u8": (None, [_B, _cp, _i]),
     "mi_batch_set_augment": (_i, [_B, _i, _i, _u64]),
     "mi_batch_last_plan": (_i, [_B, _vp]),
+    "mi_augment_plan_rrc": (_i, [_i, _u64, _i, C.c_int64, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    "mi_op_resample_u8": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "mi_batch_set_augment_rrc": (_i, [_B, _i, _u64, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "mi_batch_last_boxes": (_i, [_B, _vp]),
     "mi_op_convert": (_i, [_vp, _i, _vp, _i, _sz]),
     "mi_bf16_conv_supported": (_i, [_i] * 7),
     "mi_bf16_pw_wgrad_supported": (_i, [_i] * 4),

@@ -21,6 +21,14 @@ static constexpr DecodeTable make_decode_table() {
 }
 __device__ const DecodeTable g_decode_table = make_decode_table();
 
+// 16 aligned bytes at src + a; the last 16 bytes of the batch, cut short, are read byte-wise up to total_bytes (zeros behind them)
+__device__ __forceinline__ uint4 load16_in_batch(const uint8_t *__restrict__ src, size_t a, size_t total_bytes) {
+    if (a + 16 <= total_bytes) return *(const uint4 *)(src + a);
+    uint32_t w[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 16 && a + k < total_bytes; k++) w[k >> 2] |= (uint32_t)src[a + k] << (8 * (k & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // grid (ceil(dim_out / DEC_ROWS), n).  A cropped source row is a span of dim_out * 3 bytes that starts at an arbitrary byte (col_off * 3
 // takes every residue mod 4, an odd dim_in shifts every row): the workgroup stages each of its rows' spans in LDS with aligned 16-byte
 // loads -- start rounded down (src is 16-byte aligned, so never in front of it), the one load that would cross the end of the batch
@@ -47,16 +55,7 @@ decode_u8_kernel(const uint8_t *__restrict__ src, const int *__restrict__ plan, 
         const int r = (int)fd_div((uint32_t)i, fdCH), c = i - r * CH;
         const size_t g = row0 + (size_t)r * row_pitch;
         const size_t a = (g & ~(size_t)15) + (size_t)c * 16;
-        if (a < g + span) {
-            uint4 v;
-            if (a + 16 <= total_bytes) v = *(const uint4 *)(src + a);
-            else { // the last 16 bytes of the batch, cut short
-                uint32_t w[4] = {0, 0, 0, 0};
-                for (int k = 0; k < 16 && a + k < total_bytes; k++) w[k >> 2] |= (uint32_t)src[a + k] << (8 * (k & 3));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            *(uint4 *)(rows + ((size_t)r * CH + c) * 16) = v;
-        }
+        if (a < g + span) *(uint4 *)(rows + ((size_t)r * CH + c) * 16) = load16_in_batch(src, a, total_bytes);
     }
     __syncthreads();
 
@@ -107,5 +106,134 @@ int mid_decode_u8(mid_stream s, const uint8_t *src, const int *plan, float *out,
                        dim_out, total, CH, vec, make_fastdiv((uint32_t)CH), make_fastdiv((uint32_t)(dim_out >> 2)), make_fastdiv((uint32_t)(dim_out & 3)));
     mi_prof_end((hipStream_t)s);
     MI_LAUNCH_CHECK("decode_u8_kernel");
+    return 0;
+}
+
+// ---- random-resized crop: a box per image, resampled to dim_out x dim_out (bilinear, 8 fractional bits), flip, planes, mean ----
+// The arithmetic is integer up to the last step and written down in include/resnet_mi.h; tests/rrcref.py restates it.
+#define RS_ROWS 16      // output rows of one image per workgroup (fewer where the worst-case source rows do not fit into LDS)
+#define RS_THREADS 256
+#define RS_LDS_MAX 65536
+
+// source coordinate of output index o on an axis that scales `len` source pixels to D output pixels, in 1/256 pixels:
+// floor(clamp((2 o + 1) len - D, 0, (len - 1) 2 D) * 256 / (2 D)).  32-bit throughout: o < D <= 16384 and len <= 16384 keep
+// (2 o + 1) len below 2^29; with num = q D + r the quotient is q * 128 + (r * 128) / D, r * 128 < 2^21, the result <= (len - 1) * 256 < 2^22.
+__device__ __forceinline__ int rs_coord(int o, int len, int D) {
+    const int num = min(max((2 * o + 1) * len - D, 0), (len - 1) * 2 * D);
+    const int q = num / D, r = num - q * D;
+    return q * 128 + (r * 128) / D;
+}
+// one output value from the four neighbours of byte position p in the staged rows L0 (y0) and L1 (y1); x0, x1 are byte offsets of
+// the two pixels; v <= 255 * 65536 is exact, the conversion is the decode table's: one rounding made from a double
+__device__ __forceinline__ float rs_value(const unsigned char *L0, const unsigned char *L1, int x0, int x1, int wx, int wy, int p) {
+    const double mean_of_src[3] = {123.68, 116.78, 103.94}; // as g_decode_table
+    const int top = L0[x0 + p] * (256 - wx) + L0[x1 + p] * wx;
+    const int bot = L1[x0 + p] * (256 - wx) + L1[x1 + p] * wx;
+    return (float)((double)(top * (256 - wy) + bot * wy) * 0x1p-16 - mean_of_src[p]);
+}
+// source rows a block of `rows` output rows can touch when the box is as high as the image (upscaling touches fewer): the first
+// and the last output row lie (rows - 1) dim_in / D source rows apart, floor() of that spread moves by at most its ceiling, + y1
+static inline int rs_src_rows(int rows, int dim_in, int D) { return mi_cdiv((long)(rows - 1) * dim_in, D) + 2; }
+
+// grid (ceil(dim_out / R), n), R output rows per workgroup.  LDS: ctab[dim_out] (x0 | wx << 16 per output column, the flip folded in),
+// rtab[R] (y0 - first staged row | wy << 16), then S row buffers of CH 16-byte pieces: source rows y0(first output row) .. y1(last) of
+// the box, each the span of w * 3 bytes from its 16-byte-aligned start as in decode_u8_kernel (a wave per row, a lane per piece).  R, S
+// and CH come from the launcher, sized for h = w = dim_in; the box is clamped here, so no plan reads outside its image.
+__global__ void __launch_bounds__(RS_THREADS)
+resample_u8_kernel(const uint8_t *__restrict__ src, const int *__restrict__ boxes, float *__restrict__ out, int dim_in, int D,
+                   size_t total_bytes, int R, int S, int CH, int vec, FastDiv fdQ, FastDiv fdT) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rs_smem[];
+    uint32_t *ctab = (uint32_t *)rs_smem;
+    uint32_t *rtab = ctab + ((D + 3) & ~3);
+    unsigned char *rows = (unsigned char *)(rtab + ((R + 3) & ~3));
+    const int tid = threadIdx.x, n = blockIdx.y, h0 = blockIdx.x * R;
+    const int nrows = min(R, D - h0);
+    const int *bx = boxes + 5 * (size_t)n;
+    const int h = min(max(bx[2], 1), dim_in), w = min(max(bx[3], 1), dim_in);
+    const int r0 = min(max(bx[0], 0), dim_in - h), c0 = min(max(bx[1], 0), dim_in - w), flip = bx[4] != 0;
+
+    const int ya = rs_coord(h0, h, D) >> 8;
+    const int yb = min((rs_coord(h0 + nrows - 1, h, D) >> 8) + 1, h - 1);
+    const int nsrc = min(yb - ya + 1, S); // <= S by rs_src_rows; the min keeps LDS addressing safe whatever the arithmetic
+    for (int i = tid; i < D; i += RS_THREADS) {
+        const int fx = rs_coord(flip ? D - 1 - i : i, w, D);
+        ctab[i] = (uint32_t)(fx >> 8) | (uint32_t)(fx & 255) << 16;
+    }
+    if (tid < nrows) {
+        const int fy = rs_coord(h0 + tid, h, D);
+        rtab[tid] = (uint32_t)min((fy >> 8) - ya, S - 1) | (uint32_t)(fy & 255) << 16;
+    }
+    const int span = w * 3;
+    const size_t g0 = (((size_t)n * dim_in + r0 + ya) * dim_in + c0) * 3; // first byte of the first staged span
+    const size_t row_pitch = (size_t)dim_in * 3;
+    const int pieces = min((span + 30) >> 4, CH);
+    for (int r = tid >> 6; r < nsrc; r += RS_THREADS / 64) {
+        const size_t g = g0 + (size_t)r * row_pitch;
+        for (int c = tid & 63; c < pieces; c += 64) {
+            const size_t a = (g & ~(size_t)15) + (size_t)c * 16;
+            if (a < g + span) *(uint4 *)(rows + ((size_t)r * CH + c) * 16) = load16_in_batch(src, a, total_bytes);
+        }
+    }
+    __syncthreads();
+
+    const int Q = D >> 2, xmax = w - 1;
+    const size_t plane = (size_t)D * D;
+    float *const out_n = out + (size_t)n * 3 * plane;
+    for (int i = tid; i < nrows * Q; i += RS_THREADS) {
+        const int r = (int)fd_div((uint32_t)i, fdQ), ox = (i - r * Q) * 4;
+        const uint32_t rt = rtab[r];
+        const int y0 = rt & 0xFFFF, wy = rt >> 16, y1 = min(y0 + 1, nsrc - 1);
+        const unsigned char *L0 = rows + (size_t)y0 * CH * 16 + ((g0 + (size_t)y0 * row_pitch) & 15);
+        const unsigned char *L1 = rows + (size_t)y1 * CH * 16 + ((g0 + (size_t)y1 * row_pitch) & 15);
+        float v[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t ct = ctab[ox + j];
+            const int x0 = (ct & 0xFFFF) * 3, wx = ct >> 16, x1 = min((int)(ct & 0xFFFF) + 1, xmax) * 3;
+#pragma unroll
+            for (int p = 0; p < 3; p++) v[p][j] = rs_value(L0, L1, x0, x1, wx, wy, p);
+        }
+        float *o = out_n + (size_t)(h0 + r) * D + ox;
+#pragma unroll
+        for (int d = 0; d < 3; d++) { // plane d (0 = R) holds source position 2 - d
+            if (vec) *(float4 *)(o + d * plane) = make_float4(v[2 - d][0], v[2 - d][1], v[2 - d][2], v[2 - d][3]);
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; j++) o[d * plane + j] = v[2 - d][j];
+            }
+        }
+    }
+    const int T = D & 3;
+    for (int i = tid; i < nrows * T * 3; i += RS_THREADS) {
+        const int rd = (int)fd_div((uint32_t)i, fdT), ox = 4 * Q + (i - rd * T);
+        const int r = rd / 3, p = 2 - (rd - 3 * r);
+        const uint32_t rt = rtab[r], ct = ctab[ox];
+        const int y0 = rt & 0xFFFF, wy = rt >> 16, y1 = min(y0 + 1, nsrc - 1);
+        const int x0 = (ct & 0xFFFF) * 3, wx = ct >> 16, x1 = min((int)(ct & 0xFFFF) + 1, xmax) * 3;
+        const unsigned char *L0 = rows + (size_t)y0 * CH * 16 + ((g0 + (size_t)y0 * row_pitch) & 15);
+        const unsigned char *L1 = rows + (size_t)y1 * CH * 16 + ((g0 + (size_t)y1 * row_pitch) & 15);
+        out_n[(2 - p) * plane + (size_t)(h0 + r) * D + ox] = rs_value(L0, L1, x0, x1, wx, wy, p);
+    }
+}
+
+int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *out, int n, int dim_in, int dim_out) {
+    if (n < 1 || n > 65535 || dim_out < 1 || dim_out > 16384 || dim_in < 1 || dim_in > 16384) { mi_record_error("mid_resample_u8", "need 1 <= n <= 65535 and 1 <= dim_in, dim_out <= 16384"); return -1; }
+    if (((uintptr_t)src & 15) != 0) { mi_record_error("mid_resample_u8", "src must be 16-byte aligned"); return -1; }
+    if (((uintptr_t)out & 3) != 0 || ((uintptr_t)boxes & 3) != 0) { mi_record_error("mid_resample_u8", "out / boxes must be 4-byte aligned"); return -1; }
+    const int CH = (dim_in * 3 + 15 + 15) / 16; // 16-byte pieces the widest span can touch once its start is rounded down
+    int R = dim_out < RS_ROWS ? dim_out : RS_ROWS;
+    size_t lds;
+    for (;; R--) { // LDS for the worst case h = w = dim_in: the box is known on the device only
+        lds = (size_t)(((dim_out + 3) & ~3) + ((R + 3) & ~3)) * 4 + (size_t)rs_src_rows(R, dim_in, dim_out) * CH * 16;
+        if (lds <= RS_LDS_MAX || R == 1) break;
+    }
+    if (lds > RS_LDS_MAX) { mi_record_error("mid_resample_u8", "dim_in too large: the source rows of one output row do not fit into LDS"); return -2; }
+    const int vec = (dim_out & 3) == 0 && ((uintptr_t)out & 15) == 0;
+    const size_t total = (size_t)n * dim_in * dim_in * 3;
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 15.0 * n * dim_out * dim_out); // algorithmic, as the decode: 3 bytes in, 12 out per output pixel
+    hipLaunchKernelGGL(resample_u8_kernel, dim3(mi_cdiv(dim_out, R), n), dim3(RS_THREADS), lds, (hipStream_t)s, src, boxes, out, dim_in, dim_out,
+                       total, R, rs_src_rows(R, dim_in, dim_out), CH, vec, make_fastdiv((uint32_t)(dim_out >> 2)), make_fastdiv((uint32_t)(dim_out & 3)));
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK("resample_u8_kernel");
     return 0;
 }

@@ -6,9 +6,11 @@
  * a dumped images.buffer/labels.buffer pair, caller-filled host buffers, or a seeded synthetic pool that
  * stays resident in HBM) because the reference's /mnt/storage paths are literals.
  * MI_SRC_SHARDS_U8 (new work, no counterpart in the reference): the shard holds whole uint8 images; the crop is drawn per load by
- * mi_augment_plan and made, with the flip and the float conversion, by the decode kernel (kernels_input.hip).
+ * mi_augment_plan and made, with the flip and the float conversion, by the decode kernel (kernels_input.hip).  MI_AUG_RRC: the plan
+ * is a box per image (mi_augment_plan_rrc) and the resample kernel scales it to the input size.
  */
 #define _GNU_SOURCE
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -70,7 +72,7 @@ void mi_batch_source_shards(Batch *b, const char *dir, int layout) {
 }
 /* staging of the uint8 source: set 0 for the blocking load, set 1 for the prefetched batch */
 static void u8_ensure(Batch *b, BatchExt *e) {
-    const size_t bytes = (size_t)b->n_images * e->u8_dim_in * e->u8_dim_in * 3, plan = (size_t)b->n_images * 3 * sizeof(int);
+    const size_t bytes = (size_t)b->n_images * e->u8_dim_in * e->u8_dim_in * 3, plan = (size_t)b->n_images * 5 * sizeof(int);
     for (int k = 0; k < (e->prefetch ? 2 : 1); k++) {
         if (e->u8_pinned[k]) continue;
         e->u8_pinned[k] = (uint8_t *)mid_malloc_host(bytes);
@@ -96,14 +98,36 @@ int mi_batch_set_augment(Batch *b, int mode, int flip, uint64_t seed) {
     BatchExt *e = mi_batch_ext(b);
     if (e->source != MI_SRC_SHARDS_U8) { mi_record_host_error("mi_batch_set_augment", "the data source is not MI_SRC_SHARDS_U8"); return -1; }
     if (mode != MI_AUG_FIXED && mode != MI_AUG_CENTER && mode != MI_AUG_RANDOM) { mi_record_host_error("mi_batch_set_augment", "mode is MI_AUG_FIXED, _CENTER or _RANDOM"); return -1; }
+    if (e->aug_mode == MI_AUG_RRC) { /* the last plan is a box plan, and the batch prefetched under it still reads the pinned set */
+        e->have_plan = 0;
+        if (e->have_next) mid_event_sync(e->ev_next);
+    }
     e->aug_mode = mode; e->aug_flip = flip != 0; e->aug_seed = seed;
     e->have_next = 0; /* a batch prefetched under the old choice */
     return 0;
 }
+int mi_batch_set_augment_rrc(Batch *b, int flip, uint64_t seed, double scale_lo, double scale_hi, double ratio_lo, double ratio_hi) {
+    BatchExt *e = mi_batch_ext(b);
+    if (e->source != MI_SRC_SHARDS_U8) { mi_record_host_error("mi_batch_set_augment_rrc", "the data source is not MI_SRC_SHARDS_U8"); return -1; }
+    if (!(scale_lo > 0) || !(ratio_lo > 0) || !(scale_hi >= scale_lo) || !(ratio_hi >= ratio_lo)) {
+        mi_record_host_error("mi_batch_set_augment_rrc", "need 0 < scale_lo <= scale_hi and 0 < ratio_lo <= ratio_hi"); return -1;
+    }
+    if (e->have_next) mid_event_sync(e->ev_next); /* the batch prefetched under the old choice still reads the pinned set */
+    e->aug_mode = MI_AUG_RRC; e->aug_flip = flip != 0; e->aug_seed = seed;
+    e->rrc_scale[0] = scale_lo; e->rrc_scale[1] = scale_hi; e->rrc_ratio[0] = ratio_lo; e->rrc_ratio[1] = ratio_hi;
+    e->have_next = 0; e->have_plan = 0; /* a batch prefetched under the old choice; a plan of the other shape */
+    return 0;
+}
 int mi_batch_last_plan(const Batch *b, int *out) {
     BatchExt *e = mi_batch_ext((Batch *)b);
-    if (e->source != MI_SRC_SHARDS_U8 || !e->have_plan) return -1;
+    if (e->source != MI_SRC_SHARDS_U8 || !e->have_plan || e->aug_mode == MI_AUG_RRC) return -1;
     memcpy(out, e->plan_pinned[0], (size_t)b->n_images * 3 * sizeof(int));
+    return b->n_images;
+}
+int mi_batch_last_boxes(const Batch *b, int *out) {
+    BatchExt *e = mi_batch_ext((Batch *)b);
+    if (e->source != MI_SRC_SHARDS_U8 || !e->have_plan || e->aug_mode != MI_AUG_RRC) return -1;
+    memcpy(out, e->plan_pinned[0], (size_t)b->n_images * 5 * sizeof(int));
     return b->n_images;
 }
 int mi_augment_plan(int mode, int flip, uint64_t seed, int epoch, int64_t first_global_index, int n, int dim_in, int dim_out,
@@ -128,6 +152,45 @@ int mi_augment_plan(int mode, int flip, uint64_t seed, int epoch, int64_t first_
             out[3 * i + 2] = flip ? (int)(r >> 63) : 0;
         }
     } else { mi_record_host_error("mi_augment_plan", "mode is MI_AUG_FIXED, _CENTER or _RANDOM"); return -1; }
+    return 0;
+}
+/* torchvision's RandomResizedCrop.get_params on a square image, drawn from the counter streams (include/resnet_mi.h).  Every product
+ * and sum is rounded on its own (the file is compiled with contraction off), so math.log / exp / sqrt / round in Python give the same
+ * integers (tests/rrcref.py). */
+static double rrc_unit(uint64_t x) { return (double)(x >> 11) * 0x1p-53; }
+static int rrc_clamp(long v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : (int)v; }
+int mi_augment_plan_rrc(int flip, uint64_t seed, int epoch, int64_t first_global_index, int n, int dim_in, double scale_lo, double scale_hi,
+                        double ratio_lo, double ratio_hi, int *out) {
+    if (n < 0 || dim_in < 1) { mi_record_host_error("mi_augment_plan_rrc", "need n >= 0 and dim_in >= 1"); return -1; }
+    if (!(scale_lo > 0) || !(ratio_lo > 0) || !(scale_hi >= scale_lo) || !(ratio_hi >= ratio_lo)) {
+        mi_record_host_error("mi_augment_plan_rrc", "need 0 < scale_lo <= scale_hi and 0 < ratio_lo <= ratio_hi"); return -1;
+    }
+    const uint64_t s = mi_splitmix64_at(seed, (uint64_t)(int64_t)epoch);
+    const double area = (double)dim_in * (double)dim_in, log_lo = log(ratio_lo), log_hi = log(ratio_hi);
+    for (int i = 0; i < n; i++) {
+        const uint64_t k = mi_splitmix64_at(s, (uint64_t)(first_global_index + i));
+        int h = 0, w = 0, row0 = 0, col0 = 0, t;
+        for (t = 0; t < 10; t++) {
+            const double target = area * (scale_lo + rrc_unit(mi_splitmix64_at(k, 4 * t)) * (scale_hi - scale_lo));
+            const double ratio = exp(log_lo + rrc_unit(mi_splitmix64_at(k, 4 * t + 1)) * (log_hi - log_lo));
+            const double fw = sqrt(target * ratio), fh = sqrt(target / ratio);
+            if (!(fw >= 0.5 && fw <= dim_in + 0.5 && fh >= 0.5 && fh <= dim_in + 0.5)) continue; /* lrint of such a side is out of range */
+            const long lw = lrint(fw), lh = lrint(fh); /* half to even */
+            if (lw < 1 || lw > dim_in || lh < 1 || lh > dim_in) continue;
+            w = (int)lw; h = (int)lh;
+            row0 = (int)(((mi_splitmix64_at(k, 4 * t + 2) >> 32) * (uint64_t)(dim_in - h + 1)) >> 32);
+            col0 = (int)(((mi_splitmix64_at(k, 4 * t + 3) >> 32) * (uint64_t)(dim_in - w + 1)) >> 32);
+            break;
+        }
+        if (t == 10) { /* the fallback: the largest centred box of an allowed ratio */
+            h = w = dim_in;
+            if (ratio_lo > 1) h = rrc_clamp(lrint(dim_in / ratio_lo), 1, dim_in);
+            else if (ratio_hi < 1) w = rrc_clamp(lrint(dim_in * ratio_hi), 1, dim_in);
+            row0 = (dim_in - h) / 2; col0 = (dim_in - w) / 2;
+        }
+        out[5 * i] = row0; out[5 * i + 1] = col0; out[5 * i + 2] = h; out[5 * i + 3] = w;
+        out[5 * i + 4] = flip ? (int)(mi_splitmix64_at(k, 40) >> 63) : 0;
+    }
     return 0;
 }
 /* double-buffered H2D: while step t runs, batch t+1 of the resident shard goes pinned -> device on the copy stream
@@ -179,8 +242,10 @@ static void u8_enqueue(Batch *b, BatchExt *e, int bi, int k, mid_stream s, float
     memcpy(labels_host, b->full_shard_correct_classes + (size_t)bi * N, (size_t)N * sizeof(int));
     mid_memcpy_h2d(e->u8_dev[k], e->u8_pinned[k], bytes, s);
     mid_memcpy_h2d(labels_dev, labels_host, (size_t)N * sizeof(int), s);
-    mid_memcpy_h2d(e->plan_dev[k], e->plan_pinned[k], (size_t)N * 3 * sizeof(int), s);
-    mid_decode_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim);
+    const int rrc = e->aug_mode == MI_AUG_RRC;
+    mid_memcpy_h2d(e->plan_dev[k], e->plan_pinned[k], (size_t)N * (rrc ? 5 : 3) * sizeof(int), s);
+    if (rrc) mid_resample_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim);
+    else mid_decode_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim);
 }
 /* the plan of this rank's batch bi of the resident shard at `epoch` into plan_pinned[k]; 0, or -1 with a message */
 static int u8_plan(Batch *b, BatchExt *e, int bi, int epoch, int k) {
@@ -190,7 +255,9 @@ static int u8_plan(Batch *b, BatchExt *e, int bi, int epoch, int k) {
         return -1;
     }
     const int64_t first = (int64_t)b->cur_shard_id * b->shard_n_images + (int64_t)bi * N;
-    if (mi_augment_plan(e->aug_mode, e->aug_flip, e->aug_seed, epoch, first, N, e->u8_dim_in, b->image_dim,
+    if (e->aug_mode == MI_AUG_RRC ? mi_augment_plan_rrc(e->aug_flip, e->aug_seed, epoch, first, N, e->u8_dim_in, e->rrc_scale[0], e->rrc_scale[1],
+                                                       e->rrc_ratio[0], e->rrc_ratio[1], e->plan_pinned[k]) :
+        mi_augment_plan(e->aug_mode, e->aug_flip, e->aug_seed, epoch, first, N, e->u8_dim_in, b->image_dim,
                         e->u8_have_crops ? e->u8_crops + (size_t)bi * N * 2 : NULL, e->plan_pinned[k])) {
         fprintf(stderr, "resnet_mi: no augmentation plan for shard %d batch %d: %s\n", b->cur_shard_id, bi, mi_last_error());
         return -1;
@@ -346,7 +413,7 @@ void load_new_batch(Train_ResNet *trainer, Class_Metadata *class_metadata, Batch
                 float *ti = b->images; b->images = e->images_next; e->images_next = ti;
                 int *tl = b->correct_classes; b->correct_classes = e->labels_next; e->labels_next = tl;
                 memcpy(b->correct_classes_cpu, e->labels_next_host, (size_t)N * sizeof(int));
-                memcpy(e->plan_pinned[0], e->plan_pinned[1], (size_t)N * 3 * sizeof(int));
+                memcpy(e->plan_pinned[0], e->plan_pinned[1], (size_t)N * 5 * sizeof(int));
                 e->have_next = 0; e->have_plan = 1;
             } else if (u8_plan(b, e, bi, epoch, 0) == 0) {
                 u8_enqueue(b, e, bi, 0, g->compute, b->images, b->correct_classes, b->correct_classes_cpu);

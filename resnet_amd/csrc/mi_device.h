@@ -283,6 +283,8 @@ int mid_nchw_to_nhwc(mid_stream s, const float *in, float *out, int N, int C, in
  * (row_off, col_off, flip) in device memory; out = fp32 NCHW [n][3][dim_out][dim_out], R,G,B planes, means subtracted as mi_build_shard
  * does.  Reads nothing outside [src, src + n dim_in^2 3).  Returns 0, -1 (alignment / sizes; mid_last_error says which), -2 (dim_out too large) */
 int mid_decode_u8(mid_stream s, const uint8_t *src, const int *plan, float *out, int n, int dim_in, int dim_out);
+/* boxes [n][5] (row0, col0, h, w, flip), clamped into the image; each box resampled to dim_out^2.  -2: dim_in too large for LDS */
+int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *out, int n, int dim_in, int dim_out);
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */
 int mid_fill_uniform(mid_stream s, float *out, size_t n, uint64_t seed, uint64_t offset, float lo, float hi);
 int mid_lds_poison(mid_stream s); /* test aid: fills LDS of every CU with NaNs */

@@ -43,10 +43,11 @@ typedef struct BatchExt {
      * device staging buffer for the batch's bytes and for its plan */
     int u8_dim_in, aug_mode, aug_flip, u8_have_crops, have_plan, next_epoch;
     uint64_t aug_seed;
+    double rrc_scale[2], rrc_ratio[2]; /* MI_AUG_RRC: area share and aspect ratio, (lo, hi) each */
     uint8_t *u8_shard;           /* host, shard_n_images * dim_in^2 * 3 */
     int *u8_crops;               /* host, [shard_n_images][2] */
     uint8_t *u8_pinned[2], *u8_dev[2];
-    int *plan_pinned[2], *plan_dev[2]; /* [n_images][3]; plan_pinned[0] = the plan of the last load */
+    int *plan_pinned[2], *plan_dev[2]; /* [n_images][3], MI_AUG_RRC: [n_images][5] (room for 5 always); plan_pinned[0] = the plan of the last load */
     struct BatchExt *next;
 } BatchExt;
 BatchExt *mi_batch_ext(Batch *b);

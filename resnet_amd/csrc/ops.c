@@ -127,6 +127,9 @@ int mi_op_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C) 
 int mi_op_decode_u8(const uint8_t *src_dev, const int *plan_dev, float *out_nchw, int n, int dim_in, int dim_out) {
     return finish(mid_decode_u8(mi_global()->compute, src_dev, plan_dev, out_nchw, n, dim_in, dim_out));
 }
+int mi_op_resample_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_nchw, int n, int dim_in, int dim_out) {
+    return finish(mid_resample_u8(mi_global()->compute, src_dev, boxes_dev, out_nchw, n, dim_in, dim_out));
+}
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_poison_lds(void) { return finish(mid_lds_poison(mi_global()->compute)); }
 int mi_debug_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]) { return mid_igemm_plan(op, N, C, H, K, k, stride, out); }

@@ -116,6 +116,19 @@ class Ops:
         img = out[:total].reshape(n, 3, dim_out, dim_out)
         return (img, out[total:]) if pad_floats else img
 
+    def resample_u8(self, src, boxes, dim_out, pad_floats=0, fill=0.0):
+        """uint8 images (n, dim_in, dim_in, 3) B,G,R + int32 boxes (n, 5) (row0, col0, h, w, flip) -> fp32 (n, 3, dim_out, dim_out): every
+        box resampled to dim_out x dim_out (mi_op_resample_u8).  pad_floats, fill: as decode_u8"""
+        src = np.ascontiguousarray(src, np.uint8)
+        n, dim_in = src.shape[0], src.shape[1]
+        total = n * 3 * dim_out * dim_out
+        dsrc, dbox = self.dev(src), self.dev(np.ascontiguousarray(boxes, np.int32))
+        dout = self.dev(np.full(total + pad_floats, fill, np.float32))
+        self._chk(self.L.mi_op_resample_u8(dsrc.ptr, dbox.ptr, dout.ptr, n, dim_in, dim_out), "resample_u8")
+        out = dout.get()
+        img = out[:total].reshape(n, 3, dim_out, dim_out)
+        return (img, out[total:]) if pad_floats else img
+
     def maxpool_fwd(self, x, k, stride):
         N, Cc, H, _ = x.shape
         Ho = H // stride

@@ -151,16 +151,22 @@ class Trainer:
         if prefetch:
             self.L.mi_batch_set_prefetch(self.c_batch, 1)
 
-    AUGMENTS = {"fixed": B.MI_AUG_FIXED, "center": B.MI_AUG_CENTER, "random": B.MI_AUG_RANDOM}
+    AUGMENTS = {"fixed": B.MI_AUG_FIXED, "center": B.MI_AUG_CENTER, "random": B.MI_AUG_RANDOM, "rrc": B.MI_AUG_RRC}
 
-    def source_shards_u8(self, shard_dir, dim_in, augment="fixed", flip=True, seed=0, prefetch=False):
+    def source_shards_u8(self, shard_dir, dim_in, augment="fixed", flip=True, seed=0, prefetch=False, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3)):
         """uint8 shards of whole dim_in x dim_in images (mi_build_shard_u8); crop, flip and float conversion on the device at
-        every load.  augment: "fixed" (the shard's .crops, the reference's pixels), "center" or "random" (a new draw per epoch)"""
+        every load.  augment: "fixed" (the shard's .crops, the reference's pixels), "center", "random" (a new draw per epoch) or "rrc"
+        (random-resized crop: a box of `scale` of the image's area and aspect `ratio`, resampled to the input size; a new draw per epoch)"""
         self.L.mi_batch_source_shards_u8(self.c_batch, shard_dir.encode(), int(dim_in))
-        if self.L.mi_batch_set_augment(self.c_batch, self.AUGMENTS[augment], int(bool(flip)), int(seed)) != 0:
+        if self.AUGMENTS[augment] == B.MI_AUG_RRC:
+            rc, what = self.L.mi_batch_set_augment_rrc(self.c_batch, int(bool(flip)), int(seed), float(scale[0]), float(scale[1]),
+                                                       float(ratio[0]), float(ratio[1])), "mi_batch_set_augment_rrc: "
+        else:
+            rc, what = self.L.mi_batch_set_augment(self.c_batch, self.AUGMENTS[augment], int(bool(flip)), int(seed)), "mi_batch_set_augment: "
+        if rc != 0:
             e = self.error()
             self.L.mi_clear_error()
-            raise RuntimeError("mi_batch_set_augment: " + e)
+            raise RuntimeError(what + e)
         if prefetch:
             self.L.mi_batch_set_prefetch(self.c_batch, 1)
         self.check()
@@ -169,7 +175,14 @@ class Trainer:
         """(row_off, col_off, flip) per image of the last load_new_batch (uint8 shards), int32 (batch, 3)"""
         out = np.empty((self.batch, 3), np.int32)
         if self.L.mi_batch_last_plan(self.c_batch, out.ctypes.data) != self.batch:
-            raise RuntimeError("no plan: the source is not uint8 shards, or nothing was loaded yet")
+            raise RuntimeError("no plan: the source is not uint8 shards, the mode is rrc (last_boxes), or nothing was loaded yet")
+        return out
+
+    def last_boxes(self):
+        """(row0, col0, box_h, box_w, flip) per image of the last load_new_batch (uint8 shards, augment="rrc"), int32 (batch, 5)"""
+        out = np.empty((self.batch, 5), np.int32)
+        if self.L.mi_batch_last_boxes(self.c_batch, out.ctypes.data) != self.batch:
+            raise RuntimeError("no boxes: the source is not uint8 shards in rrc mode, or nothing was loaded yet")
         return out
 
     def fill_host_batch(self, images, labels):

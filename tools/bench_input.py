@@ -5,13 +5,17 @@
    256 -> 224, a RANDOM plan with flips, against the device pass of the fp32 NHWC shard path (mi_op_nhwc_to_nchw at 256 x 224^2 x 3)
    in the same run: each launch bracketed by HIP events on its stream (mi_prof family 4), the two kernels alternating, median of
    --runs launches after warm-up.  GB/s over the algorithmic bytes: decode N dim_out^2 (3 + 12), re-layout N dim_out^2 3 (4 + 4).
+   Beside them the resample kernel of the random-resized crop (mi_op_resample_u8) on the boxes mi_augment_plan_rrc draws with the
+   default bounds (scale 0.08 .. 1, ratio 3/4 .. 4/3): its bytes are the boxes' 3 h w in and the same 12 N dim_out^2 out.
 2. The whole training step on the real data path: ResNet-50 at batch 256, fp32 and bf16 storage, from (a) the synthetic pool resident
-   in HBM, (b) fp32 NCHW shards with prefetch, (c) uint8 shards, RANDOM crops with flips, with prefetch.  Both shards are built from
-   the same seeded class files in a temporary directory; one shard holds every timed step, so no step reads a file.  Legs (b) and (c)
-   run twice each, alternating, which gives the run-to-run spread the comparison is read against.
+   in HBM, (b) fp32 NCHW shards with prefetch, (c) uint8 shards, RANDOM crops with flips, with prefetch, (d) the same uint8 shard
+   with random-resized crops (u8 rrc).  Both shards are built from the same seeded class files in a temporary directory; one shard
+   holds every timed step, so no step reads a file.  Legs (b), (c) and (d) run three times each, alternating, which gives every leg
+   the run-to-run spread the comparisons are read against: (c) against (b), (d) against (c).
 3. Host and device bytes of the two shard sources.
   python tools/bench_input.py [--runs 30] [--steps 16] [--warmup 3] [--skip-steps]
-Exit status 1 if the decode is slower than the re-layout, or the uint8 leg slower than the fp32-shard leg by more than that spread."""
+Exit status 1 if the decode is slower than the re-layout, the uint8 leg slower than the fp32-shard leg by more than that spread, or
+the rrc leg slower than the uint8 RANDOM leg by more than the RANDOM leg's own spread."""
 import argparse
 import ctypes as C
 import json
@@ -50,10 +54,14 @@ def bench_kernels(runs, warmup=3):
     plan = np.empty((N, 3), np.int32)
     assert L.mi_augment_plan(B.MI_AUG_RANDOM, 1, 7, 0, 0, N, DIM_IN, DIM_OUT, None, plan.ctypes.data) == 0
     dplan = ops.dev(plan)
+    boxes = np.empty((N, 5), np.int32)
+    assert L.mi_augment_plan_rrc(1, 7, 0, 0, N, DIM_IN, 0.08, 1.0, 3 / 4, 4 / 3, boxes.ctypes.data) == 0
+    dboxes = ops.dev(boxes)
     out = ops.dev(shape=(N, 3, DIM_OUT, DIM_OUT))
     nhwc = ops.dev(shape=(N, DIM_OUT, DIM_OUT, 3))
     assert L.mi_op_fill_uniform(nhwc.ptr, N * DIM_OUT * DIM_OUT * 3, 1234, -124.0, 152.0) == 0
     legs = {"decode_u8": lambda: L.mi_op_decode_u8(src.ptr, dplan.ptr, out.ptr, N, DIM_IN, DIM_OUT),
+            "resample_u8": lambda: L.mi_op_resample_u8(src.ptr, dboxes.ptr, out.ptr, N, DIM_IN, DIM_OUT),
             "nhwc_to_nchw": lambda: L.mi_op_nhwc_to_nchw(nhwc.ptr, out.ptr, N, DIM_OUT, DIM_OUT, 3)}
     ms = {k: [] for k in legs}
     L.mi_prof_enable(1 << FAMILY)
@@ -67,13 +75,16 @@ def bench_kernels(runs, warmup=3):
     L.mi_prof_enable(0)
     px = N * DIM_OUT * DIM_OUT
     res = {}
-    for k, byt in (("decode_u8", px * 15), ("nhwc_to_nchw", px * 24)):
+    box_bytes = int(3 * (boxes[:, 2].astype(np.int64) * boxes[:, 3]).sum())
+    for k, byt in (("decode_u8", px * 15), ("resample_u8", box_bytes + px * 12), ("nhwc_to_nchw", px * 24)):
         med = float(np.median(ms[k]))
         res[k] = dict(ms=round(med, 4), ms_min=round(float(np.min(ms[k])), 4), ms_max=round(float(np.max(ms[k])), 4), runs=len(ms[k]),
                       algorithmic_bytes=byt, gb_per_s=round(byt / (med * 1e-3) / 1e9, 1),
                       share_of_achievable_hbm=round(byt / (med * 1e-3) / HBM_ACHIEVABLE, 3))
         print("%-13s %8.4f ms (min %.4f, max %.4f; %d runs)  %7.1f GB/s = %.1f %% of 6.3 TB/s" %
               (k, med, res[k]["ms_min"], res[k]["ms_max"], len(ms[k]), res[k]["gb_per_s"], 100 * res[k]["share_of_achievable_hbm"]))
+    res["resample_over_decode"] = round(res["resample_u8"]["ms"] / res["decode_u8"]["ms"], 3)
+    res["resample_mean_box_side"] = round(float(np.sqrt((boxes[:, 2].astype(np.float64) * boxes[:, 3]).mean())), 1)
     res["decode_over_nhwc"] = round(res["decode_u8"]["ms"] / res["nhwc_to_nchw"]["ms"], 3)
     res["decode_le_nhwc"] = res["decode_u8"]["ms"] <= res["nhwc_to_nchw"]["ms"]
     return res
@@ -111,6 +122,8 @@ def time_leg(kind, dtype, dirs, per_shard, steps, warmup):
             tr.source_synthetic(1234, 1235, pool_batches=2)
         elif kind == "f32_shards":
             tr.source_shards(dirs[0], B.MI_LAYOUT_NCHW, prefetch=True)
+        elif kind == "u8_rrc":
+            tr.source_shards_u8(dirs[1], DIM_IN, augment="rrc", flip=True, seed=7, prefetch=True)
         else:
             tr.source_shards_u8(dirs[1], DIM_IN, augment="random", flip=True, seed=7, prefetch=True)
         for _ in range(warmup):  # the first load reads the shard
@@ -136,26 +149,30 @@ def bench_steps(steps, warmup):
     try:
         f32, u8, sizes = build_shards(root, per_shard)
         for dtype in ("f32", "bf16"):
-            r = {"f32_shards": [], "u8_shards": []}
+            kinds = ("f32_shards", "u8_shards", "u8_rrc")
+            r = {k: [] for k in kinds}
             r["synthetic"], dev = time_leg("synthetic", dtype, (f32, u8), per_shard, steps, warmup)
-            for _ in range(2):
-                for kind in ("f32_shards", "u8_shards"):
+            for _ in range(3):
+                for kind in kinds:
                     r[kind].append(time_leg(kind, dtype, (f32, u8), per_shard, steps, warmup)[0])
-            spread = max(abs(r[k][0] - r[k][1]) for k in ("f32_shards", "u8_shards"))
-            best = {k: max(r[k]) for k in ("f32_shards", "u8_shards")}
+            spreads = {k: max(r[k]) - min(r[k]) for k in kinds}
+            spread = max(spreads["f32_shards"], spreads["u8_shards"])
+            best = {k: max(r[k]) for k in kinds}
             res[dtype] = dict(images_per_sec={k: (round(v, 1) if k == "synthetic" else [round(x, 1) for x in v]) for k, v in r.items()},
-                              spread_of_repeats=round(spread, 1),
+                              spread_of_repeats=round(spread, 1), spread_by_leg={k: round(v, 1) for k, v in spreads.items()},
                               gap_to_synthetic={k: round(1 - best[k] / r["synthetic"], 4) for k in best},
-                              u8_ge_f32_shards=best["u8_shards"] >= best["f32_shards"] - spread, trainer_device_bytes=dev)
-            print("%-4s synthetic %.1f img/s, fp32 shards %s, uint8 shards %s (spread of repeats %.1f)" %
-                  (dtype, r["synthetic"], ["%.1f" % x for x in r["f32_shards"]], ["%.1f" % x for x in r["u8_shards"]], spread))
+                              u8_ge_f32_shards=best["u8_shards"] >= best["f32_shards"] - spread,
+                              rrc_ge_random=best["u8_rrc"] >= best["u8_shards"] - spreads["u8_shards"], trainer_device_bytes=dev)
+            print("%-4s synthetic %.1f img/s, fp32 shards %s, uint8 shards %s, uint8 rrc %s (spread of repeats %.1f, of the uint8 leg %.1f)" %
+                  (dtype, r["synthetic"], ["%.1f" % x for x in r["f32_shards"]], ["%.1f" % x for x in r["u8_shards"]],
+                   ["%.1f" % x for x in r["u8_rrc"]], spread, spreads["u8_shards"]))
         img_in, img_out = DIM_IN * DIM_IN * 3, DIM_OUT * DIM_OUT * 3 * 4
         res["bytes"] = dict(
             shard_files=sizes, images_per_shard=per_shard,
             reference_shard_32768=dict(f32=32768 * (img_out + 4), u8=32768 * (img_in + 4 + 8)),
             per_step_h2d=dict(f32=N * (img_out + 4), u8=N * (img_in + 4 + 12)),
-            pinned_host_with_prefetch=dict(f32=2 * N * (img_out + 4), u8=2 * N * (img_in + 12) + 2 * N * 4 + N * img_out),
-            device_beside_the_trainer_with_prefetch=dict(f32=3 * N * img_out + 2 * N * 4, u8=2 * N * (img_out + 4) + 2 * N * (img_in + 12)))
+            pinned_host_with_prefetch=dict(f32=2 * N * (img_out + 4), u8=2 * N * (img_in + 20) + 2 * N * 4 + N * img_out),
+            device_beside_the_trainer_with_prefetch=dict(f32=3 * N * img_out + 2 * N * 4, u8=2 * N * (img_out + 4) + 2 * N * (img_in + 20)))
     finally:
         shutil.rmtree(root, ignore_errors=True)
     return res
@@ -174,7 +191,7 @@ def main():
     ok = out["kernels"]["decode_le_nhwc"]
     if not a.skip_steps:
         out["steps"] = bench_steps(max(a.steps, 16), a.warmup)
-        ok = ok and all(out["steps"][d]["u8_ge_f32_shards"] for d in ("f32", "bf16"))
+        ok = ok and all(out["steps"][d]["u8_ge_f32_shards"] and out["steps"][d]["rrc_ge_random"] for d in ("f32", "bf16"))
     print(json.dumps(out))
     return 0 if ok else 1
 
