@@ -319,6 +319,18 @@ int mi_op_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C);
 /* device-side seeded fill (splitmix64 counter stream, uniform [lo,hi)) -- synthetic operands for micro-benchmarks */
 /* test aid: leaves NaNs in the LDS of every CU (catches kernels that read LDS they did not write) */
 int mi_debug_poison_lds(void);
+/* test aid: red-zone mode of the device allocator behind every allocation of the library (operator tensors and workspaces, trainer, loader,
+ * optimizer).  zone_bytes 0 = off (the default); else a multiple of 4096 (-1 otherwise): an allocation of b bytes becomes zone | b | zone, the
+ * whole of it filled with fill_byte (0xFF: NaN as fp32 and bf16, -1 as int; 0x00: the control) before the pointer is returned.  Both zones
+ * are compared with the fill when the allocation is freed and, for every live padded allocation, in mi_debug_redzone_check, after a device
+ * synchronise.  The check returns the number of damaged allocations seen since the mode was last switched on, freed ones included, and
+ * mi_last_error describes the first: serial number, payload bytes, front / back zone, first..last damaged offset from the payload's start
+ * (front, negative) or end (back, from 0) and the number of damaged bytes.  Allocations keep the setting they were made under; switching
+ * while some are live is safe.  mi_debug_redzone_stats: allocations verified and zone bytes compared since the mode was last switched on, and
+ * padded allocations live now (any pointer may be NULL).  No access leaves the process's own allocations. */
+int mi_debug_redzone(size_t zone_bytes, int fill_byte);
+int mi_debug_redzone_check(void);
+void mi_debug_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live);
 /* host-only (no GPU needed): route and grid the launch planners choose for a convolution.  op 0 fwd, 1 dgrad, 2 wgrad.
  * out[0] 1 = MFMA implicit GEMM / 0 = other kernels, [1] rows per tile, [2] tiles, [3] tiles launched whole, [4] reduction
  * slices per tail tile, [5] k-steps per slice, [6] wgrad splits, [7] workgroups per class or split, [8] k-steps */

@@ -102,6 +102,7 @@ MI_DTYPE_F32, MI_DTYPE_BF16 = 0, 1
 MI_STORE_FAST, MI_STORE_RECOMPUTE_BN, MI_STORE_FULL = 0, 1, 2
 MI_ROUTE_DEFAULT, MI_ROUTE_CL, MI_ROUTE_CL2, MI_ROUTE_PW = 0, 1, 2, 3
 MI_OPT_ADAM, MI_OPT_SGD, MI_OPT_LARS = 0, 1, 2
+MI_GUARD = 256  # slack bytes mi_malloc leaves on both sides of a tensor (csrc/mi_host.h)
 
 # every symbol include/resnet_mi.h declares: name -> (restype, argtypes)
 _i, _f, _vp, _sz, _u64, _cp = C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p
@@ -175,6 +176,9 @@ PROTOTYPES = {
     "mi_op_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "mi_op_fill_uniform": (_i, [_vp, _sz, _u64, _f, _f]),
     "mi_debug_poison_lds": (_i, []),
+    "mi_debug_redzone": (_i, [_sz, _i]),
+    "mi_debug_redzone_check": (_i, []),
+    "mi_debug_redzone_stats": (None, [C.POINTER(_sz)] * 3),
     "mi_debug_conv_plan": (_i, [_i] * 7 + [_vp]),
     "mi_conv_plan": (_i, [_i] * 9 + [_vp]),
     "mi_trainer_set_dtype": (_i, [_T, _i]),

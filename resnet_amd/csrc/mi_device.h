@@ -26,6 +26,11 @@ const char *mid_last_error(void);
 void mid_clear_error(void);
 void *mid_malloc(size_t bytes);
 void mid_free(void *p);
+/* red-zone mode of mid_malloc / mid_free (test aid, runtime.hip): zone | payload | zone, all filled with fill_byte, zones compared at free and in
+ * mid_redzone_check */
+int mid_redzone(size_t zone_bytes, int fill_byte);
+int mid_redzone_check(void);
+void mid_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live);
 void *mid_malloc_host(size_t bytes); /* pinned */
 void mid_free_host(void *p);
 void mid_memcpy_h2d(void *dst, const void *src, size_t bytes, mid_stream s);

@@ -132,6 +132,9 @@ int mi_op_resample_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_n
 }
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_poison_lds(void) { return finish(mid_lds_poison(mi_global()->compute)); }
+int mi_debug_redzone(size_t zone_bytes, int fill_byte) { return mid_redzone(zone_bytes, fill_byte); }
+int mi_debug_redzone_check(void) { return mid_redzone_check(); }
+void mi_debug_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live) { mid_redzone_stats(allocs_checked, zone_bytes_checked, live); }
 int mi_debug_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]) { return mid_igemm_plan(op, N, C, H, K, k, stride, out); }
 int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]) {
     for (int i = 0; i < 7; i++) out[i] = 0;

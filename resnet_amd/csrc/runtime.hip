@@ -6,6 +6,9 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <atomic>
+#include <mutex>
+#include <vector>
 #include "mi_device.h"
 #include "mi_common.hpp"
 
@@ -53,6 +56,74 @@ void mi_trace_launch(const char *name) {
         if (e_ != hipSuccess) mi_record_error(#x, hipGetErrorString(e_)); \
     } while (0)
 
+// ---- red-zone mode of the device allocator (test aid, off by default: mi_debug_redzone) ----
+// While it is on, b bytes are allocated as zone | b | zone, all of it filled with one byte value; the zones are compared with that value
+// when the allocation is freed and in mid_redzone_check.  Every access stays inside the process's own allocations.
+struct RzEntry { char *user; size_t bytes, zone; int fill; unsigned long serial; bool damaged; };
+static std::mutex g_rz_mu;                       /* the loader's prefetch thread allocates too */
+static std::vector<RzEntry> g_rz;                /* live padded allocations */
+static std::atomic<size_t> g_rz_zone{0}, g_rz_live{0};
+static int g_rz_fill = 0, g_rz_damaged = 0;
+static unsigned long g_rz_serial = 0;
+static size_t g_rz_checked_allocs = 0, g_rz_checked_bytes = 0;
+static char g_rz_first[320] = "";
+static void *rz_malloc(size_t bytes) {
+    std::lock_guard<std::mutex> lk(g_rz_mu);
+    const size_t zone = g_rz_zone;
+    if (!zone) { /* switched off meanwhile */
+        void *q = nullptr;
+        hipError_t e0 = hipMalloc(&q, bytes);
+        if (e0 != hipSuccess) { mi_record_error("hipMalloc", hipGetErrorString(e0)); return nullptr; }
+        return q;
+    }
+    char *base = nullptr;
+    hipError_t e = hipMalloc((void **)&base, bytes + 2 * zone);
+    if (e != hipSuccess) { mi_record_error("hipMalloc", hipGetErrorString(e)); return nullptr; }
+    HIPCHK(hipMemsetAsync(base, g_rz_fill, bytes + 2 * zone, nullptr));
+    HIPCHK(hipStreamSynchronize(nullptr)); /* the fill is complete before the pointer is used on any stream */
+    g_rz.push_back(RzEntry{base + zone, bytes, zone, g_rz_fill, ++g_rz_serial, false});
+    g_rz_live = g_rz.size();
+    return base + zone;
+}
+/* compares both zones of e with its fill (the caller holds the lock and has synchronised the device) */
+static void rz_verify(RzEntry &e) {
+    std::vector<unsigned char> h(e.zone);
+    g_rz_checked_allocs++;
+    for (int side = 0; side < 2; side++) {
+        const char *z = side ? e.user + e.bytes : e.user - e.zone;
+        if (hipMemcpy(h.data(), z, e.zone, hipMemcpyDeviceToHost) != hipSuccess) { mi_record_error("mi_debug_redzone", "copy of a zone failed"); return; }
+        g_rz_checked_bytes += e.zone;
+        size_t n = 0, first = 0, last = 0;
+        for (size_t i = 0; i < e.zone; i++)
+            if (h[i] != (unsigned char)e.fill) { if (!n++) first = i; last = i; }
+        if (!n) continue;
+        if (!e.damaged) { e.damaged = true; g_rz_damaged++; }
+        if (!g_rz_first[0]) {
+            /* offsets: back zone from the payload's end (0 = the first byte behind it), front zone from its start (-1 = the byte before it) */
+            const long off = side ? 0 : -(long)e.zone;
+            snprintf(g_rz_first, sizeof g_rz_first, "mi_debug_redzone: red zone damaged: allocation #%lu of %zu bytes, %s zone, offsets %ld..%ld from the payload's %s, %zu bytes "
+                     "(fill 0x%02x, first damaged byte 0x%02x)", e.serial, e.bytes, side ? "back" : "front", (long)first + off, (long)last + off,
+                     side ? "end" : "start", n, e.fill, h[first]);
+            if (g_err[0] == 0) snprintf(g_err, sizeof g_err, "%s", g_rz_first);
+        }
+    }
+}
+/* 1: p was a padded allocation (verified and freed) */
+static int rz_free(void *p) {
+    std::lock_guard<std::mutex> lk(g_rz_mu);
+    for (size_t i = 0; i < g_rz.size(); i++) {
+        if (g_rz[i].user != (char *)p) continue;
+        HIPCHK(hipDeviceSynchronize());
+        rz_verify(g_rz[i]);
+        HIPCHK(hipFree(g_rz[i].user - g_rz[i].zone));
+        g_rz[i] = g_rz.back();
+        g_rz.pop_back();
+        g_rz_live = g_rz.size();
+        return 1;
+    }
+    return 0;
+}
+
 extern "C" {
 const char *mid_last_error(void) { return g_err; }
 void mid_clear_error(void) { g_err[0] = 0; }
@@ -68,12 +139,47 @@ int mid_set_device(int dev) {
     return 0;
 }
 void *mid_malloc(size_t bytes) {
+    if (!bytes) bytes = 4;
+    if (g_rz_zone) return rz_malloc(bytes);
     void *p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
+    hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) { mi_record_error("hipMalloc", hipGetErrorString(e)); return nullptr; }
     return p;
 }
-void mid_free(void *p) { if (p) HIPCHK(hipFree(p)); }
+void mid_free(void *p) {
+    if (!p) return;
+    if (g_rz_live && rz_free(p)) return;
+    HIPCHK(hipFree(p));
+}
+/* red-zone mode of the allocator (test aid): zone_bytes == 0 off; else a multiple of 4096 (pointers keep hipMalloc's alignment; -1 otherwise).
+ * Switching it on starts a new count of damaged allocations; allocations made under an earlier setting stay padded and checked */
+int mid_redzone(size_t zone_bytes, int fill_byte) {
+    if (zone_bytes % 4096) { mi_record_error("mi_debug_redzone", "zone_bytes is 0 or a multiple of 4096"); return -1; }
+    std::lock_guard<std::mutex> lk(g_rz_mu);
+    g_rz_zone = zone_bytes;
+    g_rz_fill = fill_byte & 0xff;
+    if (zone_bytes) {
+        g_rz_damaged = 0; g_rz_checked_allocs = g_rz_checked_bytes = 0; g_rz_first[0] = 0;
+        for (RzEntry &e : g_rz) e.damaged = false;
+    }
+    return 0;
+}
+/* verifies the zones of every live padded allocation after a device synchronise; returns the number of damaged allocations seen since the mode
+ * was last switched on (those found at mid_free included); the first one is described in mid_last_error */
+int mid_redzone_check(void) {
+    std::lock_guard<std::mutex> lk(g_rz_mu);
+    if (!g_rz.empty()) HIPCHK(hipDeviceSynchronize());
+    for (RzEntry &e : g_rz) rz_verify(e);
+    if (g_rz_damaged && g_rz_first[0] && g_err[0] == 0) snprintf(g_err, sizeof g_err, "%s", g_rz_first); /* the channel was cleared since */
+    return g_rz_damaged;
+}
+/* allocations verified and zone bytes compared since the mode was last switched on, and the padded allocations live now */
+void mid_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live) {
+    std::lock_guard<std::mutex> lk(g_rz_mu);
+    if (allocs_checked) *allocs_checked = g_rz_checked_allocs;
+    if (zone_bytes_checked) *zone_bytes_checked = g_rz_checked_bytes;
+    if (live) *live = g_rz.size();
+}
 void *mid_malloc_host(size_t bytes) {
     void *p = nullptr;
     hipError_t e = hipHostMalloc(&p, bytes ? bytes : 4, hipHostMallocDefault);
