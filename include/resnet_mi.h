@@ -331,6 +331,12 @@ int mi_debug_poison_lds(void);
 int mi_debug_redzone(size_t zone_bytes, int fill_byte);
 int mi_debug_redzone_check(void);
 void mi_debug_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live);
+/* The launch ring (RESNET_MI_TRACE=1: the last 96 kernel launches, what the abort dump prints).  Each name carries the parameters that
+ * select the kernel's instantiation, e.g. "bgemm_kernel<fwd,k3,s1,bm128,vw8,swp,sbuf>".  mi_debug_trace_names writes the names oldest
+ * first, one per line, into buf (as many as fit in cap bytes, zero-terminated) and returns how many the ring holds (0 with the trace
+ * off); mi_debug_trace_clear empties the ring. */
+int mi_debug_trace_names(char *buf, size_t cap);
+void mi_debug_trace_clear(void);
 /* host-only (no GPU needed): route and grid the launch planners choose for a convolution.  op 0 fwd, 1 dgrad, 2 wgrad.
  * out[0] 1 = MFMA implicit GEMM / 0 = other kernels, [1] rows per tile, [2] tiles, [3] tiles launched whole, [4] reduction
  * slices per tail tile, [5] k-steps per slice, [6] wgrad splits, [7] workgroups per class or split, [8] k-steps */

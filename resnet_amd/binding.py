@@ -179,6 +179,8 @@ PROTOTYPES = {
     "mi_debug_redzone": (_i, [_sz, _i]),
     "mi_debug_redzone_check": (_i, []),
     "mi_debug_redzone_stats": (None, [C.POINTER(_sz)] * 3),
+    "mi_debug_trace_names": (_i, [C.c_char_p, _sz]),
+    "mi_debug_trace_clear": (None, []),
     "mi_debug_conv_plan": (_i, [_i] * 7 + [_vp]),
     "mi_conv_plan": (_i, [_i] * 9 + [_vp]),
     "mi_trainer_set_dtype": (_i, [_T, _i]),

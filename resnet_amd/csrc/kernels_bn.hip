@@ -547,6 +547,10 @@ static int bn_vec_ew(int x_dt, int a_dt, int P, size_t total, bool *str) {
     } while (0)
 
 static size_t dt_bytes(int dt) { return dt == MID_BF16 ? 2 : 4; }
+// launch-trace name of an element-wise kernel: storage types of x and of the activations, elements per thread, planes straddled
+static const char *bn_ew_name(const char *kernel, int x_dt, int a_dt, int vec, bool str) {
+    return mi_trace_name("%s<%s,%s,v%d%s>", kernel, x_dt == MID_BF16 ? "bf16" : "f32", a_dt == MID_BF16 ? "bf16" : "f32", vec, str ? ",straddle" : "");
+}
 static struct { void *comm; int world, force; float *tmp; size_t tmp_floats; } g_bn_sync;
 
 extern "C" {
@@ -612,7 +616,7 @@ static int bn_fwd_apply(hipStream_t st, const void *x, int x_dt, const float *ga
                        means, vars, (const TA *)residual, (TA *)y, xhat_out, norm_out, C, P, fdP, fdC, total, eps, relu)
     BN_DISPATCH_EW(APPLY);
 #undef APPLY
-    MI_LAUNCH_CHECK("bn_apply_kernel");
+    MI_LAUNCH_CHECK(bn_ew_name("bn_apply_kernel", x_dt, a_dt, vec, str));
     return 0;
 }
 
@@ -757,6 +761,7 @@ static int bn_bwd_impl(hipStream_t st, float *ws, const void *x, int x_dt, const
         inv_m = 1.0f / ((float)g_bn_sync.world * (float)((size_t)N * P));
     }
     const void *dy_apply = mask_mode == 3 ? gated_out : dy; // mode 3: the gated dy is already there, no mask needed
+    const char *apply_name;
     {
     bool str;
     const int vec = bn_vec_ew(x_dt, a_dt, P, total, &str); // (shadows the reduction pass's vector width)
@@ -770,6 +775,7 @@ static int bn_bwd_impl(hipStream_t st, float *ws, const void *x, int x_dt, const
     if (mask_mode == 0 || mask_mode == 3) BN_DISPATCH_EW(BWD_A0);
     else if (mask_mode == 1) BN_DISPATCH_EW(BWD_A1);
     else BN_DISPATCH_EW(BWD_A2);
+    apply_name = bn_ew_name("bn_bwd_apply_kernel", x_dt, a_dt, vec, str);
     }
 #undef BWD_A0
 #undef BWD_A1
@@ -777,7 +783,7 @@ static int bn_bwd_impl(hipStream_t st, float *ws, const void *x, int x_dt, const
 #undef BWD_APPLY_M
     if (sync) hipLaunchKernelGGL(bn_sync_unpack, dim3(mi_cdiv(C, 256)), dim3(256), 0, st, g_bn_sync.tmp, dgamma, dbeta, C, 1.0f / (float)g_bn_sync.world);
     mi_prof_end(st);
-    MI_LAUNCH_CHECK("bn_bwd_apply_kernel");
+    MI_LAUNCH_CHECK(apply_name);
     return 0;
 }
 

@@ -1006,7 +1006,7 @@ static int cl_launch(hipStream_t st, const u16 *A, const u16 *In, u16 *Out, ClAr
     else CL_LAUNCH(1, 1);
 #undef CL_LAUNCH
     mi_prof_end(st);
-    MI_LAUNCH_CHECK("cl_conv_kernel");
+    MI_LAUNCH_CHECK_V("cl_conv_kernel<taps%d,bm%d,nbuf%d>", g.ntaps, bm, nbuf);
     return 0;
 }
 

@@ -181,9 +181,11 @@ static int launch_dconv_t(hipStream_t st, dim3 grid, size_t lds, int tk, int jm,
     return 0;
 }
 
-// one tap-kernel launch; ntr x ntc taps, weights already re-laid in wT
+// one tap-kernel launch; ntr x ntc taps, weights already re-laid in wT.  cls: 0 an operator of its own (timed here), else one parity class
+// of a stride-2 dgrad (timed by the caller): 1 on a stream of its own, 2 in series with the other three
 static int launch_dconv(hipStream_t st, const float *in, const float *wT, float *out, const float *addend, DConvArgs a,
-                        int ntr, int ntc, bool prof = true) {
+                        int ntr, int ntc, int cls = 0) {
+    const bool prof = cls == 0;
     const int PIX = 448;
     a.total_pix = (uint32_t)a.N * a.Hsub * a.Wsub;
     a.PW = (a.Wsub - 1) * a.sx + ntc;
@@ -211,7 +213,7 @@ static int launch_dconv(hipStream_t st, const float *in, const float *wT, float 
     if (lds > 64 * 1024) { mi_record_error("dconv", "LDS patch too large for this shape"); return -2; }
     a.fd_Wsub = make_fastdiv(a.Wsub); a.fd_Hsub = make_fastdiv(a.Hsub);
     a.fd_Hq = make_fastdiv(a.Hq); a.fd_PW = make_fastdiv(a.PW);
-    static int tk_pref = -1; /* experiment knob: RESNET_MI_DCONV_TK=64|32 */
+    static int tk_pref = -1; /* experiment knob: RESNET_MI_DCONV_TK=64|32|16 */
     if (tk_pref < 0) { const char *e = getenv("RESNET_MI_DCONV_TK"); tk_pref = e ? atoi(e) : 32; }
     int tk = (a.Cout % 32 == 0) ? 32 : 16;
     if (tk_pref == 64 && a.Cout % 64 == 0) tk = 64;
@@ -229,7 +231,7 @@ static int launch_dconv(hipStream_t st, const float *in, const float *wT, float 
 #undef DC
     if (prof) mi_prof_end(st);
     if (rc) { mi_record_error("dconv", "unsupported tap shape"); return rc; }
-    MI_LAUNCH_CHECK("dconv_kernel");
+    MI_LAUNCH_CHECK_V("dconv_kernel<t%dx%d,tk%d,jm%d,cc%d%s>", ntr, ntc, tk, a.jcnt <= 2 ? 2 : a.jcnt <= 5 ? 5 : 7, cc, cls == 0 ? "" : cls == 1 ? ",class on a stream" : ",class in series");
     return 0;
 }
 
@@ -643,7 +645,7 @@ static int launch_wgrad_t(hipStream_t st, const float *x, const float *dy, float
                   4.0 * ((double)a.N * a.C * a.H * a.W + (double)a.N * a.K * a.Ho * a.Wo + (double)KS * KS * a.C * a.K));
     hipLaunchKernelGGL((wgrad_kernel<KS, S, TKL, TC, NXR>), grid, dim3(256), lds, st, x, dy, part, a);
     mi_prof_end(st);
-    MI_LAUNCH_CHECK("wgrad_kernel");
+    MI_LAUNCH_CHECK_V("wgrad_kernel<k%d,s%d,tkl%d,tc%d>", KS, S, TKL, TC);
     return 0;
 }
 
@@ -777,7 +779,7 @@ int mid_conv_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float 
             hipStream_t sq = (use_aux && cls > 0) ? aux[cls - 1] : st;
             DConvArgs b = a;
             b.Hsub = Ho; b.Wsub = Ho; b.osy = b.osx = 2; b.oy0 = pa; b.ox0 = pb; b.sy = b.sx = 1; b.offy = b.offx = 0;
-            int rc = launch_dconv(sq, dy, wts[pa * 2 + pb], dx, addend, b, ntr, ntc, false);
+            int rc = launch_dconv(sq, dy, wts[pa * 2 + pb], dx, addend, b, ntr, ntc, use_aux ? 1 : 2);
             if (rc) return rc;
             if (use_aux && cls > 0) { (void)hipEventRecord(ev_join[cls - 1], sq); (void)hipStreamWaitEvent(st, ev_join[cls - 1], 0); }
         }
@@ -811,7 +813,7 @@ int mid_conv_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float 
         if (stride == 1) hipLaunchKernelGGL((wgradC_kernel<1>), grid, dim3(256), lds, st, x, dy, outp, b);
         else hipLaunchKernelGGL((wgradC_kernel<2>), grid, dim3(256), lds, st, x, dy, outp, b);
         mi_prof_end(st);
-        MI_LAUNCH_CHECK("wgradC_kernel");
+        MI_LAUNCH_CHECK(stride == 1 ? "wgradC_kernel<s1>" : "wgradC_kernel<s2>");
         if (pb.splits > 1) return mi_launch_split_reduce(st, outp, dw, (long)wsz9, pb.splits, wsz9);
         return 0;
     }

@@ -857,7 +857,8 @@ static bool igemm_wgrad_reduce_grouped(long KC, int splits) {
     if (on < 0) { const char *e = getenv("RESNET_MI_WGRAD_REDUCE_G"); on = e ? atoi(e) : 1; }
     return on && splits >= 16 && mi_cdiv(KC, 256) < 1024;
 }
-static void igemm_wgrad_reduce_launch(hipStream_t st, const float *part, float *dw, long KC, int k, int splits) {
+// returns the launch-trace name: taps, grouped or one thread per output
+static const char *igemm_wgrad_reduce_launch(hipStream_t st, const float *part, float *dw, long KC, int k, int splits) {
     const bool grouped = igemm_wgrad_reduce_grouped(KC, splits);
     if (k == 1) {
         if (grouped) hipLaunchKernelGGL((igemm_wgrad_reduce_g_kernel<1, 8>), dim3(mi_cdiv(KC, 32)), dim3(256), 0, st, part, dw, KC, splits);
@@ -866,6 +867,7 @@ static void igemm_wgrad_reduce_launch(hipStream_t st, const float *part, float *
         if (grouped) hipLaunchKernelGGL((igemm_wgrad_reduce_g_kernel<9, 8>), dim3(mi_cdiv(KC, 32)), dim3(256), 0, st, part, dw, KC, splits);
         else hipLaunchKernelGGL(igemm_wgrad_reduce_kernel<9>, dim3(mi_cdiv(KC, 256)), dim3(256), 0, st, part, dw, KC, splits);
     }
+    return mi_trace_name("igemm_wgrad_reduce_kernel<k%d,%s>", k == 1 ? 1 : 3, grouped ? "grouped" : "flat");
 }
 
 // dW[k][c] = sum_z part[z][c][k] (1x1, transposed product)
@@ -1048,6 +1050,8 @@ static int igemm_plan_wgrad(IgArgs &g, int N, int C, int H, int K, int k, int st
     *used = mi_cdiv(N * g.P, g.klen);
     return bm;
 }
+// the launch-trace name of the last igemm_kernel launch: op, taps, stride, rows per tile, vector-staged B, sliced tail round
+static thread_local const char *ig_variant = "igemm_kernel";
 template <int MODE, int KS, int S, int WMW, bool VB = false>
 static int igemm_launch_t(hipStream_t st, dim3 grid, const float *A, const float *B, float *out, const float *addend, const IgArgs &g) {
     constexpr int BM = 64 * WMW;
@@ -1063,6 +1067,8 @@ static int igemm_launch_t(hipStream_t st, dim3 grid, const float *A, const float
         attr_set = 1;
     }
     hipLaunchKernelGGL((igemm_kernel<MODE, KS, S, WMW, VB>), grid, dim3(256), lds, st, A, B, out, addend, g);
+    ig_variant = mi_trace_name("igemm_kernel<%s,k%d,s%d,bm%d%s%s>", MODE == IG_FWD ? "fwd" : MODE == IG_DGRAD ? "dgrad" : "wgrad", KS, S, BM, VB ? ",vb" : "",
+                               g.tsplit > 1 ? ",tail" : "");
     return 0;
 }
 template <int MODE>
@@ -1113,7 +1119,7 @@ int mi_igemm_fwd(hipStream_t st, mid_workspace *ws, const float *x, const float 
     }
     mi_prof_end(st);
     if (rc) return rc;
-    MI_LAUNCH_CHECK("igemm_kernel<fwd>");
+    MI_LAUNCH_CHECK(ig_variant);
     return 0;
 }
 
@@ -1156,7 +1162,7 @@ int mi_igemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const floa
     }
     mi_prof_end(st);
     if (rc) return rc;
-    MI_LAUNCH_CHECK("igemm_kernel<dgrad>");
+    MI_LAUNCH_CHECK(ig_variant);
     return 0;
 }
 
@@ -1173,7 +1179,7 @@ int mi_igemm_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const floa
         const int rc = igemm_launch<IG_WGRAD>(st, dim3(g.tiles, used), /*rows from*/ x, /*columns from*/ dy, ws->part, nullptr, g, 1, 1, bm);
         mi_prof_end(st);
         if (rc) return rc;
-        MI_LAUNCH_CHECK("igemm_kernel<wgrad, transposed>");
+        MI_LAUNCH_CHECK_V("%s,transposed", ig_variant);
         hipLaunchKernelGGL(igemm_wgrad_reduce_t_kernel, dim3(mi_cdiv((long)K * C, 256)), dim3(256), 0, st, ws->part, dw, K, C, used);
         MI_LAUNCH_CHECK("igemm_wgrad_reduce_t_kernel");
         return 0;
@@ -1190,18 +1196,16 @@ int mi_igemm_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const floa
     const int rc = igemm_launch<IG_WGRAD>(st, dim3(g.tiles, used), dy, x, ws->part, nullptr, g, k, stride, bm);
     mi_prof_end(st);
     if (rc) return rc;
-    MI_LAUNCH_CHECK("igemm_kernel<wgrad>");
+    MI_LAUNCH_CHECK(ig_variant);
     const long KC = (long)K * C;
-    igemm_wgrad_reduce_launch(st, ws->part, dw, KC, k, used);
-    MI_LAUNCH_CHECK("igemm_wgrad_reduce_kernel");
+    MI_LAUNCH_CHECK(igemm_wgrad_reduce_launch(st, ws->part, dw, KC, k, used));
     return 0;
 }
 
 // second stage of a weight gradient whose partials are [split][t][k][c] (also used by the bf16 kernel)
 int mi_igemm_wgrad_reduce(hipStream_t st, const float *part, float *dw, int K, int C, int k, int splits) {
     const long KC = (long)K * C;
-    igemm_wgrad_reduce_launch(st, part, dw, KC, k, splits);
-    MI_LAUNCH_CHECK("igemm_wgrad_reduce_kernel");
+    MI_LAUNCH_CHECK(igemm_wgrad_reduce_launch(st, part, dw, KC, k, splits));
     return 0;
 }
 

@@ -1079,6 +1079,8 @@ static void bgemm_geometry(BgArgs &g, int N, int C, int H, int K, int stride) {
     g.fdP = make_fastdiv(g.P); g.fdWo = make_fastdiv(g.Wo); g.fdPc = g.fdP;
     g.fdCb = make_fastdiv(1);
 }
+// the launch-trace name of the last bgemm_kernel launch: op, taps, stride, rows per tile, pixels per staged load, pixel-major product, one buffer
+static thread_local const char *bg_variant = "bgemm_kernel";
 template <int MODE, int KS, int S, int WMW, int VW, int SWP = 0, int SBUF = 0>
 static int bgemm_launch_t(hipStream_t st, dim3 grid, const u16 *A, const u16 *B, void *out, const u16 *addend, const BgArgs &g) {
     constexpr int BM = 64 * WMW;
@@ -1102,6 +1104,8 @@ static int bgemm_launch_t(hipStream_t st, dim3 grid, const u16 *A, const u16 *B,
         attr_set = 1;
     }
     hipLaunchKernelGGL((bgemm_kernel<MODE, KS, S, WMW, VW, SWP, SBUF>), grid, dim3(256), lds, st, A, B, out, addend, g);
+    bg_variant = mi_trace_name("bgemm_kernel<%s,k%d,s%d,bm%d,vw%d%s%s>", MODE == BG_FWD ? "fwd" : MODE == BG_DGRAD ? "dgrad" : "wgrad", KS, S, BM, VW,
+                               SWP ? ",swp" : "", SBUF ? ",sbuf" : "");
     return 0;
 }
 // One operand buffer and three resident workgroups per CU (768 slots), or two buffers and two (512)?  Measured per layer at
@@ -1155,30 +1159,14 @@ static int bgemm_launch(hipStream_t st, dim3 grid, const u16 *A, const u16 *B, v
     if (k == 3 && stride == 2) return bgemm_launch_v<MODE, 3, 2>(st, grid, A, B, out, addend, g, bm, vw);
     return -2;
 }
-// Pixels per operand load the staging may use.  The VW pixels of a load must lie in one image (plane size a multiple of VW);
-// where the source is read with stride 2 (forward and wgrad of a stride-2 layer) they must also lie in one output row.
-static int bgemm_stage_vw(int op, int P_out, int Wo, int stride) {
+// Pixels per operand load of a forward's or dgrad's staging: the 16-byte form (8), whose source pixels must be consecutive in memory --
+// every dgrad, forward with stride 1, and forward with stride 2 once x has been re-laid as parity planes (the caller checks it has the
+// buffer) -- at any plane size (the column space is padded to groups of 8 per image); RESNET_MI_BF16_VW below 8: element-wise gathers
+// (1, the first correct form).  The weight gradient's width is bgemm_wgrad_vw's.
+static int bgemm_stage_vw(void) {
     static int cap = -1;
-    if (cap < 0) { const char *e = getenv("RESNET_MI_BF16_VW"); cap = e ? atoi(e) : 8; } /* experiments: 1 = element-wise gathers only */
-    const bool strided_src = stride == 2 && op != BGOP_DGRAD;
-    const int lim = strided_src ? Wo : P_out;
-    int vw = lim % 8 == 0 ? 8 : lim % 4 == 0 ? 4 : 1;
-    if (P_out % vw) vw = 1;
-    if (vw > cap) vw = cap >= 4 ? (lim % 4 == 0 && P_out % 4 == 0 ? 4 : 1) : 1;
-    // wgrad derives its per-pixel tap masks in closed form for a span that leaves its output row at most once
-    while (op == BGOP_WGRAD && vw > 1 && Wo < vw) vw = (vw == 8 && P_out % 4 == 0) ? 4 : 1;
-    // Measured per layer at N = 256 (tools/bench_ops.py --bf16, RESNET_MI_BF16_VW=1 against 8): the vector staging wins for the
-    // weight gradients of stride-1 layers (dY and x rows read as they lie: 10-25 %), and LOSES for forward / dgrad (a wave's
-    // 64 sixteen-byte pieces then lie in 16 different channel planes -- 64 cache lines per load against 2 for the
-    // element-wise gather along the pixels: 3x3 @56 0.39 ms against 0.17) and for stride-2 sources (twice the bytes loaded)
-    static int all = -1;
-    if (all < 0) { const char *e = getenv("RESNET_MI_BF16_VW_ALL"); all = e ? atoi(e) : 0; }
-    if (op != BGOP_WGRAD) { // the 16-byte form only; its source pixels must be consecutive in memory: every dgrad, forward
-        // with stride 1, and forward with stride 2 once x has been re-laid as parity planes (the caller checks it has the buffer)
-        return cap >= 8 ? 8 : 1; /* any plane size: the column space is padded to groups of 8 per image */
-    }
-    if (!all && stride != 1) vw = 1;
-    return vw;
+    if (cap < 0) { const char *e = getenv("RESNET_MI_BF16_VW"); cap = e ? atoi(e) : 8; }
+    return cap >= 8 ? 8 : 1;
 }
 static int bgemm_fam(int k) { return k == 1 ? MI_FAM_GEMM : MI_FAM_PCONV; }
 static int bgemm_pick_bm(int M, long coltiles) {
@@ -1220,7 +1208,7 @@ int mi_bgemm_fwd(hipStream_t st, mid_workspace *ws, const u16 *x, const float *w
     }
     BgArgs g = {};
     bgemm_geometry(g, N, C, H, K, stride);
-    int svw = bgemm_stage_vw(BGOP_FWD, g.P, g.Wo, stride);
+    int svw = bgemm_stage_vw();
     ws->s2d_valid = 0; // on return: 1 = this launch left x as parity planes in ws->s2d (the layer's weight gradient may reuse them)
     if (stride == 2 && svw == 8) { // the 16-byte staging reads x as parity planes: one pass over x first
         if (ws->s2d && ws->s2d_bytes >= (size_t)N * C * g.HW * 2) {
@@ -1241,7 +1229,7 @@ int mi_bgemm_fwd(hipStream_t st, mid_workspace *ws, const u16 *x, const float *w
     const int rc = bgemm_launch<BG_FWD>(st, dim3(g.tiles), A, x, y, nullptr, g, k, stride, bm, svw);
     mi_prof_end(st);
     if (rc) return rc;
-    MI_LAUNCH_CHECK("bgemm_kernel<fwd>");
+    MI_LAUNCH_CHECK(bg_variant);
     return 0;
 }
 
@@ -1259,7 +1247,7 @@ int mi_bgemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const u16 
     }
     BgArgs g = {};
     bgemm_geometry(g, N, C, H, K, stride);
-    const int svw = bgemm_stage_vw(BGOP_DGRAD, g.P, g.Wo, stride);
+    const int svw = bgemm_stage_vw();
     const int bm = bgemm_plan_tiles(g, C, svw);
     const int ctl = mi_cdiv(g.ncols, 128);
     g.vw = bgemm_vw(g.HW);
@@ -1275,7 +1263,7 @@ int mi_bgemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const u16 
     const int rc = bgemm_launch<BG_DGRAD>(st, dim3(g.tiles, stride == 2 ? 4 : 1), A, dy, dx, addend, g, k, stride, bm, svw);
     mi_prof_end(st);
     if (rc) return rc;
-    MI_LAUNCH_CHECK("bgemm_kernel<dgrad>");
+    MI_LAUNCH_CHECK(bg_variant);
     return 0;
 }
 
@@ -1342,7 +1330,7 @@ int mi_bgemm_wgrad(hipStream_t st, mid_workspace *ws, const u16 *x, const u16 *d
     const int rr = mi_igemm_wgrad_reduce(st, ws->part, dw, K, C, k, used);
     mi_prof_end(st);
     if (rr) return rr;
-    MI_LAUNCH_CHECK("bgemm_kernel<wgrad>");
+    MI_LAUNCH_CHECK(bg_variant);
     return 0;
 }
 
@@ -1404,7 +1392,7 @@ int mid_bf16_conv_plan(int op, int N, int C, int H, int K, int k, int stride, in
         return 1;
     }
     bgemm_geometry(g, N, C, H, K, stride);
-    out[0] = bgemm_plan_tiles(g, op == BGOP_FWD ? K : C, bgemm_stage_vw(op, g.P, g.Wo, stride));
+    out[0] = bgemm_plan_tiles(g, op == BGOP_FWD ? K : C, bgemm_stage_vw());
     out[1] = 128; out[2] = g.tiles; out[3] = g.tiles; out[4] = 1; out[5] = 1; out[6] = 0;
     return 1;
 }

@@ -531,7 +531,7 @@ int mid_stem_fwd_bf16(mid_stream s, const float *x, const float *w, void *y, int
     if (y_dt == MID_BF16) hipLaunchKernelGGL(st_fwd_kernel<true>, dim3(waves / 4), dim3(256), 4 * 64 * (32 * 4 + 16), st, (const u16 *)xp, wf, y, g, ntiles, bn_part);
     else hipLaunchKernelGGL(st_fwd_kernel<false>, dim3(waves / 4), dim3(256), 4 * 64 * (32 * 4 + 16), st, (const u16 *)xp, wf, y, g, ntiles, bn_part);
     mi_prof_end(st);
-    MI_LAUNCH_CHECK("st_fwd_kernel");
+    MI_LAUNCH_CHECK(y_dt == MID_BF16 ? "st_fwd_kernel<bf16 out>" : "st_fwd_kernel<f32 out>");
     return 0;
 }
 /* the exact-fp32 pair: planes and operands fp32 (xp: mid_stem_f32_xp_bytes) */
@@ -595,7 +595,7 @@ int mid_stem_wgrad_bf16(mid_stream s, const void *xp, const void *dy, int dy_dt,
     else hipLaunchKernelGGL(st_wgrad_kernel<false>, dim3(waves / 4), dim3(256), 0, st, (const u16 *)xp, dy, scratch, g, nchunks);
     hipLaunchKernelGGL(st_wgrad_reduce_kernel, dim3((ST_K * 147 + 63) / 64), dim3(256), 0, st, scratch, dw, waves);
     mi_prof_end(st);
-    MI_LAUNCH_CHECK("st_wgrad_kernel");
+    MI_LAUNCH_CHECK(dy_dt == MID_BF16 ? "st_wgrad_kernel<bf16 dy>" : "st_wgrad_kernel<f32 dy>");
     return 0;
 }
 }

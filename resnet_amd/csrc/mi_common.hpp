@@ -8,12 +8,18 @@ void mi_record_error(const char *what, const char *detail);
 // diagnostic (RESNET_MI_TRACE=1): the names of the last launches, printed when the process is aborted (a GPU memory fault reaches
 // the host as SIGABRT from the runtime's event thread, with nothing that names the kernel)
 void mi_trace_launch(const char *name);
+// the launch's name with the parameters that pick its instantiation (rows per tile, vector width, buffering, ...), as printf builds it.
+// The ring keeps pointers, so every distinct name is kept once in static storage; with the trace off nothing is formatted and `fmt`
+// itself is returned.
+const char *mi_trace_name(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 #define MI_LAUNCH_CHECK(name)                                              \
     do {                                                                   \
-        mi_trace_launch(name);                                             \
+        const char *n_ = (name);                                           \
+        mi_trace_launch(n_);                                               \
         hipError_t e_ = hipGetLastError();                                 \
-        if (e_ != hipSuccess) { mi_record_error(name, hipGetErrorString(e_)); return -1; } \
+        if (e_ != hipSuccess) { mi_record_error(n_, hipGetErrorString(e_)); return -1; } \
     } while (0)
+#define MI_LAUNCH_CHECK_V(...) MI_LAUNCH_CHECK(mi_trace_name(__VA_ARGS__))
 
 // per-kernel-family timing with HIP events on the launch stream (bench.py roofline): begin/end bracket ONE launch
 enum { MI_FAM_DCONV = 0, MI_FAM_WGRAD = 1, MI_FAM_GEMM = 2, MI_FAM_BN = 3, MI_FAM_OTHER = 4, MI_FAM_PCONV = 5, MI_FAM_COUNT = 6 };

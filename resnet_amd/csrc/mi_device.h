@@ -31,6 +31,9 @@ void mid_free(void *p);
 int mid_redzone(size_t zone_bytes, int fill_byte);
 int mid_redzone_check(void);
 void mid_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live);
+/* the launch ring of RESNET_MI_TRACE=1 (runtime.hip): its names oldest first, one per line, into buf; returns how many it holds */
+int mid_trace_names(char *buf, size_t cap);
+void mid_trace_clear(void);
 void *mid_malloc_host(size_t bytes); /* pinned */
 void mid_free_host(void *p);
 void mid_memcpy_h2d(void *dst, const void *src, size_t bytes, mid_stream s);

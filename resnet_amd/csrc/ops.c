@@ -135,6 +135,8 @@ int mi_debug_poison_lds(void) { return finish(mid_lds_poison(mi_global()->comput
 int mi_debug_redzone(size_t zone_bytes, int fill_byte) { return mid_redzone(zone_bytes, fill_byte); }
 int mi_debug_redzone_check(void) { return mid_redzone_check(); }
 void mi_debug_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live) { mid_redzone_stats(allocs_checked, zone_bytes_checked, live); }
+int mi_debug_trace_names(char *buf, size_t cap) { return mid_trace_names(buf, cap); }
+void mi_debug_trace_clear(void) { mid_trace_clear(); }
 int mi_debug_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]) { return mid_igemm_plan(op, N, C, H, K, k, stride, out); }
 int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]) {
     for (int i = 0; i < 7; i++) out[i] = 0;

@@ -3,6 +3,7 @@
 // (e.g. :693-704, :1315-1316, :3342) with stream-ordered equivalents.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
@@ -35,13 +36,16 @@ static void mi_trace_dump(int sig) {
     signal(sig, g_trace_prev == SIG_IGN || g_trace_prev == SIG_ERR ? SIG_DFL : g_trace_prev);
     raise(sig);
 }
-void mi_trace_launch(const char *name) {
+static int mi_trace_enabled(void) {
     if (g_trace_on < 0) {
         const char *e = getenv("RESNET_MI_TRACE");
         g_trace_on = e && atoi(e) ? 1 : 0;
         if (g_trace_on && atoi(e) > 1) fprintf(stderr, "resnet_mi: launch trace on\n");
     }
-    if (!g_trace_on) return;
+    return g_trace_on;
+}
+void mi_trace_launch(const char *name) {
+    if (!mi_trace_enabled()) return;
     g_trace[g_trace_n++ % MI_TRACE_N] = name;
     /* others (Python's faulthandler, test runners) install SIGABRT handlers of their own later on: stay in front of them */
     struct sigaction cur;
@@ -49,6 +53,44 @@ void mi_trace_launch(const char *name) {
         g_trace_prev = (cur.sa_flags & SA_SIGINFO) ? SIG_DFL : cur.sa_handler;
         signal(SIGABRT, mi_trace_dump);
     }
+}
+/* variant names: each distinct one is stored once and never moves (the ring and the abort dump keep pointers) */
+#define MI_NAME_MAX 512
+#define MI_NAME_LEN 96
+static char g_names[MI_NAME_MAX][MI_NAME_LEN];
+static int g_names_n = 0;
+static std::mutex g_names_mu;
+const char *mi_trace_name(const char *fmt, ...) {
+    if (!mi_trace_enabled()) return fmt;
+    char buf[MI_NAME_LEN];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    std::lock_guard<std::mutex> lk(g_names_mu);
+    for (int i = 0; i < g_names_n; i++)
+        if (!strcmp(g_names[i], buf)) return g_names[i];
+    if (g_names_n == MI_NAME_MAX) return fmt;
+    memcpy(g_names[g_names_n], buf, sizeof buf);
+    return g_names[g_names_n++];
+}
+extern "C" {
+/* the ring's names, oldest first, one per line (what fits in cap bytes, always terminated); returns how many the ring holds */
+int mid_trace_names(char *buf, size_t cap) {
+    const unsigned n = g_trace_n < MI_TRACE_N ? g_trace_n : MI_TRACE_N;
+    size_t at = 0;
+    if (buf && cap) buf[0] = 0;
+    for (unsigned i = 0; i < n; i++) {
+        const char *s = g_trace[(g_trace_n - n + i) % MI_TRACE_N];
+        const size_t l = s ? strlen(s) : 0;
+        if (!buf || at + l + 2 > cap) continue;
+        memcpy(buf + at, s, l);
+        buf[at + l] = '\n'; buf[at + l + 1] = 0;
+        at += l + 1;
+    }
+    return (int)n;
+}
+void mid_trace_clear(void) { g_trace_n = 0; }
 }
 #define HIPCHK(x)                                                          \
     do {                                                                   \

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import routes
 import synth
 from util import check_grad, nchw, nhwc, rand, rel_l2
 
@@ -730,12 +731,13 @@ def test_bn_relu_written_twice_nchw_and_channel_last(ops, C, H, N, form):
     assert not halo.any()
 
 
-@pytest.mark.parametrize("switch", ["RESNET_MI_BF16_CL_S2=0", "RESNET_MI_BF16_CL_S1=0", "RESNET_MI_BF16_CL_DGRAD2=0", "RESNET_MI_BF16_STEM_TENSORS=f32"])
+@pytest.mark.parametrize("switch", routes.BF16_TRAINER_SWITCHES)
 def test_training_step_bf16_on_the_other_kernel_routes(switch):
     """every bf16 route switch (README) must leave a trainer that still passes the whole-step checks: the switches are read once per
     process, so the 4-block / identity-block configuration (one step pair, and 25 teacher-forced steps: test_gpu_trajectory.py) and
     the two store policies are re-run in a child process per switch (the NCHW kernels for the stride-2 / stride-1 3x3 layers, the
-    NCHW stride-2 dgrad, fp32 stem tensors)"""
+    NCHW stride-2 dgrad, fp32 stem tensors; and the bf16 trainer entries of tests/routes.py: the NCHW stride-1 3x3 dgrad, the stem on the
+    fp32 direct kernels)"""
     import os
     import subprocess
     import sys

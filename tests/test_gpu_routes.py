@@ -1,0 +1,207 @@
+"""Every RESNET_MI_* switch (README, "Environment switches"; the table is tests/routes.py) per element and through whole training steps.
+
+The switches are read once per process, so every (switch, value) runs in a child process of its own (tests/route_worker.py):
+
+* test_route_table_names_every_switch (no GPU): the switches the code reads, the table and the README agree.
+* test_operators_under_switch: the entry's operator cases through the perelement.py checkers (float64 reference, their bounds) with the
+  switch set; the launch ring must show every variant name the entry expects and at least one name the default-route child did not
+  launch on the same cases (a forced value the planner ignores proves nothing); "bitwise" entries are compared bit for bit with the
+  default child's outputs.  One default child per base route (none, and RESNET_MI_IGEMM=0 for the direct kernels' knobs) is shared.
+* test_trainer_under_switch: the whole-step checks re-run in a child with the switch set (fp32: test_training_step_parity on C1S and
+  test_store_policies_bit_identical_after_25_steps[f32]; the bf16 switches are parameters of
+  test_gpu_bf16.py::test_training_step_bf16_on_the_other_kernel_routes); "bitwise" entries also compare loss, every gradient and every
+  parameter of two steps with a default child's, bit for bit.
+
+A child that ends by a signal, times out or reports a GPU memory fault is a casualty: every later test of this file then fails at once
+without starting another process on the device.  Nothing is retried.
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+
+import numpy as np
+import pytest
+
+import routes
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+WORKER = os.path.join(HERE, "route_worker.py")
+CASUALTY = []   # the first child that died, timed out or faulted the device
+WORST = {}      # (switch=value, variant names, checker key) -> worst distance, printed at the end of the module
+TIMES = {}      # child -> wall seconds
+
+OP_ENTRIES = [e for e in routes.ROUTES if e["cases"]]
+F32_TRAINER = [e for e in routes.ROUTES if e["trainer"] in ("f32", "both")]
+BITWISE_TRAINER = [e for e in routes.ROUTES if e["trainer"] and e["relation"] == "bitwise"]
+
+
+def run_child(what, argv, env_add, timeout):
+    """one child process under its own time limit; returns the CompletedProcess, or fails the test (and marks the casualty)"""
+    if CASUALTY:
+        pytest.fail("not started: an earlier child of this module was a casualty (%s)" % CASUALTY[0])
+    env = dict(os.environ, **env_add)
+    env.setdefault("RESNET_MI_TRACE", "1")
+    t0 = time.time()
+    try:
+        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    except subprocess.TimeoutExpired:
+        CASUALTY.append("%s: no end after %d s" % (what, timeout))
+        pytest.fail(CASUALTY[0])
+    TIMES[what] = time.time() - t0
+    text = r.stdout + r.stderr
+    if r.returncode < 0 or r.returncode in (134, 137, 139) or "illegal memory access" in text or "Memory access fault" in text:
+        CASUALTY.append("%s: exit status %d\n%s" % (what, r.returncode, text[-3000:]))
+        pytest.fail(CASUALTY[0])
+    return r
+
+
+def ops_child(tmp, tag, keys, env_add):
+    out = str(tmp / (tag + ".json"))
+    r = run_child("operators " + tag, [sys.executable, WORKER, "ops", out] + keys, env_add, 600)
+    assert r.returncode == 0, "%s\n%s" % (tag, (r.stdout[-3000:] + r.stderr[-3000:]))
+    with open(out) as f:
+        return json.load(f), np.load(out + ".npz")
+
+
+def trainer_child(tmp, tag, which, env_add):
+    out = str(tmp / (tag + ".json"))
+    r = run_child("two steps " + tag, [sys.executable, WORKER, "trainer", out, which], env_add, 300)
+    assert r.returncode == 0, "%s\n%s" % (tag, (r.stdout[-3000:] + r.stderr[-3000:]))
+    return np.load(out + ".npz")
+
+
+def _base_tag(base):
+    return "default" + "".join("+%s=%s" % kv for kv in sorted(base.items()))
+
+
+@pytest.fixture(scope="module")
+def default_ops(tmp_path_factory):
+    """per base route: the default child's results over the cases of every entry on that base (started on first use)"""
+    tmp, done = tmp_path_factory.mktemp("routes_default"), {}
+
+    def get(base):
+        tag = _base_tag(base)
+        if tag not in done:
+            done[tag] = None    # a failure here is not repeated for the next entry
+            done[tag] = ops_child(tmp, tag, [e["key"] for e in OP_ENTRIES if e["base"] == base], base)
+        if done[tag] is None:
+            pytest.fail("the default child %s failed (see the first test that needed it)" % tag)
+        return done[tag]
+    return get
+
+
+@pytest.fixture(scope="module")
+def default_trainer(tmp_path_factory):
+    tmp, done = tmp_path_factory.mktemp("routes_trainer_default"), {}
+
+    def get():
+        if "d" not in done:
+            done["d"] = None
+            done["d"] = trainer_child(tmp, "default", "both", {})
+        if done["d"] is None:
+            pytest.fail("the default trainer child failed (see the first test that needed it)")
+        return done["d"]
+    return get
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _summary():
+    t0 = time.time()
+    yield
+    print("\nworst distance per switch, variant and op (fp32 and reductions: x 2^-24 A or sum|terms|, bf16: bf16 ulps); module %.0f s" % (time.time() - t0))
+    for key in sorted(WORST):
+        print("  %-28s %-9s %s  %s  %.3g" % (key[0], routes.by_key(key[0])["relation"], key[1], key[2], WORST[key]))
+    print("children, wall seconds: " + ", ".join("%s %.0f" % kv for kv in sorted(TIMES.items())))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+def _quoted_switches(text):
+    return set(re.findall(r"\"(RESNET_MI_[A-Z0-9_]+)\"", text))
+
+
+def test_route_table_names_every_switch():
+    """the switches the library reads (quoted RESNET_MI_* strings of resnet_amd/csrc/* and binding.py) are all in ROUTES or EXEMPT, the
+    table names none the code does not read, and the README's "Environment switches" paragraph names only switches the code reads -- and
+    every one of them"""
+    read = set()
+    csrc = os.path.join(ROOT, "resnet_amd", "csrc")
+    for fn in sorted(os.listdir(csrc)) + [os.path.join("..", "binding.py")]:
+        path = os.path.join(csrc, fn)
+        if os.path.isfile(path) and not fn.endswith((".o", ".so")):
+            with open(path, errors="replace") as f:
+                read |= _quoted_switches(f.read())
+    assert len(read) >= 25, sorted(read)
+    table = {e["switch"] for e in routes.ROUTES}
+    assert not table & set(routes.EXEMPT), "in both ROUTES and EXEMPT: %s" % sorted(table & set(routes.EXEMPT))
+    assert read - table - set(routes.EXEMPT) == set(), "read by the code, in neither ROUTES nor EXEMPT: %s" % sorted(read - table - set(routes.EXEMPT))
+    assert (table | set(routes.EXEMPT)) - read == set(), "in the table, read by no code: %s" % sorted((table | set(routes.EXEMPT)) - read)
+    keys = [e["key"] for e in routes.ROUTES]
+    assert len(keys) == len(set(keys))
+    for e in routes.ROUTES:
+        assert e["relation"] in ("bitwise", "bounds") and e["why"]
+        assert e["cases"] or e["trainer"], e["key"]
+        assert bool(e["cases"]) == bool(e["names"]), "%s: operator cases and expected variant names go together" % e["key"]
+    assert all(routes.EXEMPT.values())
+    with open(os.path.join(ROOT, "README.md")) as f:
+        readme = f.read()
+    start = readme.index("Environment switches")
+    para = readme[start:readme.index("\n\n", start)]
+    named = set(re.findall(r"RESNET_MI_[A-Z0-9_]+", para))
+    assert named - read == set(), "the README names switches no code reads: %s" % sorted(named - read)
+    assert read - named == set(), "the README's paragraph leaves out: %s" % sorted(read - named)
+    assert "RESNET_MI_IGEMM=0|1|2`" in para, "RESNET_MI_IGEMM takes 0, 1 or 2"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", [e["key"] for e in OP_ENTRIES])
+def test_operators_under_switch(key, default_ops, tmp_path):
+    e = routes.by_key(key)
+    base, base_raw = default_ops(e["base"])
+    got, got_raw = ops_child(tmp_path, key.replace("=", "_"), [key], routes.env_of(e))
+    ids = [routes.case_id(c) for c in e["cases"]]
+    assert got["checked"] == len(ids) == len(set(ids)) and sorted(got["cases"]) == sorted(ids), "cases checked %d, listed %d" % (got["checked"], len(ids))
+    launched = {n for cid in ids for n in got["cases"][cid]["names"]}
+    default_launched = {n for cid in ids for n in base["cases"][cid]["names"]}
+    print("%s launched %s\ndefault launched %s" % (key, sorted(launched), sorted(default_launched)))
+    new = sorted(launched - default_launched)
+    for cid in ids:
+        for k, w in got["cases"][cid]["worst"].items():
+            # the names of this case that the default run of the same case lacks: the variant this distance belongs to
+            variant = ", ".join(sorted(set(got["cases"][cid]["names"]) - set(base["cases"][cid]["names"]))) or "(the default's kernels)"
+            WORST[(key, variant, k)] = max(WORST.get((key, variant, k), 0.0), w)
+    missing = [n for n in e["names"] if n not in launched]
+    assert not missing, "%s: expected variants not launched: %s\nlaunched: %s" % (key, missing, sorted(launched))
+    assert new, "%s launched nothing the default route does not launch on the same cases: the switch was ignored\n%s" % (key, sorted(launched))
+    if e["relation"] == "bitwise":
+        for cid in ids:
+            ka, kb = got["cases"][cid]["raw"], base["cases"][cid]["raw"]
+            assert ka and len(ka) == len(kb), "%s: raw outputs saved %d, default %d" % (cid, len(ka), len(kb))
+            for a, b in zip(ka, kb):
+                x, y = got_raw[a], base_raw[b]
+                assert x.dtype == y.dtype and x.shape == y.shape, cid
+                assert x.tobytes() == y.tobytes(), "%s under %s: output %s differs from the default route's in %d of %d elements" \
+                    % (cid, key, a, int(np.count_nonzero(x != y)), x.size)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("key", [e["key"] for e in F32_TRAINER] + [e["key"] for e in BITWISE_TRAINER if e["trainer"] == "bf16"])
+def test_trainer_under_switch(key, default_trainer, tmp_path):
+    e = routes.by_key(key)
+    env = routes.env_of(e)
+    if e["trainer"] in ("f32", "both"):
+        r = run_child("whole-step checks " + key,
+                      [sys.executable, "-m", "pytest", os.path.join(HERE, "test_gpu_net.py") + "::test_training_step_parity[C1S]",
+                       os.path.join(HERE, "test_gpu_trajectory.py") + "::test_store_policies_bit_identical_after_25_steps[f32]",
+                       "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"], env, 900)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+        assert "2 passed" in r.stdout, r.stdout[-2000:]
+    if e["relation"] == "bitwise":
+        ref = default_trainer()
+        got = trainer_child(tmp_path, key.replace("=", "_"), e["trainer"], env)
+        assert len(got.files) > 10
+        for name in got.files:
+            assert got[name].tobytes() == ref[name].tobytes(), "%s under %s differs from the default trainer's" % (name, key)

@@ -26,6 +26,7 @@ def test_library_exports_every_declared_symbol():
     lib = binding.load()  # raises if the .so is missing: there is no fallback
     declared = _header_functions()
     assert len(declared) >= 55
+    assert {"mi_debug_trace_names", "mi_debug_trace_clear"} <= set(declared)
     for name in declared:
         assert hasattr(lib, name), "libresnet_mi.so does not export %s" % name
         assert name in binding.PROTOTYPES, "binding.py does not bind %s" % name

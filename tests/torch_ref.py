@@ -111,7 +111,8 @@ class TorchNet:
 # gradient rounded to bf16 (round to nearest even) where the product stores it: convolution outputs of the bottleneck
 # blocks, BN(+ReLU) outputs, block outputs, and the gradients flowing back through the same tensors; bottleneck weights
 # are rounded when used (fp32 master copies).  The stem convolution's own output is rounded too when the product stores it as bf16
-# (stem_bf16: Trainer.stem_dtype() -- the matrix-core stem; the VALU stem of inputs that are not a multiple of 32 keeps fp32 tensors).
+# (stem_bf16: Trainer.stem_dtype() -- the matrix-core stem; the VALU stem of inputs that are not a multiple of 32, or of
+# RESNET_MI_BF16_STEM=0, keeps fp32 tensors and multiplies the image and the weights unrounded: stem_rounds_operands).
 # It is the yardstick for how far bf16 storage ALONE moves a gradient from the fp32 oracle's (tests/test_gpu_bf16.py): on
 # these small random-init nets a rounded pre-activation flips ~0.3 % of the ReLU gates per layer, which is ~5 % in rel-L2.
 def _rb(t):
@@ -148,6 +149,13 @@ class _BNStoredStats(torch.autograd.Function):
         return dy, None, (dz * xh).sum(dim=(0, 2, 3)), dz.sum(dim=(0, 2, 3)), None
 
 
+def stem_rounds_operands(dims):
+    """whether the bf16 trainer's stem multiplies the bf16-rounded image and weights: on the matrix-core stem (plan_layers: an input that
+    is a multiple of 32, unless RESNET_MI_BF16_STEM=0) it does; the fp32 direct kernels that run the stem otherwise multiply them as they are"""
+    import os
+    return dims["input"] % 32 == 0 and os.environ.get("RESNET_MI_BF16_STEM", "1") != "0"
+
+
 class TorchNetBF16(TorchNet):
     """gates (optional): the DISCRETE decisions of another execution of the same step -- {name: bool NCHW array} for every ReLU
     ("stem", "b%d_red", "b%d_spa", "b%d_out": that execution's stored activation > 0) and "max_inds" (its per-plane arg-max
@@ -158,6 +166,7 @@ class TorchNetBF16(TorchNet):
         super().__init__(dims, params, eps, dtype)
         self.gates = gates
         self.stem_bf16 = stem_bf16
+        self.stem_rounds = stem_rounds_operands(dims)
         # the product's rule: batch norm as _BNStoredStats instead of bn_train of the stored tensor
         self.stats_before_rounding = stats_before_rounding
 
@@ -169,9 +178,10 @@ class TorchNetBF16(TorchNet):
     def _unit(self, x, i, K, C, k, stride, relu, name, residual=None, key=None):
         w = self.p[i].view(K, C, k, k)
         stem = name == "stem"
-        w = w + (_rb(w.detach()) - w.detach())  # rounded value, gradient to the fp32 master copy
-        if stem:  # the stem multiplies the bf16-rounded image (kernels_stem_bf16.hip).  (Its weight gradient rounds dY on the way in when
-            x = _rb(x)  # that tensor is fp32: 2^-9 relative noise per element, averaged over 10^5..10^6 terms)
+        if not stem or self.stem_rounds:
+            w = w + (_rb(w.detach()) - w.detach())  # rounded value, gradient to the fp32 master copy
+        if stem and self.stem_rounds:  # the matrix-core stem multiplies the bf16-rounded image (kernels_stem_bf16.hip).  (Its weight gradient
+            x = _rb(x)  # rounds dY on the way in when that tensor is fp32: 2^-9 relative noise per element, averaged over 10^5..10^6 terms)
         y = y_exact = F.conv2d(x, w, stride=stride, padding=k // 2)
         if not stem or self.stem_bf16:
             y = _RoundBF16.apply(y)
