@@ -354,6 +354,16 @@ int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi);
  * reduce runs grouped.  Returns 0, or -2 where the route refuses the shape (out all 0). */
 enum { MI_ROUTE_DEFAULT = 0, MI_ROUTE_CL = 1, MI_ROUTE_CL2 = 2, MI_ROUTE_PW = 3 };
 int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]);
+/* host-only (no GPU needed): the kernel routes the trainer's planner gives one convolution of a network at batch N, under the process's
+ * RESNET_MI_* switches -- the planner the trainer and the mi_op_* convolution operators themselves run through.  dtype MI_DTYPE_*, policy
+ * MI_STORE_*; site = the layer's bit in the BN'-fusion site masks (1 expansion, 2 spatial, 4 the reduction above an identity block, 0 none).
+ * out = (forward, dgrad, wgrad route, 1 where the dgrad also does the reduction pass of the batch-norm backward its output feeds).
+ * Returns 0, or -2 (out all 0): unknown dtype, policy or site, or a shape the storage type's kernels do not take.  The LDS-DMA 1x1 weight
+ * gradient is not a route of its own: MI_WG_BF16 picks it at launch (mi_conv_plan, route PW, says where). */
+enum { MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16, MI_FWD_PW /* mi_op_conv1x1_fwd_bf16_cl only */ };
+enum { MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 };
+enum { MI_WG_F32, MI_WG_BF16, MI_WG_CL, MI_WG_CL2, MI_WG_STEM_F32, MI_WG_STEM_BF16 };
+int mi_layer_routes(int dtype, int policy, int N, int C, int H, int K, int k, int stride, int site, int out[4]);
 
 
 /* ---------------- bf16-activation path (BASELINE configs[4]) ----------------
@@ -386,6 +396,10 @@ int mi_trainer_check_errors(Train_ResNet *t);
  * mi_trainer_set_nan_exit(t, 0): a report no longer ends the process (the reference's exit(1), :2899) but comes back through
  * mi_trainer_check_errors / mi_trainer_nan_location -- for tests. */
 int mi_trainer_stem_dtype(Train_ResNet *t); /* storage type of activations->init_conv_applied (the stem convolution's own output) and of its gradient: MI_DTYPE_BF16 in the bf16 mode with the matrix-core stem, else MI_DTYPE_F32 */
+/* the four numbers of mi_layer_routes for every convolution of a live trainer's table: the stem, then per block the reduction, the
+ * spatial convolution, the expansion and (where the block has one) the projection.  Fills out[4 * i ..] for the first cap / 4 of them and
+ * returns their number */
+int mi_debug_trainer_routes(const Train_ResNet *t, int *out, int cap);
 int mi_trainer_nan_location(const Train_ResNet *t);
 void mi_trainer_set_nan_exit(Train_ResNet *t, int on);
 /* test aid: the device-side merge of cross-replica batch norm (mi_dp_enable_sync_bn) on R replicas held by ONE process -- the

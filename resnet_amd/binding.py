@@ -101,6 +101,10 @@ MI_LAYOUT_NHWC, MI_LAYOUT_NCHW = 0, 1
 MI_DTYPE_F32, MI_DTYPE_BF16 = 0, 1
 MI_STORE_FAST, MI_STORE_RECOMPUTE_BN, MI_STORE_FULL = 0, 1, 2
 MI_ROUTE_DEFAULT, MI_ROUTE_CL, MI_ROUTE_CL2, MI_ROUTE_PW = 0, 1, 2, 3
+# the planner's routes (mi_layer_routes)
+MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16, MI_FWD_PW = range(6)
+MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 = range(4)
+MI_WG_F32, MI_WG_BF16, MI_WG_CL, MI_WG_CL2, MI_WG_STEM_F32, MI_WG_STEM_BF16 = range(6)
 MI_OPT_ADAM, MI_OPT_SGD, MI_OPT_LARS = 0, 1, 2
 MI_GUARD = 256  # slack bytes mi_malloc leaves on both sides of a tensor (csrc/mi_host.h)
 
@@ -183,6 +187,8 @@ PROTOTYPES = {
     "mi_debug_trace_clear": (None, []),
     "mi_debug_conv_plan": (_i, [_i] * 7 + [_vp]),
     "mi_conv_plan": (_i, [_i] * 9 + [_vp]),
+    "mi_layer_routes": (_i, [_i] * 9 + [_vp]),
+    "mi_debug_trainer_routes": (_i, [_T, _vp, _i]),
     "mi_trainer_set_dtype": (_i, [_T, _i]),
     "mi_trainer_get_dtype": (_i, [_T]),
     "mi_trainer_set_store_policy": (_i, [_T, _i]),

@@ -1,4 +1,4 @@
-/* mi_host.h -- internal host-side state shared by trainer.c / loader.c / dump.c / ops.c (plain C). */
+/* mi_host.h -- internal host-side state shared by trainer.c / layer.c / loader.c / dump.c / ops.c (plain C). */
 #ifndef MI_HOST_H
 #define MI_HOST_H
 #include "mi_device.h"
@@ -60,33 +60,73 @@ typedef struct {
     int stem_mfma, bf16_stem;    /* RESNET_MI_STEM_MFMA / RESNET_MI_BF16_STEM (0: the stem on the VALU kernels) */
     int stem_tensors_f32;        /* RESNET_MI_BF16_STEM_TENSORS=f32: the bf16 stem's output and its gradient stay fp32 tensors */
     int bnfuse_bwd;              /* RESNET_MI_BF16_BNFUSE_BWD (0: no BN' reduction in any dgrad, either storage type) */
-    int bnfuse_bwd_f32;          /* RESNET_MI_F32_BNFUSE_BWD: fp32 site mask (see plan_layers) */
+    int bnfuse_bwd_f32;          /* RESNET_MI_F32_BNFUSE_BWD: fp32 site mask (see mi_layer_plan) */
     int overlap, overlap_given;  /* RESNET_MI_OVERLAP, and whether it was set at all */
     int bnfuse;                  /* RESNET_MI_BNFUSE (0: fp32 forward BN statistics by a pass of their own) */
     int prelayout;               /* RESNET_MI_PRELAYOUT (0: each fp32 convolution re-lays its own weights) */
 } MiOptions;
 
-/* One convolution of the network and how it runs, decided once per build of the buffers (plan_layers): the kernel routes follow
- * from shape, storage type, store policy and options, and the buffers the layer owns follow from the routes. */
-enum { MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16 };
-enum { MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 };
-enum { MI_WG_F32, MI_WG_BF16, MI_WG_CL, MI_WG_CL2, MI_WG_STEM_F32, MI_WG_STEM_BF16 };
+/* One convolution of the network and how it runs (layer.c), decided once per build of the buffers: the kernel routes (MI_FWD_* /
+ * MI_DG_* / MI_WG_*, resnet_mi.h) follow from shape, storage type, store policy and options, and the buffers the layer owns and their
+ * sizes follow from the routes.  The trainer plans its table with the planner's own choices; an operator (ops.c) forces its routes. */
+enum { MI_PLANNED = -1, MI_NOT_RUN = -2 }; /* a forced route: the planner's choice / the operation is not run and needs nothing */
 typedef struct {
     const float *w;
     int C, H, K, k, stride;
+    int N, dtype, out_dt;        /* batch, storage type of the activations, and of the convolution's own output (the stem's may stay fp32) */
     const mid_wt_entry *we;      /* the weights re-laid once per forward pass (relayout_weights), or NULL */
+    int wre_fwd, wre_dgrad;      /* which re-laid forms the routes read from a weight table, */
+    size_t wre_floats;           /* and the floats of one */
     int fwd, dgrad, wgrad;       /* MI_FWD_* / MI_DG_* / MI_WG_* */
     int fz;                      /* the dgrad also does the reduction pass of the BN' its output feeds (mid_conv_dgrad_bn_*) */
     /* bf16, channel-last input planes (kernels_cl_bf16.hip) read by the forward and the weight gradient: one zero-padded plane
-     * (stride 1) or four parity planes (stride 2); cl_by_bn: the producing BN apply writes them (the reduction BN for the 3x3,
-     * the expansion BN of the block above for a stride-2 projection), else a re-layout pass in front of the forward */
-    void *cl; int cl_by_bn;
-    void *dye;                   /* MI_DG_CL / MI_DG_CL2: the output gradient re-laid channel-last (unit_bwd), read by dgrad and wgrad */
+     * (stride 1) or four parity planes (stride 2); cl_by_bn (set by the trainer, which knows the producer): the producing BN apply
+     * writes them (the reduction BN for the 3x3, the expansion BN of the block above for a stride-2 projection), else a re-layout
+     * pass in front of the forward.  MI_FWD_PW: the dense channel-last input of the 1x1 kernel */
+    void *cl; size_t cl_bytes; int cl_by_bn;
+    void *dye; size_t dye_bytes; /* MI_DG_CL / MI_DG_CL2: the output gradient re-laid channel-last (mi_layer_dy_relayout), read by dgrad and wgrad */
     /* bf16 stride 2: NCHW parity planes of the input; par_valid: the last forward left them there (the weight gradient reuses them) */
     void *par; size_t par_bytes; int par_valid;
     /* stem on the matrix cores: the batch as zero-padded parity planes + wave partials and re-laid weights (kernels_stem_bf16.hip) */
     void *xp; size_t xp_bytes; float *scratch; size_t scratch_floats;
 } MiLayer;
+/* the workspaces every convolution of a table shares: sized for the largest need of its layers */
+typedef struct {
+    mid_workspace ws;
+    float *bn_ws;
+    mid_bn_parts bn_parts;       /* statistics partials a forward convolution leaves for its batch norm; the BN' sums of a fusing dgrad */
+} MiLayerWs;
+typedef struct { size_t wt, part, bn_parts; int maxc; } MiLayerNeed;
+struct MiCtx;
+void mi_layer_init(MiLayer *L, const float *w, int C, int H, int K, int k, int stride);
+/* host only, allocates nothing: routes, fz and every size of L from (dtype, policy, options, N, shape, site = the layer's bit in the
+ * BN'-fusion site masks, 0: not a site).  force: NULL, or per operation MI_PLANNED, MI_NOT_RUN or a route.  Returns 0, or -2 where a
+ * route's *_supported test refuses the shape or the storage type */
+int mi_layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int N, int site, const int force[3]);
+/* the planned buffers at exactly their sizes (halos zeroed), tracked by the trainer c, or untracked (c == NULL: mi_layer_free) */
+void mi_layer_alloc(struct MiCtx *c, MiLayer *L);
+void mi_layer_free(MiLayer *L);
+/* no weight table (operators): the forms the channel-last routes read, made here by a launch each; e backs L->we and is freed with L */
+int mi_layer_own_weights(MiLayer *L, mid_wt_entry *e, mid_stream s);
+void mi_layer_need(const MiLayer *L, MiLayerNeed *need); /* raises *need to what L's routes ask of the shared workspaces */
+void mi_layer_ws_alloc(struct MiCtx *c, MiLayerWs *w, const MiLayerNeed *need);
+void mi_layer_ws_free(MiLayerWs *w);
+/* the runners: each returns its launcher's code.  parts: NULL, or &w->bn_parts for the statistics partials of the output */
+int mi_layer_x_relayout(const MiLayer *L, mid_stream s, const void *x);   /* x into L->cl (mi_layer_fwd does it unless cl_by_bn) */
+int mi_layer_fwd(MiLayer *L, MiLayerWs *w, mid_stream s, const void *x, void *y, mid_bn_parts *parts);
+int mi_layer_bn_fwd(const MiLayer *L, MiLayerWs *w, mid_stream s, const mid_bn_parts *parts, const void *conv_out, const float *gamma,
+                    const float *beta, const void *residual, float *means, float *vars, void *y, float *xhat_out, float *norm_out, float eps,
+                    int relu, const MiLayer *cl_reader);
+int mi_layer_dy_relayout(const MiLayer *L, mid_stream s, const void *dy); /* dy into L->dye, before the dgrad and the weight gradient */
+const mid_bn_bwd_parts *mi_layer_fz_request(const MiLayer *L, const MiLayerWs *w, mid_bn_bwd_parts *r, const void *x, const void *mask,
+                                            const float *means);
+int mi_layer_dgrad(const MiLayer *L, MiLayerWs *w, mid_stream s, const void *dy, void *dx, const void *addend, const mid_bn_bwd_parts *req,
+                   mid_bn_bwd_parts *fz);
+int mi_layer_wgrad(const MiLayer *L, MiLayerWs *w, mid_stream s, const void *x, const void *dy, float *dw);
+int mi_bn_bwd_unit(MiLayerWs *w, mid_stream s, mid_bn_bwd_parts *fz, const void *x, int x_dt, const float *gamma, const float *beta,
+                   const float *means, const float *vars, const void *dy, const void *mask_src, int mask_mode, void *gated_out, int a_dt,
+                   void *dx, float *dgamma, float *dbeta, int N, int C, int P, float eps);
+void mi_read_options(MiOptions *o); /* the process's switches (trainer.c) */
 typedef struct { MiLayer red, spa, exp, proj; } MiBlockLayers; /* proj.w == NULL: no projection */
 
 /* momentum SGD / LARS over a parameter-shaped arena (kernels_optim.hip): the chunk table and the per-chunk / per-tensor scratch,
@@ -113,9 +153,7 @@ int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, 
                   int *nan_flag, int want_norms);
 
 typedef struct MiCtx {
-    mid_workspace ws;
-    float *bn_ws;
-    mid_bn_parts bn_parts; /* statistics partials a forward convolution leaves for its batch norm */
+    MiLayerWs lw;
     /* weights re-laid for the implicit-GEMM kernel once per forward pass (one launch): host table (MiLayer.we points into it),
      * device copies for the kernel */
     mid_wt_entry *wt_tab;

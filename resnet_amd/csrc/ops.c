@@ -2,9 +2,11 @@
  * ops.c -- operator layer of the C-ABI (the prepareAndDo* wrappers of resnet.cu:1386-1509 as callable
  * entry points): each call runs one kernel family on the library's compute stream with a private
  * workspace and returns after the stream has drained.  Used by the parity tests to drive every HIP
- * kernel on its own; the trainer itself calls the mid_* launchers directly (no sync, shared workspace).
+ * kernel on its own.  The convolution operators plan one layer with their routes forced and run it
+ * through the runners the trainer runs its table through (layer.c).
  */
 #include <stdlib.h>
+#include <string.h>
 #include "mi_host.h"
 
 /* MI_GUARD bytes of slack on both sides: the bf16 convolution operators read tap-shifted operands with 16-byte loads that may
@@ -21,36 +23,58 @@ static int finish(int rc) {
     if (rc) return rc;
     return mid_last_error()[0] ? -1 : 0;
 }
-static int ws_make(mid_workspace *ws, size_t wt, size_t part) {
-    ws->wt_floats = wt; ws->part_floats = part;
-    ws->pre_fwd = ws->pre_dgrad = NULL;
-    ws->s2d = NULL; ws->s2d_bytes = 0; ws->s2d_valid = 0;
-    ws->wt = wt ? (float *)mid_malloc(wt * sizeof(float)) : NULL;
-    ws->part = part ? (float *)mid_malloc(part * sizeof(float)) : NULL;
-    return (wt && !ws->wt) || (part && !ws->part);
-}
-static void ws_free(mid_workspace *ws) { mid_free(ws->wt); mid_free(ws->part); }
 
-int mi_op_conv_fwd(const float *x, const float *w, float *y, int N, int C, int H, int K, int k, int stride) {
-    mid_workspace ws;
-    if (ws_make(&ws, mid_conv_ws_wt_floats(C, K, k), 0)) return -3;
-    int rc = finish(mid_conv_fwd(mi_global()->compute, &ws, x, w, y, N, C, H, K, k, stride));
-    ws_free(&ws);
+/* ---- the convolution operators: plan the layer with the operator's routes, allocate at the planner's sizes, run the module's
+ * runners, synchronise, free.  rc: the first failing step's code (later steps are skipped) ---- */
+typedef struct { MiLayer L; MiLayerWs w; mid_wt_entry we; mid_stream s; int rc; } OpConv;
+/* no switch reaches an operator: its routes are forced, and a dgrad + BN' operator fuses wherever its launch can */
+static const MiOptions OP_OPT = {.bnfuse_bwd = 1, .bnfuse_bwd_f32 = 7};
+/* -2: a route refuses the shape (nothing was allocated).  No weight table here: the NCHW routes re-lay their own weights into the
+ * workspace, the channel-last ones get theirs from mi_layer_own_weights (a weight gradient reads none) */
+static int op_open(OpConv *o, int dt, const MiOptions *opt, const float *w, int N, int C, int H, int K, int k, int stride, int fwd, int dgrad,
+                   int wgrad, int site) {
+    const int force[3] = {fwd, dgrad, wgrad};
+    MiLayerNeed need = {0, 0, 0, 0};
+    memset(o, 0, sizeof *o);
+    o->s = mi_global()->compute;
+    mi_layer_init(&o->L, w, C, H, K, k, stride);
+    if (mi_layer_plan(&o->L, dt, MI_STORE_FAST, opt, N, site, force)) return -2;
+    mi_layer_need(&o->L, &need);
+    mi_layer_alloc(NULL, &o->L);
+    mi_layer_ws_alloc(NULL, &o->w, &need);
+    if (wgrad == MI_NOT_RUN) o->rc = mi_layer_own_weights(&o->L, &o->we, o->s);
+    return 0;
+}
+static int op_close(OpConv *o) {
+    const int rc = finish(o->rc);
+    mi_layer_free(&o->L);
+    mi_layer_ws_free(&o->w);
     return rc;
+}
+/* one operation of one layer: the weight gradient (out = dw) where a wgrad route is given, else the dgrad (out = dx), else the forward */
+static int op_conv(int dt, int fwd, int dgrad, int wgrad, const void *x, const float *w, const void *dy, void *out, const void *addend, int N,
+                   int C, int H, int K, int k, int stride) {
+    OpConv o;
+    if (op_open(&o, dt, &OP_OPT, w, N, C, H, K, k, stride, fwd, dgrad, wgrad, 0)) return -2;
+    if (wgrad != MI_NOT_RUN) {
+        if (o.L.cl) o.rc = mi_layer_x_relayout(&o.L, o.s, x);
+        if (!o.rc) o.rc = mi_layer_dy_relayout(&o.L, o.s, dy);
+        if (!o.rc) o.rc = mi_layer_wgrad(&o.L, &o.w, o.s, x, dy, (float *)out);
+    } else if (dgrad != MI_NOT_RUN) {
+        if (!o.rc) o.rc = mi_layer_dy_relayout(&o.L, o.s, dy);
+        if (!o.rc) o.rc = mi_layer_dgrad(&o.L, &o.w, o.s, dy, out, addend, NULL, NULL);
+    } else if (!o.rc) o.rc = mi_layer_fwd(&o.L, &o.w, o.s, x, out, NULL);
+    return op_close(&o);
+}
+#define OFF MI_NOT_RUN
+int mi_op_conv_fwd(const float *x, const float *w, float *y, int N, int C, int H, int K, int k, int stride) {
+    return op_conv(MID_F32, MI_FWD_F32, OFF, OFF, x, w, NULL, y, NULL, N, C, H, K, k, stride);
 }
 int mi_op_conv_dgrad(const float *w, const float *dy, float *dx, int N, int C, int H, int K, int k, int stride, int to_add) {
-    mid_workspace ws;
-    if (ws_make(&ws, mid_conv_ws_wt_floats(C, K, k), 0)) return -3;
-    int rc = finish(mid_conv_dgrad(mi_global()->compute, &ws, w, dy, dx, to_add ? dx : NULL, N, C, H, K, k, stride));
-    ws_free(&ws);
-    return rc;
+    return op_conv(MID_F32, OFF, MI_DG_F32, OFF, NULL, w, dy, dx, to_add ? dx : NULL, N, C, H, K, k, stride);
 }
 int mi_op_conv_wgrad(const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k, int stride) {
-    mid_workspace ws;
-    if (ws_make(&ws, 0, mid_conv_ws_part_floats(N, C, H, K, k, stride))) return -3;
-    int rc = finish(mid_conv_wgrad(mi_global()->compute, &ws, x, dy, dw, N, C, H, K, k, stride));
-    ws_free(&ws);
-    return rc;
+    return op_conv(MID_F32, OFF, OFF, MI_WG_F32, x, NULL, dy, dw, NULL, N, C, H, K, k, stride);
 }
 int mi_op_bn_fwd(const float *x, const float *gamma, const float *beta, float *means, float *vars, float *y, int N, int C,
                  int H, float eps, int relu) {
@@ -156,229 +180,117 @@ int mi_op_convert(const void *in, int in_dt, void *out, int out_dt, size_t n) {
     return -2;
 }
 int mi_op_conv_fwd_bf16(const void *x, const float *w, void *y, int N, int C, int H, int K, int k, int stride) {
-    mid_workspace ws;
-    if (ws_make(&ws, (size_t)k * k * C * K, 0)) return -3;
-    void *par = NULL;
-    if (stride == 2) { ws.s2d_bytes = (size_t)N * C * H * H * 2; par = mi_malloc(ws.s2d_bytes); ws.s2d = par; }
-    int rc = finish(mid_conv_fwd_bf16(mi_global()->compute, &ws, x, w, y, N, C, H, K, k, stride, NULL));
-    mi_free(par);
-    ws_free(&ws);
-    return rc;
+    return op_conv(MID_BF16, MI_FWD_BF16, OFF, OFF, x, w, NULL, y, NULL, N, C, H, K, k, stride);
 }
 int mi_op_conv_dgrad_bf16(const float *w, const void *dy, void *dx, int N, int C, int H, int K, int k, int stride, int to_add) {
-    mid_workspace ws;
-    if (ws_make(&ws, (size_t)k * k * C * K, 0)) return -3;
-    int rc = finish(mid_conv_dgrad_bf16(mi_global()->compute, &ws, w, dy, dx, to_add ? dx : NULL, N, C, H, K, k, stride));
-    ws_free(&ws);
-    return rc;
+    return op_conv(MID_BF16, OFF, MI_DG_BF16, OFF, NULL, w, dy, dx, to_add ? dx : NULL, N, C, H, K, k, stride);
 }
 int mi_op_conv_wgrad_bf16(const void *x, const void *dy, float *dw, int N, int C, int H, int K, int k, int stride) {
-    mid_workspace ws;
-    if (!mid_bf16_supported(2, N, C, H, K, k, stride)) return -2;
-    if (ws_make(&ws, 0, mid_bf16_part_floats(N, C, H, K, k, stride))) return -3;
-    void *par = NULL;
-    if (stride == 2) { ws.s2d_bytes = (size_t)N * C * H * H * 2; par = mi_malloc(ws.s2d_bytes); ws.s2d = par; }
-    int rc = finish(mid_conv_wgrad_bf16(mi_global()->compute, &ws, x, dy, dw, N, C, H, K, k, stride));
-    mi_free(par);
-    ws_free(&ws);
-    return rc;
+    return op_conv(MID_BF16, OFF, OFF, MI_WG_BF16, x, NULL, dy, dw, NULL, N, C, H, K, k, stride);
 }
-/* dgrad of one convolution followed by the backward of the batch norm (+ReLU) in front of it, the way backwards_pass chains them in
- * bf16 storage (prepreAndDoConvolutionDeriv + activationAndBatchNormDeriv, resnet.cu:1399-1429, 1455-1480): where the launch allows, the
- * dgrad gates its output by mask > 0 and does the BN' reduction pass in its epilogue.  All image tensors bf16.
+/* dgrad of one convolution followed by the backward of the batch norm (+ReLU) in front of it, the way backwards_pass chains them
+ * (prepreAndDoConvolutionDeriv + activationAndBatchNormDeriv, resnet.cu:1399-1429, 1455-1480): where the launch allows, the dgrad gates its
+ * output by mask > 0 and does the BN' reduction pass in its epilogue (bf16 storage: the NCHW kernel; fp32: the stride-1 layers on the
+ * implicit-GEMM route).  All image tensors of storage type dt.
  * Returns < 0 on error, else the number of partial rows the dgrad left (0 = the separate reduction pass ran). */
+static int op_dgrad_bn_bwd(int dt, const float *w, const void *dy, const void *addend, void *gated, int N, int C, int H, int K, int k, int stride,
+                           const void *bn_x, const void *mask, const float *gamma, const float *beta, const float *means, const float *vars,
+                           float eps, void *bn_dx, float *dgamma, float *dbeta) {
+    OpConv o;
+    const size_t bytes = (size_t)N * C * H * H * (dt == MID_BF16 ? 2 : 4);
+    mid_bn_bwd_parts fz = {NULL}, req;
+    void *tmp = NULL;
+    if (op_open(&o, dt, &OP_OPT, w, N, C, H, K, k, stride, OFF, dt == MID_BF16 ? MI_DG_BF16 : MI_DG_F32, OFF, 1)) return -2;
+    if (addend) mid_memcpy_d2d(gated, addend, bytes, o.s);
+    if (!o.rc) o.rc = mi_layer_dgrad(&o.L, &o.w, o.s, dy, gated, addend ? gated : NULL, mi_layer_fz_request(&o.L, &o.w, &req, bn_x, mask, means), &fz);
+    const int nparts = fz.nparts;
+    /* the unfused chain: BN' gates by the mask itself (mode 3 writes the gated gradient where the fused form leaves it) */
+    if (!o.rc && !nparts && !(tmp = mi_malloc(bytes))) o.rc = -3;
+    if (!o.rc) o.rc = mi_bn_bwd_unit(&o.w, o.s, &fz, bn_x, dt, gamma, beta, means, vars, gated, mask, 3, tmp, dt, bn_dx, dgamma, dbeta, N, C, H * H, eps);
+    if (!o.rc && tmp) mid_memcpy_d2d(gated, tmp, bytes, o.s);
+    const int rc = op_close(&o);
+    mi_free(tmp);
+    return rc < 0 ? rc : nparts;
+}
 int mi_op_conv_dgrad_bn_bwd_bf16(const float *w, const void *dy, const void *addend, void *gated, int N, int C, int H, int K, int k, int stride,
                                  const void *bn_x, const void *mask, const float *gamma, const float *beta, const float *means,
                                  const float *vars, float eps, void *bn_dx, float *dgamma, float *dbeta) {
-    mid_workspace ws;
-    if (ws_make(&ws, (size_t)k * k * C * K, 0)) return -3;
-    mid_bn_bwd_parts fz = {bn_x, mask, means, NULL, mid_bn_parts_floats(N, C, H), 0};
-    fz.buf = (float *)mid_malloc(fz.floats * sizeof(float));
-    float *bws = (float *)mid_malloc(mid_bn_ws_floats(C) * sizeof(float));
-    if (addend) mid_memcpy_d2d(gated, addend, (size_t)N * C * H * H * 2, mi_global()->compute);
-    int rc = mid_conv_dgrad_bn_bf16(mi_global()->compute, &ws, w, dy, gated, addend ? gated : NULL, N, C, H, K, k, stride, &fz);
-    if (!rc) {
-        if (fz.nparts > 0)
-            rc = mid_bn_bwd_parts_t(mi_global()->compute, bws, &fz, bn_x, MID_BF16, gamma, beta, means, vars, gated, MID_BF16, bn_dx, dgamma, dbeta, N, C, H * H, eps);
-        else { /* the unfused chain: BN' gates by the mask itself (mode 3 writes the gated gradient where the fused form leaves it) */
-            void *tmp = mi_malloc((size_t)N * C * H * H * 2);
-            rc = mid_bn_bwd_t(mi_global()->compute, bws, bn_x, MID_BF16, gamma, beta, means, vars, gated, mask, tmp, MID_BF16, bn_dx, dgamma, dbeta, N, C, H * H, eps, 3);
-            if (!rc) mid_memcpy_d2d(gated, tmp, (size_t)N * C * H * H * 2, mi_global()->compute);
-            rc = finish(rc);
-            mi_free(tmp);
-        }
-    }
-    rc = finish(rc);
-    mid_free(bws);
-    mid_free(fz.buf);
-    ws_free(&ws);
-    return rc < 0 ? rc : fz.nparts;
+    return op_dgrad_bn_bwd(MID_BF16, w, dy, addend, gated, N, C, H, K, k, stride, bn_x, mask, gamma, beta, means, vars, eps, bn_dx, dgamma, dbeta);
 }
-/* the same chain in fp32 storage (backwards_pass, fp32 trainer): the stride-1 layers on the implicit-GEMM route do the reduction pass of
- * the batch-norm backward in the dgrad's epilogue */
 int mi_op_conv_dgrad_bn_bwd_f32(const float *w, const float *dy, const float *addend, float *gated, int N, int C, int H, int K, int k, int stride,
                                 const float *bn_x, const float *mask, const float *gamma, const float *beta, const float *means,
                                 const float *vars, float eps, float *bn_dx, float *dgamma, float *dbeta) {
-    mid_workspace ws;
-    if (ws_make(&ws, mid_conv_ws_wt_floats(C, K, k), 0)) return -3;
-    mid_bn_bwd_parts fz = {bn_x, mask, means, NULL, mid_bn_parts_floats(N, C, H), 0};
-    fz.buf = (float *)mid_malloc(fz.floats * sizeof(float));
-    float *bws = (float *)mid_malloc(mid_bn_ws_floats(C) * sizeof(float));
-    const size_t bytes = (size_t)N * C * H * H * 4;
-    if (addend) mid_memcpy_d2d(gated, addend, bytes, mi_global()->compute);
-    int rc = mid_conv_dgrad_bn_f32(mi_global()->compute, &ws, w, dy, gated, addend ? gated : NULL, N, C, H, K, k, stride, &fz);
-    if (!rc) {
-        if (fz.nparts > 0)
-            rc = mid_bn_bwd_parts_t(mi_global()->compute, bws, &fz, bn_x, MID_F32, gamma, beta, means, vars, gated, MID_F32, bn_dx, dgamma, dbeta, N, C, H * H, eps);
-        else { /* the unfused chain: BN' gates by the mask itself (mode 3 writes the gated gradient where the fused form leaves it) */
-            float *tmp = (float *)mid_malloc(bytes);
-            rc = mid_bn_bwd_t(mi_global()->compute, bws, bn_x, MID_F32, gamma, beta, means, vars, gated, mask, tmp, MID_F32, bn_dx, dgamma, dbeta, N, C, H * H, eps, 3);
-            if (!rc) mid_memcpy_d2d(gated, tmp, bytes, mi_global()->compute);
-            rc = finish(rc);
-            mid_free(tmp);
-        }
-    }
-    rc = finish(rc);
-    mid_free(bws);
-    mid_free(fz.buf);
-    ws_free(&ws);
-    return rc < 0 ? rc : fz.nparts;
+    return op_dgrad_bn_bwd(MID_F32, w, dy, addend, gated, N, C, H, K, k, stride, bn_x, mask, gamma, beta, means, vars, eps, bn_dx, dgamma, dbeta);
 }
-/* the bf16-mode stem (7x7 stride 2, 3 -> 64): x, y, dy fp32 tensors; image and weights rounded to bf16 inside */
-int mi_op_stem_fwd_bf16(const float *x, const float *w, float *y, int N, int H) {
-    if (!mid_stem_bf16_supported(3, H, 64, 7, 2)) return -2;
-    const size_t xb = mid_stem_bf16_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
-    void *xp = mi_malloc(xb);
-    float *sc = (float *)mid_malloc(sf * sizeof(float));
-    int rc = (!xp || !sc) ? -3 : finish(mid_stem_fwd_bf16(mi_global()->compute, x, w, y, MID_F32, xp, xb, sc, sf, N, H, NULL));
-    mid_free(sc);
-    mi_free(xp);
+/* the stem (7x7 stride 2, 3 -> 64) on the matrix cores: exact = 1 in exact fp32 (MI_FWD_STEM_F32, the stem of the fp32 storage mode where
+ * RESNET_MI_IGEMM allows the matrix cores), exact = 0 image and weights rounded to bf16 inside (MI_FWD_STEM_BF16).  x fp32; conv_dt =
+ * storage type of the stem's own output and of its gradient, a_dt = of the activations behind its BN */
+static int stem_open(OpConv *o, const float *w, int N, int H, int exact, int conv_dt, int a_dt, int wgrad) {
+    MiOptions opt = OP_OPT;
+    opt.stem_tensors_f32 = conv_dt == MID_F32;
+    if ((exact || a_dt != MID_BF16) && conv_dt != MID_F32) return -2;
+    return op_open(o, a_dt, &opt, w, N, 3, H, 64, 7, 2, exact ? MI_FWD_STEM_F32 : MI_FWD_STEM_BF16, OFF,
+                   !wgrad ? OFF : exact ? MI_WG_STEM_F32 : MI_WG_STEM_BF16, 0);
+}
+static int op_stem_fwd(const float *x, const float *w, float *y, int N, int H, int exact) {
+    OpConv o;
+    if (stem_open(&o, w, N, H, exact, MID_F32, MID_F32, 0)) return -2;
+    if (!o.rc) o.rc = mi_layer_fwd(&o.L, &o.w, o.s, x, y, NULL);
+    return op_close(&o);
+}
+static int op_stem_wgrad(const float *x, const float *w, const void *dy, int dy_dt, float *dw, int N, int H, int exact) {
+    OpConv o;
+    if (stem_open(&o, w, N, H, exact, dy_dt, dy_dt, 1)) return -2;
+    void *y = mi_malloc((size_t)N * 64 * (H / 2) * (H / 2) * (dy_dt == MID_BF16 ? 2 : 4));
+    if (!y) o.rc = -3;
+    if (!o.rc) o.rc = mi_layer_fwd(&o.L, &o.w, o.s, x, y, NULL); /* leaves the padded planes in xp */
+    if (!o.rc) o.rc = mi_layer_wgrad(&o.L, &o.w, o.s, x, dy, dw);
+    const int rc = op_close(&o);
+    mi_free(y);
     return rc;
 }
-int mi_op_stem_wgrad_bf16(const float *x, const float *w, const float *dy, float *dw, int N, int H) {
-    if (!mid_stem_bf16_supported(3, H, 64, 7, 2)) return -2;
-    const size_t xb = mid_stem_bf16_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
-    void *xp = mi_malloc(xb);
-    float *sc = (float *)mid_malloc(sf * sizeof(float));
-    float *y = (float *)mid_malloc((size_t)N * 64 * (H / 2) * (H / 2) * sizeof(float));
-    int rc = (!xp || !sc || !y) ? -3 : mid_stem_fwd_bf16(mi_global()->compute, x, w, y, MID_F32, xp, xb, sc, sf, N, H, NULL); /* leaves the padded planes in xp */
-    if (!rc) rc = mid_stem_wgrad_bf16(mi_global()->compute, xp, dy, MID_F32, dw, sc, sf, N, H);
-    rc = finish(rc);
-    mid_free(y);
-    mid_free(sc);
-    mi_free(xp);
-    return rc;
+int mi_op_stem_fwd_bf16(const float *x, const float *w, float *y, int N, int H) { return op_stem_fwd(x, w, y, N, H, 0); }
+int mi_op_stem_fwd_f32(const float *x, const float *w, float *y, int N, int H) { return op_stem_fwd(x, w, y, N, H, 1); }
+int mi_op_stem_wgrad_bf16(const float *x, const float *w, const float *dy, float *dw, int N, int H) { return op_stem_wgrad(x, w, dy, MID_F32, dw, N, H, 0); }
+int mi_op_stem_wgrad_f32(const float *x, const float *w, const float *dy, float *dw, int N, int H) { return op_stem_wgrad(x, w, dy, MID_F32, dw, N, H, 1); }
+/* the bf16 stem's weight gradient from dy stored as dy_dt (bf16: the stem tensors of the bf16 trainer, mi_trainer_stem_dtype) */
+int mi_op_stem_wgrad_bf16_t(const float *x, const float *w, const void *dy, int dy_dt, float *dw, int N, int H) {
+    return op_stem_wgrad(x, w, dy, dy_dt, dw, N, H, 0);
 }
-/* ... and in exact fp32 (the stem of the fp32 storage mode where RESNET_MI_IGEMM allows the matrix cores) */
-int mi_op_stem_fwd_f32(const float *x, const float *w, float *y, int N, int H) {
-    if (!mid_stem_bf16_supported(3, H, 64, 7, 2)) return -2;
-    const size_t xb = mid_stem_f32_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
-    void *xp = mi_malloc(xb);
-    float *sc = (float *)mid_malloc(sf * sizeof(float));
-    int rc = (!xp || !sc) ? -3 : finish(mid_stem_fwd_f32(mi_global()->compute, x, w, y, xp, xb, sc, sf, N, H, NULL));
-    mid_free(sc);
-    mi_free(xp);
-    return rc;
+/* A convolution and the batch norm behind it the way forward_pass runs the pair (resnet.cu:1386-1396 + 1431-1453; unit_fwd's two calls):
+ * the statistics come out of the convolution's own epilogue (fp32 accumulators) where its kernel leaves partials, and from a pass over
+ * conv_out where it does not.  Returns < 0 on error, > 0: the statistics were fused (number of partial rows), 0: separate pass */
+static int op_conv_bn_fwd(OpConv *o, const void *x, void *conv_out, const float *gamma, const float *beta, float *means, float *vars, void *y,
+                          float eps, int relu) {
+    mid_bn_parts *parts = &o->w.bn_parts;
+    if (!o->rc) o->rc = mi_layer_fwd(&o->L, &o->w, o->s, x, conv_out, parts);
+    if (!o->rc) o->rc = mi_layer_bn_fwd(&o->L, &o->w, o->s, parts, conv_out, gamma, beta, NULL, means, vars, y, NULL, NULL, eps, relu, NULL);
+    const int nparts = parts->nparts, rc = op_close(o);
+    return rc < 0 ? rc : nparts;
 }
-int mi_op_stem_wgrad_f32(const float *x, const float *w, const float *dy, float *dw, int N, int H) {
-    if (!mid_stem_bf16_supported(3, H, 64, 7, 2)) return -2;
-    const size_t xb = mid_stem_f32_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
-    void *xp = mi_malloc(xb);
-    float *sc = (float *)mid_malloc(sf * sizeof(float));
-    float *y = (float *)mid_malloc((size_t)N * 64 * (H / 2) * (H / 2) * sizeof(float));
-    int rc = (!xp || !sc || !y) ? -3 : mid_stem_fwd_f32(mi_global()->compute, x, w, y, xp, xb, sc, sf, N, H, NULL); /* leaves the padded planes in xp */
-    if (!rc) rc = mid_stem_wgrad_f32(mi_global()->compute, xp, dy, dw, sc, sf, N, H);
-    rc = finish(rc);
-    mid_free(y);
-    mid_free(sc);
-    mi_free(xp);
-    return rc;
-}
-/* A convolution and the batch norm behind it the way forward_pass runs the pair (resnet.cu:1386-1396 + 1431-1453): the
- * statistics come out of the convolution's own epilogue (fp32 accumulators) where the layer runs on the implicit GEMM, and
- * from a pass over conv_out where it does not.  dt = storage type of x, conv_out and y. */
+/* dt = storage type of x, conv_out and y; the layer on the fp32 route of its shape, or the bf16 NCHW kernels */
 int mi_op_conv_bn_fwd_t(const void *x, const float *w, void *conv_out, int dt, const float *gamma, const float *beta, float *means,
                         float *vars, void *y, int N, int C, int H, int K, int k, int stride, float eps, int relu) {
-    mid_workspace ws;
-    const int Ho = H / stride;
-    if (ws_make(&ws, dt == MID_BF16 ? (size_t)k * k * C * K : mid_conv_ws_wt_floats(C, K, k), 0)) return -3;
-    mid_bn_parts parts = {NULL, mid_bn_parts_floats(N, K, Ho), 0};
-    parts.buf = (float *)mid_malloc(parts.floats * sizeof(float));
-    float *bws = (float *)mid_malloc(mid_bn_ws_floats(K) * sizeof(float));
-    void *par = NULL;
-    int rc;
-    if (dt == MID_BF16) {
-        if (stride == 2) { ws.s2d_bytes = (size_t)N * C * H * H * 2; par = mi_malloc(ws.s2d_bytes); ws.s2d = par; }
-        rc = mid_conv_fwd_bf16(mi_global()->compute, &ws, x, w, conv_out, N, C, H, K, k, stride, &parts);
-    } else rc = mid_conv_fwd_stats(mi_global()->compute, &ws, (const float *)x, w, (float *)conv_out, N, C, H, K, k, stride, &parts);
-    if (!rc) rc = mid_bn_fwd_t(mi_global()->compute, bws, &parts, conv_out, dt, gamma, beta, NULL, means, vars, y, dt, NULL, NULL, N, K, Ho * Ho, eps, relu, NULL, 0);
-    rc = finish(rc);
-    mi_free(par);
-    mid_free(bws);
-    mid_free(parts.buf);
-    ws_free(&ws);
-    return rc < 0 ? rc : parts.nparts; /* > 0: the statistics were fused (number of partial rows), 0: separate pass */
+    OpConv o;
+    if (op_open(&o, dt, &OP_OPT, w, N, C, H, K, k, stride, dt == MID_BF16 ? MI_FWD_BF16 : MI_FWD_F32, OFF, OFF, 0)) return -2;
+    return op_conv_bn_fwd(&o, x, conv_out, gamma, beta, means, vars, y, eps, relu);
 }
-/* the same pair on a bf16 3x3 layer whose forward takes the channel-last kernel (unit_fwd, MI_FWD_CL): weights re-laid, input re-laid
- * into a zeroed operand, the channel-last forward leaving the statistics partials, the BN behind it.  All image tensors bf16. */
+/* the same pair on a bf16 3x3 layer whose forward takes the channel-last kernel (MI_FWD_CL): weights re-laid, input re-laid into a zeroed
+ * operand, the channel-last forward leaving the statistics partials, the BN behind it.  All image tensors bf16. */
 int mi_op_conv_bn_fwd_bf16_cl(const void *x, const float *w, void *conv_out, const float *gamma, const float *beta, float *means,
                               float *vars, void *y, int N, int C, int H, int K, int stride, float eps, int relu) {
-    if (!mid_cl_supported(0, N, C, H, K, stride)) return -2;
-    mid_stream st = mi_global()->compute;
-    const int Ho = H / stride;
-    const size_t xb = mid_cl_operand_bytes(0, N, C, H, K, stride);
-    mid_bn_parts parts = {NULL, mid_bn_parts_floats(N, K, Ho), 0}; /* (what size_workspaces gives every unit of the layer's block, or more) */
-    void *xp = mid_malloc(xb), *at = mid_malloc((size_t)9 * C * K * 2);
-    parts.buf = (float *)mid_malloc(parts.floats * sizeof(float));
-    float *bws = (float *)mid_malloc(mid_bn_ws_floats(K) * sizeof(float));
-    int rc = (!xp || !at || !parts.buf || !bws) ? -3 : 0;
-    if (!rc) { mid_memset(xp, 0, xb, st); rc = mid_bf16_prelayout_fwd(st, w, at, K, C, 3); }
-    if (!rc) rc = mid_cl_relayout(st, x, xp, N, C, H, stride == 2);
-    if (!rc) rc = mid_cl_fwd(st, xp, at, conv_out, N, C, H, K, stride, &parts);
-    if (!rc) rc = mid_bn_fwd_t(st, bws, &parts, conv_out, MID_BF16, gamma, beta, NULL, means, vars, y, MID_BF16, NULL, NULL, N, K, Ho * Ho, eps, relu, NULL, 0);
-    rc = finish(rc);
-    mid_free(bws); mid_free(parts.buf);
-    mid_free(xp); mid_free(at);
-    return rc < 0 ? rc : parts.nparts;
+    OpConv o;
+    if (op_open(&o, MID_BF16, &OP_OPT, w, N, C, H, K, 3, stride, MI_FWD_CL, OFF, OFF, 0)) return -2;
+    return op_conv_bn_fwd(&o, x, conv_out, gamma, beta, means, vars, y, eps, relu);
 }
 /* the stem and its BN + ReLU as forward_pass runs them on the matrix cores: exact = 1 MI_FWD_STEM_F32 (conv_out fp32), exact = 0
  * MI_FWD_STEM_BF16 with conv_out fp32 or bf16 (mi_trainer_stem_dtype); a_dt = storage type of y.  The statistics come from the stem
  * kernel's partials.  Returns < 0 on error, else the number of partial rows (0 = separate statistics pass). */
 int mi_op_stem_bn_fwd_t(const float *x, const float *w, void *conv_out, int conv_dt, const float *gamma, const float *beta, float *means,
                         float *vars, void *y, int a_dt, int N, int H, float eps, int exact) {
-    if (!mid_stem_bf16_supported(3, H, 64, 7, 2) || (exact && conv_dt != MID_F32)) return -2;
-    mid_stream st = mi_global()->compute;
-    const int Ho = H / 2;
-    const size_t xb = exact ? mid_stem_f32_xp_bytes(N, H) : mid_stem_bf16_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
-    /* the trainer's partials table is sized for its largest block unit, the first expansion (4 x 64 channels over a quarter of the
-     * stem's pixels): at least this */
-    mid_bn_parts parts = {NULL, mid_bn_parts_floats(N, 64, Ho), 0};
-    void *xp = mi_malloc(xb);
-    float *sc = (float *)mid_malloc(sf * sizeof(float)), *bws = (float *)mid_malloc(mid_bn_ws_floats(64) * sizeof(float));
-    parts.buf = (float *)mid_malloc(parts.floats * sizeof(float));
-    int rc = (!xp || !sc || !bws || !parts.buf) ? -3 : 0;
-    if (!rc) rc = exact ? mid_stem_fwd_f32(st, x, w, (float *)conv_out, xp, xb, sc, sf, N, H, &parts)
-                        : mid_stem_fwd_bf16(st, x, w, conv_out, conv_dt, xp, xb, sc, sf, N, H, &parts);
-    if (!rc) rc = mid_bn_fwd_t(st, bws, &parts, conv_out, conv_dt, gamma, beta, NULL, means, vars, y, a_dt, NULL, NULL, N, 64, Ho * Ho, eps, 1, NULL, 0);
-    rc = finish(rc);
-    mid_free(parts.buf); mid_free(bws); mid_free(sc);
-    mi_free(xp);
-    return rc < 0 ? rc : parts.nparts;
-}
-/* the bf16 stem's weight gradient from dy stored as dy_dt (bf16: the stem tensors of the bf16 trainer, mi_trainer_stem_dtype) */
-int mi_op_stem_wgrad_bf16_t(const float *x, const float *w, const void *dy, int dy_dt, float *dw, int N, int H) {
-    if (!mid_stem_bf16_supported(3, H, 64, 7, 2)) return -2;
-    const size_t xb = mid_stem_bf16_xp_bytes(N, H), sf = mid_stem_bf16_part_floats(N, H);
-    void *xp = mi_malloc(xb);
-    float *sc = (float *)mid_malloc(sf * sizeof(float));
-    void *y = mi_malloc((size_t)N * 64 * (H / 2) * (H / 2) * (dy_dt == MID_BF16 ? 2 : 4));
-    int rc = (!xp || !sc || !y) ? -3 : mid_stem_fwd_bf16(mi_global()->compute, x, w, y, dy_dt, xp, xb, sc, sf, N, H, NULL); /* leaves the padded planes in xp */
-    if (!rc) rc = mid_stem_wgrad_bf16(mi_global()->compute, xp, dy, dy_dt, dw, sc, sf, N, H);
-    rc = finish(rc);
-    mi_free(y);
-    mid_free(sc);
-    mi_free(xp);
-    return rc;
+    OpConv o;
+    if (stem_open(&o, w, N, H, exact, conv_dt, a_dt, 0)) return -2;
+    return op_conv_bn_fwd(&o, x, conv_out, gamma, beta, means, vars, y, eps, 1);
 }
 int mi_op_bn_fwd_t(const void *x, int x_dt, const float *gamma, const float *beta, const void *residual, float *means, float *vars,
                    void *y, int a_dt, int N, int C, int H, float eps, int relu) {
@@ -437,93 +349,23 @@ int mi_debug_bn_merge(int R, int C, float *means, float *vars, float *dgamma, fl
 /* the 3x3 convolutions of the bf16 path on channel-last zero-padded operands (kernels_cl_bf16.hip): operand re-laid, weights re-laid,
  * then the LDS-DMA kernel.  Same tensors and semantics as mi_op_conv_fwd_bf16 / mi_op_conv_dgrad_bf16 with k = 3.  -2: shape not covered */
 int mi_op_conv_fwd_bf16_cl(const void *x, const float *w, void *y, int N, int C, int H, int K, int stride) {
-    if (!mid_cl_supported(0, N, C, H, K, stride)) return -2;
-    mid_stream st = mi_global()->compute;
-    const size_t xb = mid_cl_operand_bytes(0, N, C, H, K, stride);
-    void *xp = mid_malloc(xb), *at = mid_malloc((size_t)9 * C * K * 2);
-    if (!xp || !at) { mid_free(xp); mid_free(at); return -3; }
-    mid_memset(xp, 0, xb, st);
-    int rc = mid_bf16_prelayout_fwd(st, w, at, K, C, 3);
-    if (!rc) rc = mid_cl_relayout(st, x, xp, N, C, H, stride == 2);
-    if (!rc) rc = mid_cl_fwd(st, xp, at, y, N, C, H, K, stride, NULL);
-    rc = finish(rc);
-    mid_free(xp); mid_free(at);
-    return rc;
+    return op_conv(MID_BF16, MI_FWD_CL, OFF, OFF, x, w, NULL, y, NULL, N, C, H, K, 3, stride);
 }
 /* 1x1 forward with the input re-laid dense channel-last (one tap of the channel-last kernel: both operands reduction-contiguous) */
 int mi_op_conv1x1_fwd_bf16_cl(const void *x, const float *w, void *y, int N, int C, int H, int K) {
-    if (!mid_cl_pw_supported(N, C, H, K)) return -2;
-    mid_stream st = mi_global()->compute;
-    const size_t xb = (size_t)N * H * H * C * 2 + 4096;
-    void *xp = mid_malloc(xb), *at = mid_malloc((size_t)C * K * 2);
-    if (!xp || !at) { mid_free(xp); mid_free(at); return -3; }
-    int rc = mid_bf16_prelayout_fwd(st, w, at, K, C, 1);
-    if (!rc) rc = mid_cl_relayout_dense(st, x, xp, N, C, H);
-    if (!rc) rc = mid_cl_pw_fwd(st, xp, at, y, N, C, H, K, NULL);
-    rc = finish(rc);
-    mid_free(xp); mid_free(at);
-    return rc;
+    return op_conv(MID_BF16, MI_FWD_PW, OFF, OFF, x, w, NULL, y, NULL, N, C, H, K, 1, 1);
 }
+/* stride 1: dY re-laid as one zero-padded plane; stride 2: with a zero row / column at the far end (writes every element of dx: no addend) */
 int mi_op_conv_dgrad_bf16_cl(const float *w, const void *dy, void *dx, int N, int C, int H, int K, int stride, int to_add) {
-    if (stride == 2) {
-        if (to_add || !mid_cl_dgrad2_supported(N, C, H, K)) return -2;
-        mid_stream st2 = mi_global()->compute;
-        const size_t yb2 = mid_cl_dgrad2_operand_bytes(N, K, H / 2);
-        void *dyp2 = mid_malloc(yb2), *at2 = mid_malloc((size_t)9 * C * K * 2);
-        if (!dyp2 || !at2) { mid_free(dyp2); mid_free(at2); return -3; }
-        mid_memset(dyp2, 0, yb2, st2);
-        int rc2 = mid_bf16_prelayout_dgrad(st2, w, at2, K, C, 3);
-        if (!rc2) rc2 = mid_cl_relayout_end(st2, dy, dyp2, N, K, H / 2);
-        if (!rc2) rc2 = mid_cl_dgrad2(st2, dyp2, at2, dx, N, C, H, K);
-        rc2 = finish(rc2);
-        mid_free(dyp2); mid_free(at2);
-        return rc2;
-    }
-    if (!mid_cl_supported(1, N, C, H, K, 1)) return -2;
-    mid_stream st = mi_global()->compute;
-    const size_t yb = mid_cl_operand_bytes(1, N, C, H, K, 1);
-    void *dyp = mid_malloc(yb), *at = mid_malloc((size_t)9 * C * K * 2);
-    if (!dyp || !at) { mid_free(dyp); mid_free(at); return -3; }
-    mid_memset(dyp, 0, yb, st);
-    int rc = mid_bf16_prelayout_dgrad(st, w, at, K, C, 3);
-    if (!rc) rc = mid_cl_relayout(st, dy, dyp, N, K, H, 0);
-    if (!rc) rc = mid_cl_dgrad(st, dyp, at, dx, to_add ? dx : NULL, N, C, H, K);
-    rc = finish(rc);
-    mid_free(dyp); mid_free(at);
-    return rc;
+    if (stride == 2 && to_add) return -2;
+    return op_conv(MID_BF16, OFF, stride == 2 ? MI_DG_CL2 : MI_DG_CL, OFF, NULL, w, dy, dx, to_add ? dx : NULL, N, C, H, K, 3, stride);
 }
-
 /* 3x3 weight gradient from the channel-last planes of BOTH operands (cl_wgrad2_kernel): stride 2 = the input's parity planes and the dY
  * planes of the stride-2 dgrad; stride 1 = both with a halo of 1 */
 int mi_op_conv_wgrad_bf16_cl2(const void *x, const void *dy, float *dw, int N, int C, int H, int K, int stride) {
-    if (!mid_cl_wgrad2_supported(N, C, H, K, stride)) return -2;
-    mid_stream st = mi_global()->compute;
-    const int Ho = H / stride;
-    const size_t xb = mid_cl_operand_bytes(0, N, C, H, K, stride), yb = stride == 2 ? mid_cl_dgrad2_operand_bytes(N, K, Ho) : mid_cl_operand_bytes(1, N, C, H, K, 1),
-                 pf = mid_cl_wgrad2_part_floats(N, C, H, K, stride);
-    void *xp = mid_malloc(xb), *dyp = mid_malloc(yb);
-    float *part = (float *)mid_malloc(pf * sizeof(float));
-    if (!xp || !dyp || !part) { mid_free(xp); mid_free(dyp); mid_free(part); return -3; }
-    mid_memset(xp, 0, xb, st);
-    mid_memset(dyp, 0, yb, st);
-    int rc = mid_cl_relayout(st, x, xp, N, C, H, stride == 2);
-    if (!rc) rc = stride == 2 ? mid_cl_relayout_end(st, dy, dyp, N, K, Ho) : mid_cl_relayout(st, dy, dyp, N, K, H, 0);
-    if (!rc) rc = mid_cl_wgrad2(st, xp, dyp, dw, part, pf, N, C, H, K, stride);
-    rc = finish(rc);
-    mid_free(xp); mid_free(dyp); mid_free(part);
-    return rc;
+    return op_conv(MID_BF16, MI_FWD_CL, stride == 2 ? MI_DG_CL2 : MI_DG_CL, MI_WG_CL2, x, NULL, dy, dw, NULL, N, C, H, K, 3, stride);
 }
+/* ... and from the channel-last planes of the input and dY as it is (NCHW) */
 int mi_op_conv_wgrad_bf16_cl(const void *x, const void *dy, float *dw, int N, int C, int H, int K, int stride) {
-    if (!mid_cl_wgrad_supported(N, C, H, K, stride)) return -2;
-    mid_stream st = mi_global()->compute;
-    const size_t xb = mid_cl_operand_bytes(0, N, C, H, K, stride), pf = mid_cl_wgrad_part_floats(N, C, H, K, stride);
-    void *xp = mid_malloc(xb);
-    float *part = (float *)mid_malloc(pf * sizeof(float));
-    if (!xp || !part) { mid_free(xp); mid_free(part); return -3; }
-    mid_memset(xp, 0, xb, st);
-    int rc = mid_cl_relayout(st, x, xp, N, C, H, stride == 2);
-    if (!rc) rc = mid_cl_wgrad(st, xp, dy, dw, part, pf, N, C, H, K, stride);
-    rc = finish(rc);
-    mid_free(xp); mid_free(part);
-    return rc;
+    return op_conv(MID_BF16, MI_FWD_CL, OFF, MI_WG_CL, x, NULL, dy, dw, NULL, N, C, H, K, 3, stride);
 }

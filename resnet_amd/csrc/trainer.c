@@ -333,101 +333,19 @@ static size_t max_tensor_elems(const Dims *d, ConvBlock **blocks, int N) {
     return m;
 }
 
-/* a device buffer that starts zeroed: the halos of the channel-last planes stay zero (their writers fill the interior only) */
-static void *zalloc(MiCtx *c, size_t bytes) {
-    void *p = mi_ctx_alloc(c, bytes);
-    mid_memset(p, 0, bytes, G.compute);
-    return p;
+/* the convolution table (MiCtx.stem, MiCtx.blk): every layer planned and given its buffers by layer.c; what the network adds is who
+ * writes a layer's channel-last planes (cl_by_bn), the BN'-fusion sites, and the table of weights re-laid once per forward pass */
+static void plan_one(MiCtx *c, MiLayer *L, int N, int site) {
+    ck(mi_layer_plan(L, c->dtype, c->policy, &c->opt, N, site, NULL), "convolution plan");
+    mi_layer_alloc(c, L);
 }
-static void layer_init(MiLayer *L, const float *w, int C, int H, int K, int k, int stride) {
-    memset(L, 0, sizeof *L); /* MI_FWD_F32 / MI_DG_F32 / MI_WG_F32, no buffers */
-    L->w = w; L->C = C; L->H = H; L->K = K; L->k = k; L->stride = stride;
-}
-/* routes and buffers of one bottleneck convolution; site: its bit in the BN'-fusion site masks (0: not a site) */
-static void plan_conv(MiCtx *c, MiLayer *L, int N, int site) {
-    const MiOptions *o = &c->opt;
-    const int C = L->C, H = L->H, K = L->K, s = L->stride;
-    if (c->dtype == MID_BF16) {
-        L->fwd = MI_FWD_BF16; L->dgrad = MI_DG_BF16; L->wgrad = MI_WG_BF16;
-        if (L->k == 3 && s == 1 && o->cl_s1 && mid_cl_supported(0, N, C, H, K, 1)) {
-            /* forward and weight gradient on one zero-padded channel-last plane */
-            L->cl = zalloc(c, mid_cl_operand_bytes(0, N, C, H, K, 1));
-            L->fwd = MI_FWD_CL;
-            if (o->cl_s1_dgrad && mid_cl_supported(1, N, C, H, K, 1)) { /* the dgrad on dY re-laid as one zero-padded plane */
-                L->dye = zalloc(c, mid_cl_operand_bytes(1, N, C, H, K, 1));
-                L->dgrad = MI_DG_CL;
-            }
-        }
-        if (s == 2) { /* (a 3x3: the striding convolutions are the spatial one and the projection) */
-            if (o->cl_s2 && mid_cl_supported(0, N, C, H, K, 2)) { /* forward and weight gradient on four channel-last parity planes */
-                L->cl = zalloc(c, mid_cl_operand_bytes(0, N, C, H, K, 2));
-                L->fwd = MI_FWD_CL;
-            }
-            if (o->cl_dgrad2 && mid_cl_dgrad2_supported(N, C, H, K)) { /* the dgrad on dY re-laid with a zero row / column at the far end */
-                L->dye = zalloc(c, mid_cl_dgrad2_operand_bytes(N, K, H / 2));
-                L->dgrad = MI_DG_CL2;
-            }
-        }
-        const int P = (H / s) * (H / s);
-        const int wg = L->cl && mid_cl_wgrad_supported(N, C, H, K, s), wg2 = L->cl && mid_cl_wgrad2_supported(N, C, H, K, s);
-        /* both operands channel-last (the dY planes of the dgrad) where the plane does not fill 64-pixel tiles (784, 196, 49 pixels: all
-         * of the benchmark network's stride-2 layers; -0.8 ms per step, most of it the two 7x7 layers the other kernel cannot take) */
-        if (L->dye && wg2 && (P % 64 != 0 || !wg)) L->wgrad = MI_WG_CL2;
-        else if (wg) L->wgrad = MI_WG_CL;
-        /* NCHW parity planes of a stride-2 input (kernels_igemm_bf16.hip): the NCHW forward writes them and the weight gradient reads
-         * them again (1.1 GB in all at N = 256 with every stride-2 layer on this route); behind a channel-last forward, only for
-         * shapes that no channel-last weight-gradient kernel takes (the NCHW one makes them itself) */
-        if (s == 2 && (L->fwd == MI_FWD_BF16 || (!wg && !wg2))) {
-            const size_t e = (size_t)N * C * H * H;
-            L->par_bytes = e * 2;
-            L->par = (char *)mi_ctx_alloc(c, e * 2 + 2 * MI_GUARD) + MI_GUARD;
-        }
-    }
-    /* The dgrad also does the reduction pass of the BN' its output feeds (and gates that output): sites 1 expansion dgrad -> spatial
-     * BN', 2 spatial dgrad -> reduction BN', 4 reduction dgrad -> the expansion BN' of the identity block below.  bf16: every site
-     * whose dgrad is on the NCHW kernel (RECOMPUTE_BN too: the gating tensors have just been re-derived when the dgrad runs).
-     * fp32: the sites of RESNET_MI_F32_BNFUSE_BWD on the implicit-GEMM route, not with the FULL policy (its derivative mirror keeps
-     * the ungated gradients the dump tree names).  Measured at batch 256 (same box, ms/step): none 108.3-109.5, site 4 alone
-     * 108.3-108.9, site 1 alone 109.4-110.2, sites 1+2 111.6-112.8, all 111.7-112.2 -- the fp32 epilogue keeps lane = column, so
-     * the fused form reads x / mask / addend with 4-byte accesses (four times the memory instructions of the bf16 kernel's
-     * row-major drain) and pays for it wherever the separate reduction pass was only 2 tensors; site 4 replaces a 4-tensor pass
-     * and breaks even, so it is the default. */
-    const int f32_sites = mid_igemm_mode() >= 2 ? o->bnfuse_bwd_f32 : 0;
-    L->fz = site && o->bnfuse_bwd &&
-            (L->dgrad == MI_DG_BF16 || (L->dgrad == MI_DG_F32 && (f32_sites & site) && c->policy != MI_STORE_FULL));
-}
-/* the convolution table (MiCtx.stem, MiCtx.blk): routes, the buffers they need, and the weights re-laid once per forward pass */
 static void plan_layers(MiCtx *c, const Params *p, const Dims *d, int N) {
-    const MiOptions *o = &c->opt;
     ConvBlock **blocks = p->conv_blocks;
-    const int f = d->init_conv_filters;
-    MiLayer *S = &c->stem;
-    layer_init(S, p->init_conv_layer, 3, d->input, f, d->init_kernel_dim, d->init_conv_stride);
-    c->stem_bf16 = 0;
-    const int stem_mc = mid_stem_bf16_supported(3, d->input, f, d->init_kernel_dim, d->init_conv_stride);
-    if (c->dtype == MID_F32 && mid_igemm_mode() > 0 && stem_mc && o->stem_mfma) {
-        /* fp32 storage: the stem in exact fp32 on the matrix cores (kernels_stem_bf16.hip, st32_*) */
-        S->xp_bytes = mid_stem_f32_xp_bytes(N, d->input);
-        S->scratch_floats = mid_stem_bf16_part_floats(N, d->input);
-        S->xp = falloc(c, (S->xp_bytes + 3) / 4);
-        S->scratch = falloc(c, S->scratch_floats);
-        S->fwd = MI_FWD_STEM_F32; S->wgrad = MI_WG_STEM_F32;
-    }
-    if (c->dtype == MID_BF16 && stem_mc && o->bf16_stem) {
-        /* the stem on the bf16 matrix cores (image and weights rounded to bf16 like every other convolution of this mode) */
-        S->xp_bytes = mid_stem_bf16_xp_bytes(N, d->input);
-        S->scratch_floats = mid_stem_bf16_part_floats(N, d->input);
-        S->xp = aalloc(c, (S->xp_bytes + 1) / 2);                 /* (aalloc counts 2-byte elements in bf16 mode) */
-        S->scratch = falloc(c, S->scratch_floats);
-        S->fwd = MI_FWD_STEM_BF16; S->wgrad = MI_WG_STEM_BF16;
-        /* its output and that tensor's gradient are stored as bf16 like every other convolution's (they stay in their fp32-sized buffers):
-         * 822 MB tensors at N = 256 that the stem BN reads twice forward and three times backward */
-        c->stem_bf16 = !o->stem_tensors_f32;
-    }
+    mi_layer_init(&c->stem, p->init_conv_layer, 3, d->input, d->init_conv_filters, d->init_kernel_dim, d->init_conv_stride);
+    plan_one(c, &c->stem, N, 0);
+    c->stem_bf16 = c->stem.out_dt == MID_BF16;
     free(c->blk);
     c->blk = (MiBlockLayers *)calloc((size_t)(d->n_conv_blocks > 0 ? d->n_conv_blocks : 1), sizeof(MiBlockLayers));
-    /* the weights re-laid once per forward pass (mid_conv_prelayout_all): every bf16 convolution (k-step tiles, forward and dgrad
-     * forms), the fp32 ones on the implicit-GEMM route (RESNET_MI_PRELAYOUT=0: each re-lays its own) */
     free(c->wt_tab);
     c->wt_tab = (mid_wt_entry *)calloc((size_t)(4 * d->n_conv_blocks + 1), sizeof(mid_wt_entry));
     c->wt_n = 0; c->wt_tiles = 0;
@@ -435,31 +353,27 @@ static void plan_layers(MiCtx *c, const Params *p, const Dims *d, int N) {
         const ConvBlock *b = blocks[i];
         MiBlockLayers *B = &c->blk[i];
         const int H = b->incoming_spatial_dim, s = b->stride;
-        layer_init(&B->red, b->depth_reduction, b->incoming_filters, H, b->reduced_depth, 1, 1);
-        layer_init(&B->spa, b->spatial, b->reduced_depth, H, b->reduced_depth, 3, s);
-        layer_init(&B->exp, b->depth_expansion, b->reduced_depth, H / s, b->expanded_depth, 1, 1);
-        plan_conv(c, &B->red, N, i > 0 && !blocks[i - 1]->projection ? 4 : 0);
-        plan_conv(c, &B->spa, N, 2);
-        plan_conv(c, &B->exp, N, 1);
+        mi_layer_init(&B->red, b->depth_reduction, b->incoming_filters, H, b->reduced_depth, 1, 1);
+        mi_layer_init(&B->spa, b->spatial, b->reduced_depth, H, b->reduced_depth, 3, s);
+        mi_layer_init(&B->exp, b->depth_expansion, b->reduced_depth, H / s, b->expanded_depth, 1, 1);
+        plan_one(c, &B->red, N, i > 0 && !blocks[i - 1]->projection ? 4 : 0);
+        plan_one(c, &B->spa, N, 2);
+        plan_one(c, &B->exp, N, 1);
         /* the reduction BN writes the 3x3's planes beside its NCHW output (stride 2: a re-layout pass instead where the plane is odd) */
         if (B->spa.cl) B->spa.cl_by_bn = s == 1 || !(H & 1);
         if (b->projection) {
-            layer_init(&B->proj, b->projection, b->incoming_filters, H, b->expanded_depth, s == 2 ? 3 : 1, s);
-            plan_conv(c, &B->proj, N, 0);
+            mi_layer_init(&B->proj, b->projection, b->incoming_filters, H, b->expanded_depth, s == 2 ? 3 : 1, s);
+            plan_one(c, &B->proj, N, 0);
             /* this block's input is the output of the block above: its BN + add + ReLU writes the planes too */
             if (B->proj.cl) B->proj.cl_by_bn = i > 0 && !(H & 1);
         }
         MiLayer *Ls[4] = {&B->red, &B->spa, &B->exp, &B->proj};
         for (int j = 0; j < 4; j++) {
             MiLayer *L = Ls[j];
-            int nf = 0, nd = 0;
-            if (L->w && c->dtype == MID_BF16) nf = nd = 1;
-            else if (L->w && o->prelayout) mid_conv_prelayout_needs(N, L->C, L->H, L->K, L->k, L->stride, &nf, &nd);
-            if (!nf && !nd) continue;
+            if (!L->w || (!L->wre_fwd && !L->wre_dgrad)) continue;
             mid_wt_entry *e = &c->wt_tab[c->wt_n++];
-            const size_t n = ((size_t)L->k * L->k * L->C * L->K) / (c->dtype == MID_BF16 ? 2 : 1);
             e->w = L->w; e->K = L->K; e->C = L->C; e->T = L->k * L->k;
-            e->fwd = nf ? falloc(c, n) : NULL; e->dgrad = nd ? falloc(c, n) : NULL;
+            e->fwd = L->wre_fwd ? falloc(c, L->wre_floats) : NULL; e->dgrad = L->wre_dgrad ? falloc(c, L->wre_floats) : NULL;
             e->tile0 = c->wt_tiles; c->wt_tiles += (L->C / 32) * (L->K / 32);
             L->we = e;
         }
@@ -480,38 +394,15 @@ static void plan_layers(MiCtx *c, const Params *p, const Dims *d, int N) {
     }
 }
 /* the workspaces every convolution shares, sized for the largest layer of the table */
-static void size_layer_ws(const MiCtx *c, const MiLayer *L, int N, size_t *wt, size_t *part, int *maxc) {
-    const int C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
-    size_t a = mid_conv_ws_wt_floats(C, K, k), b = mid_conv_ws_part_floats(N, C, H, K, k, s);
-    if (c->dtype == MID_BF16 && k <= 3) { size_t e = mid_bf16_part_floats(N, C, H, K, k, s); if (e > b) b = e; }
-    if (c->dtype == MID_BF16 && k == 3 && mid_cl_wgrad_supported(N, C, H, K, s)) { size_t e = mid_cl_wgrad_part_floats(N, C, H, K, s); if (e > b) b = e; }
-    if (c->dtype == MID_BF16 && k == 3 && mid_cl_wgrad2_supported(N, C, H, K, s)) { size_t e = mid_cl_wgrad2_part_floats(N, C, H, K, s); if (e > b) b = e; }
-    if (a > *wt) *wt = a;
-    if (b > *part) *part = b;
-    if (K > *maxc) *maxc = K;
-}
-static void size_workspaces(MiCtx *c, const Dims *d, int N) {
-    size_t wt = 0, part = 0, pf = 0; /* pf: largest statistics-partials table of any conv + BN unit */
-    int maxc = d->init_conv_filters;
-    size_layer_ws(c, &c->stem, N, &wt, &part, &maxc);
+static void size_workspaces(MiCtx *c, const Dims *d) {
+    MiLayerNeed need = {0, 0, 0, d->init_conv_filters};
+    mi_layer_need(&c->stem, &need);
     for (int i = 0; i < d->n_conv_blocks; i++) {
         const MiBlockLayers *B = &c->blk[i];
-        size_layer_ws(c, &B->red, N, &wt, &part, &maxc);
-        size_layer_ws(c, &B->spa, N, &wt, &part, &maxc);
-        size_layer_ws(c, &B->exp, N, &wt, &part, &maxc);
-        if (B->proj.w) size_layer_ws(c, &B->proj, N, &wt, &part, &maxc);
-        const size_t a = mid_bn_parts_floats(N, B->red.K, B->red.H), e = mid_bn_parts_floats(N, B->exp.K, B->exp.H);
-        if (a > pf) pf = a;
-        if (e > pf) pf = e;
+        const MiLayer *Ls[4] = {&B->red, &B->spa, &B->exp, &B->proj};
+        for (int j = 0; j < 4; j++) if (Ls[j]->w) mi_layer_need(Ls[j], &need);
     }
-    c->ws.s2d = NULL; c->ws.s2d_bytes = 0; c->ws.s2d_valid = 0;
-    c->ws.wt_floats = wt; c->ws.part_floats = part;
-    c->ws.wt = wt ? falloc(c, wt) : NULL;
-    c->ws.part = part ? falloc(c, part) : NULL;
-    c->bn_ws = falloc(c, mid_bn_ws_floats(maxc));
-    c->bn_parts.floats = pf;
-    c->bn_parts.buf = pf ? falloc(c, pf) : NULL;
-    c->bn_parts.nparts = 0;
+    mi_layer_ws_alloc(c, &c->lw, &need);
 }
 
 static MiCtx *ctx_of(Train_ResNet *t) { return (MiCtx *)t->backend_ctx; }
@@ -548,7 +439,7 @@ static void build_buffers(Train_ResNet *t) {
      * next to -- measured 6028 img/s serial against 5973 overlapped; an explicit RESNET_MI_OVERLAP still wins */
     if (c->dtype == MID_BF16 && !c->opt.overlap_given && !c->overlap_set) c->overlap_wgrad = 0;
     plan_layers(c, t->model->params, d, N);
-    size_workspaces(c, d, N);
+    size_workspaces(c, d);
     mid_stream_sync(G.compute);
 }
 static void drop_buffers(Train_ResNet *t) {
@@ -563,7 +454,7 @@ static void drop_buffers(Train_ResNet *t) {
 }
 
 /* the trainer's switches (MiOptions), read once per trainer: a trainer made after a change of the environment sees the change */
-static void read_options(MiOptions *o) {
+void mi_read_options(MiOptions *o) {
 #define ENV_INT(name_, default_) (getenv(name_) ? atoi(getenv(name_)) : (default_))
     o->cl_s1 = ENV_INT("RESNET_MI_BF16_CL_S1", 1) != 0;
     o->cl_s1_dgrad = ENV_INT("RESNET_MI_BF16_CL_S1_DGRAD", 1) != 0;
@@ -593,7 +484,7 @@ Train_ResNet *init_trainer(ResNet *model, Batch *cur_batch, int batch_size, floa
     c->input_reset = 1;   /* resnet.cu:2981-2982 */
     c->world = 1; c->bucket_bytes = (size_t)32 << 20;
     c->dtype = MID_F32; c->policy = MI_STORE_FAST;
-    read_options(&c->opt);
+    mi_read_options(&c->opt);
     c->overlap_wgrad = c->opt.overlap;
     c->ev_bn_done = mid_event_create(); c->ev_wgrad_done = mid_event_create();
 
@@ -674,25 +565,21 @@ static void add_full_store_extras(Train_ResNet *t) {
     c->counting_act = 0;
     c->full_store = 1;
 }
-/* every convolution of the bottleneck blocks must tile for the bf16 kernels (the stem stays on the fp32 path) */
+/* every convolution of the bottleneck blocks must tile for the bf16 NCHW kernels (the stem stays on the fp32 path): the planner's own
+ * test of those routes, over the table of the trainer's current storage type (the shapes are the same) */
 static int bf16_net_supported(const Train_ResNet *t, char *why, size_t whylen) {
-    const Dims *d = t->model->dims;
-    ConvBlock **blocks = t->model->params->conv_blocks;
-    const int N = t->batch_size;
-    for (int i = 0; i < d->n_conv_blocks; i++) {
-        const ConvBlock *b = blocks[i];
-        const int H = b->incoming_spatial_dim;
-        const int L[4][5] = {{b->incoming_filters, H, b->reduced_depth, 1, 1},
-                             {b->reduced_depth, H, b->reduced_depth, 3, b->stride},
-                             {b->reduced_depth, H / b->stride, b->expanded_depth, 1, 1},
-                             {b->incoming_filters, H, b->expanded_depth, b->stride == 2 ? 3 : 1, b->stride}};
-        for (int j = 0; j < (b->projection ? 4 : 3); j++)
-            for (int op = 0; op < 3; op++)
-                if (!mid_bf16_supported(op, N, L[j][0], L[j][1], L[j][2], L[j][3], L[j][4])) {
-                    snprintf(why, whylen, "block %d conv %d (C=%d H=%d K=%d k=%d s=%d) op %d does not tile for the bf16 kernels", i, j,
-                             L[j][0], L[j][1], L[j][2], L[j][3], L[j][4], op);
-                    return 0;
-                }
+    const MiCtx *c = (const MiCtx *)t->backend_ctx;
+    const int nchw[3] = {MI_FWD_BF16, MI_DG_BF16, MI_WG_BF16};
+    for (int i = 0; i < t->model->dims->n_conv_blocks; i++) {
+        const MiBlockLayers *B = &c->blk[i];
+        const MiLayer *Ls[4] = {&B->red, &B->spa, &B->exp, &B->proj};
+        for (int j = 0; j < 4; j++) {
+            MiLayer L = *Ls[j];
+            if (L.w && mi_layer_plan(&L, MID_BF16, c->policy, &c->opt, t->batch_size, 0, nchw)) {
+                snprintf(why, whylen, "block %d conv %d (C=%d H=%d K=%d k=%d s=%d) does not tile for the bf16 kernels", i, j, L.C, L.H, L.K, L.k, L.stride);
+                return 0;
+            }
+        }
     }
     return 1;
 }
@@ -814,46 +701,18 @@ void mi_trainer_poll_errors(Train_ResNet *t) {
 }
 
 /* conv + BN (+ReLU | +residual+ReLU): prepareAndDoConvolution + prepareAndDoBatchNormAndActivate.
- * stem: the 7x7 convolution keeps fp32 input / output in every storage type; only its BN output is an activation tensor */
-/* storage type of a convolution's output (the BN's x) and of that tensor's gradient */
-static int conv_out_dt(const MiCtx *c, const MiLayer *L) { return L == &c->stem ? (c->stem_bf16 ? MID_BF16 : MID_F32) : c->dtype; }
-/* cl_reader: a convolution this unit's output feeds; where its channel-last input planes are this BN's to write (cl_by_bn), the
- * BN apply writes them beside its NCHW output */
+ * stem: the 7x7 convolution keeps fp32 input / output in every storage type; only its BN output is an activation tensor.
+ * cl_reader: a convolution this unit's output feeds (mi_layer_bn_fwd) */
 static void unit_fwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNorm *bn, Cache_BatchNorm *cache, float *conv_out,
                      float *act_out, const float *residual, int relu, const MiLayer *cl_reader) {
     MiCtx *c = ctx_of(t);
-    const int N = t->batch_size, C = L->C, H = L->H, K = L->K, Ho = H / L->stride;
     /* the convolution leaves per-tile (count, mean, M2) partials of its output: BN reads the tensor twice, not three times (the
      * kernels with bf16 operands always do) */
     const int bf_ops = L->fwd == MI_FWD_BF16 || L->fwd == MI_FWD_CL || L->fwd == MI_FWD_STEM_BF16;
-    mid_bn_parts *parts = (c->opt.bnfuse || bf_ops) ? &c->bn_parts : NULL;
-    c->ws.s2d = L->par; c->ws.s2d_bytes = L->par_bytes; c->ws.s2d_valid = 0;
-    c->ws.pre_fwd = L->we ? L->we->fwd : NULL; /* re-laid at the start of this forward pass */
-    switch (L->fwd) {
-    case MI_FWD_STEM_F32:
-        ck(mid_stem_fwd_f32(G.compute, in, L->w, conv_out, L->xp, L->xp_bytes, L->scratch, L->scratch_floats, N, H, parts),
-           "stem convolution forward (fp32 matrix cores)");
-        break;
-    case MI_FWD_STEM_BF16: /* (the stem's tensors may be fp32 here, but its statistics still come from the kernel's accumulators) */
-        ck(mid_stem_fwd_bf16(G.compute, in, L->w, conv_out, conv_out_dt(c, L), L->xp, L->xp_bytes, L->scratch, L->scratch_floats, N, H, parts),
-           "stem convolution forward (bf16 operands)");
-        break;
-    case MI_FWD_CL: /* planes written by the producing BN apply, else re-laid here; the weight gradient reads them again */
-        if (!L->cl_by_bn) ck(mid_cl_relayout(G.compute, in, L->cl, N, C, H, L->stride == 2), "input re-layout (channel-last parity planes)");
-        ck(mid_cl_fwd(G.compute, L->cl, L->we->fwd, conv_out, N, C, H, K, L->stride, parts), "convolution forward (bf16, channel-last)");
-        L->par_valid = 0;
-        break;
-    case MI_FWD_BF16:
-        ck(mid_conv_fwd_bf16(G.compute, &c->ws, in, L->w, conv_out, N, C, H, K, L->k, L->stride, parts), "convolution forward (bf16)");
-        L->par_valid = c->ws.s2d_valid; /* the launch says whether it left the parity planes */
-        break;
-    default: ck(mid_conv_fwd_stats(G.compute, &c->ws, in, L->w, conv_out, N, C, H, K, L->k, L->stride, parts), "convolution forward");
-    }
-    c->ws.pre_fwd = NULL;
-    void *ycl = cl_reader && cl_reader->cl_by_bn ? cl_reader->cl : NULL;
-    const int Hcl = ycl ? (cl_reader->stride == 2 ? -cl_reader->H : cl_reader->H) : 0;
-    ck(mid_bn_fwd_t(G.compute, c->bn_ws, parts, conv_out, conv_out_dt(c, L), bn->gamma, bn->beta, residual, cache->means, cache->vars,
-                    act_out, c->dtype, cache->normalized_temp, cache->normalized, N, K, Ho * Ho, t->eps, relu, ycl, Hcl), "batch norm forward");
+    mid_bn_parts *parts = (c->opt.bnfuse || bf_ops) ? &c->lw.bn_parts : NULL;
+    ck(mi_layer_fwd(L, &c->lw, G.compute, in, conv_out, parts), "convolution forward");
+    ck(mi_layer_bn_fwd(L, &c->lw, G.compute, parts, conv_out, bn->gamma, bn->beta, residual, cache->means, cache->vars, act_out,
+                       cache->normalized_temp, cache->normalized, t->eps, relu, cl_reader), "batch norm forward");
 }
 
 /* the batch-norm launchers take their cross-replica setting from one process-wide slot (kernels_bn.hip): every pass binds ITS
@@ -946,110 +805,43 @@ static float *ring_take(MiCtx *c, int *slot) {
     if (slot) *slot = i;
     return c->ring_buf[i];
 }
-/* typed launch helpers: the bottleneck convolutions run on the bf16 kernels in bf16 mode, the stem always on the fp32 path.
- * req (L->fz): the dgrad also does the reduction pass of the BN' its output feeds; it hands that over in *fz (nparts > 0 when the
- * launch could do it, dx then holds the gated gradient) */
-static void conv_dgrad_t(Train_ResNet *t, const MiLayer *L, const float *dy, float *dx, const float *addend, const mid_bn_bwd_parts *req,
-                         mid_bn_bwd_parts *fz) {
-    MiCtx *c = ctx_of(t);
-    const int N = t->batch_size, C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
-    if (L->dgrad == MI_DG_CL) { /* stride 1 on the channel-last dY plane (the BN' below then runs its own reduction pass: measured neutral) */
-        ck(mid_cl_dgrad(G.compute, L->dye, L->we->dgrad, dx, addend, N, C, H, K), "convolution dgrad (bf16, channel-last)");
-        return;
-    }
-    if (L->dgrad == MI_DG_CL2) {
-        /* stride 2 on the channel-last dY: both column parities of dx per workgroup by LDS-DMA staged MFMAs (dense stores; 1.5-1.9x
-         * the NCHW kernel's four parity classes).  It writes every element of dx: no addend (the stride-2 layers' dgrads have none) */
-        ck(mid_cl_dgrad2(G.compute, L->dye, L->we->dgrad, dx, N, C, H, K), "convolution dgrad (bf16, channel-last, stride 2)");
-        return;
-    }
-    c->ws.pre_dgrad = L->we ? L->we->dgrad : NULL;
-    if (req) *fz = *req;
-    if (L->dgrad == MI_DG_BF16 && req)
-        ck(mid_conv_dgrad_bn_bf16(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s, fz), "convolution dgrad + BN' reduction (bf16)");
-    else if (req) /* fp32 storage: the stride-1 layers on the implicit-GEMM route do the same */
-        ck(mid_conv_dgrad_bn_f32(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s, fz), "convolution dgrad + BN' reduction");
-    else if (L->dgrad == MI_DG_BF16) ck(mid_conv_dgrad_bf16(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s), "convolution dgrad (bf16)");
-    else ck(mid_conv_dgrad(G.compute, &c->ws, L->w, dy, dx, addend, N, C, H, K, k, s), "convolution dgrad");
-    c->ws.pre_dgrad = NULL;
-}
-static void conv_wgrad_t(Train_ResNet *t, const MiLayer *L, mid_stream st, const float *x, const float *dy, float *dw) {
-    MiCtx *c = ctx_of(t);
-    const int N = t->batch_size, C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
-    /* the forward pass left the parity planes of x in the layer's own buffer: the weight gradient reads them again */
-    c->ws.s2d = L->par; c->ws.s2d_bytes = L->par_bytes; c->ws.s2d_valid = L->par && L->par_valid;
-    switch (L->wgrad) {
-    case MI_WG_STEM_F32:
-        ck(mid_stem_wgrad_f32(st, L->xp, dy, dw, L->scratch, L->scratch_floats, N, H), "stem convolution wgrad (fp32 matrix cores)");
-        break;
-    case MI_WG_STEM_BF16: /* the forward pass left the batch as padded bf16 parity planes */
-        ck(mid_stem_wgrad_bf16(st, L->xp, dy, conv_out_dt(c, L), dw, L->scratch, L->scratch_floats, N, H), "stem convolution wgrad (bf16 operands)");
-        break;
-    case MI_WG_CL2: /* both operands channel-last: the forward's input planes and the dY planes unit_bwd has made */
-        ck(mid_cl_wgrad2(st, L->cl, L->dye, dw, c->ws.part, c->ws.part_floats, N, C, H, K, s), "convolution wgrad (bf16, both operands channel-last)");
-        break;
-    case MI_WG_CL:
-        ck(mid_cl_wgrad(st, L->cl, dy, dw, c->ws.part, c->ws.part_floats, N, C, H, K, s), "convolution wgrad (bf16, channel-last input)");
-        break;
-    case MI_WG_BF16: ck(mid_conv_wgrad_bf16(st, &c->ws, x, dy, dw, N, C, H, K, k, s), "convolution wgrad (bf16)"); break;
-    default: ck(mid_conv_wgrad(st, &c->ws, x, dy, dw, N, C, H, K, k, s), "convolution wgrad");
-    }
-}
 /* d_slot: ring slot holding d_conv_out (mode 2), -1 otherwise.  fz: the BN'-partials hand-off between a fusing dgrad and the next
- * unit (nparts > 0: this unit's BN' reduction is done); fz_req: what this unit's dgrad is to fill it with, or NULL (fz_request) */
+ * unit (nparts > 0: this unit's BN' reduction is done); fz_req: what this unit's dgrad is to fill it with, or NULL (mi_layer_fz_request) */
 static void unit_bwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNorm *bn, const Cache_BatchNorm *cache,
                      const BatchNorm *dbn, const float *conv_out, const float *dy, const float *mask_src, int mask_mode,
                      float *gated_out, float *d_conv_out, int d_slot, float *dx, const float *addend, float *dw, mid_bn_bwd_parts *fz,
                      const mid_bn_bwd_parts *fz_req) {
     MiCtx *c = ctx_of(t);
-    const int N = t->batch_size, K = L->K, Ho = L->H / L->stride;
-    const int x_dt = conv_out_dt(c, L);
+    const int Ho = L->H / L->stride;
     /* BN' of this unit (HBM-bound) runs next to earlier units' weight gradients (FMA-bound, low-priority aux stream);
      * mask_mode 3: ReLU' of the block output fused in, and its product with the upstream gradient kept (gated_out) */
-    if (fz->nparts > 0) { /* the dgrad that produced dy gated it and left the sums: merge, finalize, apply */
-        ck(mid_bn_bwd_parts_t(G.compute, c->bn_ws, fz, conv_out, x_dt, bn->gamma, bn->beta, cache->means, cache->vars, dy, c->dtype,
-                              d_conv_out, dbn->gamma, dbn->beta, N, K, Ho * Ho, t->eps), "batch norm backward (reduction done by the dgrad)");
-        fz->nparts = 0;
-    } else
-    ck(mid_bn_bwd_t(G.compute, c->bn_ws, conv_out, x_dt, bn->gamma, bn->beta, cache->means, cache->vars, dy, mask_src, gated_out, c->dtype,
-                    d_conv_out, dbn->gamma, dbn->beta, N, K, Ho * Ho, t->eps, mask_mode), "batch norm backward");
+    ck(mi_bn_bwd_unit(&c->lw, G.compute, fz, conv_out, L->out_dt, bn->gamma, bn->beta, cache->means, cache->vars, dy, mask_src, mask_mode,
+                      gated_out, c->dtype, d_conv_out, dbn->gamma, dbn->beta, t->batch_size, L->K, Ho * Ho, t->eps), "batch norm backward");
     /* the channel-last copy of d_conv_out that the channel-last dgrad AND the weight gradient read: made here, before either is
      * launched, so that every weight-gradient schedule (the free-running one starts before the dgrad) runs the same kernels */
-    if (L->dgrad == MI_DG_CL) /* stride 1: one plane with a halo of 1 */
-        ck(mid_cl_relayout(G.compute, d_conv_out, L->dye, N, K, Ho, 0), "dY re-layout (channel-last)");
-    else if (L->dgrad == MI_DG_CL2) /* stride 2: a zero row / column at the far end */
-        ck(mid_cl_relayout_end(G.compute, d_conv_out, L->dye, N, K, Ho), "dY re-layout (channel-last)");
+    ck(mi_layer_dy_relayout(L, G.compute, d_conv_out), "dY re-layout (channel-last)");
     if (c->overlap_wgrad == 2 && d_slot >= 0) {
         /* d_conv_out is final once BN' is: the weight gradient may start now and run for as long as the slot lives */
         mid_event_record(c->ev_bn_done, G.compute);
         mid_stream_wait_event(G.aux, c->ev_bn_done);
-        conv_wgrad_t(t, L, G.aux, in, d_conv_out, dw);
+        ck(mi_layer_wgrad(L, &c->lw, G.aux, in, d_conv_out, dw), "convolution wgrad");
         mid_event_record(c->ring_ev[d_slot], G.aux);
         c->ring_busy[d_slot] = 1;
         mid_event_record(c->ev_wgrad_done, G.aux);
         c->wgrad_pending = 1;
-        if (dx) conv_dgrad_t(t, L, d_conv_out, dx, addend, fz_req, fz);
+        if (dx) ck(mi_layer_dgrad(L, &c->lw, G.compute, d_conv_out, dx, addend, fz_req, fz), "convolution dgrad");
         return;
     }
     join_wgrad(c);
-    if (dx) conv_dgrad_t(t, L, d_conv_out, dx, addend, fz_req, fz);
+    if (dx) ck(mi_layer_dgrad(L, &c->lw, G.compute, d_conv_out, dx, addend, fz_req, fz), "convolution dgrad");
     if (c->overlap_wgrad) {
         mid_event_record(c->ev_bn_done, G.compute);
         mid_stream_wait_event(G.aux, c->ev_bn_done);
-        conv_wgrad_t(t, L, G.aux, in, d_conv_out, dw);
+        ck(mi_layer_wgrad(L, &c->lw, G.aux, in, d_conv_out, dw), "convolution wgrad");
         mid_event_record(c->ev_wgrad_done, G.aux);
         c->wgrad_pending = 1;
-    } else conv_wgrad_t(t, L, G.compute, in, d_conv_out, dw);
+    } else ck(mi_layer_wgrad(L, &c->lw, G.compute, in, d_conv_out, dw), "convolution wgrad");
 }
-/* the request for a fusing dgrad (L->fz): the reduction over x / mask / means of the BN' its output feeds; NULL where L does not fuse */
-static const mid_bn_bwd_parts *fz_request(const MiCtx *c, mid_bn_bwd_parts *r, const MiLayer *L, const void *x, const void *mask,
-                                          const float *means) {
-    if (!L->fz) return NULL;
-    r->x = x; r->mask = mask; r->means = means;
-    r->buf = c->bn_parts.buf; r->floats = c->bn_parts.floats; r->nparts = 0;
-    return r;
-}
-
 /* resnet.cu:1777-2248 */
 void backwards_pass(Train_ResNet *t) {
     MiCtx *c = ctx_of(t);
@@ -1116,7 +908,7 @@ void backwards_pass(Train_ResNet *t) {
                "BN recompute");
         unit_bwd(t, &B->exp, k->post_spatial_activated, b->norm_expansion, k->norm_post_expanded, db->norm_expansion, k->post_expanded, exp_dy,
                  exp_mask, exp_mode, dk->output, dk->post_expanded, s_exp, dk->post_spatial_activated, NULL, db->depth_expansion, &fz,
-                 fz_request(c, &req, &B->exp, k->post_spatial, k->post_spatial_activated, k->norm_post_spatial->means));
+                 mi_layer_fz_request(&B->exp, &c->lw, &req, k->post_spatial, k->post_spatial_activated, k->norm_post_spatial->means));
         /* the call resnet.cu:2060-2083 forgot; present in resnet_cudnn.cu:2365-2366 */
         if (ring) { dk->post_spatial = ring_take(c, &s_spa); dk->post_reduced_activated = ring_take(c, NULL); }
         if (recompute) /* the 3x3's input, re-derived: relu(BN(post_reduced)) (resnet_clean.cu:2714) */
@@ -1125,11 +917,11 @@ void backwards_pass(Train_ResNet *t) {
                               H * H, t->eps, 1, NULL, 0), "BN recompute");
         unit_bwd(t, &B->spa, k->post_reduced_activated, b->norm_spatial, k->norm_post_spatial, db->norm_spatial, k->post_spatial,
                  dk->post_spatial_activated, NULL, 1, NULL, dk->post_spatial, s_spa, dk->post_reduced_activated, NULL, db->spatial, &fz,
-                 fz_request(c, &req, &B->spa, k->post_reduced, k->post_reduced_activated, k->norm_post_reduced->means));
+                 mi_layer_fz_request(&B->spa, &c->lw, &req, k->post_reduced, k->post_reduced_activated, k->norm_post_reduced->means));
         if (ring) dk->post_reduced = ring_take(c, &s_red);
         unit_bwd(t, &B->red, bin, b->norm_depth_reduction, k->norm_post_reduced, db->norm_depth_reduction, k->post_reduced,
                  dk->post_reduced_activated, NULL, 1, NULL, dk->post_reduced, s_red, dbin, red_addend, db->depth_reduction, &fz,
-                 kb ? fz_request(c, &req, &B->red, kb->post_expanded, kb->output_activated, kb->norm_post_expanded->means) : NULL);
+                 kb ? mi_layer_fz_request(&B->red, &c->lw, &req, kb->post_expanded, kb->output_activated, kb->norm_post_expanded->means) : NULL);
         mi_dp_reduce_ready(t, (size_t)(db->depth_reduction - c->g_arena), 0);
     }
     const int Hs = d->input / d->init_conv_stride;
@@ -1385,6 +1177,20 @@ int mi_trainer_check_errors(Train_ResNet *t) {
  * on the matrix cores, fp32 otherwise (fp32 mode; VALU stem; RESNET_MI_BF16_STEM_TENSORS=f32) */
 int mi_trainer_stem_dtype(Train_ResNet *t) { const MiCtx *c = ctx_of(t); return c->dtype == MID_BF16 && c->stem_bf16 ? MID_BF16 : MID_F32; }
 
+int mi_debug_trainer_routes(const Train_ResNet *t, int *out, int cap) {
+    const MiCtx *c = (const MiCtx *)t->backend_ctx;
+    int n = 0;
+    for (int i = -1; i < t->model->dims->n_conv_blocks; i++) {
+        const MiLayer *Ls[4] = {i < 0 ? &c->stem : &c->blk[i].red, i < 0 ? NULL : &c->blk[i].spa, i < 0 ? NULL : &c->blk[i].exp, i < 0 ? NULL : &c->blk[i].proj};
+        for (int j = 0; j < 4; j++) {
+            const MiLayer *L = Ls[j];
+            if (!L || !L->w) continue;
+            if (4 * n + 4 <= cap) { out[4 * n] = L->fwd; out[4 * n + 1] = L->dgrad; out[4 * n + 2] = L->wgrad; out[4 * n + 3] = L->fz; }
+            n++;
+        }
+    }
+    return n;
+}
 int mi_trainer_nan_location(const Train_ResNet *t) { return ((const MiCtx *)t->backend_ctx)->nan_location; }
 void mi_trainer_set_nan_exit(Train_ResNet *t, int on) {
     MiCtx *c = ctx_of(t);

@@ -39,6 +39,14 @@ class DeviceArray:
             pass
 
 
+def layer_routes(lib, dtype, policy, N, Cc, H, K, k, stride, site=0):
+    """mi_layer_routes (host only): the planner's (fwd, dgrad, wgrad, fz) for one convolution under the process's switches, or None
+    where it refuses (-2)"""
+    out = (C.c_int * 4)()
+    rc = lib.mi_layer_routes(dtype, policy, N, Cc, H, K, k, stride, site, out)
+    return tuple(out) if rc == 0 else None
+
+
 class Ops:
     def __init__(self):
         self.L = B.load()

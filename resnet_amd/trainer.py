@@ -226,6 +226,14 @@ class Trainer:
         """storage type of the stem convolution's own output and its gradient (MI_DTYPE_*)"""
         return self.L.mi_trainer_stem_dtype(self.t)
 
+    def routes(self):
+        """(fwd, dgrad, wgrad, fz) of every convolution of the trainer's table (mi_layer_routes' numbers): the stem, then per block the
+        reduction, the spatial convolution, the expansion and the projection where the block has one"""
+        n = self.L.mi_debug_trainer_routes(self.t, None, 0)
+        out = (C.c_int * (4 * n))()
+        assert self.L.mi_debug_trainer_routes(self.t, out, 4 * n) == n
+        return [tuple(out[4 * i:4 * i + 4]) for i in range(n)]
+
     def labels(self):
         return np.ctypeslib.as_array(self.c_batch.contents.correct_classes_cpu, shape=(self.batch,)).copy()
 

@@ -288,28 +288,29 @@ def conv_plan(L, dtype, route, op, N, Cn, H, K, k, s):
     return tuple(out) if rc == 0 else None
 
 
+def layer_routes(L, dtype, policy, N, Cn, H, K, k, s, site=0):
+    """mi_layer_routes: (fwd, dgrad, wgrad, fz) the library's planner -- the one its trainer and its operators run through -- gives a
+    convolution under this process's switches (MI_FWD_* / MI_DG_* / MI_WG_*, include/resnet_mi.h), or None where it refuses"""
+    import ctypes
+    out = (ctypes.c_int * 4)()
+    rc = L.mi_layer_routes(dtype, policy, N, Cn, H, K, k, s, site, out)
+    return tuple(out) if rc == 0 else None
+
+
+# the planner's bf16 routes in mi_conv_plan's route names, per op: MI_FWD_BF16 / MI_FWD_CL; MI_DG_BF16 / MI_DG_CL, MI_DG_CL2; MI_WG_BF16 /
+# MI_WG_CL / MI_WG_CL2
+BF16_ROUTE_NAMES = ({1: "default", 2: "cl"}, {1: "default", 2: "cl", 3: "cl"}, {1: "default", 2: "cl", 3: "cl2"})
+
+
 def bf16_route(L, op, N, Cn, H, K, k, s):
-    """the route plan_conv gives a bf16 layer with default switches (fwd MI_FWD_CL / dgrad MI_DG_CL, MI_DG_CL2 / wgrad MI_WG_CL2,
-    MI_WG_CL, else the NCHW kernels, whose 1x1 weight gradient takes the LDS-DMA kernel where it tiles)"""
-    # each branch restates one test of plan_conv (resnet_amd/csrc/trainer.c); mi_conv_plan answers the *_supported queries it makes
-    ok = lambda route, o: conv_plan(L, 1, route, o, N, Cn, H, K, k, s) is not None
-    # `L->k == 3 && s == 1 && o->cl_s1 && mid_cl_supported(0, ...)` and `s == 2 && o->cl_s2 && mid_cl_supported(0, ..., 2)`: L->cl, MI_FWD_CL
-    cl = k == 3 and ok("cl", "fwd")
-    # `o->cl_s1_dgrad && mid_cl_supported(1, ...)` (inside the L->cl branch) and `o->cl_dgrad2 && mid_cl_dgrad2_supported`: L->dye
-    dye = k == 3 and ((s == 1 and cl and ok("cl", "dgrad")) or (s == 2 and ok("cl", "dgrad")))
-    if op == "fwd":
-        return "cl" if cl else "default"
-    if op == "dgrad":
-        return "cl" if dye else "default"
-    # `wg = L->cl && mid_cl_wgrad_supported`, `wg2 = L->cl && mid_cl_wgrad2_supported`
-    wg, wg2 = cl and ok("cl", "wgrad"), cl and ok("cl2", "wgrad")
-    P = (H // s) ** 2
-    if dye and wg2 and (P % 64 != 0 or not wg):  # MI_WG_CL2
-        return "cl2"
-    if wg:  # MI_WG_CL
-        return "cl"
-    # MI_WG_BF16: mid_conv_wgrad_bf16 takes the LDS-DMA 1x1 kernel where mid_pw_wgrad_supported holds
-    return "pw" if k == 1 and ok("pw", "wgrad") else "default"
+    """the route the planner gives a bf16 layer (layer_routes).  The one choice it does not make: on MI_WG_BF16 a 1x1 weight gradient takes
+    the LDS-DMA kernel at launch where that tiles (mid_conv_wgrad_bf16), which mi_conv_plan's route "pw" answers"""
+    r = layer_routes(L, 1, 0, N, Cn, H, K, k, s)
+    assert r is not None, "the planner refuses the bf16 layer %s at N = %d" % ((Cn, H, K, k, s), N)
+    name = BF16_ROUTE_NAMES[OPS[op]][r[OPS[op]]]
+    if op == "wgrad" and name == "default" and k == 1 and conv_plan(L, 1, "pw", "wgrad", N, Cn, H, K, k, s) is not None:
+        return "pw"
+    return name
 
 
 def blocks(dims):
@@ -329,7 +330,7 @@ def blocks(dims):
 
 def trainer_units(dims):
     """(block, role, (C, H, K, k, stride), site) of every bottleneck convolution in plan_layers order (per block: reduction, spatial,
-    expansion, projection); site = its bit in plan_conv's BN'-fusion masks: 4 the reduction of block i > 0 whose block below (i - 1) has no
+    expansion, projection); site = its bit in the planner's BN'-fusion masks (mi_layer_plan): 4 the reduction of block i > 0 whose block below (i - 1) has no
     projection (its dgrad feeds that block's expansion BN'), 2 every spatial layer, 1 every expansion, 0 the projections"""
     bl = blocks(dims)
     out = []
@@ -376,7 +377,7 @@ def trainer_sites(dims):
 
 def trainer_conv_cases(L, dims, N):
     """(dtype, route, op, C, H, K, k, stride, where): every (layer, route) pair the trainer of this net at batch N gives in both storage
-    types (bf16: plan_conv's routes with default switches, bf16_route), and the 1x1 forward on a channel-last input
+    types (bf16: the planner's routes, bf16_route), and the 1x1 forward on a channel-last input
     (mi_op_conv1x1_fwd_bf16_cl) at every 1x1 layer"""
     cases = []
     for (Cn, H, K, k, s, where) in trainer_layers(dims):
@@ -412,7 +413,7 @@ def trainer_conv_bn_cl_cases(L, dims, N):
 
 
 def trainer_dgrad_bn_cases(L, dims, N):
-    """(dtype, C, H, K, k, stride, where) of the dgrads that also do the BN' reduction (plan_conv's L->fz, trainer.c) at batch N: fp32 the
+    """(dtype, C, H, K, k, stride, where) of the dgrads that also do the BN' reduction (the planner's fz, mi_layer_plan in layer.c) at batch N: fp32 the
     site-4 layers only (RESNET_MI_F32_BNFUSE_BWD = 4); bf16 every site (trainer_units) whose dgrad is on the NCHW kernels (bf16_route)"""
     sites = trainer_sites(dims)
     out = []

@@ -401,7 +401,7 @@ def trainer_bn_sites(L, dims=None, N=None):
             out.add((pr, f, Hs, "bwd", 1))
 
         def fuses(site, Cn, H, K, k, s):
-            """plan_conv's L->fz and whether the launch fuses: fp32 site 4 only (RESNET_MI_F32_BNFUSE_BWD = 4) where the dgrad runs on the
+            """the planner's fz (mi_layer_plan) and whether the launch fuses: fp32 site 4 only (RESNET_MI_F32_BNFUSE_BWD = 4) where the dgrad runs on the
             implicit GEMM; bf16 every site whose dgrad runs on the NCHW kernels, which fuse where the plane is a multiple of 4"""
             if not bf:  # (mi_op_conv_dgrad_bn_bwd_f32 fuses where the dgrad runs on the implicit GEMM)
                 return site == 4 and R.conv_plan(L, 0, "default", "dgrad", N, Cn, H, K, k, s) is not None

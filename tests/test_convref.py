@@ -351,7 +351,7 @@ def test_batch33_cases_reach_every_plan_kind_and_partial_tiles():
 
 def test_trajectory_nets_hold_their_trainers_routes():
     """C1S and C4I at N = 4, ResNet-50 at N = 8 (test_gpu_trajectory.py's nets and batches): every convolution of plan_layers is in the
-    list in fp32 and on the bf16 route plan_conv gives it, every route the list names plans the shape, and the 3x3 layers run channel-last
+    list in fp32 and on the bf16 route the planner gives it, every route the list names plans the shape, and the 3x3 layers run channel-last
     on the 8 x 8 and 4 x 4 planes"""
     L = _lib()
     for net, N in (("c1s", 4), ("c4i", 4), ("r50", 8)):
@@ -371,6 +371,31 @@ def test_trajectory_nets_hold_their_trainers_routes():
         if net != "r50":
             assert {layer[1] // layer[4] for layer in cl} == {8, 4}, (net, cl)
         _kinds(L, cases, N)   # (a bf16 route the trainer takes plans the shape)
+
+
+def test_layer_routes_answers_without_a_device():
+    """mi_layer_routes (the planner the trainer and the operators run through; host only): an unknown dtype, policy or site is refused with
+    -2 and an all-zero answer; every fp32 layer of ResNet-50 answers (MI_FWD_F32, MI_DG_F32, MI_WG_F32); the fp32 fz follows the site mask of
+    RESNET_MI_F32_BNFUSE_BWD (default 4: the reductions above an identity block) and is 0 under the FULL policy; the stems take the matrix
+    cores in both storage types"""
+    import ctypes
+    import os
+    import synth
+    from resnet_amd import binding as B
+    L = _lib()
+    out = (ctypes.c_int * 4)(9, 9, 9, 9)
+    for bad in ((2, 0, 0), (-1, 0, 0), (0, 3, 0), (0, -1, 0), (0, 0, 3), (0, 0, 8)):
+        assert L.mi_layer_routes(bad[0], bad[1], 8, 64, 56, 64, 1, 1, bad[2], out) == -2 and list(out) == [0, 0, 0, 0], bad
+    assert R.layer_routes(L, 1, 0, 8, 48, 8, 80, 3, 1) is None      # no bf16 kernel tiles 48 -> 80 channels
+    mask = int(os.environ.get("RESNET_MI_F32_BNFUSE_BWD", "4"))
+    units = R.trainer_units(synth.R50_DIMS)
+    assert {u[3] for u in units} == {0, 1, 2, 4}
+    for _, role, shape, site in units:
+        for policy in (B.MI_STORE_FAST, B.MI_STORE_RECOMPUTE_BN, B.MI_STORE_FULL):
+            want_fz = int(bool(site & mask)) if policy != B.MI_STORE_FULL else 0
+            assert R.layer_routes(L, 0, policy, R.N256, *shape, site=site) == (B.MI_FWD_F32, B.MI_DG_F32, B.MI_WG_F32, want_fz), (role, shape, site, policy)
+    assert R.layer_routes(L, 0, 0, R.N256, *R.STEM) == (B.MI_FWD_STEM_F32, B.MI_DG_F32, B.MI_WG_STEM_F32, 0)
+    assert R.layer_routes(L, 1, 0, R.N256, *R.STEM) == (B.MI_FWD_STEM_BF16, B.MI_DG_F32, B.MI_WG_STEM_BF16, 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

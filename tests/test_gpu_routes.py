@@ -157,6 +157,33 @@ def test_route_table_names_every_switch():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("net", ["c4i", "c1s"])
+def test_trainer_table_is_the_planners_answer(net):
+    """a live trainer's table (mi_debug_trainer_routes) holds, convolution by convolution, what mi_layer_routes answers for the stem and for
+    convref.trainer_units(dims) with the trainer's storage type, store policy and batch: fp32 under every policy, bf16 under FAST and
+    RECOMPUTE_BN (batch 4, 32 x 32 input)"""
+    import convref as R
+    from resnet_amd import Trainer
+    from resnet_amd import binding as B
+    dims, N = R.nets()[net], 4
+    tr = Trainer(dims, N)
+    try:
+        assert tr.L.mi_device_count() >= 1, "no HIP device"
+        shapes = [(R.stem_shape(dims), 0)] + [(u[2], u[3]) for u in R.trainer_units(dims)]
+        for dtype, policies in ((B.MI_DTYPE_F32, (B.MI_STORE_FAST, B.MI_STORE_RECOMPUTE_BN, B.MI_STORE_FULL)),
+                                (B.MI_DTYPE_BF16, (B.MI_STORE_FAST, B.MI_STORE_RECOMPUTE_BN))):
+            tr.set_store_policy(B.MI_STORE_FAST)
+            tr.set_dtype(dtype)
+            for policy in policies:
+                tr.set_store_policy(policy)
+                want = [R.layer_routes(tr.L, dtype, policy, N, *shape, site=site) for shape, site in shapes]
+                assert None not in want
+                assert tr.routes() == want, (net, dtype, policy)
+    finally:
+        tr.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("key", [e["key"] for e in OP_ENTRIES])
 def test_operators_under_switch(key, default_ops, tmp_path):
     e = routes.by_key(key)
