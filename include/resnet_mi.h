@@ -317,8 +317,24 @@ int mi_op_adam(float *p, const float *g, float *m, float *v, size_t n, float lr,
                float cur_b1, float cur_b2, float eps, int *nan_flag_dev);
 int mi_op_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C);
 /* device-side seeded fill (splitmix64 counter stream, uniform [lo,hi)) -- synthetic operands for micro-benchmarks */
-/* test aid: leaves NaNs in the LDS of every CU (catches kernels that read LDS they did not write) */
+/* test aids against kernels that read LDS they did not write (LDS is not cleared between dispatches; tests/test_gpu_lds.py).
+ * mi_debug_lds_fill: device synchronise, then a kernel on a private stream whose workgroups each own the largest dynamic LDS a workgroup may
+ * have (the device attribute: all of a CU's LDS, so a workgroup sits alone on its CU), 8 workgroups per CU, each writing `word` to all of
+ * it; device synchronise.  mi_debug_poison_lds is mi_debug_lds_fill(0xFFFFFFFF): NaN as fp32 and as both bf16 halves, 255 as a byte.
+ * mi_debug_lds_probe: the same geometry reading only: out[0] workgroups run, [1] distinct CUs they ran on (hardware id registers), [2] words
+ * examined, [3] words != word.  mi_debug_lds_geometry: out[0] the LDS bytes each of those workgroups owns, [1] the device's CU count
+ * (multiProcessorCount), [2] workgroups per launch.
+ * mi_debug_lds_fill_mode(on, word): while on, EVERY kernel launch of the library (any thread, any stream) is followed by device synchronise,
+ * fill, device synchronise, so each kernel of an operator or a training step finds `word` in all LDS it does not write itself; switching
+ * on fills once and restarts the counter mi_debug_lds_fills (fills since then).  The mode serialises launches and changes no value.
+ * RESNET_MI_LDS_FILL=<hex word>, read once per process, switches it on from the first launch.  Out of its reach: words a kernel reads and
+ * discards, and races inside a workgroup (those read the kernel's own earlier data, not the fill). */
+int mi_debug_lds_fill(uint32_t word);
 int mi_debug_poison_lds(void);
+int mi_debug_lds_probe(uint32_t word, size_t out[4]);
+int mi_debug_lds_geometry(size_t out[3]);
+int mi_debug_lds_fill_mode(int on, uint32_t word);
+size_t mi_debug_lds_fills(void);
 /* test aid: red-zone mode of the device allocator behind every allocation of the library (operator tensors and workspaces, trainer, loader,
  * optimizer).  zone_bytes 0 = off (the default); else a multiple of 4096 (-1 otherwise): an allocation of b bytes becomes zone | b | zone, the
  * whole of it filled with fill_byte (0xFF: NaN as fp32 and bf16, -1 as int; 0x00: the control) before the pointer is returned.  Both zones

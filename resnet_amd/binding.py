@@ -180,6 +180,11 @@ PROTOTYPES = {
     "mi_op_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "mi_op_fill_uniform": (_i, [_vp, _sz, _u64, _f, _f]),
     "mi_debug_poison_lds": (_i, []),
+    "mi_debug_lds_fill": (_i, [C.c_uint32]),
+    "mi_debug_lds_probe": (_i, [C.c_uint32, C.POINTER(_sz)]),
+    "mi_debug_lds_geometry": (_i, [C.POINTER(_sz)]),
+    "mi_debug_lds_fill_mode": (_i, [_i, C.c_uint32]),
+    "mi_debug_lds_fills": (_sz, []),
     "mi_debug_redzone": (_i, [_sz, _i]),
     "mi_debug_redzone_check": (_i, []),
     "mi_debug_redzone_stats": (None, [C.POINTER(_sz)] * 3),

@@ -297,18 +297,109 @@ __global__ void fill_labels_kernel(int *__restrict__ out, size_t n, uint64_t see
         out[i] = (int)(splitmix64_at(seed, offset + i) % (uint64_t)n_classes);
 }
 
-// ---- test aid: leave NaNs in every CU's LDS so kernels that read LDS they never wrote are caught ----
-__global__ void __launch_bounds__(1024) lds_poison_kernel(float *sink) {
-    extern __shared__ float p[];
-    for (int i = threadIdx.x; i < 16000; i += blockDim.x) p[i] = __int_as_float(0x7fc00000);
-    __syncthreads();
-    if (sink && threadIdx.x == 0 && p[blockIdx.x & 1023] == 0.f) sink[0] = 1.f;
+// ---- test aid: one word in every LDS byte of every CU, so that a kernel which reads LDS it never wrote reads that word ----
+// LDS is not cleared between dispatches.  Each workgroup owns the largest dynamic LDS a workgroup may have (all of a CU's), so it sits alone
+// on its CU and the first wave of workgroups lands one per CU; the fill kernel writes `word` to all of it, the probe kernel only reads it.
+#define MID_LDS_CU_SLOTS 1024 /* __smid() on gfx950: XCC 4 bits | shader engine 2 bits | CU 4 bits */
+__global__ void __launch_bounds__(1024) lds_fill_kernel(uint32_t word, uint32_t n_words) {
+    extern __shared__ uint32_t lds_words[];
+    for (uint32_t i = threadIdx.x; i < n_words; i += blockDim.x) lds_words[i] = word;
+}
+// counts[0] workgroups run, [1] words examined, [2] words != word; cu_seen[id] = 1 for the CU (XCC, shader engine, CU) each workgroup ran on
+__global__ void __launch_bounds__(1024) lds_probe_kernel(uint32_t word, uint32_t n_words, unsigned long long *__restrict__ counts, uint32_t *__restrict__ cu_seen) {
+    extern __shared__ uint32_t lds_words[];
+    uint32_t seen = 0, bad = 0;
+    for (uint32_t i = threadIdx.x; i < n_words; i += blockDim.x) { seen++; bad += lds_words[i] != word ? 1u : 0u; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { seen += __shfl_xor(seen, o, 64); bad += __shfl_xor(bad, o, 64); } /* registers only: the LDS stays as found */
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&counts[1], (unsigned long long)seen);
+        if (bad) atomicAdd(&counts[2], (unsigned long long)bad);
+    }
+    if (threadIdx.x == 0) {
+        atomicAdd(&counts[0], 1ull);
+        cu_seen[__smid() & (MID_LDS_CU_SLOTS - 1)] = 1u;
+    }
+}
+// bytes of dynamic LDS per workgroup (the device's limit, raised once per kernel) and the grid: 8 workgroups per CU
+static int lds_geometry(const void *kernel, int *raised, size_t *bytes, int *grid) {
+    int dev = 0, lds = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || lds < 4 || cus < 1) {
+        mi_record_error("mi_debug_lds_fill", "cannot read the device's LDS size and CU count");
+        return -1;
+    }
+    if (*raised != lds) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+            (void)hipGetLastError();
+            mi_record_error("mi_debug_lds_fill", "cannot raise the dynamic LDS limit");
+            return -1;
+        }
+        *raised = lds;
+    }
+    *bytes = (size_t)lds & ~(size_t)3;
+    *grid = 8 * cus;
+    return 0;
+}
+static int g_lds_fill_raised = 0, g_lds_probe_raised = 0;
+static hipStream_t lds_stream(void) { /* private: ordered after nothing but the device synchronise in front of it */
+    static hipStream_t st = nullptr;
+    if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); st = nullptr; }
+    return st;
 }
 
 extern "C" {
-int mid_lds_poison(mid_stream s) {
-    hipLaunchKernelGGL(lds_poison_kernel, dim3(2048), dim3(1024), 64000, (hipStream_t)s, (float *)nullptr);
-    MI_LAUNCH_CHECK("lds_poison_kernel");
+/* device synchronise, `word` into all LDS of every CU, device synchronise.  Not through MI_LAUNCH_CHECK: the fill-after-every-launch mode
+ * (runtime.hip) calls this from there.  The callers serialise (one geometry, one stream) */
+int mid_lds_fill(uint32_t word) {
+    size_t bytes = 0;
+    int grid = 0;
+    if (lds_geometry((const void *)lds_fill_kernel, &g_lds_fill_raised, &bytes, &grid)) return -1;
+    hipStream_t st = lds_stream();
+    if (!st) { mi_record_error("mi_debug_lds_fill", "cannot create a stream"); return -1; }
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(lds_fill_kernel, dim3(grid), dim3(1024), bytes, st, word, (uint32_t)(bytes / 4));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { mi_record_error("lds_fill_kernel", hipGetErrorString(e)); return -1; }
+    return 0;
+}
+/* out[0] LDS bytes each workgroup of the two kernels owns, [1] the device's CU count, [2] workgroups per launch */
+int mid_lds_geometry(size_t out[3]) {
+    size_t bytes = 0;
+    int grid = 0;
+    out[0] = out[1] = out[2] = 0;
+    if (lds_geometry((const void *)lds_fill_kernel, &g_lds_fill_raised, &bytes, &grid)) return -1;
+    out[0] = bytes; out[1] = (size_t)grid / 8; out[2] = (size_t)grid;
+    return 0;
+}
+/* the same geometry, reading only: out[0] workgroups run, [1] distinct CUs seen, [2] words examined, [3] words != word */
+int mid_lds_probe(uint32_t word, size_t out[4]) {
+    size_t bytes = 0;
+    int grid = 0;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (lds_geometry((const void *)lds_probe_kernel, &g_lds_probe_raised, &bytes, &grid)) return -1;
+    hipStream_t st = lds_stream();
+    if (!st) { mi_record_error("mi_debug_lds_probe", "cannot create a stream"); return -1; }
+    const size_t res_bytes = 3 * sizeof(unsigned long long) + MID_LDS_CU_SLOTS * sizeof(uint32_t);
+    unsigned long long *res = nullptr;
+    if (hipMalloc((void **)&res, res_bytes) != hipSuccess) { (void)hipGetLastError(); mi_record_error("mi_debug_lds_probe", "hipMalloc failed"); return -1; }
+    struct { unsigned long long counts[3]; uint32_t cu[MID_LDS_CU_SLOTS]; } h;
+    static_assert(sizeof h == 3 * sizeof(unsigned long long) + MID_LDS_CU_SLOTS * sizeof(uint32_t), "packed");
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemsetAsync(res, 0, res_bytes, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(lds_probe_kernel, dim3(grid), dim3(1024), bytes, st, word, (uint32_t)(bytes / 4), res, (uint32_t *)(res + 3));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, res, res_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(res);
+    if (e != hipSuccess) { mi_record_error("lds_probe_kernel", hipGetErrorString(e)); return -1; }
+    out[0] = (size_t)h.counts[0]; out[2] = (size_t)h.counts[1]; out[3] = (size_t)h.counts[2];
+    for (int i = 0; i < MID_LDS_CU_SLOTS; i++) out[1] += h.cu[i] ? 1 : 0;
     return 0;
 }
 int mid_maxpool_fwd_t(mid_stream s, const void *x, void *y, int dt, int *max_inds, int N, int C, int H, int k, int stride) {

@@ -295,7 +295,17 @@ int mid_decode_u8(mid_stream s, const uint8_t *src, const int *plan, float *out,
 int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *out, int n, int dim_in, int dim_out);
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */
 int mid_fill_uniform(mid_stream s, float *out, size_t n, uint64_t seed, uint64_t offset, float lo, float hi);
-int mid_lds_poison(mid_stream s); /* test aid: fills LDS of every CU with NaNs */
+/* test aids (kernels_misc.hip; callers serialise): `word` into every LDS word of every CU between two device synchronises, and a read-only
+ * pass of the same geometry: out[0] workgroups run, [1] distinct CUs seen, [2] words examined, [3] words != word */
+int mid_lds_fill(uint32_t word);
+int mid_lds_probe(uint32_t word, size_t out[4]);
+int mid_lds_geometry(size_t out[3]); /* [0] LDS bytes per workgroup of the two, [1] CUs of the device, [2] workgroups per launch */
+/* the same two under the lock of the fill-after-every-launch mode (runtime.hip), the mode's switch and its counter */
+int mid_debug_lds_fill(uint32_t word);
+int mid_debug_lds_probe(uint32_t word, size_t out[4]);
+int mid_debug_lds_geometry(size_t out[3]);
+int mid_debug_lds_fill_mode(int on, uint32_t word);
+size_t mid_debug_lds_fills(void);
 int mid_fill_labels(mid_stream s, int *out, size_t n, uint64_t seed, uint64_t offset, int n_classes);
 
 /* ---- RCCL (resolved with dlopen at first use) ---- */

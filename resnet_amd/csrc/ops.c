@@ -155,7 +155,12 @@ int mi_op_resample_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_n
     return finish(mid_resample_u8(mi_global()->compute, src_dev, boxes_dev, out_nchw, n, dim_in, dim_out));
 }
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
-int mi_debug_poison_lds(void) { return finish(mid_lds_poison(mi_global()->compute)); }
+int mi_debug_lds_fill(uint32_t word) { return finish(mid_debug_lds_fill(word)); }
+int mi_debug_poison_lds(void) { return mi_debug_lds_fill(0xFFFFFFFFu); }
+int mi_debug_lds_probe(uint32_t word, size_t out[4]) { return finish(mid_debug_lds_probe(word, out)); }
+int mi_debug_lds_geometry(size_t out[3]) { return finish(mid_debug_lds_geometry(out)); }
+int mi_debug_lds_fill_mode(int on, uint32_t word) { return finish(mid_debug_lds_fill_mode(on, word)); }
+size_t mi_debug_lds_fills(void) { return mid_debug_lds_fills(); }
 int mi_debug_redzone(size_t zone_bytes, int fill_byte) { return mid_redzone(zone_bytes, fill_byte); }
 int mi_debug_redzone_check(void) { return mid_redzone_check(); }
 void mi_debug_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live) { mid_redzone_stats(allocs_checked, zone_bytes_checked, live); }

@@ -44,15 +44,70 @@ static int mi_trace_enabled(void) {
     }
     return g_trace_on;
 }
-void mi_trace_launch(const char *name) {
-    if (!mi_trace_enabled()) return;
-    g_trace[g_trace_n++ % MI_TRACE_N] = name;
-    /* others (Python's faulthandler, test runners) install SIGABRT handlers of their own later on: stay in front of them */
-    struct sigaction cur;
-    if (sigaction(SIGABRT, NULL, &cur) == 0 && cur.sa_handler != mi_trace_dump) {
-        g_trace_prev = (cur.sa_flags & SA_SIGINFO) ? SIG_DFL : cur.sa_handler;
-        signal(SIGABRT, mi_trace_dump);
+// ---- LDS fill after every launch (test aid, off unless mi_debug_lds_fill_mode or RESNET_MI_LDS_FILL=<hex word>) ----
+// LDS is not cleared between dispatches: a kernel that reads an LDS word it never wrote reads what its predecessor on that CU left there.
+// While the mode is on, every kernel launch of the library is followed by device synchronise, one word into every LDS word of every CU
+// (mid_lds_fill), device synchronise -- so every kernel, not only the first of an operator or a step, finds that word in all LDS it does not
+// write itself.  The fill's workgroups own LDS of their own, so the mode only serialises the launches; it changes no value.
+static std::mutex g_lds_mu;                      /* the loader's prefetch thread launches too */
+static std::atomic<int> g_lds_on{-1};            /* -1: the environment has not been read yet */
+static uint32_t g_lds_word = 0;
+static std::atomic<size_t> g_lds_fills{0};
+static int lds_mode_on(void) {
+    int on = g_lds_on.load(std::memory_order_acquire);
+    if (on >= 0) return on;
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    if (g_lds_on < 0) {
+        const char *e = getenv("RESNET_MI_LDS_FILL");
+        if (e && *e) g_lds_word = (uint32_t)strtoul(e, NULL, 16);
+        g_lds_on = e && *e ? 1 : 0;
     }
+    return g_lds_on;
+}
+static void lds_fill_after_launch(void) {
+    if (hipPeekAtLastError() != hipSuccess) return; /* the launch failed: its error stays for MI_LAUNCH_CHECK */
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    if (g_lds_on != 1) return;                      /* switched off meanwhile */
+    if (mid_lds_fill(g_lds_word) == 0) g_lds_fills++; /* launches its kernel without MI_LAUNCH_CHECK: no way back into here */
+}
+void mi_trace_launch(const char *name) {
+    if (mi_trace_enabled()) {
+        g_trace[g_trace_n++ % MI_TRACE_N] = name;
+        /* others (Python's faulthandler, test runners) install SIGABRT handlers of their own later on: stay in front of them */
+        struct sigaction cur;
+        if (sigaction(SIGABRT, NULL, &cur) == 0 && cur.sa_handler != mi_trace_dump) {
+            g_trace_prev = (cur.sa_flags & SA_SIGINFO) ? SIG_DFL : cur.sa_handler;
+            signal(SIGABRT, mi_trace_dump);
+        }
+    }
+    if (lds_mode_on()) lds_fill_after_launch(); /* after the ring has the name: a fault the synchronise meets is dumped with it */
+}
+extern "C" {
+int mid_debug_lds_fill(uint32_t word) {
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    return mid_lds_fill(word);
+}
+int mid_debug_lds_probe(uint32_t word, size_t out[4]) {
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    return mid_lds_probe(word, out);
+}
+int mid_debug_lds_geometry(size_t out[3]) {
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    return mid_lds_geometry(out);
+}
+/* on: fills LDS once at once, so that the first launch under the mode finds the word too; the counter starts at zero */
+int mid_debug_lds_fill_mode(int on, uint32_t word) {
+    lds_mode_on(); /* the environment is read before the first explicit setting, never after it */
+    std::lock_guard<std::mutex> lk(g_lds_mu);
+    g_lds_on = 0;
+    if (!on) return 0;
+    if (mid_lds_fill(word)) return -1;
+    g_lds_word = word;
+    g_lds_fills = 0;
+    g_lds_on = 1;
+    return 0;
+}
+size_t mid_debug_lds_fills(void) { return g_lds_fills; }
 }
 /* variant names: each distinct one is stored once and never moves (the ring and the abort dump keep pointers) */
 #define MI_NAME_MAX 512

@@ -157,6 +157,7 @@ BF16_TRAINER_SWITCHES = ["RESNET_MI_BF16_CL_S2=0", "RESNET_MI_BF16_CL_S1=0", "RE
 # switches that select no kernel, or that another test pins
 EXEMPT = {
     "RESNET_MI_TRACE": "diagnostic: records launch names (the ring these tests read), selects nothing",
+    "RESNET_MI_LDS_FILL": "test aid: a word into all LDS after every launch (tests/test_gpu_lds.py runs the table's operator cases under it); selects nothing",
     "RESNET_MI_LIB": "which build of the library binding.py loads (tools/variant.sh), not a route inside it",
     "RESNET_MI_BNFUSE": "pinned by test_gpu_net.py::test_fused_bn_statistics_match_separate_pass (a child process per value)",
     "RESNET_MI_BF16_BNFUSE_BWD": "pinned by test_gpu_bf16.py::test_resnet50_bf16_every_block_and_both_bn_backward_routes (a trainer per value)",
