@@ -13,6 +13,9 @@
  *   ./ResNetMI --shards-u8 /data/train_data_shards/u8 --augment rrc --rrc-scale 0.08,1 --rrc-ratio 0.75,1.3333333333333333 --batch 256
  *              random-resized crop: a box of LO .. HI of the image's area and of aspect ratio LO .. HI (the defaults shown), resampled
  *              to the input size on the device
+ *   ./ResNetMI --label-smoothing 0.1 --topk 5 --device-loss
+ *              the loss head on the device (mi_trainer_set_loss): label-smoothed cross entropy, loss and top-1 / top-K error counted
+ *              there, one line of totals per epoch; --device-loss also drops forward_pass's blocking copy of the predictions
  *   ./ResNetMI --labels-file id_to_label_mapping.txt --synsets-file id_to_synset_mapping.txt --counts-file id_to_img_count_mapping.txt
  *              the class metadata of resnet.cu:3236-3242: iterations per epoch = ceil(sum of the class counts / batch) (:3309)
  *              unless --iters says otherwise
@@ -50,6 +53,11 @@ int main(int argc, char **argv) {
     if (opt(argc, argv, "--rrc-ratio", NULL) && sscanf(opt(argc, argv, "--rrc-ratio", ""), "%lf,%lf", &rrc_ratio[0], &rrc_ratio[1]) != 2) { fprintf(stderr, "--rrc-ratio LO,HI\n"); return 1; }
     int flip = 1;
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--no-flip")) flip = 0;
+    const char *smoothing_arg = opt(argc, argv, "--label-smoothing", NULL), *topk_arg = opt(argc, argv, "--topk", NULL);
+    int device_loss = 0;
+    for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--device-loss")) device_loss = 1;
+    const int loss_on_device = smoothing_arg || topk_arg || device_loss;
+    const int TOPK = atoi(topk_arg ? topk_arg : "5");
     const char *dump_root = opt(argc, argv, "--dump-root", NULL);
     const char *loss_log = opt(argc, argv, "--loss-log", "avg_loss_log.txt");
     const int resume_id = atoi(opt(argc, argv, "--resume", "-1"));           /* LOAD_FROM_DUMP_ID, resnet.cu:3299 */
@@ -84,6 +92,8 @@ int main(int argc, char **argv) {
     if (shards || shards_u8) mi_batch_set_prefetch(batch, 1);
     Train_ResNet *trainer = init_trainer(model, batch, BATCH_SIZE, LEARNING_RATE, WEIGHT_DECAY, 0.9f, 0.999f, EPS, N_EPOCHS, "my_custom");
     if (dump_root) mi_trainer_set_dump_root(trainer, dump_root); else mi_trainer_set_dump_every(trainer, 0);
+    if (loss_on_device && mi_trainer_set_loss(trainer, (float)atof(smoothing_arg ? smoothing_arg : "0"), TOPK,
+                                              MI_LOSS_DEVICE | (device_loss ? MI_LOSS_NO_PRED_COPY : 0))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (resume_id != -1) { overwrite_trainer_hyperparams(trainer, resume_id, "my_custom"); overwrite_model_params(trainer, resume_id, "my_custom"); }
 
     FILE *loss_file = fopen(loss_log, "w");
@@ -102,8 +112,13 @@ int main(int argc, char **argv) {
             const float *pred = trainer->forward_buffer->pred_cpu;
             const int *correct = trainer->cur_batch->correct_classes_cpu;
             float batch_loss = 0, batch_n_wrong = 0;
-            for (int s = 0; s < BATCH_SIZE; s++) batch_loss += -1 * logf(pred[s * N_CLASSES + correct[s]]);
-            for (int s = 0; s < BATCH_SIZE; s++) {
+            if (loss_on_device) { /* the record the loss head left (with --device-loss pred_cpu is not even written) */
+                MiLossMetrics last;
+                mi_trainer_metrics(trainer, &last, NULL, 0);
+                batch_loss = (float)last.loss_sum; batch_n_wrong = (float)last.wrong_top1;
+            }
+            for (int s = 0; s < BATCH_SIZE && !loss_on_device; s++) batch_loss += -1 * logf(pred[s * N_CLASSES + correct[s]]);
+            for (int s = 0; s < BATCH_SIZE && !loss_on_device; s++) {
                 const float v = pred[s * N_CLASSES + correct[s]];
                 for (int c = 0; c < N_CLASSES; c++)
                     if (c != correct[s] && pred[s * N_CLASSES + c] >= v) { batch_n_wrong++; break; }
@@ -117,6 +132,14 @@ int main(int argc, char **argv) {
             if (mi_last_error()[0]) { fprintf(stderr, "device error: %s\n", mi_last_error()); return 2; }
         }
         if (stop) break;
+        if (loss_on_device) {
+            MiLossMetrics total;
+            mi_trainer_metrics(trainer, NULL, &total, 1);
+            if (total.rows > 0)
+                printf("Epoch: %d ----- Images: %lld, Avg. Loss: %.4f, Top-1 error: %.2f%%, Top-%d error: %.2f%%\n", epoch, (long long)total.rows,
+                       total.loss_sum / (double)total.rows, 100.0 * (double)total.wrong_top1 / (double)total.rows, TOPK,
+                       100.0 * (double)total.wrong_topk / (double)total.rows);
+        }
         /* resnet.cu:3410-3421: per-epoch loss (a SUM over the epoch) and accuracy, rewind the data source */
         mi_trainer_end_epoch(trainer, epoch_loss, epoch_n_wrong, total_images_per_epoch);
         cur_iter_in_epoch = 0;

@@ -435,6 +435,44 @@ int mi_debug_bn_merge(int R, int C, float *means, float *vars, float *dgamma, fl
 enum { MI_OPT_ADAM = 0, MI_OPT_SGD = 1, MI_OPT_LARS = 2 };
 int mi_trainer_set_optimizer(Train_ResNet *t, int kind, float momentum, float trust_coef);
 int mi_trainer_get_optimizer(const Train_ResNet *t);
+
+/* ---------------- the loss head on the device: label smoothing, loss and top-k totals without the host ----------------
+ * The reference's head is soft-max, a blocking copy of pred to the host, -logf(p_c) and a top-1 count there (mi_host_loss), and
+ * pred - onehot in backwards_pass.  loss_head_kernel (kernels_loss.hip) does all of it in one launch, one wave per row r of logits
+ * x[0..L) with label c, smoothing eps and u = eps / (float)L:
+ *   pred      p_j = expf(x_j - mx) / s, mx = max_j x_j, s = sum_j expf(x_j - mx): the operations and the reduction order of mi_op_softmax,
+ *             the same bits
+ *   dlogits   p_j - t_j with t_c = (1.f - eps) + u and t_j = u otherwise: label-smoothed cross entropy, a batch SUM (no 1/N,
+ *             resnet.cu:1806-1811); eps = 0: the bits of mi_op_ce_deriv
+ *   row_loss  logf(s) - (1.f - eps) z_c - u sum_j z_j with z = x - mx: the shifted log-sum-exp form, finite where -logf(p_c) overflows
+ *             (p_c = 0 once x_c is ~104 below the maximum) -- the one difference from mi_host_loss
+ *   row_rank  #{ j != c : p_j >= p_c } on the p values as written: ties count against the label, the rule of mi_host_loss
+ *             (resnet.cu:3363-3383).  Top-1 is wrong <=> rank >= 1, top-k is wrong <=> rank >= k.  A NaN p_c compares false with
+ *             everything and gives rank 0, as the host rule does: that identity is kept.
+ * A label outside [0, L): no t_c term (dlogits = p - u, what mi_op_ce_deriv does), row_rank = L, row_loss = NaN, nothing outside the
+ * row is read.  A second one-wave launch sums row_loss in double, rows lane-strided then six exchange steps -- a fixed order, no
+ * floating-point atomics, the same bits for the same input -- and counts rank >= 1 and rank >= topk into two records in device memory:
+ * last (overwritten) and total (added to). */
+typedef struct { double loss_sum; int64_t rows, wrong_top1, wrong_topk, batches; } MiLossMetrics;
+/* device pointers; pred, dlogits [N][L], row_loss, row_rank [N], last_dev, total_dev: each may be NULL and is then neither computed nor
+ * stored.  Returns 0, or -1 with mi_last_error set: smoothing outside [0, 1), topk outside [1, L], N or L < 1. */
+int mi_op_loss_head(const float *logits, const int *labels, float *pred, float *dlogits, float *row_loss, int *row_rank, int N, int L,
+                    float smoothing, int topk, MiLossMetrics *last_dev, MiLossMetrics *total_dev);
+/* The trainer's head.  flags MI_LOSS_HOST (default, with smoothing 0 and topk 1): the reference's path above, launch for launch.
+ * MI_LOSS_DEVICE: forward_pass runs the loss head in place of the soft-max -- pred (softmax.buffer of a dump is unchanged),
+ * output_layer_deriv and the totals -- and backwards_pass launches no cross-entropy derivative; pred is still copied to pred_cpu and
+ * forward_pass still blocks, so mi_host_loss works as before.  MI_LOSS_DEVICE | MI_LOSS_NO_PRED_COPY: no copy and no stream
+ * synchronise in forward_pass (the NaN / Inf flag of the last update is waited for by its own event), pred_cpu is not written, and
+ * mi_host_loss synchronises and returns (float)last.loss_sum and last.wrong_top1, so a reference-style main loop runs unchanged.
+ * Both storage types (the logits are fp32 in the bf16 mode too).  May be called between steps, not between forward_pass and
+ * backwards_pass.  Returns 0, or -1 with mi_last_error set: smoothing outside [0, 1) or > 0 without MI_LOSS_DEVICE, topk outside
+ * [1, output], NO_PRED_COPY without DEVICE, unknown flag bits.  Like the optimizer the setting is not dumped: a resumed run sets it again.
+ * mi_trainer_metrics waits for the compute stream and copies the records of the last forward_pass and the running totals since the
+ * last reset (either pointer may be NULL; reset_total != 0 zeroes the total afterwards); both all zero under MI_LOSS_HOST.  Data
+ * parallel: the records are this rank's; summing them over the ranks is the caller's. */
+enum { MI_LOSS_HOST = 0, MI_LOSS_DEVICE = 1, MI_LOSS_NO_PRED_COPY = 2 };
+int mi_trainer_set_loss(Train_ResNet *t, float smoothing, int topk, int flags);
+int mi_trainer_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total);
 /* the SGD / LARS kernels on their own: p, g, b device arrays of n floats; tensor i starts at offsets_host[i] (n_tensors + 1 entries,
  * multiples of 4, the last <= n) and runs to the next offset; tensor_is_weight_host[i] 1: trust ratio and weight decay (LARS).
  * nan_flag_dev: device int or NULL.  sq_norms_out_host (optional, 2 n_tensors doubles): (|w|^2, |g|^2) per tensor before the update,

@@ -94,6 +94,14 @@ class Train_ResNet(C.Structure):
                 ("init_loaded", C.c_int), ("backend_ctx", C.c_void_p), ("dump_dir", C.c_char_p)]
 
 
+class MiLossMetrics(C.Structure):
+    _fields_ = [("loss_sum", C.c_double), ("rows", C.c_int64), ("wrong_top1", C.c_int64), ("wrong_topk", C.c_int64),
+                ("batches", C.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 MI_SRC_SHARDS, MI_SRC_BUFFER, MI_SRC_SYNTHETIC, MI_SRC_HOST = 0, 1, 2, 3
 MI_SRC_SHARDS_U8 = 4
 MI_AUG_FIXED, MI_AUG_CENTER, MI_AUG_RANDOM, MI_AUG_RRC = 0, 1, 2, 3
@@ -106,6 +114,7 @@ MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16, MI_FWD_PW
 MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 = range(4)
 MI_WG_F32, MI_WG_BF16, MI_WG_CL, MI_WG_CL2, MI_WG_STEM_F32, MI_WG_STEM_BF16 = range(6)
 MI_OPT_ADAM, MI_OPT_SGD, MI_OPT_LARS = 0, 1, 2
+MI_LOSS_HOST, MI_LOSS_DEVICE, MI_LOSS_NO_PRED_COPY = 0, 1, 2  # flags of mi_trainer_set_loss
 MI_GUARD = 256  # slack bytes mi_malloc leaves on both sides of a tensor (csrc/mi_host.h)
 
 # every symbol include/resnet_mi.h declares: name -> (restype, argtypes)
@@ -204,6 +213,9 @@ PROTOTYPES = {
     "mi_trainer_end_epoch": (None, [_T, _f, _f, _f]),
     "mi_trainer_set_optimizer": (_i, [_T, _i, _f, _f]),
     "mi_trainer_get_optimizer": (_i, [_T]),
+    "mi_op_loss_head": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
+    "mi_trainer_set_loss": (_i, [_T, _f, _i, _i]),
+    "mi_trainer_metrics": (_i, [_T, C.POINTER(MiLossMetrics), C.POINTER(MiLossMetrics), _i]),
     "mi_op_momentum_update": (_i, [_i, _vp, _vp, _vp, _sz, _vp, _i, _vp, _f, _f, _f, _f, _vp, _vp]),
     "mi_trainer_nan_location": (_i, [_T]),
     "mi_trainer_stem_dtype": (_i, [_T]),

@@ -266,6 +266,12 @@ int mid_relu_deriv(mid_stream s, const float *x, const float *up, float *out, si
 int mid_add_relu(mid_stream s, const float *a, const float *b, float *sum_out, float *act_out, size_t n);
 int mid_softmax(mid_stream s, const float *x, float *out, int N, int L);
 int mid_ce_deriv(mid_stream s, const float *pred, const int *labels, float *d, int N, int L);
+/* the loss head (kernels_loss.hip): soft-max, label-smoothed cross-entropy gradient, per-row loss and rank of the label in one launch;
+ * pred / dlogits [N][L], row_loss / row_rank [N], each may be NULL.  With last_dev or total_dev (MiLossMetrics of resnet_mi.h, device
+ * memory) a one-wave launch behind it reduces row_loss and row_rank -- both needed then -- into them: last overwritten, total added to */
+typedef struct { double loss_sum; int64_t rows, wrong_top1, wrong_topk, batches; } mid_loss_metrics;
+int mid_loss_head(mid_stream s, const float *logits, const int *labels, float *pred, float *dlogits, float *row_loss, int *row_rank, int N,
+                  int L, float smoothing, int topk, mid_loss_metrics *last_dev, mid_loss_metrics *total_dev);
 /* fused updateMeans+updateVars+updateParams (resnet.cu:605-662).  On NaN/Inf *nan_flag (device int) becomes the highest offending
  * locations[] index + 1 (check_errors, resnet.cu:2879-2907): loc_off_dev = n_loc + 1 arena offsets (floats) of the tensors, base =
  * arena offset of p[0]; loc_off_dev NULL: the flag becomes 1. */

@@ -184,6 +184,11 @@ typedef struct MiCtx {
     int params_dirty;            /* update_parameters ran since the last weight re-layout */
     MiOptim optim;               /* mi_trainer_set_optimizer: SGD / LARS instead of Adam (kind MI_OPT_ADAM: nothing built) */
     int n_updates;               /* update_parameters calls so far (the optimizer is chosen before the first) */
+    /* mi_trainer_set_loss: the head of forward_pass (MI_LOSS_* flags; 0: the reference's soft-max, host loss, ce_deriv), and for
+     * MI_LOSS_DEVICE the per-row outputs [batch] and the two records (last, total) the loss head writes */
+    float loss_smoothing; int loss_topk, loss_flags;
+    float *loss_row; int *loss_rank;
+    mid_loss_metrics *loss_metrics;
     unsigned long host_epoch_seen; /* the process-wide host-write count (mi_copy_to_device) that re-layout was made at */
     char *dump_root;
     /* every device allocation of this trainer (freed by destroy_trainer) */
@@ -234,5 +239,6 @@ float *mi_params_arena_base(const Params *p);
 void mi_dp_reduce_ready(Train_ResNet *t, size_t from_float_offset, int force);
 void mi_trainer_poll_errors(Train_ResNet *t); /* load_new_batch: wait for and read the NaN / Inf flag of the last update */
 void mi_record_host_error(const char *what, const char *detail); /* sets mi_last_error (runtime.hip) */
+int mi_loss_args_ok(const char *who, float smoothing, int topk, int L); /* ops.c: the rules of mi_op_loss_head / mi_trainer_set_loss */
 
 #endif

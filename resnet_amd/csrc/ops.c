@@ -120,6 +120,26 @@ int mi_op_matmul_lt(const float *A_kxm, const float *B, float *out, int m, int k
 int mi_op_matmul_rt(const float *A, const float *B_nxk, float *out, int m, int k, int n) { return finish(mid_gemm_nt(mi_global()->compute, A, B_nxk, out, m, k, n)); }
 int mi_op_softmax(const float *x, float *out, int N, int L) { return finish(mid_softmax(mi_global()->compute, x, out, N, L)); }
 int mi_op_ce_deriv(const float *pred, const int *labels, float *d, int N, int L) { return finish(mid_ce_deriv(mi_global()->compute, pred, labels, d, N, L)); }
+_Static_assert(sizeof(MiLossMetrics) == sizeof(mid_loss_metrics), "one record, declared on both sides of mi_device.h");
+/* the argument rules mi_op_loss_head and mi_trainer_set_loss share; 0, or -1 with mi_last_error set */
+int mi_loss_args_ok(const char *who, float smoothing, int topk, int L) {
+    if (!(smoothing >= 0.f && smoothing < 1.f)) { mi_record_host_error(who, "smoothing lies in [0, 1)"); return -1; }
+    if (topk < 1 || topk > L) { mi_record_host_error(who, "topk lies in [1, number of classes]"); return -1; }
+    return 0;
+}
+int mi_op_loss_head(const float *logits, const int *labels, float *pred, float *dlogits, float *row_loss, int *row_rank, int N, int L,
+                    float smoothing, int topk, MiLossMetrics *last_dev, MiLossMetrics *total_dev) {
+    if (N < 1 || L < 1) { mi_record_host_error("mi_op_loss_head", "N and L are at least 1"); return -1; }
+    if (mi_loss_args_ok("mi_op_loss_head", smoothing, topk, L)) return -1;
+    /* the totals are reduced from the row values: rows the caller does not want live in scratch */
+    const int totals = last_dev || total_dev;
+    float *rl = totals && !row_loss ? (float *)mid_malloc((size_t)N * sizeof(float)) : NULL;
+    int *rr = totals && !row_rank ? (int *)mid_malloc((size_t)N * sizeof(int)) : NULL;
+    const int rc = finish(mid_loss_head(mi_global()->compute, logits, labels, pred, dlogits, row_loss ? row_loss : rl, row_rank ? row_rank : rr, N, L,
+                                        smoothing, topk, (mid_loss_metrics *)last_dev, (mid_loss_metrics *)total_dev));
+    mid_free(rl); mid_free(rr);
+    return rc;
+}
 int mi_op_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, float wd, float b1, float b2, float cur_b1,
                float cur_b2, float eps, int *nan_flag_dev) {
     return finish(mid_adam(mi_global()->compute, p, (float *)g, m, v, n, lr, wd, b1, b2, cur_b1, cur_b2, eps, nan_flag_dev, 0, NULL, 0, 0));

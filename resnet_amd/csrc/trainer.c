@@ -516,6 +516,11 @@ Train_ResNet *init_trainer(ResNet *model, Batch *cur_batch, int batch_size, floa
     }
     c->ev_nan = mid_event_create();
     c->nan_location = -1;
+    c->loss_topk = 1; /* with smoothing 0 and MI_LOSS_HOST: the reference's head */
+    c->loss_row = falloc(c, (size_t)batch_size);
+    c->loss_rank = (int *)mi_ctx_alloc(c, (size_t)batch_size * sizeof(int));
+    c->loss_metrics = (mid_loss_metrics *)mi_ctx_alloc(c, 2 * sizeof(mid_loss_metrics));
+    mid_memset(c->loss_metrics, 0, 2 * sizeof(mid_loss_metrics), G.compute);
     c->next_live = g_live; g_live = c;
     c->nan_flag_dev = (int *)mi_ctx_alloc(c, sizeof(int));
     c->nan_flag_host = (int *)mid_malloc_host(sizeof(int));
@@ -767,16 +772,54 @@ void forward_pass(Train_ResNet *t) {
     const int Hl = last->incoming_spatial_dim; /* resnet.cu:1732 */
     ck(mid_avgpool_fwd_t(G.compute, bin, c->dtype, a->final_conv_output_pooled, N, d->final_depth, Hl * Hl), "average pool");
     ck(mid_gemm_nn(G.compute, a->final_conv_output_pooled, p->fully_connected, a->linear_output, N, d->final_depth, d->output), "FC forward");
-    ck(mid_softmax(G.compute, a->linear_output, t->forward_buffer->pred, N, d->output), "soft-max");
+    if (c->loss_flags & MI_LOSS_DEVICE) /* soft-max, dlogits (backwards_pass launches no ce_deriv), row losses and ranks, the two records */
+        ck(mid_loss_head(G.compute, a->linear_output, t->cur_batch->correct_classes, t->forward_buffer->pred, t->backprop_buffer->output_layer_deriv,
+                         c->loss_row, c->loss_rank, N, d->output, c->loss_smoothing, c->loss_topk, c->loss_metrics, c->loss_metrics + 1), "loss head");
+    else ck(mid_softmax(G.compute, a->linear_output, t->forward_buffer->pred, N, d->output), "soft-max");
     mid_event_record(c->ev_t[1], G.compute);
+    if (c->loss_flags & MI_LOSS_NO_PRED_COPY) { /* nothing the host reads: the queue is not drained, only the flag's own event waited for */
+        mi_trainer_poll_errors(t);
+        return;
+    }
     mid_memcpy_d2h(t->forward_buffer->pred_cpu, t->forward_buffer->pred, (size_t)N * d->output * sizeof(float), G.compute);
     mid_stream_sync(G.compute); /* the reference's blocking cudaMemcpy (:1774) */
     poll_nan_flag(t);           /* the previous update's flag copy has landed by now */
 }
 
+/* the head of forward_pass / backwards_pass (resnet_mi.h) */
+int mi_trainer_set_loss(Train_ResNet *t, float smoothing, int topk, int flags) {
+    MiCtx *c = ctx_of(t);
+    if (flags & ~(MI_LOSS_DEVICE | MI_LOSS_NO_PRED_COPY)) { mi_record_host_error("mi_trainer_set_loss", "unknown flag bits"); return -1; }
+    if (mi_loss_args_ok("mi_trainer_set_loss", smoothing, topk, t->model->dims->output)) return -1;
+    if (smoothing > 0.f && !(flags & MI_LOSS_DEVICE)) {
+        mi_record_host_error("mi_trainer_set_loss", "label smoothing needs MI_LOSS_DEVICE (the host head has none)");
+        return -1;
+    }
+    if ((flags & MI_LOSS_NO_PRED_COPY) && !(flags & MI_LOSS_DEVICE)) {
+        mi_record_host_error("mi_trainer_set_loss", "MI_LOSS_NO_PRED_COPY needs MI_LOSS_DEVICE (the host loss reads pred_cpu)");
+        return -1;
+    }
+    c->loss_smoothing = smoothing; c->loss_topk = topk; c->loss_flags = flags;
+    return 0;
+}
+int mi_trainer_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
+    MiCtx *c = ctx_of(t);
+    if (last) mid_memcpy_d2h(last, c->loss_metrics, sizeof *last, G.compute);
+    if (total) mid_memcpy_d2h(total, c->loss_metrics + 1, sizeof *total, G.compute);
+    if (reset_total) mid_memset(c->loss_metrics + 1, 0, sizeof(mid_loss_metrics), G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+
 /* resnet.cu:3363-3383 */
 float mi_host_loss(Train_ResNet *t, int *n_wrong) {
     const int N = t->batch_size, L = t->model->dims->output;
+    if (ctx_of(t)->loss_flags & MI_LOSS_NO_PRED_COPY) { /* pred_cpu was not written: the device's record of this forward_pass */
+        MiLossMetrics m = {0};
+        mi_trainer_metrics(t, &m, NULL, 0);
+        if (n_wrong) *n_wrong = (int)m.wrong_top1;
+        return (float)m.loss_sum;
+    }
     const float *pred = t->forward_buffer->pred_cpu;
     const int *lab = t->cur_batch->correct_classes_cpu;
     float loss = 0;
@@ -859,7 +902,8 @@ void backwards_pass(Train_ResNet *t) {
     c->dp_cursor = c->arena_floats;
     c->n_buckets = 0;
     /* dlogits = softmax - onehot, batch SUM (no 1/N: resnet.cu:1806-1811) */
-    ck(mid_ce_deriv(G.compute, t->forward_buffer->pred, t->cur_batch->correct_classes, bb->output_layer_deriv, N, L), "cross-entropy derivative");
+    if (!(c->loss_flags & MI_LOSS_DEVICE)) /* (the loss head of forward_pass left it) */
+        ck(mid_ce_deriv(G.compute, t->forward_buffer->pred, t->cur_batch->correct_classes, bb->output_layer_deriv, N, L), "cross-entropy derivative");
     /* FC: dW = pooled^T dlogits (:1823), dpooled = dlogits W^T (:1830) -- no transposed temporaries */
     ck(mid_gemm_tn(G.compute, a->final_conv_output_pooled, bb->output_layer_deriv, dp->fully_connected, D, N, L), "FC wgrad");
     ck(mid_gemm_nt(G.compute, bb->output_layer_deriv, p->fully_connected, da->final_conv_output_pooled, N, L, D), "FC dgrad");

@@ -195,6 +195,20 @@ class Ops:
         self._chk(self.L.mi_op_ce_deriv(dp.ptr, dl.ptr, dd.ptr, pred.shape[0], pred.shape[1]), "ce_deriv")
         return dd.get()
 
+    def loss_head(self, x, labels, smoothing=0.0, topk=5, total=None):
+        """mi_op_loss_head on logits x (N, L): returns (pred, dlogits, row_loss, row_rank, last, total), the two records as dicts.
+        total: a DeviceArray holding a MiLossMetrics to add to (a zeroed one is made otherwise)"""
+        N, L = x.shape
+        dx, dl = self.dev(np.ascontiguousarray(x, np.float32)), self.dev(np.ascontiguousarray(labels, np.int32))
+        dp, dd = self.dev(shape=x.shape), self.dev(shape=x.shape)
+        drl, drr = self.dev(shape=(N,)), self.dev(shape=(N,), dtype=np.int32)
+        nb = C.sizeof(B.MiLossMetrics)
+        dlast = self.dev(np.zeros(nb, np.uint8))
+        dtot = total if total is not None else self.dev(np.zeros(nb, np.uint8))
+        self._chk(self.L.mi_op_loss_head(dx.ptr, dl.ptr, dp.ptr, dd.ptr, drl.ptr, drr.ptr, N, L, smoothing, topk, dlast.ptr, dtot.ptr), "loss_head")
+        rec = [B.MiLossMetrics.from_buffer_copy(d.get().tobytes()).as_dict() for d in (dlast, dtot)]
+        return dp.get(), dd.get(), drl.get(), drr.get(), rec[0], rec[1]
+
     def adam(self, p, g, m, v, lr, wd, b1, b2, cur_b1, cur_b2, eps):
         dp, dg, dm, dv = (self.dev(a) for a in (p, g, m, v))
         flag = self.dev(np.zeros(1, np.int32))

@@ -65,6 +65,23 @@ class Trainer:
     def optimizer(self):
         return {v: k for k, v in self.OPTIMIZERS.items()}[self.L.mi_trainer_get_optimizer(self.t)]
 
+    def set_loss(self, smoothing=0.0, topk=5, device=True, copy_pred=True):
+        """the head of forward / backward (mi_trainer_set_loss, include/resnet_mi.h).  device: soft-max, label-smoothed cross-entropy
+        gradient, loss and top-1 / top-k totals in one launch on the GPU (metrics()); copy_pred=False also drops forward()'s blocking
+        copy of pred to the host, loss() then reads the device's record.  device=False, smoothing 0: the reference's head"""
+        flags = (B.MI_LOSS_DEVICE if device else 0) | (0 if copy_pred else B.MI_LOSS_NO_PRED_COPY)
+        if self.L.mi_trainer_set_loss(self.t, smoothing, int(topk), flags) != 0:
+            e = self.error()
+            self.L.mi_clear_error()
+            raise RuntimeError("mi_trainer_set_loss: " + e)
+
+    def metrics(self, reset=False):
+        """(last, total): loss_sum, rows, wrong_top1, wrong_topk, batches of the last forward() and summed since the last reset"""
+        last, total = B.MiLossMetrics(), B.MiLossMetrics()
+        if self.L.mi_trainer_metrics(self.t, C.byref(last), C.byref(total), int(bool(reset))) != 0:
+            raise RuntimeError("mi_trainer_metrics: " + self.error())
+        return last.as_dict(), total.as_dict()
+
     def set_lr(self, lr):
         """learning_rate for the next update_parameters and on (read at every update)"""
         self.t.contents.learning_rate = lr

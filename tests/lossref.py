@@ -1,0 +1,125 @@
+"""float64 numpy model of the device loss head (include/resnet_mi.h, "the loss head on the device"; kernels_loss.hip).
+
+Per row of logits x[0..L) with label c, smoothing eps and u = eps / L:
+  pred      p = exp(x - mx) / sum exp(x - mx), mx = max x
+  dlogits   p - t, t_c = (1 - eps) + u, t_j = u otherwise (a batch SUM: no 1/N)
+  row_loss  log(sum exp(x - mx)) - (1 - eps) (x_c - mx) - u sum_j (x_j - mx)   = -sum_j t_j log p_j
+  row_rank  #{ j != c : p_j >= p_c }  (ties count against the label; a NaN p_c compares false: rank 0)
+A label outside [0, L): dlogits = p - u, row_rank = L, row_loss = NaN.
+"""
+import numpy as np
+
+
+def softmax(x):
+    x = np.asarray(x, np.float64)
+    e = np.exp(x - x.max(axis=1, keepdims=True))
+    return e / e.sum(axis=1, keepdims=True)
+
+
+def rank_of(pred, labels):
+    """the rank rule on GIVEN probabilities (any float type: the comparisons are exact)"""
+    pred = np.asarray(pred)
+    N, L = pred.shape
+    out = np.empty(N, np.int64)
+    for r in range(N):
+        c = int(labels[r])
+        if not 0 <= c < L:
+            out[r] = L
+            continue
+        ge = pred[r] >= pred[r, c]
+        ge[c] = False
+        out[r] = int(ge.sum())
+    return out
+
+
+def host_rule_wrong(pred, labels):
+    """mi_host_loss's top-1 rule (resnet.cu:3363-3383): a row is wrong when any other class has p >= p_c"""
+    pred = np.asarray(pred)
+    out = np.zeros(pred.shape[0], bool)
+    for r in range(pred.shape[0]):
+        c = int(labels[r])
+        for j in range(pred.shape[1]):
+            if j != c and pred[r, j] >= pred[r, c]:
+                out[r] = True
+                break
+    return out
+
+
+def loss_head(x, labels, eps=0.0):
+    """(pred, dlogits, row_loss, row_rank) in float64 / int64"""
+    x = np.asarray(x, np.float64)
+    N, L = x.shape
+    u = eps / L
+    z = x - x.max(axis=1, keepdims=True)
+    s = np.exp(z).sum(axis=1)
+    pred = np.exp(z) / s[:, None]
+    t = np.full((N, L), u)
+    row_loss = np.empty(N)
+    for r in range(N):
+        c = int(labels[r])
+        if 0 <= c < L:
+            t[r, c] = (1.0 - eps) + u
+            row_loss[r] = np.log(s[r]) - (1.0 - eps) * z[r, c] - u * z[r].sum()
+        else:
+            row_loss[r] = np.nan
+    return pred, pred - t, row_loss, rank_of(pred, labels)
+
+
+SHAPES = [(2, 1), (3, 10), (5, 64), (4, 65), (8, 1000), (7, 1537)]  # (N, L): see tests/test_gpu_loss_head.py
+TIE_ROW, UNDERFLOW_ROW = 1, 0
+
+
+def make_inputs(N, L):
+    """the logits and labels of the loss-head tests: N(0, 9) logits (seed 51) with the overflow hazard x[3, 17] = 95 where it exists,
+    labels from seed 52; L >= 2: row 0's label logit 110 below the row's maximum (p_c = 0 in fp32); L >= 3: row 1 integer-valued with
+    exactly two other classes at the label's logit and every other class below it (rank 2)"""
+    import synth
+    x = synth.normal(51, N * L, 9.0).reshape(N, L).copy()
+    lab = synth.labels(52, N, L)
+    if N > 3 and L > 17:
+        x[3, 17] = 95.0
+    if L >= 2:
+        c = int(lab[UNDERFLOW_ROW])
+        x[UNDERFLOW_ROW, c] = np.delete(x[UNDERFLOW_ROW], c).max() - np.float32(110.0)
+    if L >= 3:
+        c = int(lab[TIE_ROW])
+        x[TIE_ROW] = (np.arange(L) % 4).astype(np.float32)
+        x[TIE_ROW, [c, (c + 1) % L, (c + 2) % L]] = 4.0
+    return np.ascontiguousarray(x, np.float32), lab
+
+
+def loss_bound(ref):
+    """|device row_loss - ref| allowed per row: 2^-19 (2 + ref) (derivation: DESIGN.md, "Loss head")"""
+    return 2.0 ** -19 * (2.0 + np.asarray(ref, np.float64))
+
+
+def loss_head_f32(x, labels, eps=0.0):
+    """the kernel's own formulas step by step in float32 (lane-strided sums of 64 lanes, then the exchange tree): row_loss only.  Used to hold
+    the derived bound against fp32 arithmetic without a GPU"""
+    f = np.float32
+    x = np.asarray(x, f)
+    N, L = x.shape
+    epsf = f(eps)
+    u = epsf / f(L)
+    out = np.empty(N, f)
+
+    def tree(v):
+        v = v.copy()
+        o = 32
+        while o:
+            v = v + v[np.arange(64) ^ o]
+            o >>= 1
+        return v[0]
+
+    for r in range(N):
+        c = int(labels[r])
+        mx = x[r].max()
+        z = x[r] - mx
+        e = np.exp(z)  # numpy's float32 exp: within 1 ulp, as expf
+        s_l, z_l = np.zeros(64, f), np.zeros(64, f if L <= 1024 else np.float64)  # a row of more than 16 per lane sums z in double
+        for j in range(L):
+            s_l[j % 64] += e[j]
+            z_l[j % 64] += z[j]
+        s, sz = tree(s_l), f(tree(z_l))
+        out[r] = np.log(s) - (f(1) - epsf) * z[c] - u * sz if 0 <= c < L else np.nan
+    return out

@@ -1,0 +1,74 @@
+"""The float64 model of the device loss head (tests/lossref.py) against torch's label-smoothed cross entropy and its autograd gradient, the
+model's rank rule against mi_host_loss's top-1 rule, the derived row-loss bound against an fp32 restatement of the kernel's formulas, and
+the library's exports.  No GPU."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import lossref as R
+
+
+@pytest.mark.parametrize("eps", [0.0, 0.1, 0.5])
+@pytest.mark.parametrize("shape", R.SHAPES)
+def test_model_equals_torch_cross_entropy_and_its_gradient(shape, eps):
+    x, lab = R.make_inputs(*shape)
+    pred, dlogits, row_loss, _ = R.loss_head(x, lab, eps)
+    t = torch.tensor(x, dtype=torch.float64, requires_grad=True)
+    tl = torch.tensor(lab, dtype=torch.long)
+    rows = F.cross_entropy(t, tl, label_smoothing=eps, reduction="none")
+    assert np.max(np.abs(row_loss - rows.detach().numpy()) / (1.0 + rows.detach().numpy())) <= 1e-12
+    F.cross_entropy(t, tl, label_smoothing=eps, reduction="sum").backward()
+    assert np.max(np.abs(dlogits - t.grad.numpy())) <= 1e-12
+    assert np.max(np.abs(pred - torch.softmax(t.detach(), dim=1).numpy())) <= 1e-14
+    assert np.all(np.isfinite(row_loss))
+
+
+@pytest.mark.parametrize("shape", R.SHAPES)
+def test_rank_rule(shape):
+    N, L = shape
+    x, lab = R.make_inputs(N, L)
+    pred, _, _, rank = R.loss_head(x, lab)
+    assert np.array_equal(rank >= 1, R.host_rule_wrong(pred, lab))
+    if L >= 3:
+        assert rank[R.TIE_ROW] == 2
+    if L == 1:
+        assert not rank.any()
+    p32 = pred.astype(np.float32)
+    if L >= 2:
+        assert p32[R.UNDERFLOW_ROW, lab[R.UNDERFLOW_ROW]] == 0  # every other class ties with or beats a zero
+        assert R.rank_of(p32, lab)[R.UNDERFLOW_ROW] == L - 1
+    nan = p32.copy()
+    nan[0, lab[0]] = np.nan  # a NaN p_c compares false with everything, in both rules
+    assert R.rank_of(nan, lab)[0] == 0 and not R.host_rule_wrong(nan, lab)[0]
+
+
+def test_labels_outside_the_row():
+    x, lab = R.make_inputs(3, 10)
+    bad = lab.copy()
+    bad[0], bad[2] = -1, 10
+    pred, dlogits, row_loss, rank = R.loss_head(x, bad, 0.1)
+    good = R.loss_head(x, lab, 0.1)
+    assert np.array_equal(pred, good[0]) and np.array_equal(dlogits[1], good[1][1]) and row_loss[1] == good[2][1]
+    assert rank[0] == 10 and rank[2] == 10 and np.isnan(row_loss[0]) and np.isnan(row_loss[2])
+    assert np.array_equal(dlogits[[0, 2]], pred[[0, 2]] - 0.1 / 10)
+
+
+@pytest.mark.parametrize("eps", [0.0, 0.1, 0.5])
+@pytest.mark.parametrize("shape", R.SHAPES)
+def test_fp32_formulas_stay_inside_the_derived_bound(shape, eps):
+    x, lab = R.make_inputs(*shape)
+    ref = R.loss_head(x, lab, eps)[2]
+    got = R.loss_head_f32(x, lab, eps).astype(np.float64)
+    share = np.max(np.abs(got - ref) / R.loss_bound(ref))
+    print("fp32 formulas, %s eps %g: worst |error| / bound = %.4f" % (shape, eps, share))
+    assert np.all(np.isfinite(got)) and share <= 0.06  # the share the bound's derivation leaves unused: DESIGN.md
+
+
+def test_library_exports_the_loss_entry_points():
+    from resnet_amd import binding
+    lib = binding.load()
+    for name in ("mi_op_loss_head", "mi_trainer_set_loss", "mi_trainer_metrics"):
+        assert hasattr(lib, name) and name in binding.PROTOTYPES, name
+    import ctypes as C
+    assert C.sizeof(binding.MiLossMetrics) == 40
