@@ -374,7 +374,8 @@ int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k
  * RESNET_MI_* switches -- the planner the trainer and the mi_op_* convolution operators themselves run through.  dtype MI_DTYPE_*, policy
  * MI_STORE_*; site = the layer's bit in the BN'-fusion site masks (1 expansion, 2 spatial, 4 the reduction above an identity block, 0 none).
  * out = (forward, dgrad, wgrad route, 1 where the dgrad also does the reduction pass of the batch-norm backward its output feeds).
- * Returns 0, or -2 (out all 0): unknown dtype, policy or site, or a shape the storage type's kernels do not take.  The LDS-DMA 1x1 weight
+ * Returns 0, or -2 (out all 0): unknown dtype, policy or site, or a shape the storage type's kernels do not take -- at a batch past a
+ * kernel's size limit mi_last_error says "size limit: ..." (the mi_op_* convolutions refuse the same way, before any launch).  The LDS-DMA 1x1 weight
  * gradient is not a route of its own: MI_WG_BF16 picks it at launch (mi_conv_plan, route PW, says where). */
 enum { MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16, MI_FWD_PW /* mi_op_conv1x1_fwd_bf16_cl only */ };
 enum { MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 };

@@ -547,6 +547,13 @@ static int bn_vec_ew(int x_dt, int a_dt, int P, size_t total, bool *str) {
     } while (0)
 
 static size_t dt_bytes(int dt) { return dt == MID_BF16 ? 2 : 4; }
+// the element-wise passes divide a 32-bit element index (fd_div), the reductions walk 32-bit (image, position) counts: tensors of
+// fewer than 2^32 elements.  0, or -2 with the limit recorded (nothing is launched)
+static int bn_size_ok(const char *who, int N, int C, int P) {
+    if ((double)N * C * P < 4294967296.0) return 0;
+    mi_record_error(who, "size limit: batch-norm tensors hold fewer than 2^32 elements (32-bit element indices)");
+    return -2;
+}
 // launch-trace name of an element-wise kernel: storage types of x and of the activations, elements per thread, planes straddled
 static const char *bn_ew_name(const char *kernel, int x_dt, int a_dt, int vec, bool str) {
     return mi_trace_name("%s<%s,%s,v%d%s>", kernel, x_dt == MID_BF16 ? "bf16" : "f32", a_dt == MID_BF16 ? "bf16" : "f32", vec, str ? ",straddle" : "");
@@ -601,6 +608,7 @@ static int bn_fwd_apply(hipStream_t st, const void *x, int x_dt, const float *ga
                         int P, float eps, int relu, void *ycl, int Hcl) {
     const int Hab = Hcl < 0 ? -Hcl : Hcl;
     if (ycl && x_dt == MID_BF16 && a_dt == MID_BF16 && (residual || relu) && !xhat_out && !norm_out && C % 64 == 0 && Hab * Hab == P && !(Hcl < 0 && (Hab & 1))) {
+        if (N > 65535) { mi_record_error("bn_fwd_apply", "size limit: the channel-last side output takes batches up to 65535 (one grid row per image)"); return -2; }
         hipLaunchKernelGGL(bn_apply_cl_kernel, dim3(C / 64, mi_cdiv(P, 64), N), dim3(256), 0, st, (const bf16_t *)x, gamma, beta, means, vars,
                            (const bf16_t *)residual, (bf16_t *)y, (bf16_t *)ycl, C, P, Hab, eps, make_fastdiv(Hab), Hcl < 0);
         MI_LAUNCH_CHECK("bn_apply_cl_kernel");
@@ -636,6 +644,7 @@ static int bn_stats_launch(hipStream_t st, float *ws, const void *x, int x_dt, i
 /* statistics only (means / biased vars of x): the recompute policy re-derives activations from them in backward */
 int mid_bn_stats_t(mid_stream s, float *ws, const void *x, int x_dt, float *means, float *vars, int N, int C, int P) {
     hipStream_t st = (hipStream_t)s;
+    if (bn_size_ok("mid_bn_stats_t", N, C, P)) return -2;
     const int ns = bn_nsplit(N, C);
     if (bn_stats_launch(st, ws, x, x_dt, N, C, P, ns)) return -1;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(mi_cdiv(C, 4)), dim3(256), 0, st, ws, ns, C, means, vars);
@@ -647,6 +656,7 @@ int mid_bn_stats_t(mid_stream s, float *ws, const void *x, int x_dt, float *mean
 int mid_bn_apply_t(mid_stream s, const void *x, int x_dt, const float *gamma, const float *beta, const void *residual,
                    const float *means, const float *vars, void *y, int a_dt, int N, int C, int P, float eps, int relu, void *ycl, int Hcl) {
     if (!bn_pair_ok(x_dt, a_dt)) { mi_record_error("mid_bn_apply_t", "unsupported storage types"); return -2; }
+    if (bn_size_ok("mid_bn_apply_t", N, C, P)) return -2;
     hipStream_t st = (hipStream_t)s;
     mi_prof_begin(st, MI_FAM_BN, 0.0, (double)N * C * P * (dt_bytes(x_dt) + dt_bytes(a_dt) * (residual ? 2 : 1)));
     const int rc = bn_fwd_apply(st, x, x_dt, gamma, beta, residual, means, vars, y, a_dt, nullptr, nullptr, N, C, P, eps, relu, ycl, Hcl);
@@ -659,6 +669,7 @@ int mid_bn_fwd_t(mid_stream s, float *ws, const mid_bn_parts *parts, const void 
                  int P, float eps, int relu, void *ycl, int Hcl) {
     if (!bn_pair_ok(x_dt, a_dt)) { mi_record_error("mid_bn_fwd_t", "unsupported storage types"); return -2; }
     if ((xhat_out || norm_out) && !(x_dt == MID_F32 && a_dt == MID_F32)) { mi_record_error("mid_bn_fwd_t", "full-store tensors exist in fp32 only"); return -2; }
+    if (bn_size_ok("mid_bn_fwd_t", N, C, P)) return -2;
     hipStream_t st = (hipStream_t)s;
     const double xb = (double)N * C * P * dt_bytes(x_dt), ab = (double)N * C * P * dt_bytes(a_dt);
     if (!parts || parts->nparts <= 0) {
@@ -713,6 +724,7 @@ static int bn_bwd_impl(hipStream_t st, float *ws, const void *x, int x_dt, const
                        const float *vars, const void *dy, const void *mask_src, void *gated_out, int a_dt, void *dx, float *dgamma,
                        float *dbeta, int N, int C, int P, float eps, int mask_mode, const mid_bn_bwd_parts *bparts = nullptr) {
     if (!bn_pair_ok(x_dt, a_dt)) { mi_record_error("mid_bn_bwd", "unsupported storage types"); return -2; }
+    if (bn_size_ok("mid_bn_bwd", N, C, P)) return -2;
     int ns = bn_nsplit(N, C);
     dim3 grid(C, ns), block(256);
     if (mask_mode >= 2 && !mask_src) { mi_record_error("mid_bn_bwd", "mask_src missing"); return -2; }

@@ -67,12 +67,15 @@ dconv_kernel(const float *__restrict__ in, const float *__restrict__ wT, float *
     const uint32_t R0 = fd_div(pix0, a.fd_Wsub);
     const uint32_t n0 = fd_div(R0, a.fd_Hsub);
     const int q0 = (int)(n0 * a.Hq + (R0 - n0 * a.Hsub) * a.sy);
+    // row offsets count from the workgroup's first image n0 (its 64-bit base is workgroup-uniform): the few images a workgroup's patch
+    // spans stay below 2^32 bytes (launch_dconv) whatever the size of the tensor
     for (int qr = tid; qr < a.QR; qr += blockDim.x) {
         const uint32_t q = (uint32_t)(q0 + qr);
         const uint32_t nq = fd_div(q, a.fd_Hq);
         const int ih = (int)(q - nq * a.Hq) + a.offy;
-        tbl[qr] = (nq < (uint32_t)a.N && ih >= 0 && ih < a.Hin) ? (int)((nq * a.Cin * a.Hin + ih) * a.Win) : -1;
+        tbl[qr] = (nq < (uint32_t)a.N && ih >= 0 && ih < a.Hin) ? (int)(((nq - n0) * a.Cin * a.Hin + ih) * a.Win) : -1;
     }
+    const float *in0 = in + (size_t)n0 * a.Cin * HW;
     // the pixel this lane owns
     const uint32_t p = pix0 + tid;
     const bool pvalid = p < a.total_pix;
@@ -104,7 +107,7 @@ dconv_kernel(const float *__restrict__ in, const float *__restrict__ wT, float *
 #pragma unroll
         for (int c = 0; c < CCM; c++) {
             const bool cok = c < a.CC && c0 + c < a.Cin;
-            const char *src = (const char *)(in + (size_t)(cok ? c0 + c : 0) * HW); // wave-uniform
+            const char *src = (const char *)(in0 + (size_t)(cok ? c0 + c : 0) * HW); // wave-uniform
 #pragma unroll
             for (int jj = 0; jj < JM; jj++) regs[c][jj] = *(const float *)(src + goff[jj]); // masked when stashed
         }
@@ -197,6 +200,11 @@ static int launch_dconv(hipStream_t st, const float *in, const float *wT, float 
     long nimg = (rb - 1 + a.Hsub - 1) / a.Hsub + 1;
     if (PIX % a.Wsub == 0 && (a.Hsub % rb == 0)) nimg = 1;
     a.QR = (int)((rb - 1) * a.sy + ntr + (nimg - 1) * (ntr > a.sy ? ntr - a.sy : 0));
+    // 32-bit pixel indices; 32-bit byte offsets (as int in the row table) inside the nimg + 1 images a workgroup's patch can touch
+    if ((double)a.N * a.Hsub * a.Wsub >= 2147483648.0 || (double)(nimg + 1) * a.Cin * a.Hin * a.Win >= 536870912.0) {
+        mi_record_error("dconv", "size limit: fewer than 2^31 output pixels per launch and 2^29 input elements per workgroup patch");
+        return -2;
+    }
     a.tbl_pad = (a.QR + 3) & ~3;
     a.plane = a.QR * a.PW;
     a.jcnt = (a.plane + PIX - 1) / PIX;

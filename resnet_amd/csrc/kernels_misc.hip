@@ -405,7 +405,7 @@ int mid_lds_probe(uint32_t word, size_t out[4]) {
 int mid_maxpool_fwd_t(mid_stream s, const void *x, void *y, int dt, int *max_inds, int N, int C, int H, int k, int stride) {
     const int Ho = H / stride;
     const size_t total = (size_t)N * C * Ho * Ho;
-    if ((double)N * C * H * H >= 2147483648.0) { mi_record_error("mid_maxpool_fwd", "tensor too large for 32-bit indices"); return -2; }
+    if ((double)N * C * H * H >= 2147483648.0) { mi_record_error("mid_maxpool_fwd", "size limit: max-pool inputs hold fewer than 2^31 elements (the arg-max indices are 32-bit ints)"); return -2; }
     if (k == 3 && stride == 2 && H % 8 == 0 && Ho % 4 == 0) { /* rows of 8-element vectors (16-byte aligned in both storage types), 4 outputs per thread */
         const size_t cells = total / 4;
         if (dt == MID_BF16)
@@ -434,7 +434,7 @@ template <typename T>
 static int maxpool_bwd_launch(hipStream_t st, const int *max_inds, const T *dy, T *dx, int N, int C, int H, int k, int stride) {
     const int Ho = H / stride;
     const size_t total = (size_t)N * C * H * H;
-    if ((double)total >= 2147483648.0) { mi_record_error("mid_maxpool_bwd", "tensor too large for 32-bit indices"); return -2; }
+    if ((double)total >= 2147483648.0) { mi_record_error("mid_maxpool_bwd", "size limit: max-pool inputs hold fewer than 2^31 elements (the arg-max indices are 32-bit ints)"); return -2; }
     if (k == 3 && stride == 2 && (H & 1) == 0) {
         const size_t cells = total / 4;
         hipLaunchKernelGGL(maxpool_bwd_3x3s2_kernel<T>, dim3(ew_blocks(cells)), dim3(256), 0, st, max_inds, dy, dx, (uint32_t)cells, H, Ho,
@@ -456,6 +456,7 @@ int mid_maxpool_bwd(mid_stream s, const int *max_inds, const float *dy, float *d
     return mid_maxpool_bwd_t(s, max_inds, dy, dx, MID_F32, N, C, H, k, stride);
 }
 int mid_avgpool_fwd_t(mid_stream s, const void *x, int dt, float *y, int N, int C, int P) {
+    if ((double)N * C >= 2147483648.0) { mi_record_error("mid_avgpool_fwd", "size limit: fewer than 2^31 planes (32-bit plane index)"); return -2; }
     if (dt == MID_BF16) hipLaunchKernelGGL(avgpool_fwd_kernel<bf16_t>, dim3(mi_cdiv((long)N * C, 4)), dim3(256), 0, (hipStream_t)s, (const bf16_t *)x, y, N * C, P);
     else hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(mi_cdiv((long)N * C, 4)), dim3(256), 0, (hipStream_t)s, (const float *)x, y, N * C, P);
     MI_LAUNCH_CHECK("avgpool_fwd_kernel");

@@ -5,6 +5,7 @@
  * the planner's choices and keeps the network: which tensor feeds which layer, streams, events, the weight table.  The operator layer
  * (ops.c) plans one layer with forced routes and runs the same runners.  Plain C over mi_device.h.
  */
+#include <stdio.h>
 #include <string.h>
 #include "mi_host.h"
 
@@ -14,7 +15,35 @@ void mi_layer_init(MiLayer *L, const float *w, int C, int H, int K, int k, int s
 }
 
 /* ---------------------------------------------------------------------------------------------- */
+/* The size limits of the routes ("Size limits"), for the shape a plan was refused: where a tensor is past one, the limit is
+ * recorded (mi_last_error) -- a trainer or an operator at an unsupported batch then says why.  Returns 1 where it named a limit */
+static int size_limit_named(const MiLayer *L, int dtype, int N, const int force[3]) {
+    const int C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
+    if (N < 1 || C < 1 || H < 1 || K < 1 || k < 1 || s < 1) return 0;
+    const int Ho = H / s;
+    const double in = (double)N * C * H * H, out = (double)N * K * Ho * Ho;
+    char msg[256];
+    if ((double)N * H * H >= 2147483648.0) {
+        snprintf(msg, sizeof msg, "size limit: a convolution takes fewer than 2^31 pixels per tensor (32-bit pixel indices); N = %d at %d x %d is %.0f", N, H, H, (double)N * H * H);
+    } else if (dtype == MID_BF16 && k <= 3 && (in >= 2147480000.0 || out >= 2147480000.0)) {
+        snprintf(msg, sizeof msg, "size limit: the bf16 convolutions take tensors of fewer than 2147480000 elements (32-bit byte offsets); N = %d gives %.0f in, %.0f out", N, in, out);
+    } else if (dtype == MID_BF16 && k == 3 && force && (force[0] == MI_FWD_CL || force[1] == MI_DG_CL || force[1] == MI_DG_CL2) &&
+               (double)N * (H + 2) * (H + 2) * (C > K ? C : K) * 2 >= 4294000000.0) {
+        snprintf(msg, sizeof msg, "size limit: the channel-last bf16 routes take padded operands below 4294000000 bytes (32-bit byte offsets); N = %d is past it", N);
+    } else return 0;
+    mi_record_host_error("mi_layer_plan", msg);
+    return 1;
+}
+
+static int layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int N, int site, const int force[3]);
 int mi_layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int N, int site, const int force[3]) {
+    /* every route indexes pixels (columns of the implicit GEMMs, rows of the direct kernels' patches) with 32 bits */
+    if (N >= 1 && L->H >= 1 && (double)N * L->H * L->H >= 2147483648.0) { size_limit_named(L, dtype, N, force); return -2; }
+    const int rc = layer_plan(L, dtype, policy, o, N, site, force);
+    if (rc) size_limit_named(L, dtype, N, force);
+    return rc;
+}
+static int layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int N, int site, const int force[3]) {
     const int C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
     if ((dtype != MID_F32 && dtype != MID_BF16) || N < 1 || C < 1 || H < 1 || K < 1 || k < 1 || s < 1) return -2;
     /* the 7x7 stem keeps fp32 tensors and the fp32 kernels in every storage type, unless it runs on the matrix cores */

@@ -40,7 +40,8 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// exact unsigned division by a runtime divisor through a precomputed 32-bit magic (n < 2^31, d < 2^31)
+// exact unsigned division by a runtime divisor through a precomputed 32-bit magic (every n < 2^32; d < 2^31): the round-up form of
+// Granlund and Montgomery, t = mulhi(n, magic), q = (t + ((n - t) >> 1)) >> (l - 1), in which n - t cannot underflow and t + ... cannot overflow
 struct FastDiv {
     uint32_t d, magic, shift;
 };

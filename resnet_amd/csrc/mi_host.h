@@ -101,7 +101,8 @@ struct MiCtx;
 void mi_layer_init(MiLayer *L, const float *w, int C, int H, int K, int k, int stride);
 /* host only, allocates nothing: routes, fz and every size of L from (dtype, policy, options, N, shape, site = the layer's bit in the
  * BN'-fusion site masks, 0: not a site).  force: NULL, or per operation MI_PLANNED, MI_NOT_RUN or a route.  Returns 0, or -2 where a
- * route's *_supported test refuses the shape or the storage type */
+ * route's *_supported test refuses the shape or the storage type; where a tensor is past a route's size limit ("Size
+ * limits") mi_last_error names it */
 int mi_layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int N, int site, const int force[3]);
 /* the planned buffers at exactly their sizes (halos zeroed), tracked by the trainer c, or untracked (c == NULL: mi_layer_free) */
 void mi_layer_alloc(struct MiCtx *c, MiLayer *L);

@@ -36,9 +36,9 @@ static int op_open(OpConv *o, int dt, const MiOptions *opt, const float *w, int 
     const int force[3] = {fwd, dgrad, wgrad};
     MiLayerNeed need = {0, 0, 0, 0};
     memset(o, 0, sizeof *o);
-    o->s = mi_global()->compute;
     mi_layer_init(&o->L, w, C, H, K, k, stride);
-    if (mi_layer_plan(&o->L, dt, MI_STORE_FAST, opt, N, site, force)) return -2;
+    if (mi_layer_plan(&o->L, dt, MI_STORE_FAST, opt, N, site, force)) return -2; /* (host only: a refusal touches no device) */
+    o->s = mi_global()->compute;
     mi_layer_need(&o->L, &need);
     mi_layer_alloc(NULL, &o->L);
     mi_layer_ws_alloc(NULL, &o->w, &need);
