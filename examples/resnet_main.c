@@ -16,6 +16,10 @@
  *   ./ResNetMI --label-smoothing 0.1 --topk 5 --device-loss
  *              the loss head on the device (mi_trainer_set_loss): label-smoothed cross entropy, loss and top-1 / top-K error counted
  *              there, one line of totals per epoch; --device-loss also drops forward_pass's blocking copy of the predictions
+ *   ./ResNetMI --bn-momentum 0.1 --val-u8 /data/val_shards/u8 --val-dim-in 256 --val-every 5000
+ *              evaluation: running statistics of every batch norm (mi_trainer_track_running_stats; --val-u8 alone implies momentum 0.1) and,
+ *              every STEPS iterations and at the end of every epoch, the eval pass over every %03d.images_u8 / %03d.labels under DIR
+ *              (whole dim-in^2 images, centre crop): loss per image, top-1 and top-K error of the set
  *   ./ResNetMI --labels-file id_to_label_mapping.txt --synsets-file id_to_synset_mapping.txt --counts-file id_to_img_count_mapping.txt
  *              the class metadata of resnet.cu:3236-3242: iterations per epoch = ceil(sum of the class counts / batch) (:3309)
  *              unless --iters says otherwise
@@ -29,6 +33,39 @@
 static const char *opt(int argc, char **argv, const char *name, const char *def) {
     for (int i = 1; i + 1 < argc; i++) if (!strcmp(argv[i], name)) return argv[i + 1];
     return def;
+}
+
+/* the whole validation set, shard by shard through mi_trainer_eval_u8 (each call returns its own total); 0, or -1 with a message printed */
+static int validate(Train_ResNet *trainer, const char *dir, int dim_in, int topk, const char *when) {
+    MiLossMetrics sum = {0};
+    const size_t img = (size_t)dim_in * dim_in * 3;
+    for (int id = 0;; id++) {
+        char path[4096];
+        snprintf(path, sizeof path, "%s/%03d.labels", dir, id);
+        FILE *fl = fopen(path, "rb");
+        if (!fl) break;
+        fseek(fl, 0, SEEK_END);
+        const long n = ftell(fl) / (long)sizeof(int);
+        fseek(fl, 0, SEEK_SET);
+        snprintf(path, sizeof path, "%s/%03d.images_u8", dir, id);
+        FILE *fi = fopen(path, "rb");
+        int *labels = (int *)malloc((size_t)(n > 0 ? n : 1) * sizeof(int));
+        uint8_t *images = (uint8_t *)malloc((size_t)(n > 0 ? n : 1) * img);
+        MiLossMetrics m = {0};
+        int ok = fi && n > 0 && labels && images && fread(labels, sizeof(int), (size_t)n, fl) == (size_t)n &&
+                 fread(images, img, (size_t)n, fi) == (size_t)n;
+        if (!ok) fprintf(stderr, "validation shard %03d under %s is missing, empty or short\n", id, dir);
+        else if (mi_trainer_eval_u8(trainer, images, labels, n, dim_in, topk, &m)) { fprintf(stderr, "%s\n", mi_last_error()); ok = 0; }
+        fclose(fl);
+        if (fi) fclose(fi);
+        free(labels); free(images);
+        if (!ok) return -1;
+        sum.loss_sum += m.loss_sum; sum.rows += m.rows; sum.wrong_top1 += m.wrong_top1; sum.wrong_topk += m.wrong_topk; sum.batches += m.batches;
+    }
+    if (!sum.rows) { fprintf(stderr, "no %%03d.images_u8 / %%03d.labels under %s\n", dir); return -1; }
+    printf("Validation (%s) ----- Images: %lld, Avg. Loss: %.4f, Top-1 error: %.2f%%, Top-%d error: %.2f%%\n", when, (long long)sum.rows,
+           sum.loss_sum / (double)sum.rows, 100.0 * (double)sum.wrong_top1 / (double)sum.rows, topk, 100.0 * (double)sum.wrong_topk / (double)sum.rows);
+    return 0;
 }
 
 int main(int argc, char **argv) {
@@ -58,6 +95,8 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--device-loss")) device_loss = 1;
     const int loss_on_device = smoothing_arg || topk_arg || device_loss;
     const int TOPK = atoi(topk_arg ? topk_arg : "5");
+    const char *bn_momentum_arg = opt(argc, argv, "--bn-momentum", NULL), *val_u8 = opt(argc, argv, "--val-u8", NULL);
+    const int VAL_DIM_IN = atoi(opt(argc, argv, "--val-dim-in", "256")), VAL_EVERY = atoi(opt(argc, argv, "--val-every", "0"));
     const char *dump_root = opt(argc, argv, "--dump-root", NULL);
     const char *loss_log = opt(argc, argv, "--loss-log", "avg_loss_log.txt");
     const int resume_id = atoi(opt(argc, argv, "--resume", "-1"));           /* LOAD_FROM_DUMP_ID, resnet.cu:3299 */
@@ -94,6 +133,9 @@ int main(int argc, char **argv) {
     if (dump_root) mi_trainer_set_dump_root(trainer, dump_root); else mi_trainer_set_dump_every(trainer, 0);
     if (loss_on_device && mi_trainer_set_loss(trainer, (float)atof(smoothing_arg ? smoothing_arg : "0"), TOPK,
                                               MI_LOSS_DEVICE | (device_loss ? MI_LOSS_NO_PRED_COPY : 0))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    if ((bn_momentum_arg || val_u8) && mi_trainer_track_running_stats(trainer, 1, (float)atof(bn_momentum_arg ? bn_momentum_arg : "0.1"))) {
+        fprintf(stderr, "%s\n", mi_last_error()); return 1;
+    }
     if (resume_id != -1) { overwrite_trainer_hyperparams(trainer, resume_id, "my_custom"); overwrite_model_params(trainer, resume_id, "my_custom"); }
 
     FILE *loss_file = fopen(loss_log, "w");
@@ -103,6 +145,7 @@ int main(int argc, char **argv) {
     const float total_images_per_epoch = (float)BATCH_SIZE * iterations_per_epoch;
     int cur_iter_in_epoch = (trainer->cur_dump_id + 1) % iterations_per_epoch;
     int stop = 0;
+    long steps_done = 0;
     for (int epoch = trainer->cur_epoch; epoch < N_EPOCHS && !stop; epoch++) {
         float epoch_loss = 0, epoch_n_wrong = 0;
         for (int iter = cur_iter_in_epoch; iter < iterations_per_epoch; iter++) {
@@ -130,6 +173,8 @@ int main(int argc, char **argv) {
             backwards_pass(trainer);
             update_parameters(trainer);
             if (mi_last_error()[0]) { fprintf(stderr, "device error: %s\n", mi_last_error()); return 2; }
+            steps_done++;
+            if (val_u8 && VAL_EVERY > 0 && steps_done % VAL_EVERY == 0 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "step")) return 1;
         }
         if (stop) break;
         if (loss_on_device) {
@@ -140,6 +185,7 @@ int main(int argc, char **argv) {
                        total.loss_sum / (double)total.rows, 100.0 * (double)total.wrong_top1 / (double)total.rows, TOPK,
                        100.0 * (double)total.wrong_topk / (double)total.rows);
         }
+        if (val_u8 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "epoch")) return 1;
         /* resnet.cu:3410-3421: per-epoch loss (a SUM over the epoch) and accuracy, rewind the data source */
         mi_trainer_end_epoch(trainer, epoch_loss, epoch_n_wrong, total_images_per_epoch);
         cur_iter_in_epoch = 0;

@@ -474,6 +474,65 @@ int mi_op_loss_head(const float *logits, const int *labels, float *pred, float *
 enum { MI_LOSS_HOST = 0, MI_LOSS_DEVICE = 1, MI_LOSS_NO_PRED_COPY = 2 };
 int mi_trainer_set_loss(Train_ResNet *t, float smoothing, int topk, int flags);
 int mi_trainer_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total);
+
+/* ---------------- evaluation: batch-norm running statistics, the eval pass, validation metrics ----------------
+ * The reference normalises with the statistics of the batch it is given, always.  Everything here is off by default, and with
+ * nothing enabled every launch, value and file is what it was.  Nothing is folded into the convolution weights: the eval pass runs
+ * the convolutions of forward_pass and the apply half of its batch norm (mid_bn_apply_t) with other statistics.
+ *
+ * mi_trainer_track_running_stats(t, on, momentum): call after init_trainer (and after mi_trainer_set_dtype, if used) and before the
+ * first forward_pass.  Allocates one device arena [2][channels] of floats -- every layer's running means first, then every layer's
+ * running variances, the layers in the order their gamma tensors appear in Params.locations (the stem, then per block reduction,
+ * spatial, expansion, and projection where the block has one) -- with means 0, variances 1 and an update counter of 0.  While on,
+ * forward_pass ends its batch-norm work with ONE launch of bn_running_update_kernel (kernels_bn.hip) over all layers, one thread per
+ * channel, on the compute stream behind the last BN (under sync-BN it sees the merged statistics):
+ *   rm = (1 - m) rm + m mean,   rv = (1 - m) rv + m (var unbias)
+ * torch.nn.BatchNorm2d's rule: var = the biased batch variance Cache_BatchNorm.vars holds, unbias = mi_bn_unbias(n), n = batch_size x
+ * plane (x the world size under sync-BN).  The counter goes up by one per forward_pass.  on = 0 stops the updates and refuses the eval
+ * pass; the values stay, and on = 1 again goes on from them.  Returns 0, or -1 with mi_last_error set: momentum outside (0, 1].
+ * Data parallel without sync-BN: each rank keeps the running statistics of its own batches; they are not averaged.
+ * mi_bn_unbias (host-only, no GPU needed): n / (n - 1) computed in double and rounded to float; 1 where n <= 1.
+ * mi_op_bn_running_update: the kernel on its own.  Host arrays of n_layers device pointers means_dev[i], vars_dev[i] ([channels[i]]
+ * floats each), the channel counts and the sample counts n; running_dev = [2][running_channels] floats in device memory, layer i at the
+ * sum of the channel counts before it in both halves; words past the layers' sum belong to no layer and are not touched.  Returns 0,
+ * or -1 with mi_last_error set (checked before any device call): momentum outside (0, 1], no layer, a NULL array or pointer, a
+ * channel count or sample count < 1, more channels than running_channels. */
+int mi_trainer_track_running_stats(Train_ResNet *t, int on, float momentum);
+float mi_bn_unbias(int64_t n);
+int mi_op_bn_running_update(const float *const *means_dev, const float *const *vars_dev, const int *channels, const int64_t *counts, int n_layers,
+                            float *running_dev, int running_channels, float momentum);
+/* channels: the sum of the BN layers' channel counts (26 560 for ResNet-50), 0 before tracking was ever on.  get / set: host arrays
+ * of `channels` floats each, in the arena's order; they wait for the compute stream.  set refuses (-1, nothing written) a value that
+ * is not finite or a negative variance; both return -1 where tracking was never on.  mi_trainer_running_updates: the counter. */
+int mi_trainer_running_stats_channels(const Train_ResNet *t);
+int mi_trainer_get_running_stats(Train_ResNet *t, float *means, float *vars);
+int mi_trainer_set_running_stats(Train_ResNet *t, const float *means, const float *vars);
+int64_t mi_trainer_running_updates(const Train_ResNet *t);
+/* The eval pass.  images_dev: fp32 NCHW [batch_size][3][input][input], the layout of Batch.images (t->cur_batch->images is a valid
+ * argument); labels_dev: [batch_size] ints, or NULL for no metrics (pred is then written by the soft-max kernel).  It re-lays the
+ * weights and walks the layers of forward_pass through the same convolution calls -- the launches and the output bits of training --
+ * and behind each convolution the BN apply kernel with that layer's slice of the running arena: same gamma, beta and eps, same fused
+ * residual + ReLU, same channel-last second output.  Max-pool, average pool and FC as in training; then the loss head over the first
+ * n_valid rows only, smoothing 0, no dlogits (output_layer_deriv is not touched), pred written for those rows, into the trainer's own
+ * EVAL records (mi_trainer_eval_metrics), not those of mi_trainer_metrics.  All batch_size rows go through the network; without batch
+ * statistics no row sees another, so the rows from n_valid on change nothing.  It writes no Cache_BatchNorm.means / vars, running
+ * statistic, counter, parameter, gradient or optimizer state, copies nothing to the host and synchronises nothing.  It overwrites the
+ * stored activations of the last forward_pass: a backwards_pass behind it, with no new forward_pass in between, records an error in
+ * mi_last_error and launches nothing.  Returns 0, or -1 with mi_last_error set: tracking off, the FULL store policy, n_valid outside
+ * [1, batch_size], topk outside [1, output].
+ * mi_trainer_eval_metrics: mi_trainer_metrics on the eval records.
+ * mi_trainer_eval_u8: a whole host array of n images of dim_in x dim_in x 3 bytes (B,G,R, as the uint8 shards hold them) with n labels
+ * in ceil(n / batch_size) eval passes.  It zeroes the eval total; per batch it copies bytes, labels and the MI_AUG_CENTER plan of
+ * mi_augment_plan through pinned staging, decodes with the decode kernel into an image tensor of its own (Batch.images is not used),
+ * zero-fills the image rows from n_valid = min(batch_size, remaining) on and runs the eval pass; at the end it synchronises once and
+ * returns the total in *out (rows == n).  cur_dump_id, the Batch and the shard position are not touched.  -1 as the eval pass, and for
+ * n < 1 or dim_in below the network's input.
+ * Checkpoints: while tracking is on dump_trainer also writes <dump>/bn_running.buffer -- the arena's 2 x channels floats, then the
+ * counter as int64 -- and overwrite_model_params restores both where the file exists; with tracking off a dump is byte for byte what
+ * it was. */
+int mi_trainer_eval_forward(Train_ResNet *t, const float *images_dev, const int *labels_dev, int n_valid, int topk);
+int mi_trainer_eval_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total);
+int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk, MiLossMetrics *out);
 /* the SGD / LARS kernels on their own: p, g, b device arrays of n floats; tensor i starts at offsets_host[i] (n_tensors + 1 entries,
  * multiples of 4, the last <= n) and runs to the next offset; tensor_is_weight_host[i] 1: trust ratio and weight decay (LARS).
  * nan_flag_dev: device int or NULL.  sq_norms_out_host (optional, 2 n_tensors doubles): (|w|^2, |g|^2) per tensor before the update,

@@ -216,6 +216,16 @@ PROTOTYPES = {
     "mi_op_loss_head": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
     "mi_trainer_set_loss": (_i, [_T, _f, _i, _i]),
     "mi_trainer_metrics": (_i, [_T, C.POINTER(MiLossMetrics), C.POINTER(MiLossMetrics), _i]),
+    "mi_trainer_track_running_stats": (_i, [_T, _i, _f]),
+    "mi_bn_unbias": (_f, [C.c_int64]),
+    "mi_op_bn_running_update": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _f]),
+    "mi_trainer_running_stats_channels": (_i, [_T]),
+    "mi_trainer_get_running_stats": (_i, [_T, _vp, _vp]),
+    "mi_trainer_set_running_stats": (_i, [_T, _vp, _vp]),
+    "mi_trainer_running_updates": (C.c_int64, [_T]),
+    "mi_trainer_eval_forward": (_i, [_T, _vp, _vp, _i, _i]),
+    "mi_trainer_eval_metrics": (_i, [_T, C.POINTER(MiLossMetrics), C.POINTER(MiLossMetrics), _i]),
+    "mi_trainer_eval_u8": (_i, [_T, _vp, _vp, C.c_int64, _i, _i, C.POINTER(MiLossMetrics)]),
     "mi_op_momentum_update": (_i, [_i, _vp, _vp, _vp, _sz, _vp, _i, _vp, _f, _f, _f, _f, _vp, _vp]),
     "mi_trainer_nan_location": (_i, [_T]),
     "mi_trainer_stem_dtype": (_i, [_T]),

@@ -166,6 +166,42 @@ static void dump_meta_and_checkpoint(int dump_id, Train_ResNet *t, const char *s
     free(dir);
 }
 
+/* bn_running.buffer, only while running statistics are tracked (mi_trainer_track_running_stats): the arena's 2 * channels floats
+ * (running means, then running variances, the layers in the order of the BN gammas in locations[]), then the update counter as int64 */
+static char *running_stats_path(int dump_id, Train_ResNet *t, const char *special_dir) {
+    char *path = NULL;
+    return asprintf(&path, "%s/%s/%08d/bn_running.buffer", root_of(t), special_dir, dump_id) < 0 ? NULL : path;
+}
+static void dump_running_stats(int dump_id, Train_ResNet *t, const char *special_dir) {
+    const MiCtx *c = (const MiCtx *)t->backend_ctx;
+    if (!c->rs_on) return;
+    const size_t n = 2 * (size_t)c->rs_channels;
+    float *host = (float *)malloc(n * sizeof(float));
+    char *path = running_stats_path(dump_id, t, special_dir);
+    FILE *f = path && !mi_trainer_get_running_stats(t, host, host + c->rs_channels) ? fopen(path, "wb") : NULL;
+    const int64_t updates = c->rs_updates;
+    if (!f || fwrite(host, sizeof(float), n, f) != n || fwrite(&updates, sizeof updates, 1, f) != 1)
+        fprintf(stderr, "resnet_mi: cannot write %s\n", path ? path : "bn_running.buffer");
+    if (f) fclose(f);
+    free(path); free(host);
+}
+static void restore_running_stats(Train_ResNet *t, int dump_id, const char *special_dir) {
+    MiCtx *c = (MiCtx *)t->backend_ctx;
+    if (!c->rs_on) return;
+    char *path = running_stats_path(dump_id, t, special_dir);
+    FILE *f = path ? fopen(path, "rb") : NULL; /* a dump made without tracking has none: the statistics stay as they are */
+    free(path);
+    if (!f) return;
+    const size_t n = 2 * (size_t)c->rs_channels;
+    float *host = (float *)malloc(n * sizeof(float));
+    int64_t updates = 0;
+    if (fread(host, sizeof(float), n, f) == n && fread(&updates, sizeof updates, 1, f) == 1 &&
+        !mi_trainer_set_running_stats(t, host, host + c->rs_channels)) c->rs_updates = updates;
+    else fprintf(stderr, "resnet_mi: bn_running.buffer of dump %d does not fit this network (ignored)\n", dump_id);
+    fclose(f);
+    free(host);
+}
+
 /* resnet.cu:2755-2772 */
 void dump_trainer(int dump_id, Train_ResNet *t, const char *special_dir) {
     if (!special_dir) special_dir = "default";
@@ -176,6 +212,7 @@ void dump_trainer(int dump_id, Train_ResNet *t, const char *special_dir) {
     dump_activations(dump_id, t, t->forward_buffer->activations, 0, special_dir);
     dump_activations(dump_id, t, t->backprop_buffer->activation_derivs, 1, special_dir);
     dump_meta_and_checkpoint(dump_id, t, special_dir);
+    dump_running_stats(dump_id, t, special_dir);
 }
 
 /* resnet.cu:2778-2817 */
@@ -213,4 +250,5 @@ void overwrite_model_params(Train_ResNet *t, int dump_id, const char *special_di
         }
         free(host);
     }
+    restore_running_stats(t, dump_id, special_dir);
 }

@@ -511,6 +511,30 @@ __global__ void bn_sync_emul_allreduce(float *__restrict__ bufs, int R, size_t s
     for (int r = 0; r < R; r++) bufs[(size_t)r * stride + i] = s;
 }
 
+// ---- running statistics (torch.nn.BatchNorm2d's rule; the reference has none) ----
+// One launch for every BN layer of a network: thread g owns channel c = g - first of the table entry whose [first, first + C) holds g
+// (entries ascend in first, the host builds them so), and the two arena words off + c of the mean half and of the variance half:
+//   rm = (1 - m) rm + m mean,   rv = (1 - m) rv + m (var unbias)
+// with var the biased batch variance the cache holds and unbias = n / (n - 1) from the host.  Plain fp32, no atomics: every arena word
+// of a layer is written by exactly one thread, words of no layer are not touched, nothing is read outside the table and its tensors.
+__global__ void __launch_bounds__(256)
+bn_running_update_kernel(const mid_bn_run_entry *__restrict__ tab, int n_layers, int channels, float *__restrict__ arena, size_t half, float m) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= channels) return;
+    int lo = 0, hi = n_layers - 1; /* the last entry with first <= g */
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].first <= g) lo = mid; else hi = mid - 1;
+    }
+    const mid_bn_run_entry e = tab[lo];
+    const int c = g - e.first;
+    if (c < 0 || c >= e.C) return;
+    const size_t o = (size_t)e.off + (size_t)c;
+    const float om = 1.f - m;
+    arena[o] = om * arena[o] + m * e.means[c];
+    arena[half + o] = om * arena[half + o] + m * (e.vars[c] * e.unbias);
+}
+
 // dtype codes of the storage types: MID_F32 / MID_BF16 (mi_device.h).  Supported (x, activation) pairs: (f32, f32) the
 // reference's path, (bf16, bf16) the bf16-activation path, (f32, bf16) its stem (the 7x7 convolution keeps fp32 tensors).
 static int bn_vec(int x_dt, int a_dt, int P) {
@@ -821,5 +845,16 @@ int mid_bn_bwd_gate(mid_stream s, float *ws, const float *x, const float *gamma,
                     const float *vars, const float *dy, const float *mask_src, float *gated_out, float *dx, float *dgamma,
                     float *dbeta, int N, int C, int P, float eps) {
     return bn_bwd_impl((hipStream_t)s, ws, x, MID_F32, gamma, beta, means, vars, dy, mask_src, gated_out, MID_F32, dx, dgamma, dbeta, N, C, P, eps, 3);
+}
+
+/* the running statistics of n_layers BN layers in one launch (bn_running_update_kernel).  tab_dev: the layers in device memory, first
+ * ascending from 0 without gaps (first[i + 1] = first[i] + C[i]), channels = their sum; arena = [2][half] floats, the means half then the
+ * variances half, layer i at off[i] .. off[i] + C[i] <= half of both.  The caller's table is trusted: it is built by the two host
+ * functions that check it (mi_op_bn_running_update, the trainer). */
+int mid_bn_running_update(mid_stream s, const mid_bn_run_entry *tab_dev, int n_layers, int channels, float *arena, size_t half, float momentum) {
+    if (n_layers < 1 || channels < 1 || !tab_dev || !arena) { mi_record_error("mid_bn_running_update", "no layers"); return -2; }
+    hipLaunchKernelGGL(bn_running_update_kernel, dim3(mi_cdiv(channels, 256)), dim3(256), 0, (hipStream_t)s, tab_dev, n_layers, channels, arena, half, momentum);
+    MI_LAUNCH_CHECK("bn_running_update_kernel");
+    return 0;
 }
 }

@@ -268,6 +268,15 @@ int mi_layer_bn_fwd(const MiLayer *L, MiLayerWs *w, mid_stream s, const mid_bn_p
     return mid_bn_fwd_t(s, w->bn_ws, parts, conv_out, L->out_dt, gamma, beta, residual, means, vars, y, L->dtype, xhat_out, norm_out, L->N,
                         L->K, Ho * Ho, eps, relu, ycl, Hcl);
 }
+/* the same apply with GIVEN statistics (the eval pass: a layer's running means / variances): the kernel, the storage types and the
+ * channel-last side output of mi_layer_bn_fwd, no reduction, means / vars only read */
+int mi_layer_bn_apply(const MiLayer *L, mid_stream s, const void *conv_out, const float *gamma, const float *beta, const void *residual,
+                      const float *means, const float *vars, void *y, float eps, int relu, const MiLayer *cl_reader) {
+    const int Ho = L->H / L->stride;
+    void *ycl = cl_reader && cl_reader->cl_by_bn ? cl_reader->cl : NULL;
+    const int Hcl = ycl ? (cl_reader->stride == 2 ? -cl_reader->H : cl_reader->H) : 0;
+    return mid_bn_apply_t(s, conv_out, L->out_dt, gamma, beta, residual, means, vars, y, L->dtype, L->N, L->K, Ho * Ho, eps, relu, ycl, Hcl);
+}
 
 /* the channel-last copy of dy that the channel-last dgrad AND the weight gradient read */
 int mi_layer_dy_relayout(const MiLayer *L, mid_stream s, const void *dy) {

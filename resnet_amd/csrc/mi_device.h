@@ -247,6 +247,11 @@ int mid_bn_debug_merge(mid_stream s, int R, int C, float *means, float *vars, fl
 int mid_bn_stats_t(mid_stream s, float *stats_ws, const void *x, int x_dt, float *means, float *vars, int N, int C, int P);
 int mid_bn_apply_t(mid_stream s, const void *x, int x_dt, const float *gamma, const float *beta, const void *residual,
                    const float *means, const float *vars, void *y, int a_dt, int N, int C, int P, float eps, int relu, void *ycl, int Hcl);
+/* running statistics (kernels_bn.hip, bn_running_update_kernel): one entry per BN layer -- the layer's batch statistics, its first
+ * thread (= the sum of the channel counts before it), its offset into both halves of the running arena, its channels and
+ * unbias = n / (n - 1).  One launch updates every layer: rm = (1 - m) rm + m mean, rv = (1 - m) rv + m (var unbias) */
+typedef struct { const float *means, *vars; int first, off, C; float unbias; } mid_bn_run_entry;
+int mid_bn_running_update(mid_stream s, const mid_bn_run_entry *tab_dev, int n_layers, int channels, float *arena, size_t half, float momentum);
 /* mask_mode 0..2 as mid_bn_bwd; 3 = mid_bn_bwd_gate */
 int mid_bn_bwd_t(mid_stream s, float *stats_ws, const void *x, int x_dt, const float *gamma, const float *beta, const float *means,
                  const float *vars, const void *dy, const void *mask_src, void *gated_out, int a_dt, void *dx, float *dgamma,

@@ -118,6 +118,8 @@ int mi_layer_fwd(MiLayer *L, MiLayerWs *w, mid_stream s, const void *x, void *y,
 int mi_layer_bn_fwd(const MiLayer *L, MiLayerWs *w, mid_stream s, const mid_bn_parts *parts, const void *conv_out, const float *gamma,
                     const float *beta, const void *residual, float *means, float *vars, void *y, float *xhat_out, float *norm_out, float eps,
                     int relu, const MiLayer *cl_reader);
+int mi_layer_bn_apply(const MiLayer *L, mid_stream s, const void *conv_out, const float *gamma, const float *beta, const void *residual,
+                      const float *means, const float *vars, void *y, float eps, int relu, const MiLayer *cl_reader);
 int mi_layer_dy_relayout(const MiLayer *L, mid_stream s, const void *dy); /* dy into L->dye, before the dgrad and the weight gradient */
 const mid_bn_bwd_parts *mi_layer_fz_request(const MiLayer *L, const MiLayerWs *w, mid_bn_bwd_parts *r, const void *x, const void *mask,
                                             const float *means);
@@ -190,6 +192,24 @@ typedef struct MiCtx {
     float loss_smoothing; int loss_topk, loss_flags;
     float *loss_row; int *loss_rank;
     mid_loss_metrics *loss_metrics;
+    /* mi_trainer_track_running_stats (all NULL / 0 while off; none of it is tracked in allocs[]: it survives a rebuild of the
+     * buffers): the arena [2][rs_channels] (running means, then running variances, layers in the order of the BN gammas in
+     * Params.locations), the per-layer table of bn_running_update_kernel on the device, each layer's offset on the host, the number
+     * of forward_pass updates so far; the eval pass's own loss-head rows and records (last, total); acts_from_eval: the stored
+     * activations are an eval pass's, backwards_pass refuses them */
+    int rs_on, rs_layers, rs_channels, *rs_off;
+    float rs_momentum, *rs_arena;
+    mid_bn_run_entry *rs_tab_dev;
+    int64_t rs_updates;
+    float *eval_row; int *eval_rank;
+    mid_loss_metrics *eval_metrics;
+    int acts_from_eval;
+    /* mi_trainer_eval_u8: scratch of its own -- the decoded batch, and bytes / labels / plan on the device and pinned; the event
+     * behind the last copies out of the pinned set */
+    int ev8_dim_in;
+    float *ev8_images; uint8_t *ev8_bytes_dev, *ev8_bytes_pinned;
+    int *ev8_labels_dev, *ev8_labels_pinned, *ev8_plan_dev, *ev8_plan_pinned;
+    mid_event ev8_copied;
     unsigned long host_epoch_seen; /* the process-wide host-write count (mi_copy_to_device) that re-layout was made at */
     char *dump_root;
     /* every device allocation of this trainer (freed by destroy_trainer) */

@@ -140,6 +140,37 @@ int mi_op_loss_head(const float *logits, const int *labels, float *pred, float *
     mid_free(rl); mid_free(rr);
     return rc;
 }
+/* n / (n - 1) of a batch-norm layer whose statistics are taken over n samples per channel, in double, stored as float; 1 where n <= 1 */
+float mi_bn_unbias(int64_t n) { return n > 1 ? (float)((double)n / (double)(n - 1)) : 1.f; }
+/* bn_running_update_kernel on its own: the table built and checked here (layer i at the sum of the channel counts before it) */
+int mi_op_bn_running_update(const float *const *means_dev, const float *const *vars_dev, const int *channels, const int64_t *counts, int n_layers,
+                            float *running_dev, int running_channels, float momentum) {
+    const char *who = "mi_op_bn_running_update";
+    if (!(momentum > 0.f && momentum <= 1.f)) { mi_record_host_error(who, "momentum lies in (0, 1]"); return -1; }
+    if (n_layers < 1 || !means_dev || !vars_dev || !channels || !counts || !running_dev) { mi_record_host_error(who, "at least one layer, no NULL array"); return -1; }
+    int64_t sum = 0;
+    for (int i = 0; i < n_layers; i++) {
+        if (channels[i] < 1 || !means_dev[i] || !vars_dev[i]) { mi_record_host_error(who, "every layer has at least one channel and both statistics"); return -1; }
+        if (counts[i] < 1) { mi_record_host_error(who, "every count is at least 1"); return -1; }
+        sum += channels[i];
+    }
+    if (sum > (int64_t)running_channels) { mi_record_host_error(who, "the layers' channels exceed running_channels"); return -1; }
+    mid_bn_run_entry *tab = (mid_bn_run_entry *)malloc(sizeof(mid_bn_run_entry) * (size_t)n_layers);
+    int first = 0;
+    for (int i = 0; i < n_layers; i++) {
+        tab[i].means = means_dev[i]; tab[i].vars = vars_dev[i]; tab[i].first = tab[i].off = first; tab[i].C = channels[i];
+        tab[i].unbias = mi_bn_unbias(counts[i]);
+        first += channels[i];
+    }
+    mid_stream s = mi_global()->compute;
+    mid_bn_run_entry *tab_dev = (mid_bn_run_entry *)mid_malloc(sizeof(mid_bn_run_entry) * (size_t)n_layers);
+    if (!tab_dev) { free(tab); return -3; }
+    mid_memcpy_h2d(tab_dev, tab, sizeof(mid_bn_run_entry) * (size_t)n_layers, s);
+    const int rc = finish(mid_bn_running_update(s, tab_dev, n_layers, (int)sum, running_dev, (size_t)running_channels, momentum));
+    mid_free(tab_dev);
+    free(tab);
+    return rc;
+}
 int mi_op_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, float wd, float b1, float b2, float cur_b1,
                float cur_b2, float eps, int *nan_flag_dev) {
     return finish(mid_adam(mi_global()->compute, p, (float *)g, m, v, n, lr, wd, b1, b2, cur_b1, cur_b2, eps, nan_flag_dev, 0, NULL, 0, 0));

@@ -408,6 +408,7 @@ static void size_workspaces(MiCtx *c, const Dims *d) {
 static MiCtx *ctx_of(Train_ResNet *t) { return (MiCtx *)t->backend_ctx; }
 static void free_activations_host(Activations *a);
 static void add_full_store_extras(Train_ResNet *t);
+static void rs_build_table(Train_ResNet *t);
 /* everything whose size or layout depends on the storage type / store policy: activation trees, derivative buffers,
  * workspaces, re-laid weight tables.  Called by init_trainer and again by mi_trainer_set_dtype / _set_store_policy. */
 static void build_buffers(Train_ResNet *t) {
@@ -441,6 +442,7 @@ static void build_buffers(Train_ResNet *t) {
     plan_layers(c, t->model->params, d, N);
     size_workspaces(c, d);
     mid_stream_sync(G.compute);
+    rs_build_table(t); /* (the caches the running-statistics table points at were rebuilt) */
 }
 static void drop_buffers(Train_ResNet *t) {
     MiCtx *c = (MiCtx *)t->backend_ctx;
@@ -736,6 +738,7 @@ void forward_pass(Train_ResNet *t) {
     const int N = t->batch_size, f = d->init_conv_filters;
     mid_event_record(c->ev_t[0], G.compute);
     bind_sync_bn(c);
+    c->acts_from_eval = 0;
     relayout_weights(c);
     unit_fwd(t, &c->stem, t->cur_batch->images, p->norm_init_conv, a->norm_init_conv, a->init_conv_applied, a->init_conv_activated,
              NULL, 1, NULL);
@@ -767,6 +770,11 @@ void forward_pass(Train_ResNet *t) {
                             (size_t)N * b->expanded_depth * Ho * Ho), "add + ReLU");
         }
         bin = k->output_activated;
+    }
+    if (c->rs_on) { /* behind the last BN of the pass (under sync-BN: the merged statistics), every layer's running statistics in one launch */
+        ck(mid_bn_running_update(G.compute, c->rs_tab_dev, c->rs_layers, c->rs_channels, c->rs_arena, (size_t)c->rs_channels, c->rs_momentum),
+           "running statistics");
+        c->rs_updates++;
     }
     const ConvBlock *last = p->conv_blocks[d->n_conv_blocks - 1];
     const int Hl = last->incoming_spatial_dim; /* resnet.cu:1732 */
@@ -834,6 +842,225 @@ float mi_host_loss(Train_ResNet *t, int *n_wrong) {
     return loss;
 }
 
+/* ---------------------------------------------------------------------------------------------- */
+/* Evaluation (resnet_mi.h): running statistics of every batch norm, the eval pass, its metrics. */
+typedef struct { const BatchNorm *bn; const Cache_BatchNorm *cache; } RsLayer;
+/* the BN layers in the order of their gammas in Params.locations: the stem, then per block reduction, spatial, expansion, projection */
+static int rs_collect(const Train_ResNet *t, RsLayer *out) {
+    const Params *p = t->model->params;
+    const Activations *a = t->forward_buffer->activations;
+    int n = 0;
+    out[n].bn = p->norm_init_conv; out[n++].cache = a->norm_init_conv;
+    for (int i = 0; i < t->model->dims->n_conv_blocks; i++) {
+        const ConvBlock *b = p->conv_blocks[i];
+        const Activation_ConvBlock *k = a->activation_conv_blocks[i];
+        out[n].bn = b->norm_depth_reduction; out[n++].cache = k->norm_post_reduced;
+        out[n].bn = b->norm_spatial; out[n++].cache = k->norm_post_spatial;
+        out[n].bn = b->norm_expansion; out[n++].cache = k->norm_post_expanded;
+        if (b->projection) { out[n].bn = b->norm_projection; out[n++].cache = k->norm_post_projection; }
+    }
+    return n;
+}
+/* the device table of bn_running_update_kernel: whenever the caches are rebuilt (build_buffers) or the sample count changes (sync-BN) */
+static void rs_build_table(Train_ResNet *t) {
+    MiCtx *c = ctx_of(t);
+    if (!c->rs_arena) return;
+    RsLayer *ls = (RsLayer *)malloc(sizeof(RsLayer) * (size_t)(4 * t->model->dims->n_conv_blocks + 1));
+    const int n = rs_collect(t, ls);
+    mid_bn_run_entry *tab = (mid_bn_run_entry *)malloc(sizeof(mid_bn_run_entry) * (size_t)n);
+    const int64_t world = c->sync_bn && c->sync_bn_comm ? c->world : 1; /* sync-BN: the statistics are those of every replica's samples */
+    for (int i = 0; i < n; i++) {
+        const int64_t cnt = (int64_t)t->batch_size * ls[i].bn->spatial_dim * ls[i].bn->spatial_dim * world;
+        tab[i].means = ls[i].cache->means; tab[i].vars = ls[i].cache->vars;
+        tab[i].first = tab[i].off = c->rs_off[i]; tab[i].C = ls[i].bn->depth; tab[i].unbias = mi_bn_unbias(cnt);
+    }
+    mid_memcpy_h2d(c->rs_tab_dev, tab, sizeof(mid_bn_run_entry) * (size_t)n, G.compute);
+    mid_stream_sync(G.compute);
+    free(tab); free(ls);
+}
+int mi_trainer_track_running_stats(Train_ResNet *t, int on, float momentum) {
+    MiCtx *c = ctx_of(t);
+    if (!on) { c->rs_on = 0; return 0; }
+    if (!(momentum > 0.f && momentum <= 1.f)) { mi_record_host_error("mi_trainer_track_running_stats", "momentum lies in (0, 1]"); return -1; }
+    if (!c->rs_arena) { /* the first time: means 0, variances 1, no update yet (switched off and on again, the values stay) */
+        RsLayer *ls = (RsLayer *)malloc(sizeof(RsLayer) * (size_t)(4 * t->model->dims->n_conv_blocks + 1));
+        const int n = rs_collect(t, ls);
+        c->rs_off = (int *)malloc(sizeof(int) * (size_t)(n + 1));
+        int sum = 0;
+        for (int i = 0; i < n; i++) { c->rs_off[i] = sum; sum += ls[i].bn->depth; }
+        c->rs_off[n] = sum;
+        free(ls);
+        c->rs_layers = n; c->rs_channels = sum; c->rs_updates = 0;
+        c->rs_tab_dev = (mid_bn_run_entry *)mid_malloc(sizeof(mid_bn_run_entry) * (size_t)n);
+        c->eval_row = (float *)mid_malloc(sizeof(float) * (size_t)t->batch_size);
+        c->eval_rank = (int *)mid_malloc(sizeof(int) * (size_t)t->batch_size);
+        c->eval_metrics = (mid_loss_metrics *)mid_malloc(2 * sizeof(mid_loss_metrics));
+        float *one = (float *)malloc(sizeof(float) * (size_t)sum);
+        for (int i = 0; i < sum; i++) one[i] = 1.f;
+        c->rs_arena = (float *)mid_malloc(2 * sizeof(float) * (size_t)sum);
+        if (!c->rs_tab_dev || !c->eval_row || !c->eval_rank || !c->eval_metrics || !c->rs_arena) {
+            mi_record_host_error("mi_trainer_track_running_stats", "device allocation failed");
+            mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics); mid_free(c->rs_arena);
+            c->rs_tab_dev = NULL; c->eval_row = NULL; c->eval_rank = NULL; c->eval_metrics = NULL; c->rs_arena = NULL;
+            free(one); free(c->rs_off); c->rs_off = NULL;
+            return -1;
+        }
+        mid_memset(c->rs_arena, 0, sizeof(float) * (size_t)sum, G.compute);
+        mid_memcpy_h2d(c->rs_arena + sum, one, sizeof(float) * (size_t)sum, G.compute);
+        mid_memset(c->eval_metrics, 0, 2 * sizeof(mid_loss_metrics), G.compute);
+        mid_stream_sync(G.compute);
+        free(one);
+        rs_build_table(t);
+    }
+    c->rs_on = 1; c->rs_momentum = momentum;
+    return 0;
+}
+int mi_trainer_running_stats_channels(const Train_ResNet *t) { return ((const MiCtx *)t->backend_ctx)->rs_channels; }
+int64_t mi_trainer_running_updates(const Train_ResNet *t) { return ((const MiCtx *)t->backend_ctx)->rs_updates; }
+int mi_trainer_get_running_stats(Train_ResNet *t, float *means, float *vars) {
+    MiCtx *c = ctx_of(t);
+    if (!c->rs_arena) { mi_record_host_error("mi_trainer_get_running_stats", "running statistics are not tracked (mi_trainer_track_running_stats)"); return -1; }
+    const size_t b = sizeof(float) * (size_t)c->rs_channels;
+    if (means) mid_memcpy_d2h(means, c->rs_arena, b, G.compute);
+    if (vars) mid_memcpy_d2h(vars, c->rs_arena + c->rs_channels, b, G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+int mi_trainer_set_running_stats(Train_ResNet *t, const float *means, const float *vars) {
+    MiCtx *c = ctx_of(t);
+    if (!c->rs_arena) { mi_record_host_error("mi_trainer_set_running_stats", "running statistics are not tracked (mi_trainer_track_running_stats)"); return -1; }
+    if (!means || !vars) { mi_record_host_error("mi_trainer_set_running_stats", "means and vars are both needed"); return -1; }
+    for (int i = 0; i < c->rs_channels; i++) {
+        if (!isfinite(means[i]) || !isfinite(vars[i])) { mi_record_host_error("mi_trainer_set_running_stats", "a value is not finite"); return -1; }
+        if (vars[i] < 0.f) { mi_record_host_error("mi_trainer_set_running_stats", "a variance is negative"); return -1; }
+    }
+    const size_t b = sizeof(float) * (size_t)c->rs_channels;
+    mid_memcpy_h2d(c->rs_arena, means, b, G.compute);
+    mid_memcpy_h2d(c->rs_arena + c->rs_channels, vars, b, G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+
+/* unit_fwd with the layer's running statistics in place of the batch's: the same convolution call (its statistics partials are
+ * left unused), then the apply kernel alone.  li: the layer's index in the running arena */
+static void unit_eval(Train_ResNet *t, MiLayer *L, int li, const float *in, const BatchNorm *bn, float *conv_out, float *act_out,
+                      const float *residual, int relu, const MiLayer *cl_reader) {
+    MiCtx *c = ctx_of(t);
+    const int bf_ops = L->fwd == MI_FWD_BF16 || L->fwd == MI_FWD_CL || L->fwd == MI_FWD_STEM_BF16;
+    mid_bn_parts *parts = (c->opt.bnfuse || bf_ops) ? &c->lw.bn_parts : NULL;
+    const float *rm = c->rs_arena + c->rs_off[li], *rv = rm + c->rs_channels;
+    ck(mi_layer_fwd(L, &c->lw, G.compute, in, conv_out, parts), "convolution forward");
+    ck(mi_layer_bn_apply(L, G.compute, conv_out, bn->gamma, bn->beta, residual, rm, rv, act_out, t->eps, relu, cl_reader), "batch norm (running statistics)");
+}
+static int eval_args_ok(const Train_ResNet *t, const char *who, int n_valid, int topk) {
+    const MiCtx *c = (const MiCtx *)t->backend_ctx;
+    if (!c->rs_on) { mi_record_host_error(who, "running statistics are not tracked (mi_trainer_track_running_stats)"); return -1; }
+    if (c->policy == MI_STORE_FULL) { mi_record_host_error(who, "the eval pass does not run under the FULL store policy"); return -1; }
+    if (n_valid < 1 || n_valid > t->batch_size) { mi_record_host_error(who, "n_valid lies in [1, batch_size]"); return -1; }
+    if (topk < 1 || topk > t->model->dims->output) { mi_record_host_error(who, "topk lies in [1, number of classes]"); return -1; }
+    return 0;
+}
+int mi_trainer_eval_forward(Train_ResNet *t, const float *images_dev, const int *labels_dev, int n_valid, int topk) {
+    MiCtx *c = ctx_of(t);
+    if (eval_args_ok(t, "mi_trainer_eval_forward", n_valid, topk)) return -1;
+    if (!images_dev) { mi_record_host_error("mi_trainer_eval_forward", "no images"); return -1; }
+    const Dims *d = t->model->dims;
+    const Params *p = t->model->params;
+    Activations *a = t->forward_buffer->activations;
+    const int N = t->batch_size, f = d->init_conv_filters, Hs = d->input / d->init_conv_stride;
+    int li = 0;
+    c->acts_from_eval = 1; /* the stored activations are no longer those of a forward_pass */
+    relayout_weights(c);
+    unit_eval(t, &c->stem, li++, images_dev, p->norm_init_conv, a->init_conv_applied, a->init_conv_activated, NULL, 1, NULL);
+    ck(mid_maxpool_fwd_t(G.compute, a->init_conv_activated, a->init_convblock_input, c->dtype, a->max_inds, N, f, Hs, d->init_maxpool_dim,
+                         d->init_maxpool_stride), "max-pool forward");
+    const float *bin = a->init_convblock_input;
+    for (int i = 0; i < d->n_conv_blocks; i++) {
+        const ConvBlock *b = p->conv_blocks[i];
+        MiBlockLayers *B = &c->blk[i];
+        Activation_ConvBlock *k = a->activation_conv_blocks[i];
+        const int l_red = li, l_spa = li + 1, l_exp = li + 2, l_proj = li + 3;
+        li += b->projection ? 4 : 3;
+        unit_eval(t, &B->red, l_red, bin, b->norm_depth_reduction, k->post_reduced, k->post_reduced_activated, NULL, 1, &B->spa);
+        unit_eval(t, &B->spa, l_spa, k->post_reduced_activated, b->norm_spatial, k->post_spatial, k->post_spatial_activated, NULL, 1, NULL);
+        const float *res = bin;
+        if (b->projection) {
+            unit_eval(t, &B->proj, l_proj, bin, b->norm_projection, k->transformed_residual, k->post_projection_norm_vals, NULL, 0, NULL);
+            res = k->post_projection_norm_vals;
+        }
+        unit_eval(t, &B->exp, l_exp, k->post_spatial_activated, b->norm_expansion, k->post_expanded, k->output_activated, res, 0,
+                  i + 1 < d->n_conv_blocks ? &c->blk[i + 1].proj : NULL);
+        bin = k->output_activated;
+    }
+    const int Hl = p->conv_blocks[d->n_conv_blocks - 1]->incoming_spatial_dim;
+    ck(mid_avgpool_fwd_t(G.compute, bin, c->dtype, a->final_conv_output_pooled, N, d->final_depth, Hl * Hl), "average pool");
+    ck(mid_gemm_nn(G.compute, a->final_conv_output_pooled, p->fully_connected, a->linear_output, N, d->final_depth, d->output), "FC forward");
+    /* the head over the valid rows only: pred, row losses and ranks, the eval records; no dlogits */
+    if (labels_dev)
+        ck(mid_loss_head(G.compute, a->linear_output, labels_dev, t->forward_buffer->pred, NULL, c->eval_row, c->eval_rank, n_valid, d->output, 0.f, topk,
+                         c->eval_metrics, c->eval_metrics + 1), "loss head (eval)");
+    else ck(mid_softmax(G.compute, a->linear_output, t->forward_buffer->pred, n_valid, d->output), "soft-max");
+    return 0;
+}
+int mi_trainer_eval_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
+    MiCtx *c = ctx_of(t);
+    if (!c->eval_metrics) { mi_record_host_error("mi_trainer_eval_metrics", "running statistics are not tracked (mi_trainer_track_running_stats)"); return -1; }
+    if (last) mid_memcpy_d2h(last, c->eval_metrics, sizeof *last, G.compute);
+    if (total) mid_memcpy_d2h(total, c->eval_metrics + 1, sizeof *total, G.compute);
+    if (reset_total) mid_memset(c->eval_metrics + 1, 0, sizeof(mid_loss_metrics), G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+static void ev8_free(MiCtx *c) {
+    mid_free(c->ev8_images); mid_free(c->ev8_bytes_dev); mid_free(c->ev8_labels_dev); mid_free(c->ev8_plan_dev);
+    mid_free_host(c->ev8_bytes_pinned); mid_free_host(c->ev8_labels_pinned); mid_free_host(c->ev8_plan_pinned);
+    c->ev8_images = NULL; c->ev8_bytes_dev = NULL; c->ev8_labels_dev = NULL; c->ev8_plan_dev = NULL;
+    c->ev8_bytes_pinned = NULL; c->ev8_labels_pinned = NULL; c->ev8_plan_pinned = NULL; c->ev8_dim_in = 0;
+}
+int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk, MiLossMetrics *out) {
+    MiCtx *c = ctx_of(t);
+    const char *who = "mi_trainer_eval_u8";
+    const int N = t->batch_size, D = t->model->dims->input;
+    if (eval_args_ok(t, who, 1, topk)) return -1;
+    if (!images_host || !labels_host || n < 1) { mi_record_host_error(who, "images, labels and n >= 1 are needed"); return -1; }
+    if (dim_in < D) { mi_record_host_error(who, "dim_in is smaller than the network's input"); return -1; }
+    const size_t img = (size_t)dim_in * dim_in * 3, out_img = (size_t)D * D * 3;
+    if (c->ev8_dim_in != dim_in) {
+        mid_device_sync();
+        ev8_free(c);
+        c->ev8_images = (float *)mid_malloc((size_t)N * out_img * sizeof(float));
+        c->ev8_bytes_dev = (uint8_t *)mid_malloc((size_t)N * img);
+        c->ev8_labels_dev = (int *)mid_malloc((size_t)N * sizeof(int));
+        c->ev8_plan_dev = (int *)mid_malloc((size_t)N * 3 * sizeof(int));
+        c->ev8_bytes_pinned = (uint8_t *)mid_malloc_host((size_t)N * img);
+        c->ev8_labels_pinned = (int *)mid_malloc_host((size_t)N * sizeof(int));
+        c->ev8_plan_pinned = (int *)mid_malloc_host((size_t)N * 3 * sizeof(int));
+        if (!c->ev8_images || !c->ev8_bytes_dev || !c->ev8_labels_dev || !c->ev8_plan_dev || !c->ev8_bytes_pinned || !c->ev8_labels_pinned ||
+            !c->ev8_plan_pinned) { ev8_free(c); mi_record_host_error(who, "allocation of the staging buffers failed"); return -1; }
+        if (!c->ev8_copied) c->ev8_copied = mid_event_create();
+        c->ev8_dim_in = dim_in;
+    }
+    mid_memset(c->eval_metrics + 1, 0, sizeof(mid_loss_metrics), G.compute);
+    for (int64_t at = 0; at < n; at += N) {
+        const int nv = n - at < N ? (int)(n - at) : N;
+        if (at) mid_event_sync(c->ev8_copied); /* the pinned set is free again once the last batch's copies have left it */
+        if (mi_augment_plan(MI_AUG_CENTER, 0, 0, 0, at, nv, dim_in, D, NULL, c->ev8_plan_pinned)) return -1;
+        memcpy(c->ev8_bytes_pinned, images_host + (size_t)at * img, (size_t)nv * img);
+        memcpy(c->ev8_labels_pinned, labels_host + at, (size_t)nv * sizeof(int));
+        mid_memcpy_h2d(c->ev8_bytes_dev, c->ev8_bytes_pinned, (size_t)nv * img, G.compute);
+        mid_memcpy_h2d(c->ev8_labels_dev, c->ev8_labels_pinned, (size_t)nv * sizeof(int), G.compute);
+        mid_memcpy_h2d(c->ev8_plan_dev, c->ev8_plan_pinned, (size_t)nv * 3 * sizeof(int), G.compute);
+        mid_event_record(c->ev8_copied, G.compute);
+        if (mid_decode_u8(G.compute, c->ev8_bytes_dev, c->ev8_plan_dev, c->ev8_images, nv, dim_in, D)) return -1;
+        if (nv < N) mid_memset(c->ev8_images + (size_t)nv * out_img, 0, (size_t)(N - nv) * out_img * sizeof(float), G.compute);
+        if (mi_trainer_eval_forward(t, c->ev8_images, c->ev8_labels_dev, nv, topk)) return -1;
+    }
+    MiLossMetrics total;
+    if (mi_trainer_eval_metrics(t, NULL, &total, 0)) return -1; /* the one synchronise */
+    if (out) *out = total;
+    return 0;
+}
+
 /* BN' (+fused ReLU') then conv' : prepareAndDoActivationAndBatchNormDeriv + prepreAndDoConvolutionDeriv */
 /* the aux stream must have finished the previous weight gradient before a dgrad may overwrite the rolling buffer it reads */
 static void join_wgrad(MiCtx *c) {
@@ -896,6 +1123,10 @@ void backwards_pass(Train_ResNet *t) {
     Activations *da = bb->activation_derivs;
     const int N = t->batch_size, L = d->output, D = d->final_depth, nb = d->n_conv_blocks;
     const int recompute = c->policy == MI_STORE_RECOMPUTE_BN;
+    if (c->acts_from_eval) { /* the stored activations are an eval pass's (running statistics): no gradient of any loss */
+        mi_record_host_error("backwards_pass", "the last pass was mi_trainer_eval_forward: run forward_pass first");
+        return;
+    }
     mid_event_record(c->ev_t[2], G.compute);
     bind_sync_bn(c);
     if (weights_stale(c)) relayout_weights(c); /* parameters were rewritten from the host after forward_pass */
@@ -1289,6 +1520,10 @@ void destroy_trainer(Train_ResNet *t) {
     free(t->model->dims); free(t->model);
     free(t->loss_per_epoch); free(t->accuracy_per_epoch);
     mi_optim_free(&c->optim);
+    mid_free(c->rs_arena); mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics);
+    free(c->rs_off);
+    ev8_free(c);
+    if (c->ev8_copied) mid_event_destroy(c->ev8_copied);
     free(c->loc_off);
     free(c->dump_root); free(c->blk); free(c);
     free(t);
@@ -1314,14 +1549,15 @@ void mi_dp_set_bucket_bytes(Train_ResNet *t, size_t bytes) { ctx_of(t)->bucket_b
  * broadcast like the first.  With it, DP-N equals one replica at batch N x 256 up to summation order. */
 int mi_dp_enable_sync_bn(Train_ResNet *t, const void *unique_id, int bytes) {
     MiCtx *c = ctx_of(t);
-    if (!unique_id) { c->sync_bn = 0; mid_bn_set_sync(NULL, 1, NULL, 0, 0); return 0; }
-    if (c->sync_bn_comm) { c->sync_bn = 1; return 0; }
+    if (!unique_id) { c->sync_bn = 0; mid_bn_set_sync(NULL, 1, NULL, 0, 0); rs_build_table(t); return 0; }
+    if (c->sync_bn_comm) { c->sync_bn = 1; rs_build_table(t); return 0; }
     c->sync_bn_comm = mid_rccl_comm_init(c->rank, c->world, unique_id, bytes);
     if (!c->sync_bn_comm) return -1;
     const size_t nf = MI_SYNC_BN_TMP_FLOATS;
     c->sync_bn_tmp = (float *)mid_malloc(nf * sizeof(float));
     mid_bn_set_sync(c->sync_bn_comm, c->world, c->sync_bn_tmp, nf, 1);
     c->sync_bn = 1;
+    rs_build_table(t); /* the running variances' sample count now spans the replicas */
     return 0;
 }
 int mi_dp_world(const Train_ResNet *t) { return ((MiCtx *)t->backend_ctx)->world; }

@@ -209,6 +209,25 @@ class Ops:
         rec = [B.MiLossMetrics.from_buffer_copy(d.get().tobytes()).as_dict() for d in (dlast, dtot)]
         return dp.get(), dd.get(), drl.get(), drr.get(), rec[0], rec[1]
 
+    def bn_running_update(self, means, vars_, counts, running, momentum, guard=0, fill=0.0):
+        """mi_op_bn_running_update: lists of per-layer batch means / biased vars (float32, [C_i] each) and sample counts, running (2, R)
+        float32 with R >= sum C_i (layer i at the sum of the channels before it in both rows).  Returns the updated (2, R) array;
+        guard > 0: that many floats of `fill` lie in front of and behind the arena in the same allocation and come back as well"""
+        running = np.ascontiguousarray(running, np.float32)
+        R = running.shape[1]
+        pad = np.full(guard, fill, np.float32)
+        buf = self.dev(np.concatenate([pad, running.ravel(), pad]))
+        dm = [self.dev(np.ascontiguousarray(a, np.float32)) for a in means]
+        dv = [self.dev(np.ascontiguousarray(a, np.float32)) for a in vars_]
+        n = len(dm)
+        pm, pv = (C.c_void_p * n)(*[d.ptr for d in dm]), (C.c_void_p * n)(*[d.ptr for d in dv])
+        ch = (C.c_int * n)(*[int(np.size(a)) for a in means])
+        cnt = (C.c_int64 * n)(*[int(c) for c in counts])
+        self._chk(self.L.mi_op_bn_running_update(pm, pv, ch, cnt, n, buf.ptr + 4 * guard, R, momentum), "bn_running_update")
+        out = buf.get()
+        new = out[guard:guard + 2 * R].reshape(2, R)
+        return (new, out[:guard], out[guard + 2 * R:]) if guard else new
+
     def adam(self, p, g, m, v, lr, wd, b1, b2, cur_b1, cur_b2, eps):
         dp, dg, dm, dv = (self.dev(a) for a in (p, g, m, v))
         flag = self.dev(np.zeros(1, np.int32))

@@ -82,6 +82,91 @@ class Trainer:
             raise RuntimeError("mi_trainer_metrics: " + self.error())
         return last.as_dict(), total.as_dict()
 
+    # ---- evaluation (include/resnet_mi.h, "evaluation") ----
+    def _refused(self, what):
+        e = self.error()
+        self.L.mi_clear_error()
+        raise RuntimeError(what + ": " + e)
+
+    def track_running_stats(self, momentum=0.1, on=True):
+        """keep torch.nn.BatchNorm2d's running statistics of every batch norm: one extra launch per forward(); after set_dtype, before
+        the first forward()"""
+        if self.L.mi_trainer_track_running_stats(self.t, int(bool(on)), float(momentum)) != 0:
+            self._refused("mi_trainer_track_running_stats")
+
+    def running_stats(self):
+        """(means, vars): float32 arrays over every BN layer's channels, the layers in the order of their gammas in locations[]"""
+        n = self.L.mi_trainer_running_stats_channels(self.t)
+        means, vars_ = np.empty(n, np.float32), np.empty(n, np.float32)
+        if self.L.mi_trainer_get_running_stats(self.t, means.ctypes.data, vars_.ctypes.data) != 0:
+            self._refused("mi_trainer_get_running_stats")
+        return means, vars_
+
+    def set_running_stats(self, means, vars):
+        n = self.L.mi_trainer_running_stats_channels(self.t)
+        means, vars = np.ascontiguousarray(means, np.float32).ravel(), np.ascontiguousarray(vars, np.float32).ravel()
+        if n and (means.size != n or vars.size != n):
+            raise ValueError("running statistics hold %d channels" % n)
+        if self.L.mi_trainer_set_running_stats(self.t, means.ctypes.data, vars.ctypes.data) != 0:
+            self._refused("mi_trainer_set_running_stats")
+
+    def running_updates(self):
+        return int(self.L.mi_trainer_running_updates(self.t))
+
+    def eval_forward(self, images=None, labels=None, n_valid=None, topk=5):
+        """the eval pass (running statistics, nothing trained): on the current batch, or on images (NCHW float32, up to `batch` of them;
+        missing rows are zero) and labels copied to the device.  Metrics over the first n_valid rows: eval_metrics()"""
+        b = self.c_batch.contents
+        if images is None:
+            im, lab = C.cast(b.images, C.c_void_p), C.cast(b.correct_classes, C.c_void_p)
+            n_valid = self.batch if n_valid is None else n_valid
+        else:
+            d = self.dims["input"]
+            images = np.ascontiguousarray(images, np.float32).reshape(-1, 3, d, d)
+            if images.shape[0] > self.batch:
+                raise ValueError("more images than the batch size")
+            n_valid = images.shape[0] if n_valid is None else n_valid
+            full = np.zeros((self.batch, 3, d, d), np.float32)
+            full[:images.shape[0]] = images
+            im, lab = self._eval_dev("_eval_images_dev", full.nbytes), None
+            self.L.mi_copy_to_device(im, full.ctypes.data, full.nbytes)
+            if labels is not None:
+                lab_h = np.zeros(self.batch, np.int32)
+                lab_h[:len(labels)] = np.asarray(labels, np.int32)
+                lab = self._eval_dev("_eval_labels_dev", lab_h.nbytes)
+                self.L.mi_copy_to_device(lab, lab_h.ctypes.data, lab_h.nbytes)
+        if self.L.mi_trainer_eval_forward(self.t, im, lab, int(n_valid), int(topk)) != 0:
+            self._refused("mi_trainer_eval_forward")
+
+    def _eval_dev(self, name, nbytes):
+        """a device buffer of eval_forward's own, made once"""
+        if not getattr(self, name, None):
+            p = self.L.mi_malloc(nbytes)
+            if not p:
+                raise MemoryError("mi_malloc(%d)" % nbytes)
+            setattr(self, name, p)
+        return getattr(self, name)
+
+    def eval_metrics(self, reset=False):
+        """(last, total) of the eval passes, as metrics()"""
+        last, total = B.MiLossMetrics(), B.MiLossMetrics()
+        if self.L.mi_trainer_eval_metrics(self.t, C.byref(last), C.byref(total), int(bool(reset))) != 0:
+            self._refused("mi_trainer_eval_metrics")
+        return last.as_dict(), total.as_dict()
+
+    def evaluate_u8(self, images_u8, labels, dim_in, topk=5):
+        """a whole array of dim_in x dim_in x 3 (B,G,R) byte images: centre crop, decode and eval pass per batch on the device; the
+        totals as a dict (loss_sum, rows, wrong_top1, wrong_topk, batches)"""
+        images_u8 = np.ascontiguousarray(images_u8, np.uint8)
+        labels = np.ascontiguousarray(labels, np.int32)
+        n = labels.size
+        if images_u8.size != n * dim_in * dim_in * 3:
+            raise ValueError("images_u8 does not hold %d images of %d x %d x 3 bytes" % (n, dim_in, dim_in))
+        out = B.MiLossMetrics()
+        if self.L.mi_trainer_eval_u8(self.t, images_u8.ctypes.data, labels.ctypes.data, n, int(dim_in), int(topk), C.byref(out)) != 0:
+            self._refused("mi_trainer_eval_u8")
+        return out.as_dict()
+
     def set_lr(self, lr):
         """learning_rate for the next update_parameters and on (read at every update)"""
         self.t.contents.learning_rate = lr
@@ -114,6 +199,10 @@ class Trainer:
         if self.t:
             self.L.destroy_trainer(self.t)
             self.t = None
+            for name in ("_eval_images_dev", "_eval_labels_dev"):
+                if getattr(self, name, None):
+                    self.L.mi_free(getattr(self, name))
+                    setattr(self, name, None)
 
     def _to_host(self, ptr, n, dtype=np.float32):
         out = np.empty(n, dtype)
