@@ -93,9 +93,49 @@ def loss_bound(ref):
     return 2.0 ** -19 * (2.0 + np.asarray(ref, np.float64))
 
 
-def loss_head_f32(x, labels, eps=0.0):
+def loss_bound_mem(x, labels, eps):
+    """the first-order bound DESIGN.md ("Loss head") derives for loss_head_kernel<mem> (L > 1024, lanes add z in double), per row, before
+    it is rounded up to loss_bound's 64 + 32 ref:  2^-24 (ln L + 2 + (m + 5) + 4 ls + 5 a + 6 b),  m = ceil(L / 64), ls = log s,
+    a = (1 - eps) |z_c|, b = eps mean |z_j|"""
+    x = np.asarray(x, np.float64)
+    N, L = x.shape
+    z = x - x.max(axis=1, keepdims=True)
+    ls = np.log(np.exp(z).sum(axis=1))
+    a = (1.0 - eps) * np.abs(z[np.arange(N), labels])
+    b = eps * np.abs(z).mean(axis=1)
+    return 2.0 ** -24 * (np.log(L) + 2.0 + (-(-L // 64) + 5) + 4.0 * ls + 5.0 * a + 6.0 * b)
+
+
+LONG_ROW_L = 1537
+LONG_ROW_T = (90.0, 120.0, 150.0, 180.0, 240.0)
+
+
+def long_row_corner():
+    """(x, labels): the corner the double lane sums of loss_head_kernel<mem> close ("Loss head": label at the maximum, every other
+    logit far below it, smoothing 0.5, so that u sum z is nearly all of the loss), one row of LONG_ROW_L columns per T in LONG_ROW_T.  The label is
+    the last column, logit 0; lane l of the kernel adds columns l, l + 64, ...: column j holds -t[j // 64] with t[0] = T and t[k] the
+    float among the 64 next above T whose addition to the running FLOAT sum t[0] + ... + t[k-1] loses the most (almost half an ulp of the
+    sum, every time downwards).  A float lane sum is then off by about 9 x 2^-24 relative, where the double sum is exact"""
+    f = np.float32
+    rows = []
+    for T in LONG_ROW_T:
+        t, p = [f(T)], f(T)
+        for _ in range(1, LONG_ROW_L // 64):
+            cands = f(T) + np.arange(64, dtype=f) * np.spacing(f(T))
+            lost = (np.float64(p) + cands.astype(np.float64)) - (p + cands).astype(np.float64)
+            c = cands[int(np.argmax(lost))]
+            t.append(c)
+            p = f(p + c)
+        x = -np.asarray(t, f)[np.minimum(np.arange(LONG_ROW_L) // 64, len(t) - 1)]
+        x[-1] = 0.0
+        rows.append(x)
+    return np.ascontiguousarray(rows, f), np.full(len(rows), LONG_ROW_L - 1, np.int32)
+
+
+def loss_head_f32(x, labels, eps=0.0, long_rows_in_double=True):
     """the kernel's own formulas step by step in float32 (lane-strided sums of 64 lanes, then the exchange tree): row_loss only.  Used to hold
-    the derived bound against fp32 arithmetic without a GPU"""
+    the derived bound against fp32 arithmetic without a GPU.  long_rows_in_double = False: the lanes of a row of more than 1024 columns add
+    z in float (what the kernel must NOT do: tests/test_loss_model.py shows the bound of the long-row corner then fails)"""
     f = np.float32
     x = np.asarray(x, f)
     N, L = x.shape
@@ -116,10 +156,10 @@ def loss_head_f32(x, labels, eps=0.0):
         mx = x[r].max()
         z = x[r] - mx
         e = np.exp(z)  # numpy's float32 exp: within 1 ulp, as expf
-        s_l, z_l = np.zeros(64, f), np.zeros(64, f if L <= 1024 else np.float64)  # a row of more than 16 per lane sums z in double
+        s_l, z_l = np.zeros(64, f), np.zeros(64, f if L <= 1024 or not long_rows_in_double else np.float64)  # a row of more than 16 per lane sums z in double
         for j in range(L):
             s_l[j % 64] += e[j]
             z_l[j % 64] += z[j]
-        s, sz = tree(s_l), f(tree(z_l))
+        s, sz = tree(s_l), f(tree(z_l.astype(np.float64) if L > 1024 else z_l))
         out[r] = np.log(s) - (f(1) - epsf) * z[c] - u * sz if 0 <= c < L else np.nan
     return out

@@ -1,0 +1,368 @@
+"""The mutant table of tests/test_gpu_mutants.py: one small VALUE fault per entry, planted in a copy of one source file under
+resnet_amd/csrc, built as a second library (tools/build_mutants.py -> variants/mutants/libresnet_mi_<name>.so) and loaded through
+RESNET_MI_LIB.  The entry's killers -- existing checks of the suite that reach the mutated branch -- must fail on that library.
+
+The value-only rule ("Suite sensitivity"): a mutant changes a value that is stored or accumulated (a constant, a dropped term,
+a comparison that selects between two values, a rounding, a factor of 0 on one contribution).  It never changes an address, an index, a
+loop bound, a barrier or a wait, a launch geometry, an LDS or buffer size, a *_supported predicate, or a value later code uses as an
+address or a bound; no `old` or `new` holds inline assembly.  "Skip the last slice" is "multiply the last slice by 0".
+
+name     unique; the library is libresnet_mi_<name>.so
+file     under resnet_amd/csrc; `old` occurs exactly once in it
+what     the fault and which elements it makes wrong
+branch   the code path the fault lives in (the kill matrix of DESIGN.md)
+killers  pytest node ids, one to three, the smallest cases that reach the branch; the planner's answer (convref.conv_plan:
+         rows per tile, columns per tile, tiles, first sliced tile, slices, splits, grouped) stands beside the cases that were chosen for it
+"""
+
+RAG = "tests/test_gpu_ragged.py::"
+OPS = "tests/test_gpu_ops.py::"
+BF = "tests/test_gpu_bf16.py::"
+
+MUTANTS = []
+
+
+def _m(name, file, old, new, what, branch, killers):
+    MUTANTS.append(dict(name=name, file=file, old=old, new=new, what=what, branch=branch, killers=list(killers)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# kernels_igemm.hip
+_m("igemm_tail_last_slice", "kernels_igemm.hip",
+   "for (int i = 0; i < 8; i++) v[i] += tb[(size_t)z * (BM * 128) + i * 128];",
+   "for (int i = 0; i < 8; i++) v[i] += (z == g.tsplit - 1 ? 0.f : 1.f) * tb[(size_t)z * (BM * 128) + i * 128];",
+   "igemm_tail_reduce_kernel multiplies the last reduction slice by 0: every element of a sliced tail tile lacks that slice's terms",
+   "sliced tail tiles only",
+   # plan (64, 128, 2, 0, 2, 1, 0): both tiles are cut into 2 slices; dgrad (64, 128, 2, 0, 2, 1, 0)
+   [RAG + "test_conv_route_ragged[c1s_N4-f32_default_fwd_C64_H8_K64_k3_s1]",
+    RAG + "test_conv_route_ragged[c1s_N4-f32_default_dgrad_C128_H4_K512_k1_s1]"])
+_m("igemm_fwd_m2_mean_shift", "kernels_igemm.hip",
+   "g.bn_part[2 * plane + o] = fmaxf(sq - sd * sd * inv, 0.f);\n    }\n    IG_T(4);",
+   "g.bn_part[2 * plane + o] = fmaxf(sq, 0.f);\n    }\n    IG_T(4);",
+   "the forward epilogue's BN partial keeps the sum of squares about the tile's first column as M2 (drops the mean-shift term): the "
+   "variances of every channel come out too large",
+   "unsliced forward tiles with fused statistics",
+   # plan (64, 128, 2, 2, 1, 1, 0): two whole tiles, no slices
+   [RAG + "test_conv_bn_fwd_ragged[c1s_N4-f32_C64_H8_K64_k1_s1]"])
+_m("igemm_dgrad_addend_rows64", "kernels_igemm.hip",
+   "if (MODE == IG_DGRAD && addend) v += ad[r];",
+   "if (MODE == IG_DGRAD && addend) v += (wm > 0 ? 0.f : ad[r]);",
+   "the dgrad epilogue ignores the shortcut addend in rows 64..127 of a 128-row tile",
+   "128-row tiles (waves with wm = 1), dgrad with an addend",
+   # plan (128, 128, 392, 392, 1, 1, 0): 128-row tiles; "stage 1 red" takes the shortcut gradient as its addend
+   [RAG + "test_conv_route_ragged[r50_N8-f32_default_dgrad_C256_H56_K64_k1_s1]"])
+_m("igemm_wgrad_reduce_remainder", "kernels_igemm.hip",
+   "for (; z < splits; z++)\n#pragma unroll\n        for (int t = 0; t < T; t++) s[t] += part[((long)z * T + t) * KC + i];",
+   "for (; z < splits; z++)\n#pragma unroll\n        for (int t = 0; t < T; t++) s[t] += 0.f * part[((long)z * T + t) * KC + i];",
+   "igemm_wgrad_reduce_kernel multiplies by 0 the splits behind the last whole group of U (8 for 1x1): dW lacks those splits' pixels",
+   "the remainder loop of the flat split reduction (splits % 8 != 0)",
+   # plan (128, 128, 2, 2, 1, 12, 0): 12 splits, flat reduction: splits 8..11 are the remainder
+   [RAG + "test_conv_route_ragged[r50_N8-f32_default_wgrad_C256_H56_K128_k1_s1]"])
+
+# kernels_conv.hip (the direct kernels: by default only shapes whose channel counts do not tile for the implicit GEMM reach them)
+_m("dconv_tap22_zero", "kernels_conv.hip",
+   "for (int t = 0; t < TK; t++) acc[t] = fmaf(wq[t], v, acc[t]);",
+   "for (int t = 0; t < TK; t++) acc[t] = fmaf((NTR == 3 && NTC == 3 && tr == 2 && tc == 2) ? 0.f : wq[t], v, acc[t]);",
+   "the direct 3x3 kernel reads the weight of tap (2, 2) as 0: every output lacks one of its nine taps",
+   "the 3x3 instantiation of dconv_kernel",
+   [OPS + "test_direct_kernels_per_element[fwd_C64_H8_K96_k3_s1_N2]"])
+_m("dconv_s2_dgrad_odd_odd_scale", "kernels_conv.hip",
+   "for (int t = 0; t < TK; t++) acc[t] = fmaf(wq[t], v, acc[t]);",
+   "for (int t = 0; t < TK; t++) acc[t] = fmaf((NTR == 2 && NTC == 2) ? wq[t] * 1.0009765625f : wq[t], v, acc[t]);",
+   "the (odd row, odd column) parity class of the direct stride-2 dgrad is scaled by 1 + 2^-10: a quarter of dx",
+   "the 2x2-tap parity class of the stride-2 dgrad",
+   [OPS + "test_direct_kernels_per_element[dgrad_C32_H8_K64_k3_s2_N3]"])
+_m("dconv_wgrad_image1_zero", "kernels_conv.hip",
+   "d[u][q4] = ok ? v : 0.f;",
+   "d[u][q4] = (ok && g.n != 1) ? v : 0.f;",
+   "the direct weight gradient multiplies image 1's contribution by 0",
+   "one image of the reduction",
+   [OPS + "test_direct_kernels_per_element[wgrad_C96_H14_K128_k3_s1_N2]"])
+
+# kernels_gemm.hip
+_GEMM_OLD = "acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur][i], bv[cur][j], acc[i][j], 0, 0, 0);"
+_m("gemm_nn_last_k", "kernels_gemm.hip", _GEMM_OLD,
+   "acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32((BATCH == BATCH_NONE && A_KC && !B_KC && k0 + k2 + fk == g.K - 1) ? 0.f : av[cur][i], "
+   "bv[cur][j], acc[i][j], 0, 0, 0);",
+   "the plain product A B (the FC forward) takes the last reduction element's product as 0",
+   "one instantiation (BATCH_NONE, A k-contiguous, B n-contiguous), last k",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-fc_nn]"])
+_m("gemm_rows64_last_k", "kernels_gemm.hip", _GEMM_OLD,
+   "acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32((wm > 0 && k0 + k2 + fk == kend - 1) ? 0.f : av[cur][i], bv[cur][j], acc[i][j], 0, 0, 0);",
+   "rows 64..127 of a 128-row tile lose the product of their last reduction element (X^T dY, the FC weight gradient, is the form with "
+   "more than 64 rows)",
+   "128-row tiles (waves with wm = 1), last k",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-fc_lt]"])
+
+# kernels_igemm_bf16.hip
+_m("bgemm_bn_bwd_unrounded_sums", "kernels_igemm_bf16.hip",
+   "const float g0 = on0 ? __uint_as_float(pk[e] << 16) : 0.f, g1 = on1 ? __uint_as_float(pk[e] & 0xffff0000u) : 0.f;",
+   "const float g0 = on0 ? w[2 * e] : 0.f, g1 = on1 ? w[2 * e + 1] : 0.f;",
+   "the fused BN' epilogue sums the gradient before its rounding to bf16 (the contract sums the stored one): dbeta, dgamma and the dx "
+   "made from them",
+   "the BN'-fused dgrad epilogue (pixel-major product)",
+   [RAG + "test_dgrad_bn_bwd_ragged[c1s_N4-bf16_C64_H8_K256_k1_s1]", RAG + "test_dgrad_bn_bwd_ragged[c4i_N4-bf16_C256_H8_K128_k1_s1]"])
+_m("bgemm_bn_bwd_gate_ge", "kernels_igemm_bf16.hip",
+   "const bool on0 = (int16_t)(mv[e] & 0xffffu) > 0,",
+   "const bool on0 = (int16_t)(mv[e] & 0xffffu) >= 0,",
+   "the gate of the BN'-fused dgrad is mask >= 0 on the even pixels: the gradient passes where the activation is 0",
+   "the BN'-fused dgrad epilogue, even pixels",
+   [RAG + "test_dgrad_bn_bwd_ragged[c1s_N4-bf16_C64_H8_K256_k1_s1]"])
+_m("bgemm_fwd_stats_count_padding", "kernels_igemm_bf16.hip",
+   "if (col < g.ncols && pp < (uint32_t)g.P) { okm |= 1u << (j * 4 + q); cnt += 4; }",
+   "if (col < g.ncols && pp < (uint32_t)g.P) okm |= 1u << (j * 4 + q);\n                if (col < g.ncols) cnt += 4;",
+   "the forward statistics partial counts the padding columns of Pc (planes that are no multiple of 8 pixels) in n: means and variances "
+   "of every channel",
+   "planes with P % 8 == 4 (14 x 14: Pc = 200), pixel-major epilogue",
+   # plan (64, 128, 52, 52, 1, 1, 0)-like: P = 196, Pc = 200
+   [RAG + "test_conv_bn_fwd_ragged[r50_N8-bf16_C1024_H14_K256_k1_s1]"])
+_m("bgemm_f2b_truncates", "kernels_igemm_bf16.hip",
+   "out[i] = bg_f2bf(in[i]);",
+   "out[i] = (u16)(__float_as_uint(in[i]) >> 16);",
+   "the fp32 -> bf16 conversion kernel truncates instead of rounding to the nearest even",
+   "bg_f2b_kernel",
+   [BF + "test_conversion_is_round_to_nearest_even"])
+
+# kernels_cl_bf16.hip
+_m("cl_fwd_stats_past_the_end", "kernels_cl_bf16.hip",
+   "const float dlt = col < g.ncols ? acc[i][j][r] - s0 : 0.f;",
+   "const float dlt = acc[i][j][r] - s0;",
+   "the channel-last forward's statistics partial of the partial last column tile sums the columns past the end as well",
+   "the partial last column tile",
+   # 8 x 196 = 1568 columns = 24.5 waves of 64: the last wave holds 32 real columns and 32 past the end.  (The small nets' 64 columns
+   # end ON a wave boundary: a wave that lies wholly past the end sees 64 copies of the last pixel, d = 0 for each of them, and the
+   # mutant writes the same bits -- it survived c1s_N4-bf16_cl_C128_H4_K128_k3_s1 and ..._C128_H8_K128_k3_s2)
+   [RAG + "test_conv_bn_fwd_ragged[r50_N8-bf16_cl_C256_H28_K256_k3_s2]"])
+_m("cl_dgrad2_odd_column_ulp", "kernels_cl_bf16.hip",
+   "u32x4 v = {cl_pack2(acc[0][i][j][4 * q], acc[1][i][j][4 * q]),",
+   "u32x4 v = {cl_pack2(acc[0][i][j][4 * q], acc[1][i][j][4 * q] * 1.0078125f),",
+   "cl_dgrad2_kernel scales the odd column parity of every fourth grid pixel by 1 + 2^-7, one bf16 ulp",
+   "odd output columns",
+   [RAG + "test_conv_route_ragged[c1s_N4-bf16_cl_dgrad_C128_H8_K128_k3_s2]"])
+_m("cl_wgrad2_last_split", "kernels_cl_bf16.hip",
+   "            compute((it - r_beg) & 1);\n        }\n    }\n"
+   "    float *o = part + ((size_t)((size_t)split * 9 + t) * g.K) * g.C + c0 + wn * 64 + (lane & 31);\n"
+   "#pragma unroll\n    for (int i = 0; i < 2; i++)\n#pragma unroll\n        for (int j = 0; j < 2; j++)\n#pragma unroll\n"
+   "            for (int r = 0; r < 16; r++)\n"
+   "                o[(size_t)(m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * g.C + j * 32] = acc[i][j][r];",
+   "            compute((it - r_beg) & 1);\n        }\n    }\n"
+   "    float *o = part + ((size_t)((size_t)split * 9 + t) * g.K) * g.C + c0 + wn * 64 + (lane & 31);\n"
+   "    const float keep = (r_beg > 0 && r_end == g.rtiles) ? 0.f : 1.f;\n"
+   "#pragma unroll\n    for (int i = 0; i < 2; i++)\n#pragma unroll\n        for (int j = 0; j < 2; j++)\n#pragma unroll\n"
+   "            for (int r = 0; r < 16; r++)\n"
+   "                o[(size_t)(m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * g.C + j * 32] = keep * acc[i][j][r];",
+   "cl_wgrad2_kernel multiplies its last split's partial by 0 (where there is more than one split)",
+   "the last reduction split",
+   # plan (128, 128, 9, 9, 1, 4, 0): 4 splits
+   [RAG + "test_conv_route_ragged[r50_N8-bf16_cl2_wgrad_C128_H56_K128_k3_s2]"])
+_m("pw_wgrad_last_split", "kernels_cl_bf16.hip",
+   "    // partials [split][k][c]\n    float *o = part + ((size_t)split * g.K) * g.C + c0 + wn * 64 + (lane & 31);\n"
+   "#pragma unroll\n    for (int i = 0; i < 2; i++)\n#pragma unroll\n        for (int j = 0; j < 2; j++)\n#pragma unroll\n"
+   "            for (int r = 0; r < 16; r++)\n"
+   "                o[(size_t)(m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * g.C + j * 32] = acc[i][j][r];",
+   "    // partials [split][k][c]\n    float *o = part + ((size_t)split * g.K) * g.C + c0 + wn * 64 + (lane & 31);\n"
+   "    const float keep = (r_beg > 0 && r_end == g.rtiles) ? 0.f : 1.f;\n"
+   "#pragma unroll\n    for (int i = 0; i < 2; i++)\n#pragma unroll\n        for (int j = 0; j < 2; j++)\n#pragma unroll\n"
+   "            for (int r = 0; r < 16; r++)\n"
+   "                o[(size_t)(m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * g.C + j * 32] = keep * acc[i][j][r];",
+   "the 1x1 LDS-DMA weight gradient (pw_wgrad_kernel) multiplies its last split's partial by 0",
+   "the last reduction split",
+   # plan (128, 128, 4, 4, 1, 6, 0): 6 splits
+   [RAG + "test_conv_route_ragged[r50_N8-bf16_pw_wgrad_C128_H28_K512_k1_s1]"])
+
+# kernels_stem_bf16.hip
+_m("stem_fwd_tap66_zero", "kernels_stem_bf16.hip",
+   "if (s >= 0) v = w[(size_t)k * 147 + gq * 7 + s]; // KCRS",
+   "if (s >= 0 && !(gq % 7 == 6 && s == 6)) v = w[(size_t)k * 147 + gq * 7 + s]; // KCRS",
+   "the bf16 stem forward reads tap (6, 6) of every input channel as 0",
+   "one of 49 taps (the forward weight operand)",
+   [RAG + "test_stem_ragged[c1s_N4-bf16_fwd]"])
+_m("stem_exact_image_rounded", "kernels_stem_bf16.hip",
+   "        xp[e] = v;\n",
+   "        xp[e] = mi_bf2f(mi_f2bf(v));\n",
+   "the exact-fp32 stem pair rounds the image to bf16 when it pads it into parity planes: forward and weight gradient",
+   "st32_pad_kernel",
+   [RAG + "test_stem_ragged[c1s_N4-f32_wgrad]", RAG + "test_stem_ragged[c1s_N4-f32_fwd]"])
+_m("stem_wgrad_reduce_remainder", "kernels_stem_bf16.hip",
+   "for (; w < nwaves; w += 4) s[0] += p[(size_t)w * WS];",
+   "for (; w < nwaves; w += 4) s[0] += 0.f * p[(size_t)w * WS];",
+   "st_wgrad_reduce_kernel multiplies by 0 the partials behind the last whole group of 32 waves",
+   "the remainder loop of the stem's weight-gradient reduction",
+   # waves = min(N P / 16, 1024) rounded up to 4: 64 at N = 4, H = 32 and 1024 at H = 224 are multiples of 32 (no remainder: the mutant
+   # survived c1s_N4-bf16_wgrad); 144 at N = 1, H = 96 leaves 16 waves to the remainder loop
+   [BF + "test_stem_bf16[96-1]"])
+
+# kernels_bn.hip
+_m("bn_wel_merge_between_term", "kernels_bn.hip",
+   "r.m2 = a.m2 + b.m2 + d * d * a.n * f;",
+   "r.m2 = a.m2 + b.m2;",
+   "wel_merge drops d*d*a.n*f, the between-group term of M2: every variance is too small",
+   "every merge of two partial statistics",
+   [RAG + "test_bn_fwd_ragged[c1s_N4-f32_C64_H8]"])
+_m("bn_apply_no_eps", "kernels_bn.hip",
+   "sd0 = sqrtf(vars[c] + eps), g0 = gamma[c], b0 = beta[c];\n        int nfirst = V;",
+   "sd0 = sqrtf(vars[c]), g0 = gamma[c], b0 = beta[c];\n        int nfirst = V;",
+   "bn_apply_kernel divides by sqrtf(var) without eps: channels of small variance",
+   "the apply kernel (the statistics and the backward keep eps)",
+   [RAG + "test_bn_fwd_ragged[c1s_N4-f32_C256_H8]", RAG + "test_bn_fwd_ragged[c1s_N4-f32_C64_H8]"])
+_m("bn_apply_straddle_beta", "kernels_bn.hip",
+   "b1 = beta[c1];\n        }",
+   "b1 = b0;\n        }",
+   "in a vector that straddles two channel planes the second channel's elements take the first channel's beta",
+   "the straddling vectors of 7 x 7 planes (STR)",
+   [RAG + "test_bn_fwd_ragged[r50_N8-f32_C512_H7]"])
+_m("bn_bwd_dx_no_mean_dy", "kernels_bn.hip",
+   "xv[q] = scale * (gq - k1 - xh * k2);",
+   "xv[q] = scale * (gq - xh * k2);",
+   "the backward dx drops the mean(dy) term",
+   "bn_bwd_apply_kernel",
+   [RAG + "test_bn_bwd_ragged[c1s_N4-f32_C256_H8_mode0]"])
+_m("bn_bwd_gate_ge", "kernels_bn.hip",
+   "if (EXT) on = m > 0.f;",
+   "if (EXT) on = m >= 0.f;",
+   "the external-mask gate of the BN backward reduction is mask >= 0: the gated gradient and the sums take dy where the activation is 0",
+   "the external-mask modes (2, 3) of bn_bwd_reduce_kernel",
+   [RAG + "test_bn_bwd_ragged[c1s_N4-f32_C256_H8_mode3]"])
+_m("bn_bwd_gate_y_ge", "kernels_bn.hip",
+   "if (MASK == 1) on = bn_y(xh, g, b) > 0.f;\n        if (EXT) on = m > 0.f;",
+   "if (MASK == 1) on = bn_y(xh, g, b) >= 0.f;\n        if (EXT) on = m > 0.f;",
+   "the recomputed gate of the BN backward reduction is y >= 0: dbeta and dgamma take dy where y is exactly 0",
+   "mode 1 of bn_bwd_reduce_kernel, elements with y == 0 (x == mean in a beta == 0 channel)",
+   [RAG + "test_bn_bwd_ragged[c1s_N4-f32_C64_H8_mode1]"])
+_m("bn_running_biased_var", "kernels_bn.hip",
+   "m * (e.vars[c] * e.unbias);",
+   "m * (e.vars[c]);",
+   "bn_running_update_kernel folds the biased batch variance into the running variance",
+   "the running-variance half of the arena",
+   ["tests/test_gpu_eval.py::test_running_update_kernel[momentum_0.1]"])
+_m("bn_sync_no_between_replica", "kernels_bn.hip",
+   "tmp[c] = vars[c] + d * d;",
+   "tmp[c] = vars[c];",
+   "the sync-BN merge drops the between-replica mean term of the variance",
+   "bn_sync_k2",
+   ["tests/test_gpu_dp.py::test_sync_bn_merge_of_two_different_replicas_equals_the_whole_batch[shape0]"])
+
+# kernels_misc.hip
+_m("softmax_no_max", "kernels_misc.hip",
+   "    mx = wave_max(mx);\n    float s = 0.f;\n    for (int j = lane; j < L; j += 64) s += expf(xr[j] - mx);",
+   "    mx = 0.f * wave_max(mx);\n    float s = 0.f;\n    for (int j = lane; j < L; j += 64) s += expf(xr[j] - mx);",
+   "the soft-max does not subtract the row maximum: rows with logits past +-88 overflow or vanish",
+   "rows with large logits",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-softmax_ce_deriv]"])
+_m("adam_v_corrected_with_beta1", "kernels_misc.hip",
+   "va = vi / (1.f - cur_b2);",
+   "va = vi / (1.f - cur_b1);",
+   "Adam corrects the second moment with beta1^t",
+   "every element",
+   [OPS + "test_softmax_ce_adam"])
+_m("adam_m_on_nan_gradient", "kernels_misc.hip",
+   "if (isnan(gi) || isinf(gi)) b = true;",
+   "if (isnan(gi) || isinf(gi)) { b = true; m[i] = b1 * mi + (1.f - b1) * gi; }",
+   "Adam updates m from a NaN / Inf gradient (the guard keeps the old moments)",
+   "elements with a non-finite gradient",
+   [OPS + "test_softmax_ce_adam"])
+_m("maxpool_last_of_equal_maxima", "kernels_misc.hip",
+   "if (e > mv[j]) { mv[j] = e;",
+   "if (e >= mv[j]) { mv[j] = e;",
+   "the 3x3 stride-2 max-pool takes the last of equal maxima inside a window (the index stays in the window)",
+   "windows with ties",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-maxpool_f32]"])
+_m("avgpool_bwd_divisor", "kernels_misc.hip",
+   "stf<T>(dx + e, dy[e / P] / (float)P);",
+   "stf<T>(dx + e, dy[e / P] / (float)(P + 1));",
+   "the average-pool backward divides by H^2 + 1",
+   "every element",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-avgpool_f32]"])
+_m("misc_bf16_store_truncates", "kernels_misc.hip",
+   "{ *p = mi_f2bf(v); }",
+   "{ *p = (bf16_t)(__float_as_uint(v) >> 16); }",
+   "the pooling kernels' scalar bf16 store truncates (max-pool values are bf16 already: only the average-pool backward rounds)",
+   "bf16 storage, avgpool_bwd_kernel",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-avgpool_bf16]"])
+
+# kernels_optim.hip
+_m("lars_denominator_no_wd", "kernels_optim.hip",
+   "tr = trust_coef * wn / (gn + wd * wn);",
+   "tr = trust_coef * wn / gn;",
+   "the LARS trust ratio's denominator drops wd * |w|",
+   "weight tensors, wd > 0",
+   ["tests/test_gpu_optim.py::test_operator_per_element_at_resnet50_geometry[lars-5e-05]"])
+_m("lars_wd_on_gamma_beta", "kernels_optim.hip",
+   "else wdt = 0.f;",
+   "else wdt = wd;",
+   "LARS keeps weight decay on BN gamma / beta and the FC bias",
+   "non-weight tensors, wd > 0",
+   ["tests/test_gpu_optim.py::test_operator_per_element_at_resnet50_geometry[lars-5e-05]"])
+_m("optim_scalar_tail_no_momentum", "kernels_optim.hip",
+   "opt_elem<KIND>(w, q, b, s, wdt, lr, mu, skip, bad);",
+   "opt_elem<KIND>(w, q, b, s, wdt, lr, 0.f, skip, bad);",
+   "the scalar tail behind the float4 body of a chunk runs with momentum 0: the last len % 4 elements of a tensor",
+   "tensors whose length is no multiple of 4",
+   ["tests/test_gpu_optim.py::test_operator_scalar_tail[sgd]", "tests/test_gpu_optim.py::test_operator_scalar_tail[lars]"])
+
+# kernels_input.hip
+_m("decode_r_plane_b_mean", "kernels_input.hip",
+   "{123.68, 116.78, 103.94}; // subtracted from source byte 0",
+   "{123.68, 116.78, 123.68}; // subtracted from source byte 0",
+   "the decode subtracts the B mean from the R plane",
+   "one of three planes",
+   ["tests/test_gpu_input_u8.py::test_decode_sweep[37-30-1]"])
+_m("resample_row_weight", "kernels_input.hip",
+   "(double)(top * (256 - wy) + bot * wy)",
+   "(double)(top * (255 - wy) + bot * wy)",
+   "the resample blends the upper source row with weight 255 - wy",
+   "every element",
+   ["tests/test_gpu_input_rrc.py::test_resample_sweep[37-30-1]"])
+_m("resample_tail_no_row_weight", "kernels_input.hip",
+   "out_n[(2 - p) * plane + (size_t)(h0 + r) * D + ox] = rs_value(L0, L1, x0, x1, wx, wy, p);",
+   "out_n[(2 - p) * plane + (size_t)(h0 + r) * D + ox] = rs_value(L0, L1, x0, x1, wx, 0, p);",
+   "the scalar tail columns of the resample (dim_out % 4 of them) ignore the vertical weight",
+   "the last dim_out % 4 columns of a row",
+   ["tests/test_gpu_input_rrc.py::test_resample_sweep[37-30-1]"])
+
+# kernels_loss.hip
+_m("loss_u_over_l_minus_1", "kernels_loss.hip",
+   "const float u = eps / (float)L, tc",
+   "const float u = eps / (float)(L - 1), tc",
+   "the smoothing mass per class is eps / (L - 1)",
+   "eps > 0",
+   ["tests/test_gpu_loss_head.py::test_loss_head[shape1-0.1]"])
+_m("loss_rank_tie_strict", "kernels_loss.hip",
+   "p_ >= pc) ? 1 : 0;",
+   "p_ > pc) ? 1 : 0;",
+   "the rank counts p_j > p_c: ties no longer count against the label",
+   "rows with ties",
+   ["tests/test_gpu_loss_head.py::test_loss_head[shape1-0.0]"])
+_m("loss_long_row_float_sum", "kernels_loss.hip",
+   "szd += (double)z;",
+   "szd = (double)(float)((float)szd + z);",
+   "rows longer than LOSS_REG_COLS add z per lane in float instead of double",
+   "loss_head_kernel<mem> (L > 1024)",
+   ["tests/test_gpu_loss_head.py::test_long_row_sums_z_in_double"])
+
+# mi_common.hpp (one header mutant: it recompiles every .hip file)
+_m("pack_bf2_truncates", "mi_common.hpp",
+   "    bf2_ r = __builtin_convertvector(v, bf2_);\n    return *(uint32_t *)&r;",
+   "    (void)v; (void)sizeof(bf2_);\n    return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u);",
+   "mi_pack_bf2 truncates: every bf16 store of the batch-norm, pooling and stem kernels",
+   "bf16 storage",
+   [RAG + "test_bn_fwd_ragged[c1s_N4-bf16_C64_H8]"])
+
+KERNEL_FILES = ["kernels_bn.hip", "kernels_cl_bf16.hip", "kernels_conv.hip", "kernels_gemm.hip", "kernels_igemm.hip", "kernels_igemm_bf16.hip",
+                "kernels_input.hip", "kernels_loss.hip", "kernels_misc.hip", "kernels_optim.hip", "kernels_stem_bf16.hip"]
+
+
+def by_name(name):
+    for m in MUTANTS:
+        if m["name"] == name:
+            return m
+    raise KeyError(name)
+
+
+def all_killers():
+    seen = []
+    for m in MUTANTS:
+        for k in m["killers"]:
+            if k not in seen:
+                seen.append(k)
+    return seen

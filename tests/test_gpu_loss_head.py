@@ -87,6 +87,25 @@ def test_loss_head(ops, shape, eps):
     assert last1["wrong_topk"] == last1["wrong_top1"] == last["wrong_top1"] and last1["loss_sum"] == last["loss_sum"]
 
 
+def test_long_row_sums_z_in_double(ops):
+    """loss_head_kernel<mem> (rows of more than 1024 columns) adds z per lane in double.  lossref.long_row_corner builds the corner that
+    needs it: label at the maximum, every other logit 90 .. 240 below it, smoothing 0.5 (u sum z is nearly all of the loss), the logits
+    chosen so that a FLOAT lane sum loses almost half an ulp at every addition.  Bound: the first-order <mem> bound DESIGN.md derives
+    (lossref.loss_bound_mem: 2^-24 (ln L + 2 + m + 5 + 4 ls + 5 a + 6 b), about a fifth of loss_bound here), not loss_bound's rounded-up
+    64 + 32 ref, which float lane sums also meet.  tests/test_loss_model.py: the fp32 restatement with double lanes uses 0.18 of it, with
+    float lanes 1.3 to 1.4 times it"""
+    x, lab = R.long_row_corner()
+    eps = 0.5
+    pred, dl, rl, rr, last, _ = ops.loss_head(x, lab, eps, 5)
+    assert _same(pred, ops.softmax(x))
+    assert not rr.any(), "the label is every row's only maximum"
+    ref = R.loss_head(x, lab, eps)[2]
+    share = np.abs(rl.astype(np.float64) - ref) / R.loss_bound_mem(x, lab, eps)
+    print("row_loss of the long-row corner: |error| / <mem> bound = %s" % np.round(share, 3))
+    assert np.all(np.isfinite(rl))
+    assert np.all(share <= 1.0), "row_loss out of bounds: |error| / bound %s" % np.round(share, 3)
+
+
 def _bad_labels(lab, L):
     bad = lab.copy()
     bad[0], bad[-1] = -1, L

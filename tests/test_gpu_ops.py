@@ -343,6 +343,27 @@ def test_conv_shape_sweep(ops, oracle, shape):
     check_grad(ops.conv_wgrad(nchw(x), nchw(dy), k, stride), oracle.conv_wgrad(x, dy, k, stride), "wgrad %s" % (shape,))
 
 
+# (op, C, H, K, k, stride, N, addend): shapes whose channel counts do not tile for the implicit GEMM, so that the DEFAULT route runs the
+# direct kernels of kernels_conv.hip: K % 64 != 0 (forward), C % 64 != 0 (dgrad: stride 1, and stride 2 with its four parity classes),
+# C % 128 != 0 and C != 64 (weight gradient)
+DIRECT = [("fwd", 64, 8, 96, 3, 1, 2, False), ("dgrad", 32, 8, 64, 3, 1, 3, True), ("dgrad", 32, 8, 64, 3, 2, 3, False),
+          ("dgrad", 32, 8, 64, 3, 2, 3, True), ("wgrad", 96, 14, 128, 3, 1, 2, False)]
+
+
+@pytest.mark.parametrize("case", DIRECT, ids=["%s_C%d_H%d_K%d_k%d_s%d_N%d%s" % (c[:7] + ("_addend" if c[7] else "",)) for c in DIRECT])
+def test_direct_kernels_per_element(ops, case):
+    """the direct kernels (dconv_kernel 3x3 and its 1- / 2- / 4-tap parity classes, wgrad_kernel) per element against the float64
+    reference, bounds of convref.py (C_FACTOR 2^-24 A) -- test_conv_shape_sweep reaches them only through a rel-L2 norm, the per-element
+    files only under RESNET_MI_IGEMM=0 in child processes.  The planner must send the case to no implicit-GEMM plan"""
+    import convref as R
+    import perelement as P
+    op, C, H, K, k, stride, N, addend = case
+    assert R.conv_plan(ops.L, 0, "default", op, N, C, H, K, k, stride) is None, "the implicit GEMM takes this shape: not a direct-kernel case"
+    worst = {}
+    P.conv_route(ops, ("f32", "default", op, C, H, K, k, stride, "red" if addend else ""), N, lambda key, w: worst.update({key: w}))
+    assert worst
+
+
 # (C, H, K, k, stride, N): dgrads as backwards_pass chains them with the batch-norm backward in front of them
 DGRAD_BN_SHAPES = [
     (64, 56, 256, 1, 1, 2),      # expansion dgrad -> spatial BN'

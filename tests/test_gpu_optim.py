@@ -147,6 +147,35 @@ def test_operator_guards(ops, kind):
     _check_update(kind + " guards", _split(nw, offs), _split(nb, offs), ref_w, ref_b)
 
 
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_operator_scalar_tail(ops, kind):
+    """a tensor whose length is no multiple of 4 ends in scalar code behind the float4 body of its last chunk (the norm pass and the
+    update).  Every ResNet-50 tensor is a multiple of 4 long, so the ResNet-50 geometry never runs it; a 10-class FC bias does.  Three
+    tensors, the last 8192 + 7 floats (one whole chunk, then a chunk of one float4 and three scalars) -- the operator takes a tensor's
+    length from the gap to the next offset, and only the last tensor's end need not be a multiple of 4.  Momentum state of the size of
+    the gradient and three calls, so that mu b is as large as the step; bounds as test_operator_per_element_at_resnet50_geometry"""
+    offs = [0, 64, 64 + 4096, 64 + 4096 + 8192 + 7]
+    is_w = [0, 1, 1]
+    lr = 0.5 if kind == "lars" else 0.01
+    w, g, b = _spread_state(offs, 41)
+    wd = float(np.float32(5e-5))
+    for call in range(3):
+        if call:
+            g = _spread_state(offs, 140 + call)[1]
+        nw, ng, nb, flag, sq = ops.momentum_update(KINDS[kind], w, g, b, offs, is_w, lr, wd, MU, TAU)
+        assert flag == 0 and not np.any(ng)
+        ref_sq = R.sq_norms(_split(w, offs), _split(g, offs))
+        e = np.abs(sq - ref_sq) / np.maximum(ref_sq, 1e-300)
+        assert e.max() <= NORM_REL, "%s call %d: squared norm of tensor %d off by %.3e relative" % (kind, call, int(np.argmax(e) // 2), e.max())
+        ref_w, _, ref_b, rflag = R.step(KINDS[kind], _split(w, offs), _split(g, offs), _split(b, offs), is_w, float(np.float32(lr)), wd, MU, TAU)
+        assert rflag == 0
+        _check_update("%s scalar tail call %d" % (kind, call), _split(nw, offs), _split(nb, offs), ref_w, ref_b)
+        # the three scalar elements on their own: a fault there is 3 of 8199 elements of the tensor's rel-L2
+        tail = slice(offs[-1] - 3, offs[-1])
+        _check_update("%s scalar tail call %d, the last three elements" % (kind, call), [nw[tail]], [nb[tail]], [ref_w[-1][-3:]], [ref_b[-1][-3:]])
+        w, b = nw, nb
+
+
 def test_lars_all_zero_gradient_takes_the_trust_one_path(ops):
     dims = synth.C1S_DIMS
     offs, is_w = _small_geometry(dims), _is_weight(dims)

@@ -65,6 +65,23 @@ def test_fp32_formulas_stay_inside_the_derived_bound(shape, eps):
     assert np.all(np.isfinite(got)) and share <= 0.06  # the share the bound's derivation leaves unused: DESIGN.md
 
 
+def test_long_row_corner_needs_the_double_lane_sums():
+    """the rows of lossref.long_row_corner against the first-order <mem> bound of DESIGN.md (lossref.loss_bound_mem, tighter than loss_bound):
+    the fp32 restatement with double lane sums stays inside it with room, the same formulas with float lane sums do not -- the check
+    tests/test_gpu_loss_head.py::test_long_row_sums_z_in_double makes on the device"""
+    x, lab = R.long_row_corner()
+    assert x.shape == (len(R.LONG_ROW_T), R.LONG_ROW_L) and x.shape[1] > 1024
+    eps = 0.5
+    ref = R.loss_head(x, lab, eps)[2]
+    bound = R.loss_bound_mem(x, lab, eps)
+    assert np.all(bound < R.loss_bound(ref))
+    good = np.abs(R.loss_head_f32(x, lab, eps).astype(np.float64) - ref) / bound
+    bad = np.abs(R.loss_head_f32(x, lab, eps, long_rows_in_double=False).astype(np.float64) - ref) / bound
+    print("double lane sums: worst |error| / bound %.3f; float lane sums: %s" % (good.max(), np.round(bad, 3)))
+    assert good.max() <= 0.5
+    assert np.all(bad > 1.0)
+
+
 def test_library_exports_the_loss_entry_points():
     from resnet_amd import binding
     lib = binding.load()
