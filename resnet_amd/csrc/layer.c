@@ -1,9 +1,10 @@
 /*
  * layer.c -- everything that follows from one MiLayer alone (mi_host.h): the planner that gives a convolution its forward, dgrad and
  * wgrad kernel routes and the sizes of the buffers those routes need, the allocation of exactly those buffers, the layer's share of
- * the workspaces, and the runners that re-lay operands and launch in the routes' order.  The trainer (trainer.c) plans its table with
- * the planner's choices and keeps the network: which tensor feeds which layer, streams, events, the weight table.  The operator layer
- * (ops.c) plans one layer with forced routes and runs the same runners.  Plain C over mi_device.h.
+ * the workspaces, and the runners that re-lay operands and launch in the routes' order.  The trainer (trainer.c) keeps the network as
+ * one table of units (MiUnit: a MiLayer with its batch norm, its tensors and the unit whose channel-last planes it writes), plans every
+ * unit's layer with the planner's choices, and owns streams, events and the weight table.  The operator layer (ops.c) plans one layer
+ * with forced routes and runs the same runners.  Plain C over mi_device.h.
  */
 #include <stdio.h>
 #include <string.h>

@@ -130,7 +130,29 @@ int mi_bn_bwd_unit(MiLayerWs *w, mid_stream s, mid_bn_bwd_parts *fz, const void 
                    const float *means, const float *vars, const void *dy, const void *mask_src, int mask_mode, void *gated_out, int a_dt,
                    void *dx, float *dgamma, float *dbeta, int N, int C, int P, float eps);
 void mi_read_options(MiOptions *o); /* the process's switches (trainer.c) */
-typedef struct { MiLayer red, spa, exp, proj; } MiBlockLayers; /* proj.w == NULL: no projection */
+
+/* One convolution + batch norm unit of the trainer's network, and everything about it that is fixed until the buffers are rebuilt
+ * (trainer.c, build_units).  Forward tensors, parameters and parameter gradients only: nothing here points into the derivative tree,
+ * whose tensors overlap mode 2 re-points from the ring on every backward pass */
+enum { MI_U_STEM, MI_U_RED, MI_U_SPA, MI_U_EXP, MI_U_PROJ };
+typedef struct MiUnit {
+    MiLayer L;
+    int block, role;             /* block -1: the stem */
+    int site;                    /* the layer's bit in the BN'-fusion site masks (mi_layer_plan; 0: not a site) */
+    int rs_off;                  /* where its channels start in the running-statistics arena */
+    const BatchNorm *bn;
+    BatchNorm *dbn;              /* (gamma, beta) gradients */
+    Cache_BatchNorm *cache;      /* batch statistics of the last forward_pass (FULL: x-hat and BN output too) */
+    float *dw;                   /* weight gradient */
+    const float *in;             /* NULL: the pass's images (stem) */
+    float *conv_out, *act_out;   /* the convolution's output; BN (+ReLU | +residual+ReLU) of it */
+    const float *residual;
+    int relu;
+    struct MiUnit *cl_reader;    /* the unit whose channel-last input planes this unit's BN apply writes (reduction -> spatial,
+                                  * expansion -> the next block's projection), or NULL */
+    const float *add; float *sum; /* FULL, expansion: the residual is added by a pass of its own, which keeps the pre-ReLU sum */
+    float *out;                  /* what the units behind read: act_out, or that pass's output */
+} MiUnit;
 
 /* momentum SGD / LARS over a parameter-shaped arena (kernels_optim.hip): the chunk table and the per-chunk / per-tensor scratch,
  * built once per arena geometry */
@@ -164,8 +186,12 @@ typedef struct MiCtx {
     mid_wt_entry *wt_tab_dev;
     int *wt_tile_entry_dev;
     MiOptions opt;
-    MiLayer stem;
-    MiBlockLayers *blk;          /* per block */
+    /* the network, written down once per build of the buffers (build_units; drop_buffers empties it) and read by every pass: the
+     * units in the order of the BN gammas in Params.locations -- the stem, then per block reduction, spatial, expansion and the
+     * projection where there is one.  That order is the running-statistics arena's, mi_debug_trainer_routes' and the weight
+     * table's.  blk_unit[i]: block i's reduction unit (unit_of) */
+    MiUnit *units;
+    int n_units, *blk_unit;
     int *nan_flag_dev, *nan_flag_host;
     int nan_check_pending;       /* update_parameters queued a copy of the flag; read it at the next host sync point */
     mid_event ev_nan;            /* recorded behind that copy */
@@ -193,11 +219,11 @@ typedef struct MiCtx {
     float *loss_row; int *loss_rank;
     mid_loss_metrics *loss_metrics;
     /* mi_trainer_track_running_stats (all NULL / 0 while off; none of it is tracked in allocs[]: it survives a rebuild of the
-     * buffers): the arena [2][rs_channels] (running means, then running variances, layers in the order of the BN gammas in
-     * Params.locations), the per-layer table of bn_running_update_kernel on the device, each layer's offset on the host, the number
-     * of forward_pass updates so far; the eval pass's own loss-head rows and records (last, total); acts_from_eval: the stored
-     * activations are an eval pass's, backwards_pass refuses them */
-    int rs_on, rs_layers, rs_channels, *rs_off;
+     * buffers): the arena [2][rs_channels] (running means, then running variances, units in the table's order at MiUnit.rs_off),
+     * the per-unit table of bn_running_update_kernel on the device, the number of forward_pass updates so far; the eval pass's
+     * own loss-head rows and records (last, total); acts_from_eval: the stored activations are an eval pass's, backwards_pass
+     * refuses them */
+    int rs_on, rs_channels;
     float rs_momentum, *rs_arena;
     mid_bn_run_entry *rs_tab_dev;
     int64_t rs_updates;

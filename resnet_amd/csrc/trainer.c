@@ -333,50 +333,97 @@ static size_t max_tensor_elems(const Dims *d, ConvBlock **blocks, int N) {
     return m;
 }
 
-/* the convolution table (MiCtx.stem, MiCtx.blk): every layer planned and given its buffers by layer.c; what the network adds is who
- * writes a layer's channel-last planes (cl_by_bn), the BN'-fusion sites, and the table of weights re-laid once per forward pass */
-static void plan_one(MiCtx *c, MiLayer *L, int N, int site) {
-    ck(mi_layer_plan(L, c->dtype, c->policy, &c->opt, N, site, NULL), "convolution plan");
-    mi_layer_alloc(c, L);
+static MiCtx *ctx_of(Train_ResNet *t) { return (MiCtx *)t->backend_ctx; }
+/* The unit table (MiCtx.units, mi_host.h): the one place that says what the network is -- every conv + BN unit's shape, parameters,
+ * gradients, and which forward tensors it reads and writes.  build_buffers calls it once the forward tree exists (FULL: with its
+ * extras); every pass below reads the table and none walks the trees for these facts again. */
+static MiUnit *unit_of(const MiCtx *c, int block, int role) {
+    if (role == MI_U_STEM) return c->units;
+    MiUnit *u = c->units + c->blk_unit[block] + (role - MI_U_RED);
+    return u < c->units + c->n_units && u->block == block ? u : NULL; /* (NULL: no projection) */
 }
-static void plan_layers(MiCtx *c, const Params *p, const Dims *d, int N) {
-    ConvBlock **blocks = p->conv_blocks;
-    mi_layer_init(&c->stem, p->init_conv_layer, 3, d->input, d->init_conv_filters, d->init_kernel_dim, d->init_conv_stride);
-    plan_one(c, &c->stem, N, 0);
-    c->stem_bf16 = c->stem.out_dt == MID_BF16;
-    free(c->blk);
-    c->blk = (MiBlockLayers *)calloc((size_t)(d->n_conv_blocks > 0 ? d->n_conv_blocks : 1), sizeof(MiBlockLayers));
+static MiUnit *unit_new(MiCtx *c, int block, int role, int site, const float *w, int C, int H, int K, int k, int stride, const BatchNorm *bn,
+                        BatchNorm *dbn, float *dw, Cache_BatchNorm *cache) {
+    MiUnit *u = &c->units[c->n_units++];
+    mi_layer_init(&u->L, w, C, H, K, k, stride);
+    u->block = block; u->role = role; u->site = site;
+    u->bn = bn; u->dbn = dbn; u->dw = dw; u->cache = cache;
+    u->rs_off = u == c->units ? 0 : u[-1].rs_off + u[-1].bn->depth;
+    return u;
+}
+static void unit_tensors(MiUnit *u, const float *in, float *conv_out, float *act_out, const float *residual, int relu) {
+    u->in = in; u->conv_out = conv_out; u->act_out = u->out = act_out; u->residual = residual; u->relu = relu;
+}
+static void build_units(Train_ResNet *t) {
+    MiCtx *c = ctx_of(t);
+    const Dims *d = t->model->dims;
+    const Params *p = t->model->params, *dp = t->backprop_buffer->param_derivs;
+    const Activations *a = t->forward_buffer->activations;
+    const int nb = d->n_conv_blocks;
+    c->units = (MiUnit *)calloc((size_t)(4 * nb + 1), sizeof(MiUnit));
+    c->blk_unit = (int *)calloc((size_t)(nb > 0 ? nb : 1), sizeof(int));
+    c->n_units = 0;
+    MiUnit *stem = unit_new(c, -1, MI_U_STEM, 0, p->init_conv_layer, 3, d->input, d->init_conv_filters, d->init_kernel_dim, d->init_conv_stride,
+                            p->norm_init_conv, dp->norm_init_conv, dp->init_conv_layer, a->norm_init_conv);
+    unit_tensors(stem, NULL, a->init_conv_applied, a->init_conv_activated, NULL, 1);
+    const float *bin = a->init_convblock_input; /* the block's input: the max-pool's output, then the output of the block above */
+    MiUnit *above = NULL;                       /* and the expansion unit that wrote it */
+    for (int i = 0; i < nb; i++) {
+        const ConvBlock *b = p->conv_blocks[i], *db = dp->conv_blocks[i];
+        const Activation_ConvBlock *k = a->activation_conv_blocks[i];
+        const int H = b->incoming_spatial_dim, s = b->stride, inc = b->incoming_filters, rd = b->reduced_depth, ex = b->expanded_depth;
+        c->blk_unit[i] = c->n_units;
+        /* BN' sites (mi_layer_plan): the reduction's dgrad feeds the expansion BN' of an identity block below it */
+        MiUnit *red = unit_new(c, i, MI_U_RED, i > 0 && !p->conv_blocks[i - 1]->projection ? 4 : 0, b->depth_reduction, inc, H, rd, 1, 1,
+                               b->norm_depth_reduction, db->norm_depth_reduction, db->depth_reduction, k->norm_post_reduced);
+        MiUnit *spa = unit_new(c, i, MI_U_SPA, 2, b->spatial, rd, H, rd, 3, s, b->norm_spatial, db->norm_spatial, db->spatial, k->norm_post_spatial);
+        MiUnit *expa = unit_new(c, i, MI_U_EXP, 1, b->depth_expansion, rd, H / s, ex, 1, 1, b->norm_expansion, db->norm_expansion,
+                               db->depth_expansion, k->norm_post_expanded);
+        unit_tensors(red, bin, k->post_reduced, k->post_reduced_activated, NULL, 1);
+        unit_tensors(spa, red->out, k->post_spatial, k->post_spatial_activated, NULL, 1);
+        red->cl_reader = spa; /* the reduction BN writes the 3x3's planes beside its NCHW output */
+        const float *res = bin;
+        if (b->projection) { /* resnet.cu:1685-1704; 3x3 where the block strides */
+            MiUnit *proj = unit_new(c, i, MI_U_PROJ, 0, b->projection, inc, H, ex, s == 2 ? 3 : 1, s, b->norm_projection, db->norm_projection,
+                                    db->projection, k->norm_post_projection);
+            unit_tensors(proj, bin, k->transformed_residual, k->post_projection_norm_vals, NULL, 0);
+            /* this block's input is the output of the block above: its BN + add + ReLU writes the projection's planes too */
+            if (above && !above->add) above->cl_reader = proj;
+            res = proj->out;
+        }
+        if (!c->full_store) /* BN(expanded) + addVec + doActivation in one kernel (:1670, :1717, :1723) */
+            unit_tensors(expa, spa->out, k->post_expanded, k->output_activated, res, 0);
+        else { /* the BN output and the pre-ReLU sum are kept: the add is a pass of its own */
+            unit_tensors(expa, spa->out, k->post_expanded, k->post_expanded_norm_vals, NULL, 0);
+            expa->add = res; expa->sum = k->output; expa->out = k->output_activated;
+        }
+        bin = expa->out; above = expa;
+    }
+}
+/* every unit's convolution planned and given its buffers by layer.c; what the network adds is who writes a layer's channel-last planes
+ * (cl_by_bn), the table of weights re-laid once per forward pass, and the workspaces sized for the largest layer */
+static void plan_layers(MiCtx *c, const Dims *d, int N) {
+    MiUnit *const end = c->units + c->n_units;
+    MiLayerNeed need = {0, 0, 0, d->init_conv_filters};
     free(c->wt_tab);
-    c->wt_tab = (mid_wt_entry *)calloc((size_t)(4 * d->n_conv_blocks + 1), sizeof(mid_wt_entry));
+    c->wt_tab = (mid_wt_entry *)calloc((size_t)c->n_units, sizeof(mid_wt_entry));
     c->wt_n = 0; c->wt_tiles = 0;
-    for (int i = 0; i < d->n_conv_blocks; i++) {
-        const ConvBlock *b = blocks[i];
-        MiBlockLayers *B = &c->blk[i];
-        const int H = b->incoming_spatial_dim, s = b->stride;
-        mi_layer_init(&B->red, b->depth_reduction, b->incoming_filters, H, b->reduced_depth, 1, 1);
-        mi_layer_init(&B->spa, b->spatial, b->reduced_depth, H, b->reduced_depth, 3, s);
-        mi_layer_init(&B->exp, b->depth_expansion, b->reduced_depth, H / s, b->expanded_depth, 1, 1);
-        plan_one(c, &B->red, N, i > 0 && !blocks[i - 1]->projection ? 4 : 0);
-        plan_one(c, &B->spa, N, 2);
-        plan_one(c, &B->exp, N, 1);
-        /* the reduction BN writes the 3x3's planes beside its NCHW output (stride 2: a re-layout pass instead where the plane is odd) */
-        if (B->spa.cl) B->spa.cl_by_bn = s == 1 || !(H & 1);
-        if (b->projection) {
-            mi_layer_init(&B->proj, b->projection, b->incoming_filters, H, b->expanded_depth, s == 2 ? 3 : 1, s);
-            plan_one(c, &B->proj, N, 0);
-            /* this block's input is the output of the block above: its BN + add + ReLU writes the planes too */
-            if (B->proj.cl) B->proj.cl_by_bn = i > 0 && !(H & 1);
-        }
-        MiLayer *Ls[4] = {&B->red, &B->spa, &B->exp, &B->proj};
-        for (int j = 0; j < 4; j++) {
-            MiLayer *L = Ls[j];
-            if (!L->w || (!L->wre_fwd && !L->wre_dgrad)) continue;
-            mid_wt_entry *e = &c->wt_tab[c->wt_n++];
-            e->w = L->w; e->K = L->K; e->C = L->C; e->T = L->k * L->k;
-            e->fwd = L->wre_fwd ? falloc(c, L->wre_floats) : NULL; e->dgrad = L->wre_dgrad ? falloc(c, L->wre_floats) : NULL;
-            e->tile0 = c->wt_tiles; c->wt_tiles += (L->C / 32) * (L->K / 32);
-            L->we = e;
-        }
+    for (MiUnit *u = c->units; u < end; u++) {
+        MiLayer *L = &u->L;
+        ck(mi_layer_plan(L, c->dtype, c->policy, &c->opt, N, u->site, NULL), "convolution plan");
+        mi_layer_alloc(c, L);
+        mi_layer_need(L, &need);
+        if (!L->wre_fwd && !L->wre_dgrad) continue;
+        mid_wt_entry *e = &c->wt_tab[c->wt_n++];
+        e->w = L->w; e->K = L->K; e->C = L->C; e->T = L->k * L->k;
+        e->fwd = L->wre_fwd ? falloc(c, L->wre_floats) : NULL; e->dgrad = L->wre_dgrad ? falloc(c, L->wre_floats) : NULL;
+        e->tile0 = c->wt_tiles; c->wt_tiles += (L->C / 32) * (L->K / 32);
+        L->we = e;
+    }
+    c->stem_bf16 = c->units->L.out_dt == MID_BF16;
+    for (MiUnit *u = c->units; u < end; u++) { /* (stride 2: a re-layout pass instead where the plane is odd) */
+        MiLayer *R = u->cl_reader ? &u->cl_reader->L : NULL;
+        if (R && R->cl) R->cl_by_bn = R->stride == 1 || !(R->H & 1);
     }
     c->wt_tab_dev = NULL; c->wt_tile_entry_dev = NULL;
     if (c->wt_n) {
@@ -392,20 +439,9 @@ static void plan_layers(MiCtx *c, const Params *p, const Dims *d, int N) {
         mid_stream_sync(G.compute);
         free(te);
     }
-}
-/* the workspaces every convolution shares, sized for the largest layer of the table */
-static void size_workspaces(MiCtx *c, const Dims *d) {
-    MiLayerNeed need = {0, 0, 0, d->init_conv_filters};
-    mi_layer_need(&c->stem, &need);
-    for (int i = 0; i < d->n_conv_blocks; i++) {
-        const MiBlockLayers *B = &c->blk[i];
-        const MiLayer *Ls[4] = {&B->red, &B->spa, &B->exp, &B->proj};
-        for (int j = 0; j < 4; j++) if (Ls[j]->w) mi_layer_need(Ls[j], &need);
-    }
     mi_layer_ws_alloc(c, &c->lw, &need);
 }
 
-static MiCtx *ctx_of(Train_ResNet *t) { return (MiCtx *)t->backend_ctx; }
 static void free_activations_host(Activations *a);
 static void add_full_store_extras(Train_ResNet *t);
 static void rs_build_table(Train_ResNet *t);
@@ -439,8 +475,8 @@ static void build_buffers(Train_ResNet *t) {
     /* bf16: the weight gradients are no longer bound by the matrix pipe but by memory, like the batch norm they would run
      * next to -- measured 6028 img/s serial against 5973 overlapped; an explicit RESNET_MI_OVERLAP still wins */
     if (c->dtype == MID_BF16 && !c->opt.overlap_given && !c->overlap_set) c->overlap_wgrad = 0;
-    plan_layers(c, t->model->params, d, N);
-    size_workspaces(c, d);
+    build_units(t);
+    plan_layers(c, d, N);
     mid_stream_sync(G.compute);
     rs_build_table(t); /* (the caches the running-statistics table points at were rebuilt) */
 }
@@ -453,6 +489,8 @@ static void drop_buffers(Train_ResNet *t) {
     t->forward_buffer->activations = NULL; t->backprop_buffer->activation_derivs = NULL;
     c->wt_n = 0; c->wt_tiles = 0; c->wt_tab_dev = NULL; c->wt_tile_entry_dev = NULL;
     c->wgrad_pending = 0;
+    free(c->units); free(c->blk_unit); /* the table pointed into what was just freed */
+    c->units = NULL; c->blk_unit = NULL; c->n_units = 0;
 }
 
 /* the trainer's switches (MiOptions), read once per trainer: a trainer made after a change of the environment sees the change */
@@ -577,15 +615,11 @@ static void add_full_store_extras(Train_ResNet *t) {
 static int bf16_net_supported(const Train_ResNet *t, char *why, size_t whylen) {
     const MiCtx *c = (const MiCtx *)t->backend_ctx;
     const int nchw[3] = {MI_FWD_BF16, MI_DG_BF16, MI_WG_BF16};
-    for (int i = 0; i < t->model->dims->n_conv_blocks; i++) {
-        const MiBlockLayers *B = &c->blk[i];
-        const MiLayer *Ls[4] = {&B->red, &B->spa, &B->exp, &B->proj};
-        for (int j = 0; j < 4; j++) {
-            MiLayer L = *Ls[j];
-            if (L.w && mi_layer_plan(&L, MID_BF16, c->policy, &c->opt, t->batch_size, 0, nchw)) {
-                snprintf(why, whylen, "block %d conv %d (C=%d H=%d K=%d k=%d s=%d) does not tile for the bf16 kernels", i, j, L.C, L.H, L.K, L.k, L.stride);
-                return 0;
-            }
+    for (const MiUnit *u = c->units + 1; u < c->units + c->n_units; u++) {
+        MiLayer L = u->L;
+        if (mi_layer_plan(&L, MID_BF16, c->policy, &c->opt, t->batch_size, 0, nchw)) {
+            snprintf(why, whylen, "block %d conv %d (C=%d H=%d K=%d k=%d s=%d) does not tile for the bf16 kernels", u->block, u->role - MI_U_RED, L.C, L.H, L.K, L.k, L.stride);
+            return 0;
         }
     }
     return 1;
@@ -709,17 +743,29 @@ void mi_trainer_poll_errors(Train_ResNet *t) {
 
 /* conv + BN (+ReLU | +residual+ReLU): prepareAndDoConvolution + prepareAndDoBatchNormAndActivate.
  * stem: the 7x7 convolution keeps fp32 input / output in every storage type; only its BN output is an activation tensor.
- * cl_reader: a convolution this unit's output feeds (mi_layer_bn_fwd) */
-static void unit_fwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNorm *bn, Cache_BatchNorm *cache, float *conv_out,
-                     float *act_out, const float *residual, int relu, const MiLayer *cl_reader) {
+ * running 0: the batch's statistics, left in the unit's cache; 1: the unit's running statistics, read only -- the same convolution call
+ * (its statistics partials are left unused), then the apply kernel alone */
+static void unit_fwd(Train_ResNet *t, MiUnit *u, const float *images, int running) {
     MiCtx *c = ctx_of(t);
+    MiLayer *L = &u->L;
+    const BatchNorm *bn = u->bn;
+    const MiLayer *reader = u->cl_reader ? &u->cl_reader->L : NULL;
     /* the convolution leaves per-tile (count, mean, M2) partials of its output: BN reads the tensor twice, not three times (the
      * kernels with bf16 operands always do) */
     const int bf_ops = L->fwd == MI_FWD_BF16 || L->fwd == MI_FWD_CL || L->fwd == MI_FWD_STEM_BF16;
     mid_bn_parts *parts = (c->opt.bnfuse || bf_ops) ? &c->lw.bn_parts : NULL;
-    ck(mi_layer_fwd(L, &c->lw, G.compute, in, conv_out, parts), "convolution forward");
-    ck(mi_layer_bn_fwd(L, &c->lw, G.compute, parts, conv_out, bn->gamma, bn->beta, residual, cache->means, cache->vars, act_out,
-                       cache->normalized_temp, cache->normalized, t->eps, relu, cl_reader), "batch norm forward");
+    ck(mi_layer_fwd(L, &c->lw, G.compute, u->in ? u->in : images, u->conv_out, parts), "convolution forward");
+    if (running) {
+        const float *rm = c->rs_arena + u->rs_off, *rv = rm + c->rs_channels;
+        ck(mi_layer_bn_apply(L, G.compute, u->conv_out, bn->gamma, bn->beta, u->residual, rm, rv, u->act_out, t->eps, u->relu, reader),
+           "batch norm (running statistics)");
+    } else
+        ck(mi_layer_bn_fwd(L, &c->lw, G.compute, parts, u->conv_out, bn->gamma, bn->beta, u->residual, u->cache->means, u->cache->vars, u->act_out,
+                           u->cache->normalized_temp, u->cache->normalized, t->eps, u->relu, reader), "batch norm forward");
+    if (u->add) { /* FULL policy, expansion */
+        const int Ho = L->H / L->stride;
+        ck(mid_add_relu(G.compute, u->act_out, u->add, u->sum, u->out, (size_t)L->N * L->K * Ho * Ho), "add + ReLU");
+    }
 }
 
 /* the batch-norm launchers take their cross-replica setting from one process-wide slot (kernels_bn.hip): every pass binds ITS
@@ -729,57 +775,41 @@ static void bind_sync_bn(const MiCtx *c) {
     if (c->sync_bn && c->sync_bn_comm) mid_bn_set_sync(c->sync_bn_comm, c->world, c->sync_bn_tmp, MI_SYNC_BN_TMP_FLOATS, 1);
     else mid_bn_set_sync(NULL, 1, NULL, 0, 0);
 }
-/* resnet.cu:1526-1775 */
-void forward_pass(Train_ResNet *t) {
+/* resnet.cu:1526-1775 up to the logits, for forward_pass (running 0) and the eval pass (running 1, see unit_fwd) */
+static void forward_trunk(Train_ResNet *t, const float *images, int running) {
     MiCtx *c = ctx_of(t);
     const Dims *d = t->model->dims;
     const Params *p = t->model->params;
     Activations *a = t->forward_buffer->activations;
-    const int N = t->batch_size, f = d->init_conv_filters;
-    mid_event_record(c->ev_t[0], G.compute);
-    bind_sync_bn(c);
-    c->acts_from_eval = 0;
+    const int N = t->batch_size, nb = d->n_conv_blocks;
     relayout_weights(c);
-    unit_fwd(t, &c->stem, t->cur_batch->images, p->norm_init_conv, a->norm_init_conv, a->init_conv_applied, a->init_conv_activated,
-             NULL, 1, NULL);
-    const int Hs = d->input / d->init_conv_stride;
-    ck(mid_maxpool_fwd_t(G.compute, a->init_conv_activated, a->init_convblock_input, c->dtype, a->max_inds, N, f, Hs, d->init_maxpool_dim,
-                         d->init_maxpool_stride), "max-pool forward");
-    const float *bin = a->init_convblock_input;
-    for (int i = 0; i < d->n_conv_blocks; i++) {
-        const ConvBlock *b = p->conv_blocks[i];
-        MiBlockLayers *B = &c->blk[i];
-        Activation_ConvBlock *k = a->activation_conv_blocks[i];
-        const int Ho = b->incoming_spatial_dim / b->stride;
-        unit_fwd(t, &B->red, bin, b->norm_depth_reduction, k->norm_post_reduced, k->post_reduced, k->post_reduced_activated, NULL, 1, &B->spa);
-        unit_fwd(t, &B->spa, k->post_reduced_activated, b->norm_spatial, k->norm_post_spatial, k->post_spatial, k->post_spatial_activated,
-                 NULL, 1, NULL);
-        const float *res = bin;
-        if (b->projection) { /* resnet.cu:1685-1704 */
-            unit_fwd(t, &B->proj, bin, b->norm_projection, k->norm_post_projection, k->transformed_residual, k->post_projection_norm_vals,
-                     NULL, 0, NULL);
-            res = k->post_projection_norm_vals;
-        }
-        if (!c->full_store) { /* BN(expanded) + addVec + doActivation in one kernel (:1670, :1717, :1723) */
-            unit_fwd(t, &B->exp, k->post_spatial_activated, b->norm_expansion, k->norm_post_expanded, k->post_expanded, k->output_activated,
-                     res, 0, i + 1 < d->n_conv_blocks ? &c->blk[i + 1].proj : NULL); /* (the next block's projection input) */
-        } else {
-            unit_fwd(t, &B->exp, k->post_spatial_activated, b->norm_expansion, k->norm_post_expanded, k->post_expanded,
-                     k->post_expanded_norm_vals, NULL, 0, NULL);
-            ck(mid_add_relu(G.compute, k->post_expanded_norm_vals, res, k->output, k->output_activated,
-                            (size_t)N * b->expanded_depth * Ho * Ho), "add + ReLU");
-        }
-        bin = k->output_activated;
+    unit_fwd(t, unit_of(c, -1, MI_U_STEM), images, running);
+    ck(mid_maxpool_fwd_t(G.compute, a->init_conv_activated, a->init_convblock_input, c->dtype, a->max_inds, N, d->init_conv_filters,
+                         d->input / d->init_conv_stride, d->init_maxpool_dim, d->init_maxpool_stride), "max-pool forward");
+    for (int i = 0; i < nb; i++) { /* the table keeps the order of Params.locations; the projection runs before the expansion that adds it */
+        unit_fwd(t, unit_of(c, i, MI_U_RED), images, running);
+        unit_fwd(t, unit_of(c, i, MI_U_SPA), images, running);
+        if (unit_of(c, i, MI_U_PROJ)) unit_fwd(t, unit_of(c, i, MI_U_PROJ), images, running);
+        unit_fwd(t, unit_of(c, i, MI_U_EXP), images, running);
     }
-    if (c->rs_on) { /* behind the last BN of the pass (under sync-BN: the merged statistics), every layer's running statistics in one launch */
-        ck(mid_bn_running_update(G.compute, c->rs_tab_dev, c->rs_layers, c->rs_channels, c->rs_arena, (size_t)c->rs_channels, c->rs_momentum),
+    if (!running && c->rs_on) { /* behind the last BN of the pass (under sync-BN: the merged statistics), every unit's running statistics in one launch */
+        ck(mid_bn_running_update(G.compute, c->rs_tab_dev, c->n_units, c->rs_channels, c->rs_arena, (size_t)c->rs_channels, c->rs_momentum),
            "running statistics");
         c->rs_updates++;
     }
-    const ConvBlock *last = p->conv_blocks[d->n_conv_blocks - 1];
-    const int Hl = last->incoming_spatial_dim; /* resnet.cu:1732 */
-    ck(mid_avgpool_fwd_t(G.compute, bin, c->dtype, a->final_conv_output_pooled, N, d->final_depth, Hl * Hl), "average pool");
+    const int Hl = p->conv_blocks[nb - 1]->incoming_spatial_dim; /* resnet.cu:1732 */
+    ck(mid_avgpool_fwd_t(G.compute, unit_of(c, nb - 1, MI_U_EXP)->out, c->dtype, a->final_conv_output_pooled, N, d->final_depth, Hl * Hl), "average pool");
     ck(mid_gemm_nn(G.compute, a->final_conv_output_pooled, p->fully_connected, a->linear_output, N, d->final_depth, d->output), "FC forward");
+}
+void forward_pass(Train_ResNet *t) {
+    MiCtx *c = ctx_of(t);
+    const Dims *d = t->model->dims;
+    Activations *a = t->forward_buffer->activations;
+    const int N = t->batch_size;
+    mid_event_record(c->ev_t[0], G.compute);
+    bind_sync_bn(c);
+    c->acts_from_eval = 0;
+    forward_trunk(t, t->cur_batch->images, 0);
     if (c->loss_flags & MI_LOSS_DEVICE) /* soft-max, dlogits (backwards_pass launches no ce_deriv), row losses and ranks, the two records */
         ck(mid_loss_head(G.compute, a->linear_output, t->cur_batch->correct_classes, t->forward_buffer->pred, t->backprop_buffer->output_layer_deriv,
                          c->loss_row, c->loss_rank, N, d->output, c->loss_smoothing, c->loss_topk, c->loss_metrics, c->loss_metrics + 1), "loss head");
@@ -810,13 +840,16 @@ int mi_trainer_set_loss(Train_ResNet *t, float smoothing, int topk, int flags) {
     c->loss_smoothing = smoothing; c->loss_topk = topk; c->loss_flags = flags;
     return 0;
 }
-int mi_trainer_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
-    MiCtx *c = ctx_of(t);
-    if (last) mid_memcpy_d2h(last, c->loss_metrics, sizeof *last, G.compute);
-    if (total) mid_memcpy_d2h(total, c->loss_metrics + 1, sizeof *total, G.compute);
-    if (reset_total) mid_memset(c->loss_metrics + 1, 0, sizeof(mid_loss_metrics), G.compute);
+/* the two records (last, total) a loss head keeps on the device */
+static int read_metrics(mid_loss_metrics *rec, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
+    if (last) mid_memcpy_d2h(last, rec, sizeof *last, G.compute);
+    if (total) mid_memcpy_d2h(total, rec + 1, sizeof *total, G.compute);
+    if (reset_total) mid_memset(rec + 1, 0, sizeof(mid_loss_metrics), G.compute);
     mid_stream_sync(G.compute);
     return mid_last_error()[0] ? -1 : 0;
+}
+int mi_trainer_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
+    return read_metrics(ctx_of(t)->loss_metrics, last, total, reset_total);
 }
 
 /* resnet.cu:3363-3383 */
@@ -844,53 +877,32 @@ float mi_host_loss(Train_ResNet *t, int *n_wrong) {
 
 /* ---------------------------------------------------------------------------------------------- */
 /* Evaluation (resnet_mi.h): running statistics of every batch norm, the eval pass, its metrics. */
-typedef struct { const BatchNorm *bn; const Cache_BatchNorm *cache; } RsLayer;
-/* the BN layers in the order of their gammas in Params.locations: the stem, then per block reduction, spatial, expansion, projection */
-static int rs_collect(const Train_ResNet *t, RsLayer *out) {
-    const Params *p = t->model->params;
-    const Activations *a = t->forward_buffer->activations;
-    int n = 0;
-    out[n].bn = p->norm_init_conv; out[n++].cache = a->norm_init_conv;
-    for (int i = 0; i < t->model->dims->n_conv_blocks; i++) {
-        const ConvBlock *b = p->conv_blocks[i];
-        const Activation_ConvBlock *k = a->activation_conv_blocks[i];
-        out[n].bn = b->norm_depth_reduction; out[n++].cache = k->norm_post_reduced;
-        out[n].bn = b->norm_spatial; out[n++].cache = k->norm_post_spatial;
-        out[n].bn = b->norm_expansion; out[n++].cache = k->norm_post_expanded;
-        if (b->projection) { out[n].bn = b->norm_projection; out[n++].cache = k->norm_post_projection; }
-    }
-    return n;
-}
-/* the device table of bn_running_update_kernel: whenever the caches are rebuilt (build_buffers) or the sample count changes (sync-BN) */
+/* the device table of bn_running_update_kernel, one entry per unit: whenever the caches are rebuilt (build_buffers) or the sample count
+ * changes (sync-BN) */
 static void rs_build_table(Train_ResNet *t) {
     MiCtx *c = ctx_of(t);
     if (!c->rs_arena) return;
-    RsLayer *ls = (RsLayer *)malloc(sizeof(RsLayer) * (size_t)(4 * t->model->dims->n_conv_blocks + 1));
-    const int n = rs_collect(t, ls);
+    const int n = c->n_units;
     mid_bn_run_entry *tab = (mid_bn_run_entry *)malloc(sizeof(mid_bn_run_entry) * (size_t)n);
     const int64_t world = c->sync_bn && c->sync_bn_comm ? c->world : 1; /* sync-BN: the statistics are those of every replica's samples */
     for (int i = 0; i < n; i++) {
-        const int64_t cnt = (int64_t)t->batch_size * ls[i].bn->spatial_dim * ls[i].bn->spatial_dim * world;
-        tab[i].means = ls[i].cache->means; tab[i].vars = ls[i].cache->vars;
-        tab[i].first = tab[i].off = c->rs_off[i]; tab[i].C = ls[i].bn->depth; tab[i].unbias = mi_bn_unbias(cnt);
+        const MiUnit *u = &c->units[i];
+        const int64_t cnt = (int64_t)t->batch_size * u->bn->spatial_dim * u->bn->spatial_dim * world;
+        tab[i].means = u->cache->means; tab[i].vars = u->cache->vars;
+        tab[i].first = tab[i].off = u->rs_off; tab[i].C = u->bn->depth; tab[i].unbias = mi_bn_unbias(cnt);
     }
     mid_memcpy_h2d(c->rs_tab_dev, tab, sizeof(mid_bn_run_entry) * (size_t)n, G.compute);
     mid_stream_sync(G.compute);
-    free(tab); free(ls);
+    free(tab);
 }
 int mi_trainer_track_running_stats(Train_ResNet *t, int on, float momentum) {
     MiCtx *c = ctx_of(t);
     if (!on) { c->rs_on = 0; return 0; }
     if (!(momentum > 0.f && momentum <= 1.f)) { mi_record_host_error("mi_trainer_track_running_stats", "momentum lies in (0, 1]"); return -1; }
     if (!c->rs_arena) { /* the first time: means 0, variances 1, no update yet (switched off and on again, the values stay) */
-        RsLayer *ls = (RsLayer *)malloc(sizeof(RsLayer) * (size_t)(4 * t->model->dims->n_conv_blocks + 1));
-        const int n = rs_collect(t, ls);
-        c->rs_off = (int *)malloc(sizeof(int) * (size_t)(n + 1));
-        int sum = 0;
-        for (int i = 0; i < n; i++) { c->rs_off[i] = sum; sum += ls[i].bn->depth; }
-        c->rs_off[n] = sum;
-        free(ls);
-        c->rs_layers = n; c->rs_channels = sum; c->rs_updates = 0;
+        const MiUnit *lastu = &c->units[c->n_units - 1];
+        const int n = c->n_units, sum = lastu->rs_off + lastu->bn->depth;
+        c->rs_channels = sum; c->rs_updates = 0;
         c->rs_tab_dev = (mid_bn_run_entry *)mid_malloc(sizeof(mid_bn_run_entry) * (size_t)n);
         c->eval_row = (float *)mid_malloc(sizeof(float) * (size_t)t->batch_size);
         c->eval_rank = (int *)mid_malloc(sizeof(int) * (size_t)t->batch_size);
@@ -902,7 +914,7 @@ int mi_trainer_track_running_stats(Train_ResNet *t, int on, float momentum) {
             mi_record_host_error("mi_trainer_track_running_stats", "device allocation failed");
             mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics); mid_free(c->rs_arena);
             c->rs_tab_dev = NULL; c->eval_row = NULL; c->eval_rank = NULL; c->eval_metrics = NULL; c->rs_arena = NULL;
-            free(one); free(c->rs_off); c->rs_off = NULL;
+            free(one);
             return -1;
         }
         mid_memset(c->rs_arena, 0, sizeof(float) * (size_t)sum, G.compute);
@@ -941,17 +953,6 @@ int mi_trainer_set_running_stats(Train_ResNet *t, const float *means, const floa
     return mid_last_error()[0] ? -1 : 0;
 }
 
-/* unit_fwd with the layer's running statistics in place of the batch's: the same convolution call (its statistics partials are
- * left unused), then the apply kernel alone.  li: the layer's index in the running arena */
-static void unit_eval(Train_ResNet *t, MiLayer *L, int li, const float *in, const BatchNorm *bn, float *conv_out, float *act_out,
-                      const float *residual, int relu, const MiLayer *cl_reader) {
-    MiCtx *c = ctx_of(t);
-    const int bf_ops = L->fwd == MI_FWD_BF16 || L->fwd == MI_FWD_CL || L->fwd == MI_FWD_STEM_BF16;
-    mid_bn_parts *parts = (c->opt.bnfuse || bf_ops) ? &c->lw.bn_parts : NULL;
-    const float *rm = c->rs_arena + c->rs_off[li], *rv = rm + c->rs_channels;
-    ck(mi_layer_fwd(L, &c->lw, G.compute, in, conv_out, parts), "convolution forward");
-    ck(mi_layer_bn_apply(L, G.compute, conv_out, bn->gamma, bn->beta, residual, rm, rv, act_out, t->eps, relu, cl_reader), "batch norm (running statistics)");
-}
 static int eval_args_ok(const Train_ResNet *t, const char *who, int n_valid, int topk) {
     const MiCtx *c = (const MiCtx *)t->backend_ctx;
     if (!c->rs_on) { mi_record_host_error(who, "running statistics are not tracked (mi_trainer_track_running_stats)"); return -1; }
@@ -965,36 +966,9 @@ int mi_trainer_eval_forward(Train_ResNet *t, const float *images_dev, const int 
     if (eval_args_ok(t, "mi_trainer_eval_forward", n_valid, topk)) return -1;
     if (!images_dev) { mi_record_host_error("mi_trainer_eval_forward", "no images"); return -1; }
     const Dims *d = t->model->dims;
-    const Params *p = t->model->params;
     Activations *a = t->forward_buffer->activations;
-    const int N = t->batch_size, f = d->init_conv_filters, Hs = d->input / d->init_conv_stride;
-    int li = 0;
     c->acts_from_eval = 1; /* the stored activations are no longer those of a forward_pass */
-    relayout_weights(c);
-    unit_eval(t, &c->stem, li++, images_dev, p->norm_init_conv, a->init_conv_applied, a->init_conv_activated, NULL, 1, NULL);
-    ck(mid_maxpool_fwd_t(G.compute, a->init_conv_activated, a->init_convblock_input, c->dtype, a->max_inds, N, f, Hs, d->init_maxpool_dim,
-                         d->init_maxpool_stride), "max-pool forward");
-    const float *bin = a->init_convblock_input;
-    for (int i = 0; i < d->n_conv_blocks; i++) {
-        const ConvBlock *b = p->conv_blocks[i];
-        MiBlockLayers *B = &c->blk[i];
-        Activation_ConvBlock *k = a->activation_conv_blocks[i];
-        const int l_red = li, l_spa = li + 1, l_exp = li + 2, l_proj = li + 3;
-        li += b->projection ? 4 : 3;
-        unit_eval(t, &B->red, l_red, bin, b->norm_depth_reduction, k->post_reduced, k->post_reduced_activated, NULL, 1, &B->spa);
-        unit_eval(t, &B->spa, l_spa, k->post_reduced_activated, b->norm_spatial, k->post_spatial, k->post_spatial_activated, NULL, 1, NULL);
-        const float *res = bin;
-        if (b->projection) {
-            unit_eval(t, &B->proj, l_proj, bin, b->norm_projection, k->transformed_residual, k->post_projection_norm_vals, NULL, 0, NULL);
-            res = k->post_projection_norm_vals;
-        }
-        unit_eval(t, &B->exp, l_exp, k->post_spatial_activated, b->norm_expansion, k->post_expanded, k->output_activated, res, 0,
-                  i + 1 < d->n_conv_blocks ? &c->blk[i + 1].proj : NULL);
-        bin = k->output_activated;
-    }
-    const int Hl = p->conv_blocks[d->n_conv_blocks - 1]->incoming_spatial_dim;
-    ck(mid_avgpool_fwd_t(G.compute, bin, c->dtype, a->final_conv_output_pooled, N, d->final_depth, Hl * Hl), "average pool");
-    ck(mid_gemm_nn(G.compute, a->final_conv_output_pooled, p->fully_connected, a->linear_output, N, d->final_depth, d->output), "FC forward");
+    forward_trunk(t, images_dev, 1);
     /* the head over the valid rows only: pred, row losses and ranks, the eval records; no dlogits */
     if (labels_dev)
         ck(mid_loss_head(G.compute, a->linear_output, labels_dev, t->forward_buffer->pred, NULL, c->eval_row, c->eval_rank, n_valid, d->output, 0.f, topk,
@@ -1005,11 +979,7 @@ int mi_trainer_eval_forward(Train_ResNet *t, const float *images_dev, const int 
 int mi_trainer_eval_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
     MiCtx *c = ctx_of(t);
     if (!c->eval_metrics) { mi_record_host_error("mi_trainer_eval_metrics", "running statistics are not tracked (mi_trainer_track_running_stats)"); return -1; }
-    if (last) mid_memcpy_d2h(last, c->eval_metrics, sizeof *last, G.compute);
-    if (total) mid_memcpy_d2h(total, c->eval_metrics + 1, sizeof *total, G.compute);
-    if (reset_total) mid_memset(c->eval_metrics + 1, 0, sizeof(mid_loss_metrics), G.compute);
-    mid_stream_sync(G.compute);
-    return mid_last_error()[0] ? -1 : 0;
+    return read_metrics(c->eval_metrics, last, total, reset_total);
 }
 static void ev8_free(MiCtx *c) {
     mid_free(c->ev8_images); mid_free(c->ev8_bytes_dev); mid_free(c->ev8_labels_dev); mid_free(c->ev8_plan_dev);
@@ -1076,17 +1046,17 @@ static float *ring_take(MiCtx *c, int *slot) {
     return c->ring_buf[i];
 }
 /* d_slot: ring slot holding d_conv_out (mode 2), -1 otherwise.  fz: the BN'-partials hand-off between a fusing dgrad and the next
- * unit (nparts > 0: this unit's BN' reduction is done); fz_req: what this unit's dgrad is to fill it with, or NULL (mi_layer_fz_request) */
-static void unit_bwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNorm *bn, const Cache_BatchNorm *cache,
-                     const BatchNorm *dbn, const float *conv_out, const float *dy, const float *mask_src, int mask_mode,
-                     float *gated_out, float *d_conv_out, int d_slot, float *dx, const float *addend, float *dw, mid_bn_bwd_parts *fz,
-                     const mid_bn_bwd_parts *fz_req) {
+ * unit (nparts > 0: this unit's BN' reduction is done); fz_req: what this unit's dgrad is to fill it with, or NULL (unit_fz_request) */
+static void unit_bwd(Train_ResNet *t, MiUnit *u, const float *dy, const float *mask_src, int mask_mode, float *gated_out, float *d_conv_out,
+                     int d_slot, float *dx, const float *addend, mid_bn_bwd_parts *fz, const mid_bn_bwd_parts *fz_req) {
     MiCtx *c = ctx_of(t);
+    MiLayer *L = &u->L;
+    const float *in = u->in ? u->in : t->cur_batch->images;
     const int Ho = L->H / L->stride;
     /* BN' of this unit (HBM-bound) runs next to earlier units' weight gradients (FMA-bound, low-priority aux stream);
      * mask_mode 3: ReLU' of the block output fused in, and its product with the upstream gradient kept (gated_out) */
-    ck(mi_bn_bwd_unit(&c->lw, G.compute, fz, conv_out, L->out_dt, bn->gamma, bn->beta, cache->means, cache->vars, dy, mask_src, mask_mode,
-                      gated_out, c->dtype, d_conv_out, dbn->gamma, dbn->beta, t->batch_size, L->K, Ho * Ho, t->eps), "batch norm backward");
+    ck(mi_bn_bwd_unit(&c->lw, G.compute, fz, u->conv_out, L->out_dt, u->bn->gamma, u->bn->beta, u->cache->means, u->cache->vars, dy, mask_src,
+                      mask_mode, gated_out, c->dtype, d_conv_out, u->dbn->gamma, u->dbn->beta, t->batch_size, L->K, Ho * Ho, t->eps), "batch norm backward");
     /* the channel-last copy of d_conv_out that the channel-last dgrad AND the weight gradient read: made here, before either is
      * launched, so that every weight-gradient schedule (the free-running one starts before the dgrad) runs the same kernels */
     ck(mi_layer_dy_relayout(L, G.compute, d_conv_out), "dY re-layout (channel-last)");
@@ -1094,7 +1064,7 @@ static void unit_bwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNo
         /* d_conv_out is final once BN' is: the weight gradient may start now and run for as long as the slot lives */
         mid_event_record(c->ev_bn_done, G.compute);
         mid_stream_wait_event(G.aux, c->ev_bn_done);
-        ck(mi_layer_wgrad(L, &c->lw, G.aux, in, d_conv_out, dw), "convolution wgrad");
+        ck(mi_layer_wgrad(L, &c->lw, G.aux, in, d_conv_out, u->dw), "convolution wgrad");
         mid_event_record(c->ring_ev[d_slot], G.aux);
         c->ring_busy[d_slot] = 1;
         mid_event_record(c->ev_wgrad_done, G.aux);
@@ -1107,10 +1077,21 @@ static void unit_bwd(Train_ResNet *t, MiLayer *L, const float *in, const BatchNo
     if (c->overlap_wgrad) {
         mid_event_record(c->ev_bn_done, G.compute);
         mid_stream_wait_event(G.aux, c->ev_bn_done);
-        ck(mi_layer_wgrad(L, &c->lw, G.aux, in, d_conv_out, dw), "convolution wgrad");
+        ck(mi_layer_wgrad(L, &c->lw, G.aux, in, d_conv_out, u->dw), "convolution wgrad");
         mid_event_record(c->ev_wgrad_done, G.aux);
         c->wgrad_pending = 1;
-    } else ck(mi_layer_wgrad(L, &c->lw, G.compute, in, d_conv_out, dw), "convolution wgrad");
+    } else ck(mi_layer_wgrad(L, &c->lw, G.compute, in, d_conv_out, u->dw), "convolution wgrad");
+}
+/* the request for u's fusing dgrad: the reduction pass of the BN' of the unit that made u's input (mi_layer_fz_request) */
+static const mid_bn_bwd_parts *unit_fz_request(MiCtx *c, const MiUnit *u, const MiUnit *producer, mid_bn_bwd_parts *req) {
+    return mi_layer_fz_request(&u->L, &c->lw, req, producer->conv_out, producer->out, producer->cache->means);
+}
+/* RECOMPUTE_BN: relu(BN(conv_out)) of a unit, re-derived into the scratch the unit behind it reads (resnet_clean.cu:2714, :2753) */
+static void unit_recompute(Train_ResNet *t, const MiUnit *u) {
+    MiCtx *c = ctx_of(t);
+    const int Ho = u->L.H / u->L.stride;
+    ck(mid_bn_apply_t(G.compute, u->conv_out, c->dtype, u->bn->gamma, u->bn->beta, NULL, u->cache->means, u->cache->vars, u->act_out, c->dtype,
+                      t->batch_size, u->L.K, Ho * Ho, t->eps, 1, NULL, 0), "BN recompute");
 }
 /* resnet.cu:1777-2248 */
 void backwards_pass(Train_ResNet *t) {
@@ -1146,66 +1127,50 @@ void backwards_pass(Train_ResNet *t) {
     const int ring = c->overlap_wgrad == 2;
     mid_bn_bwd_parts fz = {NULL}, req; /* BN'-partials hand-off from a fusing dgrad to the next unit (unit_bwd) */
     for (int i = nb - 1; i >= 0; i--) {
-        const ConvBlock *b = p->conv_blocks[i];
-        const ConvBlock *db = dp->conv_blocks[i];
-        MiBlockLayers *B = &c->blk[i];
-        const Activation_ConvBlock *k = a->activation_conv_blocks[i];
-        const Activation_ConvBlock *kb = i == 0 ? NULL : a->activation_conv_blocks[i - 1]; /* the block below */
+        MiUnit *red = unit_of(c, i, MI_U_RED), *spa = unit_of(c, i, MI_U_SPA), *expa = unit_of(c, i, MI_U_EXP), *proj = unit_of(c, i, MI_U_PROJ);
+        const MiUnit *below = i == 0 ? NULL : unit_of(c, i - 1, MI_U_EXP); /* the unit that made this block's input */
         Activation_ConvBlock *dk = da->activation_conv_blocks[i];
-        const float *bin = i == 0 ? a->init_convblock_input : kb->output_activated;
         float *dbin = i == 0 ? da->init_convblock_input : da->activation_conv_blocks[i - 1]->output_activated;
-        const int H = b->incoming_spatial_dim, Ho = H / b->stride;
         const float *up = dk->output_activated; /* dL/d(block output) */
         const float *exp_dy, *exp_mask, *red_addend;
         int exp_mode, s_proj = -1, s_exp = -1, s_spa = -1, s_red = -1;
         if (ring) { /* this block's derivative tensors: fresh ring slots (resnet_cudnn_lowmem.cu:2152-2170 keeps four) */
             dk->output = ring_take(c, NULL);
-            if (b->projection) dk->transformed_residual = ring_take(c, &s_proj);
+            if (proj) dk->transformed_residual = ring_take(c, &s_proj);
         }
         const int up_gated = fz.nparts > 0; /* the block above's reduction dgrad already gated `up` by this block's output and summed for the expansion BN' */
-        if (b->projection) {
+        if (proj) {
             /* ReLU' of the block output (doActivationDeriv, :1934) is fused into the projection BN' as an external mask; that
              * pass also leaves relu'(out) * up in dk->output, which the expansion BN' then reads instead of up + mask */
-            unit_bwd(t, &B->proj, bin, b->norm_projection, k->norm_post_projection, db->norm_projection, k->transformed_residual, up,
-                     k->output_activated, 3, dk->output, dk->transformed_residual, s_proj, dbin, NULL, db->projection, &fz, NULL);
+            unit_bwd(t, proj, up, expa->out, 3, dk->output, dk->transformed_residual, s_proj, dbin, NULL, &fz, NULL);
             exp_dy = dk->output; exp_mask = NULL; exp_mode = 0;
             red_addend = dbin; /* reduce-conv dgrad accumulates onto the projection path (toAdd, :2157) */
         } else {
             /* doActivationDeriv (:1934) rides in the expansion BN' reduce pass, which also leaves relu'(out) * up in dk->output
              * (one pass over the block output less than a separate ReLU' kernel) */
-            exp_dy = up; exp_mask = k->output_activated; exp_mode = 3;
+            exp_dy = up; exp_mask = expa->out; exp_mode = 3;
             red_addend = up_gated ? up : dk->output; /* identity shortcut: setVal 0 + addVec (:2003-2004) folded into the dgrad epilogue */
         }
         if (ring) { dk->post_expanded = ring_take(c, &s_exp); dk->post_spatial_activated = ring_take(c, NULL); }
-        if (recompute) /* the expansion's input, re-derived: relu(BN(post_spatial)) (resnet_clean.cu:2753) */
-            ck(mid_bn_apply_t(G.compute, k->post_spatial, c->dtype, b->norm_spatial->gamma, b->norm_spatial->beta, NULL, k->norm_post_spatial->means,
-                              k->norm_post_spatial->vars, k->post_spatial_activated, c->dtype, N, b->reduced_depth, Ho * Ho, t->eps, 1, NULL, 0),
-               "BN recompute");
-        unit_bwd(t, &B->exp, k->post_spatial_activated, b->norm_expansion, k->norm_post_expanded, db->norm_expansion, k->post_expanded, exp_dy,
-                 exp_mask, exp_mode, dk->output, dk->post_expanded, s_exp, dk->post_spatial_activated, NULL, db->depth_expansion, &fz,
-                 mi_layer_fz_request(&B->exp, &c->lw, &req, k->post_spatial, k->post_spatial_activated, k->norm_post_spatial->means));
+        if (recompute) unit_recompute(t, spa); /* the expansion's input */
+        unit_bwd(t, expa, exp_dy, exp_mask, exp_mode, dk->output, dk->post_expanded, s_exp, dk->post_spatial_activated, NULL, &fz,
+                 unit_fz_request(c, expa, spa, &req));
         /* the call resnet.cu:2060-2083 forgot; present in resnet_cudnn.cu:2365-2366 */
         if (ring) { dk->post_spatial = ring_take(c, &s_spa); dk->post_reduced_activated = ring_take(c, NULL); }
-        if (recompute) /* the 3x3's input, re-derived: relu(BN(post_reduced)) (resnet_clean.cu:2714) */
-            ck(mid_bn_apply_t(G.compute, k->post_reduced, c->dtype, b->norm_depth_reduction->gamma, b->norm_depth_reduction->beta, NULL,
-                              k->norm_post_reduced->means, k->norm_post_reduced->vars, k->post_reduced_activated, c->dtype, N, b->reduced_depth,
-                              H * H, t->eps, 1, NULL, 0), "BN recompute");
-        unit_bwd(t, &B->spa, k->post_reduced_activated, b->norm_spatial, k->norm_post_spatial, db->norm_spatial, k->post_spatial,
-                 dk->post_spatial_activated, NULL, 1, NULL, dk->post_spatial, s_spa, dk->post_reduced_activated, NULL, db->spatial, &fz,
-                 mi_layer_fz_request(&B->spa, &c->lw, &req, k->post_reduced, k->post_reduced_activated, k->norm_post_reduced->means));
+        if (recompute) unit_recompute(t, red); /* the 3x3's input */
+        unit_bwd(t, spa, dk->post_spatial_activated, NULL, 1, NULL, dk->post_spatial, s_spa, dk->post_reduced_activated, NULL, &fz,
+                 unit_fz_request(c, spa, red, &req));
         if (ring) dk->post_reduced = ring_take(c, &s_red);
-        unit_bwd(t, &B->red, bin, b->norm_depth_reduction, k->norm_post_reduced, db->norm_depth_reduction, k->post_reduced,
-                 dk->post_reduced_activated, NULL, 1, NULL, dk->post_reduced, s_red, dbin, red_addend, db->depth_reduction, &fz,
-                 kb ? mi_layer_fz_request(&B->red, &c->lw, &req, kb->post_expanded, kb->output_activated, kb->norm_post_expanded->means) : NULL);
-        mi_dp_reduce_ready(t, (size_t)(db->depth_reduction - c->g_arena), 0);
+        unit_bwd(t, red, dk->post_reduced_activated, NULL, 1, NULL, dk->post_reduced, s_red, dbin, red_addend, &fz,
+                 below ? unit_fz_request(c, red, below, &req) : NULL);
+        mi_dp_reduce_ready(t, (size_t)(red->dw - c->g_arena), 0);
     }
     const int Hs = d->input / d->init_conv_stride;
     int s_stem = -1;
     if (ring) { da->init_conv_activated = ring_take(c, NULL); da->init_conv_applied = ring_take(c, &s_stem); }
     ck(mid_maxpool_bwd_t(G.compute, a->max_inds, da->init_convblock_input, da->init_conv_activated, c->dtype, N, d->init_conv_filters, Hs,
                          d->init_maxpool_dim, d->init_maxpool_stride), "max-pool backward");
-    unit_bwd(t, &c->stem, t->cur_batch->images, p->norm_init_conv, a->norm_init_conv, dp->norm_init_conv, a->init_conv_applied,
-             da->init_conv_activated, NULL, 1, NULL, da->init_conv_applied, s_stem, NULL, NULL, dp->init_conv_layer, &fz, NULL);
+    unit_bwd(t, unit_of(c, -1, MI_U_STEM), da->init_conv_activated, NULL, 1, NULL, da->init_conv_applied, s_stem, NULL, NULL, &fz, NULL);
     mi_dp_reduce_ready(t, 0, 1);
     mid_event_record(c->ev_t[3], G.compute);
 }
@@ -1455,14 +1420,9 @@ int mi_trainer_stem_dtype(Train_ResNet *t) { const MiCtx *c = ctx_of(t); return 
 int mi_debug_trainer_routes(const Train_ResNet *t, int *out, int cap) {
     const MiCtx *c = (const MiCtx *)t->backend_ctx;
     int n = 0;
-    for (int i = -1; i < t->model->dims->n_conv_blocks; i++) {
-        const MiLayer *Ls[4] = {i < 0 ? &c->stem : &c->blk[i].red, i < 0 ? NULL : &c->blk[i].spa, i < 0 ? NULL : &c->blk[i].exp, i < 0 ? NULL : &c->blk[i].proj};
-        for (int j = 0; j < 4; j++) {
-            const MiLayer *L = Ls[j];
-            if (!L || !L->w) continue;
-            if (4 * n + 4 <= cap) { out[4 * n] = L->fwd; out[4 * n + 1] = L->dgrad; out[4 * n + 2] = L->wgrad; out[4 * n + 3] = L->fz; }
-            n++;
-        }
+    for (; n < c->n_units; n++) {
+        const MiLayer *L = &c->units[n].L;
+        if (4 * n + 4 <= cap) { out[4 * n] = L->fwd; out[4 * n + 1] = L->dgrad; out[4 * n + 2] = L->wgrad; out[4 * n + 3] = L->fz; }
     }
     return n;
 }
@@ -1521,11 +1481,10 @@ void destroy_trainer(Train_ResNet *t) {
     free(t->loss_per_epoch); free(t->accuracy_per_epoch);
     mi_optim_free(&c->optim);
     mid_free(c->rs_arena); mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics);
-    free(c->rs_off);
     ev8_free(c);
     if (c->ev8_copied) mid_event_destroy(c->ev8_copied);
     free(c->loc_off);
-    free(c->dump_root); free(c->blk); free(c);
+    free(c->dump_root); free(c->units); free(c->blk_unit); free(c);
     free(t);
 }
 

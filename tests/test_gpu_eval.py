@@ -283,6 +283,46 @@ def test_training_is_untouched():
         assert _same(b, c), "with / without an eval pass between the steps: tensor %d of (params, means, vars) differs" % i
 
 
+def _four_steps_and_eval(dtype, first_policy, rebuild_to=None):
+    """two steps, (a change of the store policy: every buffer dropped and rebuilt), two more steps, one eval pass with labels"""
+    dims, batch = NETS["C4I"]
+    tr = _trainer(dims, batch, dtype, first_policy)
+    try:
+        for step in range(4):
+            if step == 2 and rebuild_to is not None:
+                tr.set_store_policy(rebuild_to)
+            _load(tr, dims, batch, step)
+            tr.forward(); tr.backward(); tr.update()
+        assert tr.check_errors() == 0
+        im, lab = synth.make_batch(dims, batch, step=4)
+        tr.eval_forward(T.nhwc_to_nchw(im), lab)
+        tr.check()
+        rm, rv = tr.running_stats()
+        return {"params": [tr.get("params", i) for i in range(tr.n_locations)], "running means": rm, "running vars": rv,
+                "updates": tr.running_updates(), "pred": tr.activation("softmax"), "metrics": tr.eval_metrics()}
+    finally:
+        tr.close()
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_the_network_follows_a_rebuild_of_the_buffers(dtype):
+    """C4I has every role of a unit (a projection block, an identity block with a block behind it, a striding block) and both
+    BN-written channel-last edges.  FAST and RECOMPUTE_BN are bit-identical (test_store_policies_bit_identical_after_25_steps), so a
+    trainer that changes policy between steps 2 and 3 must end where one that had the second policy from the start ends -- unless
+    something kept from before the rebuild (a cache pointer of the running-statistics table, a plane's writer, a weight-table
+    entry) is still read"""
+    from resnet_amd import binding as B
+    a = _four_steps_and_eval(dtype, B.MI_STORE_FAST, rebuild_to=B.MI_STORE_RECOMPUTE_BN)
+    b = _four_steps_and_eval(dtype, B.MI_STORE_RECOMPUTE_BN)
+    for i, (x, y) in enumerate(zip(a["params"], b["params"])):
+        assert _same(x, y), "parameter tensor %d differs behind the rebuild" % i
+    for name in ("running means", "running vars", "pred"):
+        assert _same(a[name], b[name]), "%s differ behind the rebuild" % name
+    assert a["updates"] == b["updates"] == 4
+    assert a["metrics"] == b["metrics"] and a["metrics"][0]["rows"] == NETS["C4I"][1]
+    assert np.float64(a["metrics"][0]["loss_sum"]).tobytes() == np.float64(b["metrics"][0]["loss_sum"]).tobytes()
+
+
 def test_backward_behind_an_eval_pass_is_refused():
     dims, batch = synth.C1S_DIMS, 4
     tr = _trainer(dims, batch)
