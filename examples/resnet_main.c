@@ -16,6 +16,9 @@
  *   ./ResNetMI --label-smoothing 0.1 --topk 5 --device-loss
  *              the loss head on the device (mi_trainer_set_loss): label-smoothed cross entropy, loss and top-1 / top-K error counted
  *              there, one line of totals per epoch; --device-loss also drops forward_pass's blocking copy of the predictions
+ *   ./ResNetMI --label-smoothing 0.1 --mixup 0.2 --cutmix 1.0 --mix-prob 1.0 --mix-seed 7
+ *              mixup / CutMix on the device at every load (mi_trainer_set_mix; implies the device loss head): Beta(A, A) weights with A in
+ *              (0, 1], 0 = that mode off; with both on each step draws one of them with equal odds; --mix-prob P: the share of steps mixed
  *   ./ResNetMI --bn-momentum 0.1 --val-u8 /data/val_shards/u8 --val-dim-in 256 --val-every 5000
  *              evaluation: running statistics of every batch norm (mi_trainer_track_running_stats; --val-u8 alone implies momentum 0.1) and,
  *              every STEPS iterations and at the end of every epoch, the eval pass over every %03d.images_u8 / %03d.labels under DIR
@@ -93,7 +96,10 @@ int main(int argc, char **argv) {
     const char *smoothing_arg = opt(argc, argv, "--label-smoothing", NULL), *topk_arg = opt(argc, argv, "--topk", NULL);
     int device_loss = 0;
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--device-loss")) device_loss = 1;
-    const int loss_on_device = smoothing_arg || topk_arg || device_loss;
+    const double MIXUP = atof(opt(argc, argv, "--mixup", "0")), CUTMIX = atof(opt(argc, argv, "--cutmix", "0")), MIX_PROB = atof(opt(argc, argv, "--mix-prob", "1"));
+    const unsigned long long mix_seed = strtoull(opt(argc, argv, "--mix-seed", "0"), NULL, 10);
+    const int mixing = MIXUP != 0 || CUTMIX != 0;
+    const int loss_on_device = smoothing_arg || topk_arg || device_loss || mixing;
     const int TOPK = atoi(topk_arg ? topk_arg : "5");
     const char *bn_momentum_arg = opt(argc, argv, "--bn-momentum", NULL), *val_u8 = opt(argc, argv, "--val-u8", NULL);
     const int VAL_DIM_IN = atoi(opt(argc, argv, "--val-dim-in", "256")), VAL_EVERY = atoi(opt(argc, argv, "--val-every", "0"));
@@ -133,6 +139,7 @@ int main(int argc, char **argv) {
     if (dump_root) mi_trainer_set_dump_root(trainer, dump_root); else mi_trainer_set_dump_every(trainer, 0);
     if (loss_on_device && mi_trainer_set_loss(trainer, (float)atof(smoothing_arg ? smoothing_arg : "0"), TOPK,
                                               MI_LOSS_DEVICE | (device_loss ? MI_LOSS_NO_PRED_COPY : 0))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    if (mixing && mi_trainer_set_mix(trainer, MIXUP, CUTMIX, MIX_PROB, 0.5, mix_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if ((bn_momentum_arg || val_u8) && mi_trainer_track_running_stats(trainer, 1, (float)atof(bn_momentum_arg ? bn_momentum_arg : "0.1"))) {
         fprintf(stderr, "%s\n", mi_last_error()); return 1;
     }

@@ -270,7 +270,7 @@ void mi_trainer_last_timings(Train_ResNet *t, float out_ms[5]);
 
 /* optional per-kernel-family timing with HIP events on the launch stream (used by bench.py's roofline):
  * family 0 direct (VALU) conv fwd/dgrad, 1 direct (VALU) conv wgrad, 2 1x1 conv / FC on MFMA, 3 batch norm,
- * 5 3x3 conv on the MFMA implicit GEMM (fwd, dgrad, wgrad), 4 the input-side passes (uint8 decode, NHWC -> NCHW).
+ * 5 3x3 conv on the MFMA implicit GEMM (fwd, dgrad, wgrad), 4 the input-side passes (uint8 decode, NHWC -> NCHW, mixup / CutMix).
  * flops/bytes are the ALGORITHMIC work of the timed launches. */
 void mi_prof_enable(int on); /* 0 off, 1 all families, otherwise a bit mask of (1 << family) */
 void mi_prof_reset(void);
@@ -630,6 +630,64 @@ int mi_op_resample_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_n
 int mi_batch_set_augment_rrc(Batch *b, int flip, uint64_t seed, double scale_lo, double scale_hi, double ratio_lo, double ratio_hi);
 /* the boxes of the last load, int [n_images][5]; returns n_images, or -1 (another source or mode, or nothing loaded yet) */
 int mi_batch_last_boxes(const Batch *b, int *out);
+
+/* ---------------- mixing: mixup and CutMix in place, a two-label loss head ----------------
+ * mixup (Zhang et al. 2018) blends every image of a batch with a partner, CutMix (Yun et al. 2019) pastes a box of the partner into it;
+ * the loss weighs both images' labels.  The partner of row i is row n - 1 - i (timm's x.flip(0)), one weight lam and one box per batch.
+ * Everything here is off by default, and with nothing enabled every launch, value and dumped file is what it was.
+ *
+ * mi_mix_plan: host-only and deterministic, a pure function of its arguments.  mode 0 none (lam = 1.f), 1 mixup, 2 CutMix; the box is
+ * rows [y0, y1) x columns [x0, x1) (all 0 unless mode 2).  s = splitmix64_at(seed, epoch), k = splitmix64_at(s, step world + rank)
+ * (the index modulo 2^64), d(j) = splitmix64_at(k, j), U(x) = (x >> 11) 2^-53 (the counter streams of synth.c, as the RRC plan):
+ *   U(d(0)) >= prob: mode 0.  Else with both alphas > 0: U(d(1)) < switch_prob picks CutMix, else mixup; with one alpha > 0 that mode.
+ *   lam ~ Beta(alpha, alpha), alpha the chosen mode's, by Johnk's method: try t = 0 .. 63: X = pow(U(d(2 + 2t)), 1 / alpha), Y = pow(U(d(3 +
+ *   2t)), 1 / alpha); the first try with 0 < X + Y <= 1 gives lam = X / (X + Y); no try taken: lam = 0.5.
+ *   CutMix (timm's rand_bbox on a D x D image, D = dim): cut = (int)(D sqrt(1 - lam)), cy = ((d(130) >> 32) D) >> 32, cx likewise from
+ *   d(131), y0 = clamp(cy - cut / 2, 0, D), y1 = clamp(cy + cut / 2, 0, D) (cut / 2 the integer quotient), x0, x1 likewise; then
+ *   lam = 1 - (double)((y1 - y0) (x1 - x0)) / (D D).
+ * Plain double arithmetic, every operation rounded on its own (1 / alpha included); lam is that double rounded to float once.
+ * Returns 0, or -1 with mi_last_error set: an alpha outside [0, 1] (0 = that mode off; Johnk's acceptance rate falls off above 1; the
+ * recipes use 0.2, 0.8 and 1.0), both alphas 0, prob or switch_prob outside [0, 1], dim outside [1, 16384], rank outside [0, world). */
+typedef struct { int mode; float lam; int y0, x0, y1, x1; } MiMixPlan;
+int mi_mix_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, double mixup_alpha, double cutmix_alpha, double prob,
+                double switch_prob, int dim, MiMixPlan *out);
+/* the mix kernels on their own (kernels_input.hip): images_nchw fp32 [n][3][dim][dim] in device memory, mixed IN PLACE, row i with row
+ * n - 1 - i; for odd n the middle row is not touched.  plan_host: a MiMixPlan in host memory.
+ *   mode 1: a' = (lam (x) a) (+) (mu (x) b), b' = (lam (x) b) (+) (mu (x) a), mu = 1.f - lam, (x) and (+) fp32 operations rounded one by one
+ *           (no fused multiply-add): the bits of a float32 numpy model.  lam = 1.f leaves every value (-0.f becomes +0.f beside a finite
+ *           partner, a non-finite partner makes NaN: 0 (x) inf).  16-byte accesses where image_size % 4 == 0 and images is 16-byte aligned.
+ *   mode 2: inside rows [y0, y1) x columns [x0, x1) of every plane a and b change places, bit for bit; the box is clamped on the
+ *           device (y0 into [0, dim], y1 into [y0, dim], x likewise): nothing outside it is read or written, an empty box launches nothing.
+ *   mode 0: nothing is launched.
+ * Returns 0, or -1 with mi_last_error set and nothing launched: n outside [1, 65535], image_size != 3 dim^2, dim outside [1, 16384], a NULL
+ * pointer, images not 4-byte aligned, an unknown mode, mode 1 with lam outside [0, 1]. */
+int mi_op_mix_batch(float *images_nchw, int n, int image_size /* 3 dim^2 */, int dim, const MiMixPlan *plan_host);
+/* the two-label head: mi_op_loss_head with labels a (the image's own) and b (its partner's) per row and one weight lam in [0, 1].  With
+ * u = eps / (float)L, wa = (1.f - eps) (x) lam, wb = (1.f - eps) (x) (1.f - lam), each product rounded once:
+ *   pred      the bits of mi_op_softmax
+ *   dlogits   p_j - t_j, t_j = w_j (+) u, w_j = (j == a ? wa : 0.f) (+) (j == b ? wb : 0.f), in that order: at lam = 1.f that is (1.f - eps)
+ *             + u on a and u elsewhere, the bits of mi_op_loss_head, whatever labels_b holds
+ *   row_loss  logf(s) - wa z_a - wb z_b - u sum_j z_j (rows longer than 1024 keep the double lane sums); the bound of mi_op_loss_head,
+ *             2^-19 (2 + ref), holds against the two-label float64 value ("Loss head")
+ *   row_rank  measured against label a alone.  On a mixed batch it says whether the image's own class still leads: a training-time
+ *             indicator, not an accuracy
+ * a outside [0, L): as mi_op_loss_head (no t_a term, rank L, loss NaN).  b outside [0, L) with wb > 0: no t_b term, row_loss = NaN; with
+ * wb == 0 labels_b is not read.  Nothing outside the row is read.  The reduce launch and the records are mi_op_loss_head's.  Returns 0,
+ * or -1 as mi_op_loss_head, and for lam outside [0, 1] or labels_b NULL. */
+int mi_op_loss_head_mix(const float *logits, const int *labels_a, const int *labels_b, float lam, float *pred, float *dlogits, float *row_loss,
+                        int *row_rank, int N, int L, float smoothing, int topk, MiLossMetrics *last_dev, MiLossMetrics *total_dev);
+/* The trainer.  While mixing is on load_new_batch ends, for every data source and behind the prefetch swap, on the compute stream, with:
+ * the plan of (seed, cur_epoch, cur_dump_id before its increment, the Batch's rank and world: mi_batch_set_rank_slice) -- values a dump
+ * saves, so a resumed run and a prefetching run see the same draws --, the mix launch on Batch.images (dim = the network's input), and
+ * one launch that writes labels_b[i] = labels[n - 1 - i] into an array of the trainer's; forward_pass then runs the two-label head with
+ * that array and the plan's lam (mode 0: the one-label head, no other launch).  correct_classes keeps the images' own labels, and
+ * mi_trainer_metrics' top-1 / top-k counts are measured against them.  backwards_pass is unchanged.  The eval entry points never mix;
+ * mi_trainer_eval_forward on the CURRENT batch (Batch.images) sees the mixed pixels.  Refused (-1, mi_last_error set) unless the head
+ * is MI_LOSS_DEVICE, and for arguments mi_mix_plan refuses; mi_trainer_set_loss in turn refuses to drop MI_LOSS_DEVICE while mixing is
+ * on.  Both alphas 0 switch it off.  May be called between steps.  Like the optimizer and the loss setting it is not dumped: a
+ * resumed run sets it again.  mi_trainer_last_mix: the plan of the last load_new_batch (all 0 before the first); -1 while mixing is off. */
+int mi_trainer_set_mix(Train_ResNet *t, double mixup_alpha, double cutmix_alpha, double prob, double switch_prob, uint64_t seed);
+int mi_trainer_last_mix(const Train_ResNet *t, MiMixPlan *out);
 
 /* typed operator layer: x_dt = storage type of the convolution-side tensors (x, dx), a_dt = of the activation-side tensors
  * (y, residual, dy, mask_src, gated_out).  Supported pairs: (F32,F32), (BF16,BF16), (F32,BF16). */

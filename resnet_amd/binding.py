@@ -94,6 +94,13 @@ class Train_ResNet(C.Structure):
                 ("init_loaded", C.c_int), ("backend_ctx", C.c_void_p), ("dump_dir", C.c_char_p)]
 
 
+class MiMixPlan(C.Structure):
+    _fields_ = [("mode", C.c_int), ("lam", C.c_float), ("y0", C.c_int), ("x0", C.c_int), ("y1", C.c_int), ("x1", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class MiLossMetrics(C.Structure):
     _fields_ = [("loss_sum", C.c_double), ("rows", C.c_int64), ("wrong_top1", C.c_int64), ("wrong_topk", C.c_int64),
                 ("batches", C.c_int64)]
@@ -244,6 +251,11 @@ PROTOTYPES = {
     "mi_batch_last_plan": (_i, [_B, _vp]),
     "mi_augment_plan_rrc": (_i, [_i, _u64, _i, C.c_int64, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "mi_op_resample_u8": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "mi_mix_plan": (_i, [_u64, _i, C.c_int64, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _i, C.POINTER(MiMixPlan)]),
+    "mi_op_mix_batch": (_i, [_vp, _i, _i, _i, C.POINTER(MiMixPlan)]),
+    "mi_op_loss_head_mix": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
+    "mi_trainer_set_mix": (_i, [_T, C.c_double, C.c_double, C.c_double, C.c_double, _u64]),
+    "mi_trainer_last_mix": (_i, [_T, C.POINTER(MiMixPlan)]),
     "mi_batch_set_augment_rrc": (_i, [_B, _i, _u64, C.c_double, C.c_double, C.c_double, C.c_double]),
     "mi_batch_last_boxes": (_i, [_B, _vp]),
     "mi_op_convert": (_i, [_vp, _i, _vp, _i, _sz]),

@@ -237,3 +237,112 @@ int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *o
     MI_LAUNCH_CHECK("resample_u8_kernel");
     return 0;
 }
+
+// ---- mixup / CutMix: a batch mixed in place, row i with row n - 1 - i (include/resnet_mi.h, "mixing"; tests/mixref.py) ----
+// A pair is closed under both operations: a thread reads the same element of both images and writes both, so there is no second
+// buffer and no order between workgroups.  The middle row of an odd batch pairs with itself and is left alone (grid.y = n / 2).
+#define MIX_THREADS 256
+#define MIX_MAX_BLOCKS_X 128
+
+// a' = lam (x) a (+) mu (x) b, b' = lam (x) b (+) mu (x) a: every operation rounded on its own.  The pragma, not __fmul_rn / __fadd_rn:
+// those are plain * and + to the compiler, which contracts them into a fused multiply-add like any other
+__device__ __forceinline__ void mix_pair(float &a, float &b, float lam, float mu) {
+#pragma clang fp contract(off)
+    const float la = lam * a, mb = mu * b, lb = lam * b, ma = mu * a;
+    const float na = la + mb, nb = lb + ma;
+    a = na; b = nb;
+}
+// grid (x, n / 2).  Work items of a pair: quads 16-byte groups first (0 where the images are not all 16-byte aligned), then the
+// image_size - 4 quads elements behind them one by one; grid-stride over both
+__global__ void __launch_bounds__(MIX_THREADS)
+mixup_kernel(float *__restrict__ images, int n, size_t image_size, size_t quads, float lam, float mu) {
+    float *a = images + (size_t)blockIdx.y * image_size, *b = images + (size_t)(n - 1 - (int)blockIdx.y) * image_size;
+    const size_t items = quads + (image_size - 4 * quads), step = (size_t)gridDim.x * MIX_THREADS;
+    for (size_t i = (size_t)blockIdx.x * MIX_THREADS + threadIdx.x; i < items; i += step) {
+        if (i < quads) {
+            float4 va = ((const float4 *)a)[i], vb = ((const float4 *)b)[i];
+            mix_pair(va.x, vb.x, lam, mu); mix_pair(va.y, vb.y, lam, mu); mix_pair(va.z, vb.z, lam, mu); mix_pair(va.w, vb.w, lam, mu);
+            ((float4 *)a)[i] = va; ((float4 *)b)[i] = vb;
+        } else {
+            const size_t e = 4 * quads + (i - quads);
+            float va = a[e], vb = b[e];
+            mix_pair(va, vb, lam, mu);
+            a[e] = va; b[e] = vb;
+        }
+    }
+}
+// grid (x, n / 2), a wave per row segment: rows [y0, y1) x columns [x0, x1) of the three planes of a pair change places, as words.
+// The box is clamped here (0 <= y0 <= y1 <= D, x likewise): no plan addresses outside the pair.  vec (image_size % 4 == 0: both
+// images' segments start at the same offset from a 16-byte boundary): the elements up to that boundary one lane each, whole 16-byte
+// groups lane-strided, the rest one lane each; else every element on its own
+__global__ void __launch_bounds__(MIX_THREADS)
+cutmix_kernel(float *__restrict__ images, int n, int D, int y0, int x0, int y1, int x1, int vec) {
+    y0 = min(max(y0, 0), D); y1 = min(max(y1, y0), D);
+    x0 = min(max(x0, 0), D); x1 = min(max(x1, x0), D);
+    const int h = y1 - y0, w = x1 - x0, lane = threadIdx.x & 63;
+    const size_t plane = (size_t)D * D, image_size = 3 * plane;
+    uint32_t *a = (uint32_t *)images + (size_t)blockIdx.y * image_size, *b = (uint32_t *)images + (size_t)(n - 1 - (int)blockIdx.y) * image_size;
+    const int waves = MIX_THREADS / 64;
+    for (int sgm = blockIdx.x * waves + (threadIdx.x >> 6); sgm < 3 * h; sgm += gridDim.x * waves) {
+        const int d = sgm / h, y = y0 + (sgm - d * h);
+        const size_t o = (size_t)d * plane + (size_t)y * D + x0;
+        uint32_t *pa = a + o, *pb = b + o;
+        int head = w, nq = 0;
+        if (vec) {
+            head = min((int)(((16 - ((uintptr_t)pa & 15)) & 15) >> 2), w);
+            nq = (w - head) >> 2;
+        }
+        if (lane < head) { const uint32_t t = pa[lane]; pa[lane] = pb[lane]; pb[lane] = t; }
+        if (!vec) for (int e = 64 + lane; e < w; e += 64) { const uint32_t t = pa[e]; pa[e] = pb[e]; pb[e] = t; }
+        else {
+            uint4 *qa = (uint4 *)(pa + head), *qb = (uint4 *)(pb + head);
+            for (int q = lane; q < nq; q += 64) { const uint4 t = qa[q]; qa[q] = qb[q]; qb[q] = t; }
+            const int e = head + 4 * nq + lane;
+            if (e < w) { const uint32_t t = pa[e]; pa[e] = pb[e]; pb[e] = t; }
+        }
+    }
+}
+// labels_b[i] = labels[n - 1 - i]: the partner's label of every row (the middle row of an odd batch: its own)
+__global__ void __launch_bounds__(MIX_THREADS)
+mix_labels_kernel(const int *__restrict__ labels, int *__restrict__ labels_b, int n) {
+    const int i = blockIdx.x * MIX_THREADS + threadIdx.x;
+    if (i < n) labels_b[i] = labels[n - 1 - i];
+}
+
+int mid_mix_batch(mid_stream s, float *images, int n, size_t image_size, int dim, int mode, float lam, int y0, int x0, int y1, int x1) {
+    if (!images || n < 1 || n > 65535 || dim < 1 || dim > 16384 || image_size != (size_t)3 * dim * dim) {
+        mi_record_error("mid_mix_batch", "need images, 1 <= n <= 65535, 1 <= dim <= 16384 and image_size = 3 dim^2"); return -1;
+    }
+    if (((uintptr_t)images & 3) != 0) { mi_record_error("mid_mix_batch", "images must be 4-byte aligned"); return -1; }
+    if (mode != 0 && mode != 1 && mode != 2) { mi_record_error("mid_mix_batch", "mode is 0 (none), 1 (mixup) or 2 (CutMix)"); return -1; }
+    if (mode == 1 && !(lam >= 0.f && lam <= 1.f)) { mi_record_error("mid_mix_batch", "lam lies in [0, 1]"); return -1; }
+    const int pairs = n / 2;
+    if (mode == 0 || pairs == 0) return 0;
+    const int vec = (image_size & 3) == 0 && ((uintptr_t)images & 15) == 0;
+    if (mode == 1) {
+        const size_t quads = vec ? image_size / 4 : 0, items = quads + (image_size - 4 * quads);
+        const size_t bx = (items + MIX_THREADS - 1) / MIX_THREADS;
+        mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 6.0 * pairs * image_size, 16.0 * pairs * image_size); // both images of a pair read and written once
+        hipLaunchKernelGGL(mixup_kernel, dim3((unsigned)(bx < MIX_MAX_BLOCKS_X ? bx : MIX_MAX_BLOCKS_X), pairs), dim3(MIX_THREADS), 0, (hipStream_t)s, images, n,
+                           image_size, quads, lam, 1.f - lam);
+        mi_prof_end((hipStream_t)s);
+        MI_LAUNCH_CHECK(vec ? "mixup_kernel<vec>" : "mixup_kernel<elem>");
+        return 0;
+    }
+    const int cy0 = min(max(y0, 0), dim), cy1 = min(max(y1, cy0), dim), cx0 = min(max(x0, 0), dim), cx1 = min(max(x1, cx0), dim); // the kernel's clamp
+    const int h = cy1 - cy0, w = cx1 - cx0;
+    if (h == 0 || w == 0) return 0;
+    const int bx = mi_cdiv(3 * h, MIX_THREADS / 64);
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 16.0 * pairs * 3 * h * w); // the box of both images read and written once
+    hipLaunchKernelGGL(cutmix_kernel, dim3(bx < MIX_MAX_BLOCKS_X ? bx : MIX_MAX_BLOCKS_X, pairs), dim3(MIX_THREADS), 0, (hipStream_t)s, images, n, dim, y0, x0, y1,
+                       x1, vec);
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK(vec ? "cutmix_kernel<vec>" : "cutmix_kernel<elem>");
+    return 0;
+}
+int mid_mix_labels(mid_stream s, const int *labels, int *labels_b, int n) {
+    if (!labels || !labels_b || n < 1) { mi_record_error("mid_mix_labels", "need both arrays and n >= 1"); return -1; }
+    hipLaunchKernelGGL(mix_labels_kernel, dim3(mi_cdiv(n, MIX_THREADS)), dim3(MIX_THREADS), 0, (hipStream_t)s, labels, labels_b, n);
+    MI_LAUNCH_CHECK("mix_labels_kernel");
+    return 0;
+}

@@ -11,6 +11,14 @@
 //                                                                    top-k wrong <=> rank >= k; a NaN p_c compares false: rank 0
 // A label outside [0, L): no t_c term (dlogits = p - u: what ce_deriv_kernel does), row_rank = L, row_loss = NaN, nothing read outside the
 // row.  Every output may be NULL: it is then neither computed nor stored.
+//
+// MIX (mixup / CutMix, mi_op_loss_head_mix): two labels a, b per row and one weight lam for the launch, wa = (1.f - eps) (x) lam,
+// wb = (1.f - eps) (x) (1.f - lam), each product rounded on its own:
+//   dlogits_j = p_j - t_j, t_j = w_j + u, w_j = (j == a ? wa : 0.f) + (j == b ? wb : 0.f)   lam = 1.f: (1.f - eps) + u on a, u elsewhere,
+//                                                                    the bits above whatever b is
+//   row_loss  = logf(s) - wa z_a - wb z_b - u sum_j z_j
+//   row_rank  against a, the image's own label (a training-time indicator)
+// a outside [0, L): as above.  b outside [0, L) with wb > 0: no t_b term, row_loss = NaN; with wb == 0 b is never looked at.
 #include "mi_common.hpp"
 #include "mi_device.h"
 
@@ -22,12 +30,25 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     return v;
 }
 
+// a product and a sum that stay two roundings where they meet (the pragma, not __fmul_rn / __fadd_rn: those are plain * and + to the
+// compiler, which contracts them into a fused multiply-add like any other)
+__device__ __forceinline__ float loss_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    const float r = a * b;
+    return r;
+}
+__device__ __forceinline__ float loss_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    const float r = a + b;
+    return r;
+}
+
 // REG: x_j, then expf(x_j - mx), in v[] -- one read of the row and one expf per element; the values, and the order lane `lane` adds its
 // elements lane, lane + 64, ... in, are those of the re-reading form
-template <bool REG>
+template <bool REG, bool MIX>
 __global__ void __launch_bounds__(64)
-loss_head_kernel(const float *__restrict__ x, const int *__restrict__ labels, float *__restrict__ pred, float *__restrict__ dlogits,
-                 float *__restrict__ row_loss, int *__restrict__ row_rank, int L, float eps) {
+loss_head_kernel(const float *__restrict__ x, const int *__restrict__ labels, const int *__restrict__ labels_b, float lam,
+                 float *__restrict__ pred, float *__restrict__ dlogits, float *__restrict__ row_loss, int *__restrict__ row_rank, int L, float eps) {
     constexpr int NV = REG ? LOSS_REG_COLS / 64 : 1;
     const int row = blockIdx.x, lane = threadIdx.x;
     const float *xr = x + (size_t)row * L;
@@ -70,6 +91,10 @@ loss_head_kernel(const float *__restrict__ x, const int *__restrict__ labels, fl
     s = wave_sum(s);
     const float u = eps / (float)L, tc = (1.f - eps) + u;
     const float zc = valid ? xr[c] - mx : 0.f;
+    /* MIX: the second label counts only where it carries weight; wa, wb are products rounded once (no contraction into the sums below) */
+    const float wa = MIX ? loss_mul_rn(1.f - eps, lam) : 0.f, wb = MIX ? loss_mul_rn(1.f - eps, 1.f - lam) : 0.f;
+    const int cb = MIX && wb > 0.f ? labels_b[row] : -1;
+    const bool valid_b = cb >= 0 && cb < L, lost_b = MIX && wb > 0.f && !valid_b;
     const float pc = expf(zc) / s; /* p_c as the loop below writes it */
     int above = 0;
 #define LOSS_COLUMN(j_, e_)                                             \
@@ -77,7 +102,8 @@ loss_head_kernel(const float *__restrict__ x, const int *__restrict__ labels, fl
         const float p_ = (e_) / s;                                      \
         const size_t o_ = (size_t)row * L + (j_);                       \
         if (pred) pred[o_] = p_;                                        \
-        if (dlogits) dlogits[o_] = p_ - (valid && (j_) == c ? tc : u);  \
+        if (dlogits) dlogits[o_] = p_ - (MIX ? loss_add_rn(loss_add_rn(valid && (j_) == c ? wa : 0.f, valid_b && (j_) == cb ? wb : 0.f), u) \
+                                             : (valid && (j_) == c ? tc : u));                                                      \
         above += ((j_) != c && p_ >= pc) ? 1 : 0;                       \
     } while (0)
     if (REG) {
@@ -96,7 +122,10 @@ loss_head_kernel(const float *__restrict__ x, const int *__restrict__ labels, fl
     }
     if (row_loss) {
         if (REG) sz = wave_sum(sz);
-        if (lane == 0) row_loss[row] = valid ? logf(s) - (1.f - eps) * zc - u * sz : __int_as_float(0x7fc00000);
+        if (MIX) {
+            const float zb = valid_b ? xr[cb] - mx : 0.f;
+            if (lane == 0) row_loss[row] = valid && !lost_b ? logf(s) - wa * zc - wb * zb - u * sz : __int_as_float(0x7fc00000);
+        } else if (lane == 0) row_loss[row] = valid ? logf(s) - (1.f - eps) * zc - u * sz : __int_as_float(0x7fc00000);
     }
 }
 
@@ -122,19 +151,39 @@ loss_reduce_kernel(const float *__restrict__ row_loss, const int *__restrict__ r
     if (total) { total->loss_sum += sum; total->rows += N; total->wrong_top1 += w1; total->wrong_topk += wk; total->batches += 1; }
 }
 
-extern "C" int mid_loss_head(mid_stream s, const float *logits, const int *labels, float *pred, float *dlogits, float *row_loss, int *row_rank,
-                             int N, int L, float smoothing, int topk, mid_loss_metrics *last_dev, mid_loss_metrics *total_dev) {
+// labels_b == NULL: the one-label head; else the two-label head with the launch's weight lam
+static int loss_head_launch(const char *who, mid_stream s, const float *logits, const int *labels, const int *labels_b, float lam, float *pred,
+                            float *dlogits, float *row_loss, int *row_rank, int N, int L, float smoothing, int topk, mid_loss_metrics *last_dev,
+                            mid_loss_metrics *total_dev) {
     const bool reg = L <= LOSS_REG_COLS;
     if ((last_dev || total_dev) && !(row_loss && row_rank)) {
-        mi_record_error("mid_loss_head", "the batch totals are taken from row_loss and row_rank: neither may be NULL with them");
+        mi_record_error(who, "the batch totals are taken from row_loss and row_rank: neither may be NULL with them");
         return -1;
     }
-    if (reg) hipLaunchKernelGGL(loss_head_kernel<true>, dim3(N), dim3(64), 0, (hipStream_t)s, logits, labels, pred, dlogits, row_loss, row_rank, L, smoothing);
-    else hipLaunchKernelGGL(loss_head_kernel<false>, dim3(N), dim3(64), 0, (hipStream_t)s, logits, labels, pred, dlogits, row_loss, row_rank, L, smoothing);
-    MI_LAUNCH_CHECK(reg ? "loss_head_kernel<reg>" : "loss_head_kernel<mem>");
+#define LOSS_LAUNCH(REG_, MIX_) \
+    hipLaunchKernelGGL((loss_head_kernel<REG_, MIX_>), dim3(N), dim3(64), 0, (hipStream_t)s, logits, labels, labels_b, lam, pred, dlogits, row_loss, row_rank, L, smoothing)
+    if (labels_b) {
+        if (reg) LOSS_LAUNCH(true, true); else LOSS_LAUNCH(false, true);
+        MI_LAUNCH_CHECK(reg ? "loss_head_mix_kernel<reg>" : "loss_head_mix_kernel<mem>");
+    } else {
+        if (reg) LOSS_LAUNCH(true, false); else LOSS_LAUNCH(false, false);
+        MI_LAUNCH_CHECK(reg ? "loss_head_kernel<reg>" : "loss_head_kernel<mem>");
+    }
+#undef LOSS_LAUNCH
     if (last_dev || total_dev) {
         hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, row_loss, row_rank, N, topk, last_dev, total_dev);
         MI_LAUNCH_CHECK("loss_reduce_kernel");
     }
     return 0;
+}
+extern "C" int mid_loss_head(mid_stream s, const float *logits, const int *labels, float *pred, float *dlogits, float *row_loss, int *row_rank,
+                             int N, int L, float smoothing, int topk, mid_loss_metrics *last_dev, mid_loss_metrics *total_dev) {
+    return loss_head_launch("mid_loss_head", s, logits, labels, NULL, 1.f, pred, dlogits, row_loss, row_rank, N, L, smoothing, topk, last_dev, total_dev);
+}
+extern "C" int mid_loss_head_mix(mid_stream s, const float *logits, const int *labels_a, const int *labels_b, float lam, float *pred, float *dlogits,
+                                 float *row_loss, int *row_rank, int N, int L, float smoothing, int topk, mid_loss_metrics *last_dev,
+                                 mid_loss_metrics *total_dev) {
+    if (!labels_b) { mi_record_error("mid_loss_head_mix", "labels_b is NULL"); return -1; }
+    return loss_head_launch("mid_loss_head_mix", s, logits, labels_a, labels_b, lam, pred, dlogits, row_loss, row_rank, N, L, smoothing, topk, last_dev,
+                            total_dev);
 }

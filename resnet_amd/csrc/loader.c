@@ -193,6 +193,43 @@ int mi_augment_plan_rrc(int flip, uint64_t seed, int epoch, int64_t first_global
     }
     return 0;
 }
+/* mixup / CutMix: what one step's batch is mixed with (include/resnet_mi.h, "mixing"; tests/mixref.py restates it with math.pow /
+ * math.sqrt).  Every product, quotient and sum is rounded on its own, as in the RRC plan */
+int mi_mix_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, double mixup_alpha, double cutmix_alpha, double prob,
+                double switch_prob, int dim, MiMixPlan *out) {
+    const char *who = "mi_mix_plan";
+    if (!out) { mi_record_host_error(who, "out is NULL"); return -1; }
+    memset(out, 0, sizeof *out);
+    out->lam = 1.f;
+    if (!(mixup_alpha >= 0 && mixup_alpha <= 1) || !(cutmix_alpha >= 0 && cutmix_alpha <= 1)) {
+        mi_record_host_error(who, "an alpha lies in (0, 1] (Johnk's method), or is 0: that mode is off"); return -1;
+    }
+    if (!(mixup_alpha > 0) && !(cutmix_alpha > 0)) { mi_record_host_error(who, "both alphas are 0: nothing to draw"); return -1; }
+    if (!(prob >= 0 && prob <= 1) || !(switch_prob >= 0 && switch_prob <= 1)) { mi_record_host_error(who, "prob and switch_prob lie in [0, 1]"); return -1; }
+    if (dim < 1 || dim > 16384) { mi_record_host_error(who, "need 1 <= dim <= 16384"); return -1; }
+    if (world < 1 || rank < 0 || rank >= world) { mi_record_host_error(who, "need 0 <= rank < world"); return -1; }
+    const uint64_t s = mi_splitmix64_at(seed, (uint64_t)(int64_t)epoch);
+    const uint64_t k = mi_splitmix64_at(s, (uint64_t)step * (uint64_t)world + (uint64_t)rank); /* modulo 2^64: the trainer's first step is -1 */
+    if (rrc_unit(mi_splitmix64_at(k, 0)) >= prob) return 0; /* mode 0 */
+    const int cut_mode = mixup_alpha > 0 && cutmix_alpha > 0 ? rrc_unit(mi_splitmix64_at(k, 1)) < switch_prob : cutmix_alpha > 0;
+    const double inv = 1.0 / (cut_mode ? cutmix_alpha : mixup_alpha);
+    double lam = 0.5; /* no try taken */
+    for (int t = 0; t < 64; t++) {
+        const double X = pow(rrc_unit(mi_splitmix64_at(k, 2 + 2 * t)), inv), Y = pow(rrc_unit(mi_splitmix64_at(k, 3 + 2 * t)), inv);
+        const double sum = X + Y;
+        if (sum > 0 && sum <= 1) { lam = X / sum; break; }
+    }
+    out->mode = cut_mode ? 2 : 1;
+    if (cut_mode) { /* timm's rand_bbox on a dim x dim image */
+        const int D = dim, cut = (int)(D * sqrt(1.0 - lam));
+        const int cy = (int)(((mi_splitmix64_at(k, 130) >> 32) * (uint64_t)D) >> 32), cx = (int)(((mi_splitmix64_at(k, 131) >> 32) * (uint64_t)D) >> 32);
+        out->y0 = rrc_clamp(cy - cut / 2, 0, D); out->y1 = rrc_clamp(cy + cut / 2, 0, D);
+        out->x0 = rrc_clamp(cx - cut / 2, 0, D); out->x1 = rrc_clamp(cx + cut / 2, 0, D);
+        lam = 1.0 - (double)((int64_t)(out->y1 - out->y0) * (out->x1 - out->x0)) / (double)((int64_t)D * D);
+    }
+    out->lam = (float)lam;
+    return 0;
+}
 /* double-buffered H2D: while step t runs, batch t+1 of the resident shard goes pinned -> device on the copy stream
  * (the reference copies synchronously at the top of every step, resnet.cu:1315-1316) */
 void mi_batch_set_prefetch(Batch *b, int on) {
@@ -450,6 +487,8 @@ void load_new_batch(Train_ResNet *trainer, Class_Metadata *class_metadata, Batch
         memcpy(b->correct_classes_cpu, e->pool_labels_host + (size_t)j * N, (size_t)N * sizeof(int));
         e->pool_next = (j + 1) % e->pool_batches;
     }
+    /* mixup / CutMix, every source: behind the load (or the prefetch swap) on the compute stream, drawn at the step the dump saves */
+    if (e->status == 0) mi_trainer_mix_batch(trainer, b, e->rank, e->world);
     b->cur_batch_in_shard += 1;
     trainer->cur_dump_id += 1;
 }

@@ -277,6 +277,10 @@ int mid_ce_deriv(mid_stream s, const float *pred, const int *labels, float *d, i
 typedef struct { double loss_sum; int64_t rows, wrong_top1, wrong_topk, batches; } mid_loss_metrics;
 int mid_loss_head(mid_stream s, const float *logits, const int *labels, float *pred, float *dlogits, float *row_loss, int *row_rank, int N,
                   int L, float smoothing, int topk, mid_loss_metrics *last_dev, mid_loss_metrics *total_dev);
+/* the two-label head of mixup / CutMix: t_j = ((j == a ? wa : 0) + (j == b ? wb : 0)) + u with wa = (1.f - eps) lam, wb = (1.f - eps)
+ * (1.f - lam); rank against labels_a; everything else as mid_loss_head, whose bits it gives at lam = 1.f (row_loss apart) */
+int mid_loss_head_mix(mid_stream s, const float *logits, const int *labels_a, const int *labels_b, float lam, float *pred, float *dlogits,
+                      float *row_loss, int *row_rank, int N, int L, float smoothing, int topk, mid_loss_metrics *last_dev, mid_loss_metrics *total_dev);
 /* fused updateMeans+updateVars+updateParams (resnet.cu:605-662).  On NaN/Inf *nan_flag (device int) becomes the highest offending
  * locations[] index + 1 (check_errors, resnet.cu:2879-2907): loc_off_dev = n_loc + 1 arena offsets (floats) of the tensors, base =
  * arena offset of p[0]; loc_off_dev NULL: the flag becomes 1. */
@@ -304,6 +308,13 @@ int mid_nchw_to_nhwc(mid_stream s, const float *in, float *out, int N, int C, in
 int mid_decode_u8(mid_stream s, const uint8_t *src, const int *plan, float *out, int n, int dim_in, int dim_out);
 /* boxes [n][5] (row0, col0, h, w, flip), clamped into the image; each box resampled to dim_out^2.  -2: dim_in too large for LDS */
 int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *out, int n, int dim_in, int dim_out);
+/* mixup / CutMix in place on fp32 NCHW images [n][3][dim][dim], row i paired with row n - 1 - i (the middle row of an odd n is not touched).
+ * mode 0: nothing is launched.  1: a' = lam a + (1.f - lam) b and b' likewise, every operation rounded on its own.  2: the box rows
+ * [y0, y1) x columns [x0, x1) of every plane changes places, clamped into the image on the device; an empty box launches nothing.
+ * -1: n outside [1, 65535], image_size != 3 dim^2, NULL or misaligned images, unknown mode, lam outside [0, 1] */
+int mid_mix_batch(mid_stream s, float *images, int n, size_t image_size, int dim, int mode, float lam, int y0, int x0, int y1, int x1);
+/* labels_b[i] = labels[n - 1 - i] */
+int mid_mix_labels(mid_stream s, const int *labels, int *labels_b, int n);
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */
 int mid_fill_uniform(mid_stream s, float *out, size_t n, uint64_t seed, uint64_t offset, float lo, float hi);
 /* test aids (kernels_misc.hip; callers serialise): `word` into every LDS word of every CU between two device synchronises, and a read-only

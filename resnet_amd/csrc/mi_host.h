@@ -218,6 +218,13 @@ typedef struct MiCtx {
     float loss_smoothing; int loss_topk, loss_flags;
     float *loss_row; int *loss_rank;
     mid_loss_metrics *loss_metrics;
+    /* mi_trainer_set_mix (all 0 / NULL while off; labels_b is not tracked in allocs[]): the settings, the plan of the last
+     * load_new_batch and the partners' labels [batch] the two-label head reads */
+    int mix_on;
+    double mix_alpha[2], mix_prob, mix_switch; /* [0] mixup, [1] CutMix */
+    uint64_t mix_seed;
+    MiMixPlan mix_last;
+    int *mix_labels_b;
     /* mi_trainer_track_running_stats (all NULL / 0 while off; none of it is tracked in allocs[]: it survives a rebuild of the
      * buffers): the arena [2][rs_channels] (running means, then running variances, units in the table's order at MiUnit.rs_off),
      * the per-unit table of bn_running_update_kernel on the device, the number of forward_pass updates so far; the eval pass's
@@ -284,6 +291,9 @@ int mi_dp_plan_buckets(const Dims *d, size_t bucket_bytes, size_t *from, size_t 
 size_t mi_params_arena_floats(const Params *p);
 float *mi_params_arena_base(const Params *p);
 void mi_dp_reduce_ready(Train_ResNet *t, size_t from_float_offset, int force);
+/* trainer.c, the last steps of load_new_batch while mixing is on: the plan of this load, the mix launch on Batch.images and the
+ * partners' labels, on the compute stream */
+void mi_trainer_mix_batch(Train_ResNet *t, Batch *b, int rank, int world);
 void mi_trainer_poll_errors(Train_ResNet *t); /* load_new_batch: wait for and read the NaN / Inf flag of the last update */
 void mi_record_host_error(const char *what, const char *detail); /* sets mi_last_error (runtime.hip) */
 int mi_loss_args_ok(const char *who, float smoothing, int topk, int L); /* ops.c: the rules of mi_op_loss_head / mi_trainer_set_loss */

@@ -140,6 +140,21 @@ int mi_op_loss_head(const float *logits, const int *labels, float *pred, float *
     mid_free(rl); mid_free(rr);
     return rc;
 }
+int mi_op_loss_head_mix(const float *logits, const int *labels_a, const int *labels_b, float lam, float *pred, float *dlogits, float *row_loss,
+                        int *row_rank, int N, int L, float smoothing, int topk, MiLossMetrics *last_dev, MiLossMetrics *total_dev) {
+    const char *who = "mi_op_loss_head_mix";
+    if (N < 1 || L < 1) { mi_record_host_error(who, "N and L are at least 1"); return -1; }
+    if (mi_loss_args_ok(who, smoothing, topk, L)) return -1;
+    if (!(lam >= 0.f && lam <= 1.f)) { mi_record_host_error(who, "lam lies in [0, 1]"); return -1; }
+    if (!labels_b) { mi_record_host_error(who, "labels_b is NULL"); return -1; }
+    const int totals = last_dev || total_dev;
+    float *rl = totals && !row_loss ? (float *)mid_malloc((size_t)N * sizeof(float)) : NULL;
+    int *rr = totals && !row_rank ? (int *)mid_malloc((size_t)N * sizeof(int)) : NULL;
+    const int rc = finish(mid_loss_head_mix(mi_global()->compute, logits, labels_a, labels_b, lam, pred, dlogits, row_loss ? row_loss : rl,
+                                            row_rank ? row_rank : rr, N, L, smoothing, topk, (mid_loss_metrics *)last_dev, (mid_loss_metrics *)total_dev));
+    mid_free(rl); mid_free(rr);
+    return rc;
+}
 /* n / (n - 1) of a batch-norm layer whose statistics are taken over n samples per channel, in double, stored as float; 1 where n <= 1 */
 float mi_bn_unbias(int64_t n) { return n > 1 ? (float)((double)n / (double)(n - 1)) : 1.f; }
 /* bn_running_update_kernel on its own: the table built and checked here (layer i at the sum of the channel counts before it) */
@@ -204,6 +219,12 @@ int mi_op_decode_u8(const uint8_t *src_dev, const int *plan_dev, float *out_nchw
 }
 int mi_op_resample_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_nchw, int n, int dim_in, int dim_out) {
     return finish(mid_resample_u8(mi_global()->compute, src_dev, boxes_dev, out_nchw, n, dim_in, dim_out));
+}
+int mi_op_mix_batch(float *images_nchw, int n, int image_size, int dim, const MiMixPlan *plan_host) {
+    if (!plan_host) { mi_record_host_error("mi_op_mix_batch", "plan_host is NULL"); return -1; }
+    if (image_size < 1) { mi_record_host_error("mi_op_mix_batch", "image_size = 3 dim^2"); return -1; }
+    return finish(mid_mix_batch(mi_global()->compute, images_nchw, n, (size_t)image_size, dim, plan_host->mode, plan_host->lam, plan_host->y0,
+                                plan_host->x0, plan_host->y1, plan_host->x1));
 }
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_lds_fill(uint32_t word) { return finish(mid_debug_lds_fill(word)); }

@@ -810,7 +810,11 @@ void forward_pass(Train_ResNet *t) {
     bind_sync_bn(c);
     c->acts_from_eval = 0;
     forward_trunk(t, t->cur_batch->images, 0);
-    if (c->loss_flags & MI_LOSS_DEVICE) /* soft-max, dlogits (backwards_pass launches no ce_deriv), row losses and ranks, the two records */
+    if (c->mix_on && c->mix_last.mode != 0) /* the batch was mixed by load_new_batch: both labels of every row, weighted lam / 1 - lam */
+        ck(mid_loss_head_mix(G.compute, a->linear_output, t->cur_batch->correct_classes, c->mix_labels_b, c->mix_last.lam, t->forward_buffer->pred,
+                             t->backprop_buffer->output_layer_deriv, c->loss_row, c->loss_rank, N, d->output, c->loss_smoothing, c->loss_topk,
+                             c->loss_metrics, c->loss_metrics + 1), "two-label loss head");
+    else if (c->loss_flags & MI_LOSS_DEVICE) /* soft-max, dlogits (backwards_pass launches no ce_deriv), row losses and ranks, the two records */
         ck(mid_loss_head(G.compute, a->linear_output, t->cur_batch->correct_classes, t->forward_buffer->pred, t->backprop_buffer->output_layer_deriv,
                          c->loss_row, c->loss_rank, N, d->output, c->loss_smoothing, c->loss_topk, c->loss_metrics, c->loss_metrics + 1), "loss head");
     else ck(mid_softmax(G.compute, a->linear_output, t->forward_buffer->pred, N, d->output), "soft-max");
@@ -837,8 +841,45 @@ int mi_trainer_set_loss(Train_ResNet *t, float smoothing, int topk, int flags) {
         mi_record_host_error("mi_trainer_set_loss", "MI_LOSS_NO_PRED_COPY needs MI_LOSS_DEVICE (the host loss reads pred_cpu)");
         return -1;
     }
+    if (c->mix_on && !(flags & MI_LOSS_DEVICE)) {
+        mi_record_host_error("mi_trainer_set_loss", "mixing is on (mi_trainer_set_mix): the host head has one label per row");
+        return -1;
+    }
     c->loss_smoothing = smoothing; c->loss_topk = topk; c->loss_flags = flags;
     return 0;
+}
+/* mixup / CutMix (resnet_mi.h, "mixing") */
+int mi_trainer_set_mix(Train_ResNet *t, double mixup_alpha, double cutmix_alpha, double prob, double switch_prob, uint64_t seed) {
+    MiCtx *c = ctx_of(t);
+    if (mixup_alpha == 0 && cutmix_alpha == 0) { c->mix_on = 0; memset(&c->mix_last, 0, sizeof c->mix_last); return 0; }
+    if (!(c->loss_flags & MI_LOSS_DEVICE)) {
+        mi_record_host_error("mi_trainer_set_mix", "mixing needs MI_LOSS_DEVICE (mi_trainer_set_loss): the host head has one label per row");
+        return -1;
+    }
+    MiMixPlan probe; /* the argument rules are mi_mix_plan's */
+    if (mi_mix_plan(seed, 0, 0, 0, 1, mixup_alpha, cutmix_alpha, prob, switch_prob, t->model->dims->input, &probe)) return -1;
+    if (!c->mix_labels_b) c->mix_labels_b = (int *)mid_malloc(sizeof(int) * (size_t)t->batch_size);
+    if (!c->mix_labels_b) { mi_record_host_error("mi_trainer_set_mix", "no device memory for the second labels"); return -1; }
+    c->mix_alpha[0] = mixup_alpha; c->mix_alpha[1] = cutmix_alpha; c->mix_prob = prob; c->mix_switch = switch_prob; c->mix_seed = seed;
+    memset(&c->mix_last, 0, sizeof c->mix_last);
+    c->mix_on = 1;
+    return 0;
+}
+int mi_trainer_last_mix(const Train_ResNet *t, MiMixPlan *out) {
+    const MiCtx *c = ctx_of((Train_ResNet *)t);
+    if (!c->mix_on || !out) { mi_record_host_error("mi_trainer_last_mix", "mixing is off (mi_trainer_set_mix)"); return -1; }
+    *out = c->mix_last;
+    return 0;
+}
+void mi_trainer_mix_batch(Train_ResNet *t, Batch *b, int rank, int world) {
+    MiCtx *c = ctx_of(t);
+    if (!c->mix_on) return;
+    if (mi_mix_plan(c->mix_seed, t->cur_epoch, t->cur_dump_id, rank, world, c->mix_alpha[0], c->mix_alpha[1], c->mix_prob, c->mix_switch,
+                    b->image_dim, &c->mix_last)) { memset(&c->mix_last, 0, sizeof c->mix_last); return; }
+    const MiMixPlan *p = &c->mix_last;
+    if (p->mode == 0) return;
+    ck(mid_mix_batch(G.compute, b->images, b->n_images, (size_t)b->image_size, b->image_dim, p->mode, p->lam, p->y0, p->x0, p->y1, p->x1), "mix");
+    ck(mid_mix_labels(G.compute, b->correct_classes, c->mix_labels_b, b->n_images), "mix labels");
 }
 /* the two records (last, total) a loss head keeps on the device */
 static int read_metrics(mid_loss_metrics *rec, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
@@ -1480,6 +1521,7 @@ void destroy_trainer(Train_ResNet *t) {
     free(t->model->dims); free(t->model);
     free(t->loss_per_epoch); free(t->accuracy_per_epoch);
     mi_optim_free(&c->optim);
+    mid_free(c->mix_labels_b);
     mid_free(c->rs_arena); mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics);
     ev8_free(c);
     if (c->ev8_copied) mid_event_destroy(c->ev8_copied);

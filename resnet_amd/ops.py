@@ -209,6 +209,40 @@ class Ops:
         rec = [B.MiLossMetrics.from_buffer_copy(d.get().tobytes()).as_dict() for d in (dlast, dtot)]
         return dp.get(), dd.get(), drl.get(), drr.get(), rec[0], rec[1]
 
+    @staticmethod
+    def mix_plan_struct(mode=0, lam=1.0, box=(0, 0, 0, 0)):
+        """a MiMixPlan: mode 0 none / 1 mixup / 2 CutMix, box = (y0, x0, y1, x1)"""
+        return B.MiMixPlan(int(mode), float(lam), *[int(v) for v in box])
+
+    def mix_batch(self, images, plan, offset_floats=0):
+        """mi_op_mix_batch: fp32 images (n, 3, D, D) mixed in place on the device, row i with row n - 1 - i, under plan (a MiMixPlan,
+        or a dict with mode, lam, y0, x0, y1, x1); returns the mixed batch.  offset_floats: the batch starts that many floats into its
+        device buffer (1: a pointer that is 4- but not 16-byte aligned)"""
+        images = np.ascontiguousarray(images, np.float32)
+        n, _, D, _ = images.shape
+        if isinstance(plan, dict):
+            plan = B.MiMixPlan(plan["mode"], plan["lam"], plan["y0"], plan["x0"], plan["y1"], plan["x1"])
+        buf = np.zeros(offset_floats + images.size, np.float32)
+        buf[offset_floats:] = images.ravel()
+        d = self.dev(buf)
+        self._chk(self.L.mi_op_mix_batch(d.ptr + 4 * offset_floats, n, 3 * D * D, D, C.byref(plan)), "mix_batch")
+        return d.get()[offset_floats:].reshape(images.shape)
+
+    def loss_head_mix(self, x, labels_a, labels_b, lam, smoothing=0.0, topk=5, total=None):
+        """mi_op_loss_head_mix on logits x (N, L) with two labels per row and the weight lam: returns what loss_head returns"""
+        N, L = x.shape
+        dx = self.dev(np.ascontiguousarray(x, np.float32))
+        da, db = self.dev(np.ascontiguousarray(labels_a, np.int32)), self.dev(np.ascontiguousarray(labels_b, np.int32))
+        dp, dd = self.dev(shape=x.shape), self.dev(shape=x.shape)
+        drl, drr = self.dev(shape=(N,)), self.dev(shape=(N,), dtype=np.int32)
+        nb = C.sizeof(B.MiLossMetrics)
+        dlast = self.dev(np.zeros(nb, np.uint8))
+        dtot = total if total is not None else self.dev(np.zeros(nb, np.uint8))
+        self._chk(self.L.mi_op_loss_head_mix(dx.ptr, da.ptr, db.ptr, float(lam), dp.ptr, dd.ptr, drl.ptr, drr.ptr, N, L, smoothing, topk, dlast.ptr,
+                                             dtot.ptr), "loss_head_mix")
+        rec = [B.MiLossMetrics.from_buffer_copy(d.get().tobytes()).as_dict() for d in (dlast, dtot)]
+        return dp.get(), dd.get(), drl.get(), drr.get(), rec[0], rec[1]
+
     def bn_running_update(self, means, vars_, counts, running, momentum, guard=0, fill=0.0):
         """mi_op_bn_running_update: lists of per-layer batch means / biased vars (float32, [C_i] each) and sample counts, running (2, R)
         float32 with R >= sum C_i (layer i at the sum of the channels before it in both rows).  Returns the updated (2, R) array;

@@ -88,6 +88,21 @@ class Trainer:
         self.L.mi_clear_error()
         raise RuntimeError(what + ": " + e)
 
+    # ---- mixing (include/resnet_mi.h, "mixing") ----
+    def set_mix(self, mixup=0.2, cutmix=1.0, prob=1.0, switch=0.5, seed=0):
+        """mixup / CutMix on the device at every load_new_batch (row i with row batch - 1 - i) and the two-label loss head in forward();
+        needs set_loss(device=True) first.  mixup, cutmix: the Beta(alpha, alpha) parameters in (0, 1], 0 = that mode off (both 0: mixing
+        off); prob: the share of steps that mix; switch: the share of CutMix among them when both are on"""
+        if self.L.mi_trainer_set_mix(self.t, float(mixup), float(cutmix), float(prob), float(switch), int(seed)) != 0:
+            self._refused("mi_trainer_set_mix")
+
+    def last_mix(self):
+        """the plan of the last load_new_batch as a dict: mode (0 none, 1 mixup, 2 CutMix), lam, y0, x0, y1, x1"""
+        p = B.MiMixPlan()
+        if self.L.mi_trainer_last_mix(self.t, C.byref(p)) != 0:
+            self._refused("mi_trainer_last_mix")
+        return p.as_dict()
+
     def track_running_stats(self, momentum=0.1, on=True):
         """keep torch.nn.BatchNorm2d's running statistics of every batch norm: one extra launch per forward(); after set_dtype, before
         the first forward()"""

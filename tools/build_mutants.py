@@ -4,7 +4,9 @@
 Per entry: the patched copy of its one source file goes to variants/mutants/src_<name>/, is compiled with the Makefile's HIPFLAGS (-I the
 real csrc, so every other header is the real one; a header mutant's copy lies in front of it on the include path and every .hip file is
 recompiled), and linked with the normal build's other objects to variants/mutants/libresnet_mi_<name>.so.  variants/mutants/MANIFEST.json
-holds name -> sha256(source file + old + new + flags); a rerun rebuilds only entries whose hash changed or whose library is missing.
+holds name -> sha256(source file + old + new + flags + every other source and header of the library); a rerun rebuilds only entries whose
+hash changed or whose library is missing.  The other sources count because their objects are linked in: a library left from before an
+entry point was added lacks it, and the binding refuses to load such a library.
 The normal build (make in resnet_amd/csrc) must have run: its objects are linked in.
 
   python tools/build_mutants.py [-j JOBS] [name ...]        JOBS <= 16 (default 8)
@@ -53,9 +55,21 @@ def patched(m):
     return src, src.replace(m["old"], m["new"])
 
 
-def entry_hash(m, src, flags):
+def tree_digest():
+    """sha256 over everything the library is built from: resnet_amd/csrc (sources, headers, Makefile) and include/"""
     h = hashlib.sha256()
-    for part in (src, m["old"], m["new"], flags):
+    files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".c", ".h", ".hpp")) or f == "Makefile"]
+    inc = os.path.join(ROOT, "include")
+    files += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
+    for path in sorted(files):
+        with open(path, "rb") as f:
+            h.update(os.path.basename(path).encode() + b"\0" + f.read() + b"\0")
+    return h.hexdigest()
+
+
+def entry_hash(m, src, flags, tree=None):
+    h = hashlib.sha256()
+    for part in (src, m["old"], m["new"], flags, tree or tree_digest()):
         h.update(part.encode())
         h.update(b"\0")
     return h.hexdigest()
@@ -116,7 +130,8 @@ def expected_manifest():
     """name -> hash for the table and the tree as they are (tests/test_mutants_table.py compares the file with this)"""
     import mutants
     mk = makefile_vars()
-    return {m["name"]: entry_hash(m, patched(m)[0], mk["HIPFLAGS"]) for m in mutants.MUTANTS}
+    tree = tree_digest()
+    return {m["name"]: entry_hash(m, patched(m)[0], mk["HIPFLAGS"], tree) for m in mutants.MUTANTS}
 
 
 def main():
@@ -138,9 +153,10 @@ def main():
     if len(set(names)) != len(names):
         raise SystemExit("build_mutants: names are not unique")
     todo = []
+    tree = tree_digest()
     for m in table:
         src, text = patched(m)
-        h = entry_hash(m, src, mk["HIPFLAGS"])
+        h = entry_hash(m, src, mk["HIPFLAGS"], tree)
         if have.get(m["name"]) != h or not os.path.exists(lib_path(m["name"])):
             todo.append((m, text, h))
     # entries that left the table: their libraries go, so that the directory holds what the manifest names
