@@ -23,6 +23,12 @@
  *              evaluation: running statistics of every batch norm (mi_trainer_track_running_stats; --val-u8 alone implies momentum 0.1) and,
  *              every STEPS iterations and at the end of every epoch, the eval pass over every %03d.images_u8 / %03d.labels under DIR
  *              (whole dim-in^2 images, centre crop): loss per image, top-1 and top-K error of the set
+ *   ./ResNetMI --ema 0.99998 --ema-every 32 --ema-warmup --val-u8 /data/val_shards/u8
+ *              weight averaging (mi_trainer_set_ema): an exponential moving average of the parameters and the batch-norm running statistics,
+ *              updated on the device behind every N-th update_parameters (default 1) with e <- e + (1 - DECAY) (p - e); --ema-warmup: timm's
+ *              min(DECAY, (1 + k) / (10 + k)) for update k.  DECAY is used as given: torchvision's correction for world, batch, N and the
+ *              number of epochs is the caller's.  --ema alone implies --bn-momentum 0.1; with --val-u8 every validation is printed twice,
+ *              for the raw weights and for the EMA weights
  *   ./ResNetMI --labels-file id_to_label_mapping.txt --synsets-file id_to_synset_mapping.txt --counts-file id_to_img_count_mapping.txt
  *              the class metadata of resnet.cu:3236-3242: iterations per epoch = ceil(sum of the class counts / batch) (:3309)
  *              unless --iters says otherwise
@@ -39,7 +45,7 @@ static const char *opt(int argc, char **argv, const char *name, const char *def)
 }
 
 /* the whole validation set, shard by shard through mi_trainer_eval_u8 (each call returns its own total); 0, or -1 with a message printed */
-static int validate(Train_ResNet *trainer, const char *dir, int dim_in, int topk, const char *when) {
+static int validate_one(Train_ResNet *trainer, const char *dir, int dim_in, int topk, const char *when) {
     MiLossMetrics sum = {0};
     const size_t img = (size_t)dim_in * dim_in * 3;
     for (int id = 0;; id++) {
@@ -69,6 +75,18 @@ static int validate(Train_ResNet *trainer, const char *dir, int dim_in, int topk
     printf("Validation (%s) ----- Images: %lld, Avg. Loss: %.4f, Top-1 error: %.2f%%, Top-%d error: %.2f%%\n", when, (long long)sum.rows,
            sum.loss_sum / (double)sum.rows, 100.0 * (double)sum.wrong_top1 / (double)sum.rows, topk, 100.0 * (double)sum.wrong_topk / (double)sum.rows);
     return 0;
+}
+/* with --ema: the set twice, scored with the raw weights and with the averaged ones (mi_trainer_eval_use_ema) */
+static int validate(Train_ResNet *trainer, const char *dir, int dim_in, int topk, const char *when, int ema) {
+    char label[64];
+    if (!ema) return validate_one(trainer, dir, dim_in, topk, when);
+    snprintf(label, sizeof label, "%s, raw weights", when);
+    if (validate_one(trainer, dir, dim_in, topk, label)) return -1;
+    snprintf(label, sizeof label, "%s, EMA weights", when);
+    if (mi_trainer_eval_use_ema(trainer, 1)) { fprintf(stderr, "%s\n", mi_last_error()); return -1; }
+    const int rc = validate_one(trainer, dir, dim_in, topk, label);
+    mi_trainer_eval_use_ema(trainer, 0);
+    return rc;
 }
 
 int main(int argc, char **argv) {
@@ -103,6 +121,10 @@ int main(int argc, char **argv) {
     const int TOPK = atoi(topk_arg ? topk_arg : "5");
     const char *bn_momentum_arg = opt(argc, argv, "--bn-momentum", NULL), *val_u8 = opt(argc, argv, "--val-u8", NULL);
     const int VAL_DIM_IN = atoi(opt(argc, argv, "--val-dim-in", "256")), VAL_EVERY = atoi(opt(argc, argv, "--val-every", "0"));
+    const char *ema_arg = opt(argc, argv, "--ema", NULL);
+    const int EMA_EVERY = atoi(opt(argc, argv, "--ema-every", "1"));
+    int ema_warmup = 0;
+    for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--ema-warmup")) ema_warmup = 1;
     const char *dump_root = opt(argc, argv, "--dump-root", NULL);
     const char *loss_log = opt(argc, argv, "--loss-log", "avg_loss_log.txt");
     const int resume_id = atoi(opt(argc, argv, "--resume", "-1"));           /* LOAD_FROM_DUMP_ID, resnet.cu:3299 */
@@ -140,9 +162,11 @@ int main(int argc, char **argv) {
     if (loss_on_device && mi_trainer_set_loss(trainer, (float)atof(smoothing_arg ? smoothing_arg : "0"), TOPK,
                                               MI_LOSS_DEVICE | (device_loss ? MI_LOSS_NO_PRED_COPY : 0))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (mixing && mi_trainer_set_mix(trainer, MIXUP, CUTMIX, MIX_PROB, 0.5, mix_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
-    if ((bn_momentum_arg || val_u8) && mi_trainer_track_running_stats(trainer, 1, (float)atof(bn_momentum_arg ? bn_momentum_arg : "0.1"))) {
+    if ((bn_momentum_arg || val_u8 || ema_arg) && mi_trainer_track_running_stats(trainer, 1, (float)atof(bn_momentum_arg ? bn_momentum_arg : "0.1"))) {
         fprintf(stderr, "%s\n", mi_last_error()); return 1;
     }
+    /* before a resume: overwrite_model_params then restores the averaged model and its counter from the dump, where it holds them */
+    if (ema_arg && mi_trainer_set_ema(trainer, atof(ema_arg), EMA_EVERY, ema_warmup)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (resume_id != -1) { overwrite_trainer_hyperparams(trainer, resume_id, "my_custom"); overwrite_model_params(trainer, resume_id, "my_custom"); }
 
     FILE *loss_file = fopen(loss_log, "w");
@@ -181,7 +205,7 @@ int main(int argc, char **argv) {
             update_parameters(trainer);
             if (mi_last_error()[0]) { fprintf(stderr, "device error: %s\n", mi_last_error()); return 2; }
             steps_done++;
-            if (val_u8 && VAL_EVERY > 0 && steps_done % VAL_EVERY == 0 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "step")) return 1;
+            if (val_u8 && VAL_EVERY > 0 && steps_done % VAL_EVERY == 0 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "step", ema_arg != NULL)) return 1;
         }
         if (stop) break;
         if (loss_on_device) {
@@ -192,7 +216,7 @@ int main(int argc, char **argv) {
                        total.loss_sum / (double)total.rows, 100.0 * (double)total.wrong_top1 / (double)total.rows, TOPK,
                        100.0 * (double)total.wrong_topk / (double)total.rows);
         }
-        if (val_u8 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "epoch")) return 1;
+        if (val_u8 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "epoch", ema_arg != NULL)) return 1;
         /* resnet.cu:3410-3421: per-epoch loss (a SUM over the epoch) and accuracy, rewind the data source */
         mi_trainer_end_epoch(trainer, epoch_loss, epoch_n_wrong, total_images_per_epoch);
         cur_iter_in_epoch = 0;

@@ -533,6 +533,64 @@ int64_t mi_trainer_running_updates(const Train_ResNet *t);
 int mi_trainer_eval_forward(Train_ResNet *t, const float *images_dev, const int *labels_dev, int n_valid, int topk);
 int mi_trainer_eval_metrics(Train_ResNet *t, MiLossMetrics *last, MiLossMetrics *total, int reset_total);
 int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk, MiLossMetrics *out);
+/* ---------------- weight averaging: an exponential moving average (EMA) of the model, and evaluation with it ----------------
+ * torchvision's --model-ema / timm's ModelEmaV2 on the device.  Off by default; while mi_trainer_set_ema was never called every launch,
+ * value and dumped file is what it was.
+ *
+ * The update is torch.lerp(e, p, w) on float32, one element at a time (ema_update_kernel, kernels_optim.hip):
+ *   w <  0.5f :  e' = fmaf(w, p - e, e)
+ *   w >= 0.5f :  e' = fmaf(-(1.f - w), p - e, p)          (p - e and 1.f - w each rounded to float once)
+ *   e' not finite (p or e is not, or p - e overflows): the element keeps its value; no flag is raised
+ * These are torch.lerp's bits; the unfused e + w (p - e) rounds twice and differs.  Where p == e the value stays (for w < 0.5f a -0.f
+ * becomes +0.f), and w == 1.f gives p's bits (but a p of -0.f below e becomes +0.f).
+ * mi_ema_weight(decay, warmup, k): host only, no GPU needed, a pure function.  k = the number of EMA updates done before this one;
+ * d_k = warmup ? min(decay, (1 + k) / (10 + k)) : decay in double (timm's warm-up), w = (float)(1.0 - d_k); decay in [0, 1).  torchvision's
+ * correction for averaging every `steps` updates of a batch of world x batch over `epochs` epochs (adjust = world batch steps / epochs,
+ * decay' = 1 - min(1, (1 - decay) adjust)) is the caller's: pass the corrected decay.
+ * mi_op_ema_update / mi_op_exchange: the two kernels on their own, on device arrays of n floats; exchange swaps a and b as 32-bit words
+ * (NaN payloads and -0 survive).  Both pointers 16-byte aligned: 16-byte accesses with an element-wise tail of n % 4; otherwise an
+ * element-wise instantiation.  -1 with mi_last_error set and nothing launched: a NULL pointer or one that is not 4-byte aligned, w
+ * outside [0, 1] or NaN, overlapping ranges (exchange), n == 0, n > 2^40.
+ *
+ * mi_trainer_set_ema(t, decay, every, warmup).  What is averaged: the whole parameter arena (its padding words are zero and stay zero)
+ * and the whole running-statistics arena (torchvision's use_buffers=True), with the same w.  The first call allocates both copies, fills
+ * them from the current parameters and running statistics on the device and zeroes the EMA update counter; later calls change the
+ * setting only.  While every >= 1, update_parameters ends -- behind the optimizer, under data parallel behind the last bucket's update, on
+ * the compute stream, with no host synchronisation, copy or new stream -- with the two EMA launches in the update that brings the
+ * trainer's update count to a multiple of `every`; w = mi_ema_weight(decay, warmup, counter), then the counter goes up.  every == 0
+ * switches the updates off and keeps values and counter; switching on again continues from them.  Data parallel: every rank averages the
+ * same parameters; without sync-BN each rank averages its own running statistics.  Returns 0, or -1 with mi_last_error set and nothing
+ * changed: running statistics were never tracked (mi_trainer_track_running_stats: an averaged model could not be evaluated), decay
+ * outside [0, 1) or NaN, every < 0.  May be called between steps.  Like the optimizer and the loss setting it is not dumped.
+ * mi_trainer_ema_reset: the snapshot again, counter 0.  mi_trainer_ema_updates: the counter (0 before mi_trainer_set_ema).
+ * mi_trainer_ema_get_location / _set_location: tensor i of locations[] of the averaged model, Params.sizes[i] floats on the host;
+ * mi_trainer_ema_get_running_stats / _set_running_stats: as mi_trainer_get_running_stats / _set_running_stats.  The setters refuse (-1,
+ * nothing written) a value that is not finite and a negative variance; all return -1 before mi_trainer_set_ema or for an index outside
+ * locations[].
+ *
+ * mi_trainer_eval_use_ema(t, on): while on, mi_trainer_eval_forward and mi_trainer_eval_u8 score the averaged model.  exchange_kernel swaps
+ * the parameter arena with its averaged copy and the running arena with its averaged copy, in place on the compute stream; the eval
+ * trunk runs (it re-lays the weights at its start); the same launches swap back.  mi_trainer_eval_u8 exchanges once around its whole
+ * batch loop.  No host copy, no synchronisation; the re-laid weight copies are marked stale, so no later pass uses the averaged ones.
+ * BETWEEN THE TWO EXCHANGES THE PARAMETER ARENA HOLDS THE AVERAGED MODEL: an asynchronous read of Params.locations or of the running
+ * statistics on a stream of the caller's must be ordered behind the call.  -1 before mi_trainer_set_ema.
+ *
+ * Checkpoints: once mi_trainer_set_ema was called (every == 0 included) dump_trainer also writes <dump>/ema/%03d.buffer -- raw fp32 per
+ * locations[] index, the format of model_params/ -- and <dump>/ema_state.buffer: the counter as int64, then the averaged running arena's
+ * 2 x channels floats.  overwrite_model_params on a trainer with mi_trainer_set_ema called restores both where they all exist and fit;
+ * otherwise the averaged model becomes a snapshot of the restored parameters and statistics with counter 0 and one note goes to stderr. */
+float mi_ema_weight(double decay, int warmup, int64_t k);
+int mi_op_ema_update(float *ema, const float *p, size_t n, float w);
+int mi_op_exchange(float *a, float *b, size_t n);
+void mi_debug_ema_geometry(size_t out[4]); /* [0] threads of a workgroup, floats of its turn [1] vector [2] element-wise, [3] the grid's cap */
+int mi_trainer_set_ema(Train_ResNet *t, double decay, int every, int warmup);
+int mi_trainer_ema_reset(Train_ResNet *t);
+int64_t mi_trainer_ema_updates(const Train_ResNet *t);
+int mi_trainer_eval_use_ema(Train_ResNet *t, int on);
+int mi_trainer_ema_get_location(Train_ResNet *t, int i, float *host);
+int mi_trainer_ema_set_location(Train_ResNet *t, int i, const float *host);
+int mi_trainer_ema_get_running_stats(Train_ResNet *t, float *means, float *vars);
+int mi_trainer_ema_set_running_stats(Train_ResNet *t, const float *means, const float *vars);
 /* the SGD / LARS kernels on their own: p, g, b device arrays of n floats; tensor i starts at offsets_host[i] (n_tensors + 1 entries,
  * multiples of 4, the last <= n) and runs to the next offset; tensor_is_weight_host[i] 1: trust ratio and weight decay (LARS).
  * nan_flag_dev: device int or NULL.  sq_norms_out_host (optional, 2 n_tensors doubles): (|w|^2, |g|^2) per tensor before the update,

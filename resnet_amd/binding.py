@@ -233,6 +233,18 @@ PROTOTYPES = {
     "mi_trainer_eval_forward": (_i, [_T, _vp, _vp, _i, _i]),
     "mi_trainer_eval_metrics": (_i, [_T, C.POINTER(MiLossMetrics), C.POINTER(MiLossMetrics), _i]),
     "mi_trainer_eval_u8": (_i, [_T, _vp, _vp, C.c_int64, _i, _i, C.POINTER(MiLossMetrics)]),
+    "mi_ema_weight": (_f, [C.c_double, _i, C.c_int64]),
+    "mi_op_ema_update": (_i, [_vp, _vp, _sz, _f]),
+    "mi_op_exchange": (_i, [_vp, _vp, _sz]),
+    "mi_debug_ema_geometry": (None, [C.POINTER(_sz)]),
+    "mi_trainer_set_ema": (_i, [_T, C.c_double, _i, _i]),
+    "mi_trainer_ema_reset": (_i, [_T]),
+    "mi_trainer_ema_updates": (C.c_int64, [_T]),
+    "mi_trainer_eval_use_ema": (_i, [_T, _i]),
+    "mi_trainer_ema_get_location": (_i, [_T, _i, _vp]),
+    "mi_trainer_ema_set_location": (_i, [_T, _i, _vp]),
+    "mi_trainer_ema_get_running_stats": (_i, [_T, _vp, _vp]),
+    "mi_trainer_ema_set_running_stats": (_i, [_T, _vp, _vp]),
     "mi_op_momentum_update": (_i, [_i, _vp, _vp, _vp, _sz, _vp, _i, _vp, _f, _f, _f, _f, _vp, _vp]),
     "mi_trainer_nan_location": (_i, [_T]),
     "mi_trainer_stem_dtype": (_i, [_T]),

@@ -202,6 +202,67 @@ static void restore_running_stats(Train_ResNet *t, int dump_id, const char *spec
     free(host);
 }
 
+/* the averaged model, once mi_trainer_set_ema was called: ema/%03d.buffer per locations[] index in the format of model_params/, and
+ * ema_state.buffer -- the EMA update counter as int64, then the averaged running arena's 2 * channels floats */
+static void dump_ema(int dump_id, Train_ResNet *t, const char *special_dir) {
+    const MiCtx *c = (const MiCtx *)t->backend_ctx;
+    if (!c->ema_arena) return;
+    const Params *p = t->model->params;
+    char *dir = NULL, *path = NULL;
+    if (asprintf(&dir, "%s/%s/%08d/ema", root_of(t), special_dir, dump_id) < 0) return;
+    int rc = 0;
+    for (int i = p->n_locations - 1; i >= 0 && !rc; i--) {
+        char nm[32];
+        snprintf(nm, sizeof nm, "%03d.buffer", i);
+        rc = write_dev(dir, nm, c->ema_arena + c->loc_off[i], p->sizes[i]);
+    }
+    free(dir);
+    const size_t n = 2 * (size_t)c->rs_channels;
+    float *host = (float *)malloc(n * sizeof(float));
+    const int64_t updates = c->ema_updates;
+    FILE *f = NULL;
+    if (!rc && asprintf(&path, "%s/%s/%08d/ema_state.buffer", root_of(t), special_dir, dump_id) >= 0 &&
+        !mi_trainer_ema_get_running_stats(t, host, host + c->rs_channels)) f = fopen(path, "wb");
+    if (!f || fwrite(&updates, sizeof updates, 1, f) != 1 || fwrite(host, sizeof(float), n, f) != n)
+        fprintf(stderr, "resnet_mi: cannot write the averaged model of dump %d\n", dump_id);
+    if (f) fclose(f);
+    free(path); free(host);
+}
+/* ... and back, behind the parameters and the running statistics: everything is read before anything is written, so a dump without
+ * ema/ (or with files that do not fit this network) leaves a snapshot of what was just restored, counter 0 */
+static void restore_ema(Train_ResNet *t, int dump_id, const char *special_dir) {
+    MiCtx *c = (MiCtx *)t->backend_ctx;
+    if (!c->ema_arena) return;
+    const Params *p = t->model->params;
+    const size_t n = 2 * (size_t)c->rs_channels;
+    float *arena = (float *)calloc(c->arena_floats, sizeof(float)), *stats = (float *)malloc(n * sizeof(float));
+    int64_t updates = 0;
+    int ok = 0;
+    char *path = NULL;
+    if (asprintf(&path, "%s/%s/%08d/ema_state.buffer", root_of(t), special_dir, dump_id) >= 0) {
+        FILE *f = fopen(path, "rb");
+        if (f) {
+            ok = fread(&updates, sizeof updates, 1, f) == 1 && fread(stats, sizeof(float), n, f) == n && fgetc(f) == EOF && updates >= 0;
+            fclose(f);
+        }
+        free(path);
+    }
+    for (int i = 0; i < p->n_locations && ok; i++) {
+        const size_t sz = (size_t)p->sizes[i];
+        if (asprintf(&path, "%s/%s/%08d/ema/%03d.buffer", root_of(t), special_dir, dump_id, i) < 0) { ok = 0; break; }
+        FILE *f = fopen(path, "rb");
+        ok = f && fread(arena + c->loc_off[i], sizeof(float), sz, f) == sz && fgetc(f) == EOF;
+        if (f) fclose(f);
+        free(path);
+    }
+    if (ok) ok = !mi_trainer_ema_restore(t, arena, stats, updates);
+    if (!ok) {
+        fprintf(stderr, "resnet_mi: dump %d holds no averaged model that fits: the EMA restarts from the restored parameters, counter 0\n", dump_id);
+        mi_trainer_ema_reset(t);
+    }
+    free(arena); free(stats);
+}
+
 /* resnet.cu:2755-2772 */
 void dump_trainer(int dump_id, Train_ResNet *t, const char *special_dir) {
     if (!special_dir) special_dir = "default";
@@ -213,6 +274,7 @@ void dump_trainer(int dump_id, Train_ResNet *t, const char *special_dir) {
     dump_activations(dump_id, t, t->backprop_buffer->activation_derivs, 1, special_dir);
     dump_meta_and_checkpoint(dump_id, t, special_dir);
     dump_running_stats(dump_id, t, special_dir);
+    dump_ema(dump_id, t, special_dir);
 }
 
 /* resnet.cu:2778-2817 */
@@ -251,4 +313,5 @@ void overwrite_model_params(Train_ResNet *t, int dump_id, const char *special_di
         free(host);
     }
     restore_running_stats(t, dump_id, special_dir);
+    restore_ema(t, dump_id, special_dir);
 }

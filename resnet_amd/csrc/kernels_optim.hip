@@ -13,6 +13,9 @@
 // Guards (the contract of adam_kernel): a non-finite gradient element keeps its w and b and stays in the arena, finite
 // gradients are cleared; a non-finite result keeps w and b; LARS leaves a whole tensor untouched when its trust ratio is not
 // finite.  *nan_flag becomes the highest offending tensor index + 1 (atomicMax on an int).
+//
+// Behind them the two kernels of weight averaging ("Weight averaging"), which know no tensors: ema_update_kernel, e <- lerp(e,
+// p, w) over a whole arena, and exchange_kernel, which swaps two arenas word for word around an eval pass on the averaged model.
 #include "mi_common.hpp"
 #include "mi_device.h"
 
@@ -164,7 +167,132 @@ optim_update_kernel(float *__restrict__ p, float *__restrict__ g, float *__restr
     if (bad && nan_flag) atomicMax(nan_flag, t + 1);
 }
 
+// ---- weight averaging: the EMA of an arena and the exchange of two arenas.  Pure streaming, no tensor table: a workgroup's turn is
+// EMA_TURN items of V floats (V = 4: 16-byte accesses, both pointers 16-byte aligned; V = 1: any 4-byte aligned pair), every load of a
+// whole turn in flight before the first use, a grid of at most EMA_MAX_GRID workgroups striding over 64-bit item indices.  The n % 4
+// floats behind the last float4 are the first workgroup's, element-wise ----
+#define EMA_PER_THREAD 4
+#define EMA_TURN (OPT_THREADS * EMA_PER_THREAD)
+#define EMA_MAX_GRID 2048
+#define EMA_MAX_N ((size_t)1 << 40)
+
+// torch.lerp(e, p, w) with its products contracted: the difference rounded once, then one fma on either side of w = 0.5 (omw = 1.f - w,
+// rounded once).  A result that is not finite (p or e is not, or the difference overflows) leaves the element as it is
+__device__ __forceinline__ float ema_elem(float e, float pv, float w, float omw) {
+    const float d = pv - e;
+    const float r = w < 0.5f ? fmaf(w, d, e) : fmaf(-omw, d, pv);
+    return fin(r) ? r : e;
+}
+
+template <int V>
+__global__ void __launch_bounds__(OPT_THREADS)
+ema_update_kernel(float *__restrict__ ema, const float *__restrict__ p, size_t n, float w) {
+    const float omw = 1.f - w;
+    const size_t items = n / V, stride = (size_t)gridDim.x * EMA_TURN;
+    for (size_t base = (size_t)blockIdx.x * EMA_TURN; base < items; base += stride) {
+        float e[EMA_PER_THREAD][V], q[EMA_PER_THREAD][V];
+        if (base + EMA_TURN <= items) { // a whole turn: every load in flight before the first update
+#pragma unroll
+            for (int k = 0; k < EMA_PER_THREAD; k++) {
+                const size_t i = (base + threadIdx.x + k * OPT_THREADS) * V;
+                VecIO<float, V>::load(ema + i, e[k]); VecIO<float, V>::load(p + i, q[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < EMA_PER_THREAD; k++) {
+#pragma unroll
+                for (int j = 0; j < V; j++) e[k][j] = ema_elem(e[k][j], q[k][j], w, omw);
+                VecIO<float, V>::store(ema + (base + threadIdx.x + k * OPT_THREADS) * V, e[k]);
+            }
+        } else {
+            for (size_t it = base + threadIdx.x; it < items; it += OPT_THREADS) {
+                VecIO<float, V>::load(ema + it * V, e[0]); VecIO<float, V>::load(p + it * V, q[0]);
+#pragma unroll
+                for (int j = 0; j < V; j++) e[0][j] = ema_elem(e[0][j], q[0][j], w, omw);
+                VecIO<float, V>::store(ema + it * V, e[0]);
+            }
+        }
+    }
+    if (V > 1 && blockIdx.x == 0) {
+        const size_t i = items * V + threadIdx.x;
+        if (i < n) ema[i] = ema_elem(ema[i], p[i], w, omw);
+    }
+}
+
+// a <-> b as 32-bit words: no arithmetic touches a value, NaN payloads and -0 change places as they are
+template <int V> struct ExWord;
+template <> struct ExWord<1> { typedef uint32_t T; };
+template <> struct ExWord<4> { typedef uint4 T; };
+template <int V>
+__global__ void __launch_bounds__(OPT_THREADS)
+exchange_kernel(uint32_t *__restrict__ a, uint32_t *__restrict__ b, size_t n) {
+    typedef typename ExWord<V>::T T;
+    T *av = (T *)a, *bv = (T *)b;
+    const size_t items = n / V, stride = (size_t)gridDim.x * EMA_TURN;
+    for (size_t base = (size_t)blockIdx.x * EMA_TURN; base < items; base += stride) {
+        if (base + EMA_TURN <= items) {
+            T x[EMA_PER_THREAD], y[EMA_PER_THREAD];
+#pragma unroll
+            for (int k = 0; k < EMA_PER_THREAD; k++) {
+                const size_t i = base + threadIdx.x + k * OPT_THREADS;
+                x[k] = av[i]; y[k] = bv[i];
+            }
+#pragma unroll
+            for (int k = 0; k < EMA_PER_THREAD; k++) {
+                const size_t i = base + threadIdx.x + k * OPT_THREADS;
+                av[i] = y[k]; bv[i] = x[k];
+            }
+        } else {
+            for (size_t it = base + threadIdx.x; it < items; it += OPT_THREADS) {
+                const T x = av[it], y = bv[it];
+                av[it] = y; bv[it] = x;
+            }
+        }
+    }
+    if (V > 1 && blockIdx.x == 0) {
+        const size_t i = items * V + threadIdx.x;
+        if (i < n) { const uint32_t x = a[i], y = b[i]; a[i] = y; b[i] = x; }
+    }
+}
+
+// the grid of both: one workgroup per turn of V-float items, capped (n >= 1)
+static unsigned ema_grid(size_t n, int V) {
+    const size_t turns = (n / V + EMA_TURN - 1) / EMA_TURN;
+    return (unsigned)(turns < 1 ? 1 : turns > EMA_MAX_GRID ? EMA_MAX_GRID : turns);
+}
+
 extern "C" {
+int mid_ema_update(mid_stream s, float *ema, const float *p, size_t n, float w) {
+    const char *who = "mid_ema_update";
+    if (!ema || !p) { mi_record_error(who, "a pointer is NULL"); return -1; }
+    if ((((uintptr_t)ema | (uintptr_t)p) & 3) != 0) { mi_record_error(who, "ema / p must be 4-byte aligned"); return -1; }
+    if (!(w >= 0.f && w <= 1.f)) { mi_record_error(who, "w lies in [0, 1]"); return -1; }
+    if (n == 0 || n > EMA_MAX_N) { mi_record_error(who, "n lies in [1, 2^40]"); return -1; }
+    const bool vec = (((uintptr_t)ema | (uintptr_t)p) & 15) == 0;
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 12.0 * (double)n); // algorithmic: e and p in, e out
+    if (vec) hipLaunchKernelGGL(ema_update_kernel<4>, dim3(ema_grid(n, 4)), dim3(OPT_THREADS), 0, (hipStream_t)s, ema, p, n, w);
+    else hipLaunchKernelGGL(ema_update_kernel<1>, dim3(ema_grid(n, 1)), dim3(OPT_THREADS), 0, (hipStream_t)s, ema, p, n, w);
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK(vec ? "ema_update_kernel<vector>" : "ema_update_kernel<element-wise>");
+    return 0;
+}
+int mid_exchange(mid_stream s, float *a, float *b, size_t n) {
+    const char *who = "mid_exchange";
+    if (!a || !b) { mi_record_error(who, "a pointer is NULL"); return -1; }
+    if ((((uintptr_t)a | (uintptr_t)b) & 3) != 0) { mi_record_error(who, "a / b must be 4-byte aligned"); return -1; }
+    if (n == 0 || n > EMA_MAX_N) { mi_record_error(who, "n lies in [1, 2^40]"); return -1; }
+    const uintptr_t lo = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)a : (uintptr_t)b, hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
+    if (hi - lo < n * sizeof(float)) { mi_record_error(who, "the two ranges overlap"); return -1; }
+    const bool vec = (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 16.0 * (double)n); // algorithmic: both in, both out
+    if (vec) hipLaunchKernelGGL(exchange_kernel<4>, dim3(ema_grid(n, 4)), dim3(OPT_THREADS), 0, (hipStream_t)s, (uint32_t *)a, (uint32_t *)b, n);
+    else hipLaunchKernelGGL(exchange_kernel<1>, dim3(ema_grid(n, 1)), dim3(OPT_THREADS), 0, (hipStream_t)s, (uint32_t *)a, (uint32_t *)b, n);
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK(vec ? "exchange_kernel<vector>" : "exchange_kernel<element-wise>");
+    return 0;
+}
+/* the launch geometry, for tests and documents: [0] threads, [1] floats of one workgroup's turn in the vector instantiation, [2] in the
+ * element-wise one, [3] the grid's cap */
+void mid_ema_geometry(size_t out[4]) { out[0] = OPT_THREADS; out[1] = (size_t)EMA_TURN * 4; out[2] = EMA_TURN; out[3] = EMA_MAX_GRID; }
 int mid_optim_norms(mid_stream s, const float *p, const float *g, const mid_chunk *chunks, int c0, int c1, double *part) {
     if (c1 <= c0) return 0;
     hipLaunchKernelGGL(optim_norm_kernel, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, chunks, c0, (double2 *)part);

@@ -300,6 +300,13 @@ int mid_optim_trust(mid_stream s, const double *part, const int *first_chunk, co
                     float wd, double *sq, float *trust);
 int mid_optim_update(mid_stream s, int kind, float *p, float *g, float *b, const mid_chunk *chunks, int c0, int c1, const int *is_weight,
                      const float *trust, float lr, float wd, float momentum, int *nan_flag);
+/* weight averaging (kernels_optim.hip).  ema[i] = lerp(ema[i], p[i], w), torch.lerp's float32 bits: d = p - e rounded, then fmaf(w, d, e)
+ * for w < 0.5f and fmaf(-(1.f - w), d, p) otherwise; a result that is not finite keeps e.  exchange: a[i] <-> b[i] as 32-bit words.  Both
+ * pointers 16-byte aligned: 16-byte accesses; otherwise element-wise.  -1, mid_last_error set, nothing launched: a NULL pointer, a pointer
+ * that is not 4-byte aligned, w outside [0, 1] or NaN, overlapping ranges (exchange), n == 0 or n > 2^40 */
+int mid_ema_update(mid_stream s, float *ema, const float *p, size_t n, float w);
+int mid_exchange(mid_stream s, float *a, float *b, size_t n);
+void mid_ema_geometry(size_t out[4]); /* [0] threads, floats of one workgroup's turn [1] vector [2] element-wise, [3] the grid's cap */
 int mid_nhwc_to_nchw(mid_stream s, const float *in, float *out, int N, int H, int W, int C);
 int mid_nchw_to_nhwc(mid_stream s, const float *in, float *out, int N, int C, int H, int W);
 /* uint8 shards (kernels_input.hip): src = n whole images [dim_in][dim_in][3] bytes (B,G,R interleaved), 16-byte aligned; plan = int [n][3]

@@ -237,6 +237,14 @@ typedef struct MiCtx {
     float *eval_row; int *eval_rank;
     mid_loss_metrics *eval_metrics;
     int acts_from_eval;
+    /* mi_trainer_set_ema (all NULL / 0 before the first call; not tracked in allocs[] either): the averaged copies of the parameter
+     * arena [arena_floats] and of the running arena [2][rs_channels], the setting, the number of EMA updates so far; ema_eval: the
+     * eval entry points score the averaged model (mi_trainer_eval_use_ema); ema_swapped: the arenas are exchanged right now, by
+     * mi_trainer_eval_u8 around its batch loop -- the eval passes inside it do not exchange again */
+    float *ema_arena, *ema_rs;
+    double ema_decay;
+    int ema_every, ema_warmup, ema_eval, ema_swapped;
+    int64_t ema_updates;
     /* mi_trainer_eval_u8: scratch of its own -- the decoded batch, and bytes / labels / plan on the device and pinned; the event
      * behind the last copies out of the pinned set */
     int ev8_dim_in;
@@ -294,6 +302,9 @@ void mi_dp_reduce_ready(Train_ResNet *t, size_t from_float_offset, int force);
 /* trainer.c, the last steps of load_new_batch while mixing is on: the plan of this load, the mix launch on Batch.images and the
  * partners' labels, on the compute stream */
 void mi_trainer_mix_batch(Train_ResNet *t, Batch *b, int rank, int world);
+/* trainer.c, for dump.c's restore: the whole averaged model from host arrays laid out as the two device arenas are (params: arena_floats
+ * floats, padding words included; stats: 2 * rs_channels) and the counter; -1 before mi_trainer_set_ema */
+int mi_trainer_ema_restore(Train_ResNet *t, const float *params_arena_host, const float *stats_host, int64_t updates);
 void mi_trainer_poll_errors(Train_ResNet *t); /* load_new_batch: wait for and read the NaN / Inf flag of the last update */
 void mi_record_host_error(const char *what, const char *detail); /* sets mi_last_error (runtime.hip) */
 int mi_loss_args_ok(const char *who, float smoothing, int topk, int L); /* ops.c: the rules of mi_op_loss_head / mi_trainer_set_loss */

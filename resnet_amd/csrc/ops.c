@@ -213,7 +213,19 @@ int mi_op_momentum_update(int kind, float *p, float *g, float *b, size_t n, cons
     mi_optim_free(&o);
     return rc;
 }
-int mi_op_nhwc_to_nchw(const float *in, float *out, int N, int H, int W, int C) { return finish(mid_nhwc_to_nchw(mi_global()->compute, in, out, N, H, W, C)); }
+/* weight averaging (resnet_mi.h): the weight of update k, host only; the two kernels on their own (the launchers refuse what the header lists) */
+float mi_ema_weight(double decay, int warmup, int64_t k) {
+    double d = decay;
+    if (warmup) {
+        const double ramp = (1.0 + (double)k) / (10.0 + (double)k);
+        if (ramp < d) d = ramp;
+    }
+    return (float)(1.0 - d);
+}
+int mi_op_ema_update(float *ema, const float *p, size_t n, float w) { return finish(mid_ema_update(mi_global()->compute, ema, p, n, w)); }
+int mi_op_exchange(float *a, float *b, size_t n) { return finish(mid_exchange(mi_global()->compute, a, b, n)); }
+void mi_debug_ema_geometry(size_t out[4]) { mid_ema_geometry(out); }
+int mi_op_nhwc_to_nchw(const float *in,float *out, int N, int H, int W, int C) { return finish(mid_nhwc_to_nchw(mi_global()->compute, in, out, N, H, W, C)); }
 int mi_op_decode_u8(const uint8_t *src_dev, const int *plan_dev, float *out_nchw, int n, int dim_in, int dim_out) {
     return finish(mid_decode_u8(mi_global()->compute, src_dev, plan_dev, out_nchw, n, dim_in, dim_out));
 }

@@ -654,7 +654,8 @@ int mi_trainer_get_dtype(const Train_ResNet *t) { return ((MiCtx *)t->backend_ct
 size_t mi_trainer_activation_bytes(const Train_ResNet *t) { return ((MiCtx *)t->backend_ctx)->act_bytes; }
 size_t mi_trainer_device_bytes(const Train_ResNet *t) {
     const MiCtx *c = (MiCtx *)t->backend_ctx;
-    return c->dev_bytes + c->arena_floats * sizeof(float); /* + the parameter arena (owned by the model) */
+    const size_t ema = c->ema_arena ? (c->arena_floats + 2 * (size_t)c->rs_channels) * sizeof(float) : 0; /* mi_trainer_set_ema's two arenas */
+    return c->dev_bytes + c->arena_floats * sizeof(float) + ema; /* + the parameter arena (owned by the model) */
 }
 void mi_trainer_set_dump_every(Train_ResNet *t, int every) { ctx_of(t)->dump_every = every; }
 void mi_trainer_set_overlap(Train_ResNet *t, int mode) {
@@ -1002,6 +1003,17 @@ static int eval_args_ok(const Train_ResNet *t, const char *who, int n_valid, int
     if (topk < 1 || topk > t->model->dims->output) { mi_record_host_error(who, "topk lies in [1, number of classes]"); return -1; }
     return 0;
 }
+/* mi_trainer_eval_use_ema: the parameter arena <-> its averaged copy and the running arena <-> its averaged copy, in place on the compute
+ * stream, in front of and behind the eval passes that score the averaged model.  The trunk re-lays the weights at its start, so it runs
+ * on whatever the arena holds; the re-laid copies it leaves are the averaged model's, hence params_dirty.  Returns 1 where it exchanged */
+static int ema_exchange(Train_ResNet *t) {
+    MiCtx *c = ctx_of(t);
+    if (!c->ema_eval || !c->ema_arena) return 0;
+    ck(mid_exchange(G.compute, mi_params_arena_base(t->model->params), c->ema_arena, c->arena_floats), "exchange (parameters)");
+    ck(mid_exchange(G.compute, c->rs_arena, c->ema_rs, 2 * (size_t)c->rs_channels), "exchange (running statistics)");
+    c->params_dirty = 1;
+    return 1;
+}
 int mi_trainer_eval_forward(Train_ResNet *t, const float *images_dev, const int *labels_dev, int n_valid, int topk) {
     MiCtx *c = ctx_of(t);
     if (eval_args_ok(t, "mi_trainer_eval_forward", n_valid, topk)) return -1;
@@ -1009,7 +1021,9 @@ int mi_trainer_eval_forward(Train_ResNet *t, const float *images_dev, const int 
     const Dims *d = t->model->dims;
     Activations *a = t->forward_buffer->activations;
     c->acts_from_eval = 1; /* the stored activations are no longer those of a forward_pass */
+    const int swapped = !c->ema_swapped && ema_exchange(t);
     forward_trunk(t, images_dev, 1);
+    if (swapped) ema_exchange(t); /* back: the head below reads logits only */
     /* the head over the valid rows only: pred, row losses and ranks, the eval records; no dlogits */
     if (labels_dev)
         ck(mid_loss_head(G.compute, a->linear_output, labels_dev, t->forward_buffer->pred, NULL, c->eval_row, c->eval_rank, n_valid, d->output, 0.f, topk,
@@ -1027,6 +1041,26 @@ static void ev8_free(MiCtx *c) {
     mid_free_host(c->ev8_bytes_pinned); mid_free_host(c->ev8_labels_pinned); mid_free_host(c->ev8_plan_pinned);
     c->ev8_images = NULL; c->ev8_bytes_dev = NULL; c->ev8_labels_dev = NULL; c->ev8_plan_dev = NULL;
     c->ev8_bytes_pinned = NULL; c->ev8_labels_pinned = NULL; c->ev8_plan_pinned = NULL; c->ev8_dim_in = 0;
+}
+static int eval_u8_batches(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk) {
+    MiCtx *c = ctx_of(t);
+    const int N = t->batch_size, D = t->model->dims->input;
+    const size_t img = (size_t)dim_in * dim_in * 3, out_img = (size_t)D * D * 3;
+    for (int64_t at = 0; at < n; at += N) {
+        const int nv = n - at < N ? (int)(n - at) : N;
+        if (at) mid_event_sync(c->ev8_copied); /* the pinned set is free again once the last batch's copies have left it */
+        if (mi_augment_plan(MI_AUG_CENTER, 0, 0, 0, at, nv, dim_in, D, NULL, c->ev8_plan_pinned)) return -1;
+        memcpy(c->ev8_bytes_pinned, images_host + (size_t)at * img, (size_t)nv * img);
+        memcpy(c->ev8_labels_pinned, labels_host + at, (size_t)nv * sizeof(int));
+        mid_memcpy_h2d(c->ev8_bytes_dev, c->ev8_bytes_pinned, (size_t)nv * img, G.compute);
+        mid_memcpy_h2d(c->ev8_labels_dev, c->ev8_labels_pinned, (size_t)nv * sizeof(int), G.compute);
+        mid_memcpy_h2d(c->ev8_plan_dev, c->ev8_plan_pinned, (size_t)nv * 3 * sizeof(int), G.compute);
+        mid_event_record(c->ev8_copied, G.compute);
+        if (mid_decode_u8(G.compute, c->ev8_bytes_dev, c->ev8_plan_dev, c->ev8_images, nv, dim_in, D)) return -1;
+        if (nv < N) mid_memset(c->ev8_images + (size_t)nv * out_img, 0, (size_t)(N - nv) * out_img * sizeof(float), G.compute);
+        if (mi_trainer_eval_forward(t, c->ev8_images, c->ev8_labels_dev, nv, topk)) return -1;
+    }
+    return 0;
 }
 int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk, MiLossMetrics *out) {
     MiCtx *c = ctx_of(t);
@@ -1052,24 +1086,112 @@ int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *l
         c->ev8_dim_in = dim_in;
     }
     mid_memset(c->eval_metrics + 1, 0, sizeof(mid_loss_metrics), G.compute);
-    for (int64_t at = 0; at < n; at += N) {
-        const int nv = n - at < N ? (int)(n - at) : N;
-        if (at) mid_event_sync(c->ev8_copied); /* the pinned set is free again once the last batch's copies have left it */
-        if (mi_augment_plan(MI_AUG_CENTER, 0, 0, 0, at, nv, dim_in, D, NULL, c->ev8_plan_pinned)) return -1;
-        memcpy(c->ev8_bytes_pinned, images_host + (size_t)at * img, (size_t)nv * img);
-        memcpy(c->ev8_labels_pinned, labels_host + at, (size_t)nv * sizeof(int));
-        mid_memcpy_h2d(c->ev8_bytes_dev, c->ev8_bytes_pinned, (size_t)nv * img, G.compute);
-        mid_memcpy_h2d(c->ev8_labels_dev, c->ev8_labels_pinned, (size_t)nv * sizeof(int), G.compute);
-        mid_memcpy_h2d(c->ev8_plan_dev, c->ev8_plan_pinned, (size_t)nv * 3 * sizeof(int), G.compute);
-        mid_event_record(c->ev8_copied, G.compute);
-        if (mid_decode_u8(G.compute, c->ev8_bytes_dev, c->ev8_plan_dev, c->ev8_images, nv, dim_in, D)) return -1;
-        if (nv < N) mid_memset(c->ev8_images + (size_t)nv * out_img, 0, (size_t)(N - nv) * out_img * sizeof(float), G.compute);
-        if (mi_trainer_eval_forward(t, c->ev8_images, c->ev8_labels_dev, nv, topk)) return -1;
-    }
+    c->ema_swapped = ema_exchange(t); /* the averaged model: one exchange around the whole loop, not one per batch */
+    const int rc = eval_u8_batches(t, images_host, labels_host, n, dim_in, topk);
+    if (c->ema_swapped) { c->ema_swapped = 0; ema_exchange(t); }
+    if (rc) return -1;
     MiLossMetrics total;
     if (mi_trainer_eval_metrics(t, NULL, &total, 0)) return -1; /* the one synchronise */
     if (out) *out = total;
     return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Weight averaging (resnet_mi.h): an EMA of the parameter arena and of the running-statistics arena. */
+static void ema_snapshot(Train_ResNet *t) {
+    MiCtx *c = ctx_of(t);
+    mid_memcpy_d2d(c->ema_arena, mi_params_arena_base(t->model->params), c->arena_floats * sizeof(float), G.compute);
+    mid_memcpy_d2d(c->ema_rs, c->rs_arena, 2 * sizeof(float) * (size_t)c->rs_channels, G.compute);
+    mid_stream_sync(G.compute);
+    c->ema_updates = 0;
+}
+int mi_trainer_set_ema(Train_ResNet *t, double decay, int every, int warmup) {
+    MiCtx *c = ctx_of(t);
+    const char *who = "mi_trainer_set_ema";
+    if (!c->rs_arena) { mi_record_host_error(who, "running statistics were never tracked (mi_trainer_track_running_stats): an averaged model could not be evaluated"); return -1; }
+    if (!(decay >= 0.0 && decay < 1.0)) { mi_record_host_error(who, "decay lies in [0, 1)"); return -1; }
+    if (every < 0) { mi_record_host_error(who, "every is >= 0 (0: no updates)"); return -1; }
+    if (!c->ema_arena) { /* the first time: both arenas, a copy of the current values, no update yet */
+        float *pa = (float *)mid_malloc(c->arena_floats * sizeof(float)), *rs = (float *)mid_malloc(2 * sizeof(float) * (size_t)c->rs_channels);
+        if (!pa || !rs) { mid_free(pa); mid_free(rs); mi_record_host_error(who, "device allocation failed"); return -1; }
+        c->ema_arena = pa; c->ema_rs = rs;
+        ema_snapshot(t);
+    }
+    c->ema_decay = decay; c->ema_every = every; c->ema_warmup = warmup != 0;
+    return 0;
+}
+static int ema_ready(const MiCtx *c, const char *who) {
+    if (c->ema_arena) return 1;
+    mi_record_host_error(who, "no averaged model (mi_trainer_set_ema)");
+    return 0;
+}
+int mi_trainer_ema_reset(Train_ResNet *t) {
+    if (!ema_ready(ctx_of(t), "mi_trainer_ema_reset")) return -1;
+    ema_snapshot(t);
+    return mid_last_error()[0] ? -1 : 0;
+}
+int64_t mi_trainer_ema_updates(const Train_ResNet *t) { return ((const MiCtx *)t->backend_ctx)->ema_updates; }
+int mi_trainer_eval_use_ema(Train_ResNet *t, int on) {
+    MiCtx *c = ctx_of(t);
+    if (!ema_ready(c, "mi_trainer_eval_use_ema")) return -1;
+    c->ema_eval = on != 0;
+    return 0;
+}
+static int ema_location_ok(const MiCtx *c, const char *who, int i, const void *host) {
+    if (!ema_ready(c, who)) return 0;
+    if (i < 0 || i >= c->n_loc) { mi_record_host_error(who, "no such location"); return 0; }
+    if (!host) { mi_record_host_error(who, "no host array"); return 0; }
+    return 1;
+}
+int mi_trainer_ema_get_location(Train_ResNet *t, int i, float *host) {
+    MiCtx *c = ctx_of(t);
+    if (!ema_location_ok(c, "mi_trainer_ema_get_location", i, host)) return -1;
+    mid_memcpy_d2h(host, c->ema_arena + c->loc_off[i], sizeof(float) * (size_t)t->model->params->sizes[i], G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+int mi_trainer_ema_set_location(Train_ResNet *t, int i, const float *host) {
+    MiCtx *c = ctx_of(t);
+    const char *who = "mi_trainer_ema_set_location";
+    if (!ema_location_ok(c, who, i, host)) return -1;
+    const size_t n = (size_t)t->model->params->sizes[i];
+    for (size_t j = 0; j < n; j++) if (!isfinite(host[j])) { mi_record_host_error(who, "a value is not finite"); return -1; }
+    mid_memcpy_h2d(c->ema_arena + c->loc_off[i], host, sizeof(float) * n, G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+int mi_trainer_ema_get_running_stats(Train_ResNet *t, float *means, float *vars) {
+    MiCtx *c = ctx_of(t);
+    if (!ema_ready(c, "mi_trainer_ema_get_running_stats")) return -1;
+    const size_t b = sizeof(float) * (size_t)c->rs_channels;
+    if (means) mid_memcpy_d2h(means, c->ema_rs, b, G.compute);
+    if (vars) mid_memcpy_d2h(vars, c->ema_rs + c->rs_channels, b, G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+int mi_trainer_ema_set_running_stats(Train_ResNet *t, const float *means, const float *vars) {
+    MiCtx *c = ctx_of(t);
+    const char *who = "mi_trainer_ema_set_running_stats";
+    if (!ema_ready(c, who)) return -1;
+    if (!means || !vars) { mi_record_host_error(who, "means and vars are both needed"); return -1; }
+    for (int i = 0; i < c->rs_channels; i++) {
+        if (!isfinite(means[i]) || !isfinite(vars[i])) { mi_record_host_error(who, "a value is not finite"); return -1; }
+        if (vars[i] < 0.f) { mi_record_host_error(who, "a variance is negative"); return -1; }
+    }
+    const size_t b = sizeof(float) * (size_t)c->rs_channels;
+    mid_memcpy_h2d(c->ema_rs, means, b, G.compute);
+    mid_memcpy_h2d(c->ema_rs + c->rs_channels, vars, b, G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
+int mi_trainer_ema_restore(Train_ResNet *t, const float *params_arena_host, const float *stats_host, int64_t updates) {
+    MiCtx *c = ctx_of(t);
+    if (!ema_ready(c, "mi_trainer_ema_restore")) return -1;
+    mid_memcpy_h2d(c->ema_arena, params_arena_host, c->arena_floats * sizeof(float), G.compute);
+    mid_memcpy_h2d(c->ema_rs, stats_host, 2 * sizeof(float) * (size_t)c->rs_channels, G.compute);
+    mid_stream_sync(G.compute);
+    c->ema_updates = updates;
+    return mid_last_error()[0] ? -1 : 0;
 }
 
 /* BN' (+fused ReLU') then conv' : prepareAndDoActivationAndBatchNormDeriv + prepreAndDoConvolutionDeriv */
@@ -1424,12 +1546,19 @@ void update_parameters(Train_ResNet *t) {
         mid_memset(t->cur_batch->images, 0, (size_t)t->batch_size * t->cur_batch->image_size * sizeof(float), G.compute);
         mid_memset(t->cur_batch->correct_classes, 0, (size_t)t->batch_size * sizeof(int), G.compute);
     }
+    c->n_updates++;
+    /* weight averaging: behind the optimizer (data parallel: behind the last bucket's update), one launch per arena on this stream */
+    if (c->ema_every > 0 && c->n_updates % c->ema_every == 0) {
+        const float w = mi_ema_weight(c->ema_decay, c->ema_warmup, c->ema_updates);
+        ck(mid_ema_update(G.compute, c->ema_arena, p_arena, c->arena_floats, w), "EMA (parameters)");
+        ck(mid_ema_update(G.compute, c->ema_rs, c->rs_arena, 2 * (size_t)c->rs_channels, w), "EMA (running statistics)");
+        c->ema_updates++;
+    }
     mid_event_record(c->ev_t[5], G.compute);
     mid_memcpy_d2h(c->nan_flag_host, c->nan_flag_dev, sizeof(int), G.compute);
     mid_event_record(c->ev_nan, G.compute);
     c->nan_check_pending = 1;
     c->params_dirty = 1; /* the re-laid weight copies are stale until the next forward_pass */
-    c->n_updates++;
     t->cur_mean_decay = cur_b1;
     t->cur_var_decay = cur_b2;
 }
@@ -1523,6 +1652,7 @@ void destroy_trainer(Train_ResNet *t) {
     mi_optim_free(&c->optim);
     mid_free(c->mix_labels_b);
     mid_free(c->rs_arena); mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics);
+    mid_free(c->ema_arena); mid_free(c->ema_rs);
     ev8_free(c);
     if (c->ev8_copied) mid_event_destroy(c->ev8_copied);
     free(c->loc_off);

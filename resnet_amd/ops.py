@@ -262,6 +262,44 @@ class Ops:
         new = out[guard:guard + 2 * R].reshape(2, R)
         return (new, out[:guard], out[guard + 2 * R:]) if guard else new
 
+    def _guarded(self, arr, offset_floats, guard, fill):
+        """arr (float32 or uint32 words) in an allocation of its own: offset_floats + guard words of `fill` in front of it, guard behind.
+        Returns (device array, word offset of arr, host dtype)"""
+        arr = np.ascontiguousarray(arr).ravel()
+        assert arr.dtype.itemsize == 4
+        pad = np.full(guard, fill, np.float32).view(arr.dtype)
+        lead = np.full(offset_floats, fill, np.float32).view(arr.dtype)
+        return self.dev(np.concatenate([lead, pad, arr, pad])), offset_floats + guard
+
+    def ema_geometry(self):
+        """(threads, floats of one workgroup's turn in the vector / the element-wise instantiation, grid cap) of the two kernels below"""
+        out = (C.c_size_t * 4)()
+        self.L.mi_debug_ema_geometry(out)
+        return tuple(int(v) for v in out)
+
+    def ema_update(self, ema, p, w, offset_floats=0, guard=0, fill=0.0):
+        """mi_op_ema_update: ema <- lerp(ema, p, w) on float32 arrays of one length.  Both operands start offset_floats floats (+ the guard)
+        into 16-byte-aligned allocations of their own (0 with a guard that is a multiple of 4: the vector instantiation, 1: the element-wise
+        one).  Returns (ema, p); guard > 0: each as (values, guard in front, guard behind), the guards pre-filled with `fill`"""
+        n = int(np.size(ema))
+        de, at = self._guarded(np.asarray(ema, np.float32), offset_floats, guard, fill)
+        dp, _ = self._guarded(np.asarray(p, np.float32), offset_floats, guard, fill)
+        self._chk(self.L.mi_op_ema_update(de.ptr + 4 * at, dp.ptr + 4 * at, n, float(w)), "ema_update")
+        return self._unguard(de, at, n, guard), self._unguard(dp, at, n, guard)
+
+    def exchange(self, a, b, offset_floats=0, guard=0, fill=0.0):
+        """mi_op_exchange: a <-> b as 32-bit words (float32 or uint32 arrays of one length); operands placed and returned as ema_update's"""
+        n = int(np.size(a))
+        da, at = self._guarded(a, offset_floats, guard, fill)
+        db, _ = self._guarded(b, offset_floats, guard, fill)
+        self._chk(self.L.mi_op_exchange(da.ptr + 4 * at, db.ptr + 4 * at, n), "exchange")
+        return self._unguard(da, at, n, guard), self._unguard(db, at, n, guard)
+
+    @staticmethod
+    def _unguard(d, at, n, guard):
+        out = d.get()
+        return (out[at:at + n], out[at - guard:at], out[at + n:]) if guard else out[at:at + n]
+
     def adam(self, p, g, m, v, lr, wd, b1, b2, cur_b1, cur_b2, eps):
         dp, dg, dm, dv = (self.dev(a) for a in (p, g, m, v))
         flag = self.dev(np.zeros(1, np.int32))

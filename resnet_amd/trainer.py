@@ -182,6 +182,56 @@ class Trainer:
             self._refused("mi_trainer_eval_u8")
         return out.as_dict()
 
+    # ---- weight averaging (include/resnet_mi.h, "weight averaging") ----
+    def set_ema(self, decay=0.9999, every=1, warmup=False):
+        """keep an exponential moving average of the parameters and the BN running statistics on the device: e <- lerp(e, p, 1 - decay)
+        behind every `every`-th update() (0: updates off, values kept); warmup: timm's min(decay, (1 + k) / (10 + k)).  The first call
+        takes a snapshot of the current values; needs track_running_stats() first"""
+        if self.L.mi_trainer_set_ema(self.t, float(decay), int(every), int(bool(warmup))) != 0:
+            self._refused("mi_trainer_set_ema")
+
+    def ema_reset(self):
+        """the snapshot again, update counter 0"""
+        if self.L.mi_trainer_ema_reset(self.t) != 0:
+            self._refused("mi_trainer_ema_reset")
+
+    def ema_updates(self):
+        return int(self.L.mi_trainer_ema_updates(self.t))
+
+    def ema_get(self, i):
+        out = np.empty(self.sizes[i] if 0 <= i < self.n_locations else 1, np.float32)
+        if self.L.mi_trainer_ema_get_location(self.t, int(i), out.ctypes.data) != 0:
+            self._refused("mi_trainer_ema_get_location")
+        return out
+
+    def ema_set(self, i, arr):
+        arr = np.ascontiguousarray(arr, np.float32).ravel()
+        if 0 <= i < self.n_locations and arr.size != self.sizes[i]:
+            raise ValueError("location %d holds %d floats" % (i, self.sizes[i]))
+        if self.L.mi_trainer_ema_set_location(self.t, int(i), arr.ctypes.data) != 0:
+            self._refused("mi_trainer_ema_set_location")
+
+    def ema_running_stats(self):
+        """(means, vars) of the averaged model, as running_stats()"""
+        n = self.L.mi_trainer_running_stats_channels(self.t)
+        means, vars_ = np.empty(n, np.float32), np.empty(n, np.float32)
+        if self.L.mi_trainer_ema_get_running_stats(self.t, means.ctypes.data, vars_.ctypes.data) != 0:
+            self._refused("mi_trainer_ema_get_running_stats")
+        return means, vars_
+
+    def set_ema_running_stats(self, means, vars):
+        n = self.L.mi_trainer_running_stats_channels(self.t)
+        means, vars = np.ascontiguousarray(means, np.float32).ravel(), np.ascontiguousarray(vars, np.float32).ravel()
+        if n and (means.size != n or vars.size != n):
+            raise ValueError("running statistics hold %d channels" % n)
+        if self.L.mi_trainer_ema_set_running_stats(self.t, means.ctypes.data, vars.ctypes.data) != 0:
+            self._refused("mi_trainer_ema_set_running_stats")
+
+    def eval_use_ema(self, on=True):
+        """while on, eval_forward() and evaluate_u8() score the averaged model (the arenas are exchanged around the pass, on the device)"""
+        if self.L.mi_trainer_eval_use_ema(self.t, int(bool(on))) != 0:
+            self._refused("mi_trainer_eval_use_ema")
+
     def set_lr(self, lr):
         """learning_rate for the next update_parameters and on (read at every update)"""
         self.t.contents.learning_rate = lr
