@@ -375,12 +375,38 @@ int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k
  * MI_STORE_*; site = the layer's bit in the BN'-fusion site masks (1 expansion, 2 spatial, 4 the reduction above an identity block, 0 none).
  * out = (forward, dgrad, wgrad route, 1 where the dgrad also does the reduction pass of the batch-norm backward its output feeds).
  * Returns 0, or -2 (out all 0): unknown dtype, policy or site, or a shape the storage type's kernels do not take -- at a batch past a
- * kernel's size limit mi_last_error says "size limit: ..." (the mi_op_* convolutions refuse the same way, before any launch).  The LDS-DMA 1x1 weight
- * gradient is not a route of its own: MI_WG_BF16 picks it at launch (mi_conv_plan, route PW, says where). */
+ * kernel's size limit mi_last_error says "size limit: ..." (the mi_op_* convolutions refuse the same way, before any launch).  A route is
+ * a family of kernels; which kernel of the family runs is planned with it (mi_layer_kernels).  The LDS-DMA 1x1 weight gradient is not a
+ * route of its own: it is one of MI_WG_BF16's two kernels. */
 enum { MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16, MI_FWD_PW /* mi_op_conv1x1_fwd_bf16_cl only */ };
 enum { MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 };
 enum { MI_WG_F32, MI_WG_BF16, MI_WG_CL, MI_WG_CL2, MI_WG_STEM_F32, MI_WG_STEM_BF16 };
 int mi_layer_routes(int dtype, int policy, int N, int C, int H, int K, int k, int stride, int site, int out[4]);
+/* host-only: the kernel of each operation inside those routes, out = (forward, dgrad, wgrad), arguments and return value as
+ * mi_layer_routes.  Each id stands for one launcher; beside it the name its convolution launch leaves in the launch ring
+ * (mi_debug_trace_names; the name goes on with "<" and the instantiation's parameters).  MI_*_F32 asks, in this order: the implicit GEMM
+ * where RESNET_MI_IGEMM allows it (0: nowhere; 1: 1x1 weight gradients and the 3x3 stride-2 layers with K >= 2C, C >= 256; 2, the
+ * default: everywhere) and its shape-and-size gate passes, the plain GEMM for a 1x1, then the direct kernels (a weight gradient: the C
+ * form where its gate passes).  MI_WG_BF16 is the LDS-DMA kernel for the 1x1 shapes it tiles unless RESNET_MI_BF16_PW_WGRAD=0. */
+enum {
+    MI_K_NONE,        /* the operation is not run */
+    MI_K_IGEMM,       /* "igemm_kernel"      MI_*_F32: fp32 implicit GEMM on the matrix cores */
+    MI_K_GEMM1X1,     /* "gemm_mfma_kernel"  MI_*_F32: a 1x1 as a plain MFMA GEMM */
+    MI_K_DCONV,       /* "dconv_kernel"      MI_FWD_F32 / MI_DG_F32: direct convolution */
+    MI_K_WGRADC,      /* "wgradC_kernel"     MI_WG_F32: direct weight gradient, C form */
+    MI_K_WGRAD,       /* "wgrad_kernel"      MI_WG_F32: direct weight gradient */
+    MI_K_BGEMM,       /* "bgemm_kernel"      MI_*_BF16: bf16 NCHW */
+    MI_K_PW_WGRAD,    /* "pw_wgrad_kernel"   MI_WG_BF16: LDS-DMA 1x1 weight gradient */
+    MI_K_CL_CONV,     /* "cl_conv_kernel"    MI_FWD_CL / MI_FWD_PW / MI_DG_CL */
+    MI_K_CL_DGRAD2,   /* "cl_dgrad2_kernel"  MI_DG_CL2 */
+    MI_K_CL_WGRAD,    /* "cl_wgrad_kernel"   MI_WG_CL */
+    MI_K_CL_WGRAD2,   /* "cl_wgrad2_kernel"  MI_WG_CL2 */
+    MI_K_ST32_FWD,    /* "st32_fwd_kernel"   MI_FWD_STEM_F32 */
+    MI_K_ST32_WGRAD,  /* "st32_wgrad_kernel" MI_WG_STEM_F32 */
+    MI_K_ST_FWD,      /* "st_fwd_kernel"     MI_FWD_STEM_BF16 */
+    MI_K_ST_WGRAD     /* "st_wgrad_kernel"   MI_WG_STEM_BF16 */
+};
+int mi_layer_kernels(int dtype, int policy, int N, int C, int H, int K, int k, int stride, int site, int out[3]);
 
 
 /* ---------------- bf16-activation path (BASELINE configs[4]) ----------------

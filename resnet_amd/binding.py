@@ -120,6 +120,12 @@ MI_ROUTE_DEFAULT, MI_ROUTE_CL, MI_ROUTE_CL2, MI_ROUTE_PW = 0, 1, 2, 3
 MI_FWD_F32, MI_FWD_BF16, MI_FWD_CL, MI_FWD_STEM_F32, MI_FWD_STEM_BF16, MI_FWD_PW = range(6)
 MI_DG_F32, MI_DG_BF16, MI_DG_CL, MI_DG_CL2 = range(4)
 MI_WG_F32, MI_WG_BF16, MI_WG_CL, MI_WG_CL2, MI_WG_STEM_F32, MI_WG_STEM_BF16 = range(6)
+# the kernel inside a route (mi_layer_kernels): id -> the name its convolution launch starts with in the launch ring
+MI_KERNEL_NAMES = ("", "igemm_kernel", "gemm_mfma_kernel", "dconv_kernel", "wgradC_kernel", "wgrad_kernel", "bgemm_kernel", "pw_wgrad_kernel",
+                   "cl_conv_kernel", "cl_dgrad2_kernel", "cl_wgrad_kernel", "cl_wgrad2_kernel", "st32_fwd_kernel", "st32_wgrad_kernel",
+                   "st_fwd_kernel", "st_wgrad_kernel")
+(MI_K_NONE, MI_K_IGEMM, MI_K_GEMM1X1, MI_K_DCONV, MI_K_WGRADC, MI_K_WGRAD, MI_K_BGEMM, MI_K_PW_WGRAD, MI_K_CL_CONV, MI_K_CL_DGRAD2, MI_K_CL_WGRAD,
+ MI_K_CL_WGRAD2, MI_K_ST32_FWD, MI_K_ST32_WGRAD, MI_K_ST_FWD, MI_K_ST_WGRAD) = range(16)
 MI_OPT_ADAM, MI_OPT_SGD, MI_OPT_LARS = 0, 1, 2
 MI_LOSS_HOST, MI_LOSS_DEVICE, MI_LOSS_NO_PRED_COPY = 0, 1, 2  # flags of mi_trainer_set_loss
 MI_GUARD = 256  # slack bytes mi_malloc leaves on both sides of a tensor (csrc/mi_host.h)
@@ -209,6 +215,7 @@ PROTOTYPES = {
     "mi_debug_conv_plan": (_i, [_i] * 7 + [_vp]),
     "mi_conv_plan": (_i, [_i] * 9 + [_vp]),
     "mi_layer_routes": (_i, [_i] * 9 + [_vp]),
+    "mi_layer_kernels": (_i, [_i] * 9 + [_vp]),
     "mi_debug_trainer_routes": (_i, [_T, _vp, _i]),
     "mi_trainer_set_dtype": (_i, [_T, _i]),
     "mi_trainer_get_dtype": (_i, [_T]),

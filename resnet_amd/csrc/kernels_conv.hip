@@ -657,56 +657,30 @@ static int launch_wgrad_t(hipStream_t st, const float *x, const float *dy, float
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------
-// 1x1 convolutions live in kernels_gemm.hip
-int mi_conv1x1_fwd(hipStream_t st, const float *x, const float *w, float *y, int N, int C, int P, int K);
-int mi_conv1x1_dgrad(hipStream_t st, const float *w, const float *dy, float *dx, const float *addend, int N, int C,
-                     int P, int K);
-int mi_conv1x1_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int P,
-                     int K);
-size_t mi_conv1x1_wgrad_part_floats(int N, int C, int P, int K);
-// kernels_igemm.hip: implicit GEMM on fp32 MFMA (1x1 layers, the 3x3/s2 projection shortcuts; policy in mi_igemm_supported)
-enum { IGOP_FWD = 0, IGOP_DGRAD = 1, IGOP_WGRAD = 2 };
-int mi_igemm_supported(int op, int N, int C, int H, int K, int k, int stride);
-size_t mi_igemm_part_floats(int N, int C, int H, int K, int k, int stride);
-size_t mi_igemm_tail_floats(void);
-int mi_igemm_fwd(hipStream_t st, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K, int k,
-                 int stride, mid_bn_parts *parts);
-int mi_igemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend, int N,
-                   int C, int H, int K, int k, int stride, mid_bn_bwd_parts *fz = nullptr);
-int mi_igemm_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k,
-                   int stride);
-
 extern "C" {
 
-/* re-laid weights, followed by the partial tiles of igemm's reduction-sliced tail workgroups (compute stream only) */
-size_t mid_conv_ws_wt_floats(int C, int K, int k) { return (size_t)k * k * C * K + (k <= 3 ? mi_igemm_tail_floats() : 0); }
-
-size_t mid_conv_ws_part_floats(int N, int C, int H, int K, int k, int stride) {
-    if (mi_igemm_supported(IGOP_WGRAD, N, C, H, K, k, stride)) return mi_igemm_part_floats(N, C, H, K, k, stride);
-    if (k == 1) return mi_conv1x1_wgrad_part_floats(N, C, H * H, K);
+/* the direct kernels' launchers, one entry point each: which of them a convolution runs is the planner's choice (layer.c); a shape the
+ * kernel does not take is an error here */
+size_t mid_conv_ws_wt_floats(int C, int K, int k) { return (size_t)k * k * C * K; } /* re-laid weights */
+int mid_direct_wgradC_supported(int N, int C, int H, int K, int k, int stride) { WbPlan pb; return !wgradB_plan(N, C, H, K, k, stride, &pb); }
+size_t mid_direct_wgradC_part_floats(int N, int C, int H, int K, int k, int stride) {
     WbPlan pb;
-    if (!wgradB_plan(N, C, H, K, k, stride, &pb)) return pb.splits > 1 ? (size_t)pb.splits * K * C * 9 : 0;
+    if (wgradB_plan(N, C, H, K, k, stride, &pb)) return 0;
+    return pb.splits > 1 ? (size_t)pb.splits * K * C * 9 : 0;
+}
+size_t mid_direct_wgrad_part_floats(int N, int C, int H, int K, int k, int stride) {
     WgPlan p;
     if (wgrad_plan(N, C, H, K, k, stride, &p)) return 0;
     return (size_t)p.splits * K * C * k * k;
 }
 
-int mid_conv_fwd(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K,
-                 int k, int stride) {
-    return mid_conv_fwd_stats(s, ws, x, w, y, N, C, H, K, k, stride, nullptr);
-}
-int mid_conv_fwd_stats(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K,
-                       int k, int stride, mid_bn_parts *parts) {
+int mid_direct_fwd(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K, int k, int stride) {
     hipStream_t st = (hipStream_t)s;
-    if (parts) parts->nparts = 0;
-    if (mi_igemm_supported(IGOP_FWD, N, C, H, K, k, stride)) return mi_igemm_fwd(st, ws, x, w, y, N, C, H, K, k, stride, parts);
-    if (k == 1 && stride == 1) return mi_conv1x1_fwd(st, x, w, y, N, C, H * H, K);
     if (!((k == 3 && (stride == 1 || stride == 2)) || (k == 7 && stride == 2)) || H % stride) {
-        mi_record_error("mid_conv_fwd", "unsupported kernel/stride");
+        mi_record_error("mid_direct_fwd", "unsupported kernel/stride");
         return -2;
     }
-    if (!ws || ws->wt_floats < (size_t)k * k * C * K) { mi_record_error("mid_conv_fwd", "workspace too small"); return -3; }
+    if (!ws || ws->wt_floats < (size_t)k * k * C * K) { mi_record_error("mid_direct_fwd", "workspace too small"); return -3; }
     unsigned char src[49];
     for (int t = 0; t < k * k; t++) src[t] = (unsigned char)t;
     if (launch_wt(st, w, ws->wt, C, K, k * k, k, C, 0, src)) return -1;
@@ -717,22 +691,12 @@ int mid_conv_fwd_stats(mid_stream s, mid_workspace *ws, const float *x, const fl
     return launch_dconv(st, x, ws->wt, y, nullptr, a, k, k);
 }
 
-/* dgrad + the reduction pass of the batch-norm backward its output feeds, where the launch takes the fp32 implicit-GEMM route with
- * stride 1: fz->nparts > 0 on return says the epilogue did it (dx then holds the gated gradient); 0 = plain dgrad was run */
-int mid_conv_dgrad_bn_f32(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend,
-                          int N, int C, int H, int K, int k, int stride, mid_bn_bwd_parts *fz) {
-    if (fz) fz->nparts = 0;
-    if (fz && stride == 1 && mi_igemm_supported(IGOP_DGRAD, N, C, H, K, k, stride))
-        return mi_igemm_dgrad((hipStream_t)s, ws, w, dy, dx, addend, N, C, H, K, k, stride, fz);
-    return mid_conv_dgrad(s, ws, w, dy, dx, addend, N, C, H, K, k, stride);
-}
-int mid_conv_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend,
-                   int N, int C, int H, int K, int k, int stride) {
+/* dx = dgrad (+ addend when addend != NULL; addend may alias dx) */
+int mid_direct_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend, int N, int C, int H,
+                     int K, int k, int stride) {
     hipStream_t st = (hipStream_t)s;
-    if (mi_igemm_supported(IGOP_DGRAD, N, C, H, K, k, stride)) return mi_igemm_dgrad(st, ws, w, dy, dx, addend, N, C, H, K, k, stride);
-    if (k == 1 && stride == 1) return mi_conv1x1_dgrad(st, w, dy, dx, addend, N, C, H * H, K);
-    if (k != 3 || (stride != 1 && stride != 2) || H % stride) { mi_record_error("mid_conv_dgrad", "unsupported kernel/stride"); return -2; }
-    if (!ws || ws->wt_floats < (size_t)9 * C * K) { mi_record_error("mid_conv_dgrad", "workspace too small"); return -3; }
+    if (k != 3 || (stride != 1 && stride != 2) || H % stride) { mi_record_error("mid_direct_dgrad", "unsupported kernel/stride"); return -2; }
+    if (!ws || ws->wt_floats < (size_t)9 * C * K) { mi_record_error("mid_direct_dgrad", "workspace too small"); return -3; }
     const int Ho = H / stride;
     DConvArgs a = {};
     a.N = N; a.Cin = K; a.Hin = Ho; a.Win = Ho; a.Cout = C; a.Hof = H; a.Wof = H;
@@ -795,40 +759,39 @@ int mid_conv_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float 
     return 0;
 }
 
-int mid_conv_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H,
-                   int K, int k, int stride) {
+int mid_direct_wgradC(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k, int stride) {
     hipStream_t st = (hipStream_t)s;
-    if (mi_igemm_supported(IGOP_WGRAD, N, C, H, K, k, stride)) return mi_igemm_wgrad(st, ws, x, dy, dw, N, C, H, K, k, stride);
-    if (k == 1 && stride == 1) return mi_conv1x1_wgrad(st, ws, x, dy, dw, N, C, H * H, K);
     WbPlan pb;
-    if (!wgradB_plan(N, C, H, K, k, stride, &pb)) {
-        const size_t wsz9 = (size_t)K * C * 9;
-        if (pb.splits > 1 && (!ws || ws->part_floats < wsz9 * pb.splits)) { mi_record_error("mid_conv_wgrad", "workspace too small"); return -3; }
-        WcArgs b;
-        b.N = N; b.C = C; b.H = H; b.W = H; b.K = K; b.Ho = H / stride; b.Wo = H / stride; b.pad = 1;
-        b.NPX = pb.npx; b.rows = pb.rows; b.segw = pb.segw; b.QPR = pb.qpr; b.DP = pb.rows * pb.qpr * 4;
-        b.cpp = pb.cpp; b.chunks_total = pb.chunks; b.chunks_per_split = pb.cps;
-        b.PR = pb.PR; b.PW = pb.PW; b.cwlog2 = pb.cwlog2; b.pitch = pb.pitch; b.jcnt = pb.jcnt;
-        b.xs_floats = (64 * pb.pitch + 16 + 3) & ~3;
-        b.fd_cpp = make_fastdiv(pb.cpp); b.fd_Wo = make_fastdiv(b.Wo); b.fd_PR = make_fastdiv(pb.PR);
-        b.fd_Q4 = make_fastdiv(pb.qpr * 4); b.fd_PW = make_fastdiv(pb.PW);
-        b.part_stride = wsz9;
-        float *outp = pb.splits == 1 ? dw : ws->part;
-        dim3 grid(K / 32, C / 64, pb.splits);
-        const size_t lds = (size_t)2 * (b.xs_floats + 32 * WC_DPK) * 4;
-        mi_prof_begin(st, MI_FAM_WGRAD, 2.0 * 9 * (double)N * b.Ho * b.Wo * C * K,
-                      4.0 * ((double)N * C * H * H + (double)N * K * b.Ho * b.Wo + 9.0 * C * K));
-        if (stride == 1) hipLaunchKernelGGL((wgradC_kernel<1>), grid, dim3(256), lds, st, x, dy, outp, b);
-        else hipLaunchKernelGGL((wgradC_kernel<2>), grid, dim3(256), lds, st, x, dy, outp, b);
-        mi_prof_end(st);
-        MI_LAUNCH_CHECK(stride == 1 ? "wgradC_kernel<s1>" : "wgradC_kernel<s2>");
-        if (pb.splits > 1) return mi_launch_split_reduce(st, outp, dw, (long)wsz9, pb.splits, wsz9);
-        return 0;
-    }
+    if (wgradB_plan(N, C, H, K, k, stride, &pb)) { mi_record_error("mid_direct_wgradC", "unsupported shape"); return -2; }
+    const size_t wsz9 = (size_t)K * C * 9;
+    if (pb.splits > 1 && (!ws || ws->part_floats < wsz9 * pb.splits)) { mi_record_error("mid_direct_wgradC", "workspace too small"); return -3; }
+    WcArgs b;
+    b.N = N; b.C = C; b.H = H; b.W = H; b.K = K; b.Ho = H / stride; b.Wo = H / stride; b.pad = 1;
+    b.NPX = pb.npx; b.rows = pb.rows; b.segw = pb.segw; b.QPR = pb.qpr; b.DP = pb.rows * pb.qpr * 4;
+    b.cpp = pb.cpp; b.chunks_total = pb.chunks; b.chunks_per_split = pb.cps;
+    b.PR = pb.PR; b.PW = pb.PW; b.cwlog2 = pb.cwlog2; b.pitch = pb.pitch; b.jcnt = pb.jcnt;
+    b.xs_floats = (64 * pb.pitch + 16 + 3) & ~3;
+    b.fd_cpp = make_fastdiv(pb.cpp); b.fd_Wo = make_fastdiv(b.Wo); b.fd_PR = make_fastdiv(pb.PR);
+    b.fd_Q4 = make_fastdiv(pb.qpr * 4); b.fd_PW = make_fastdiv(pb.PW);
+    b.part_stride = wsz9;
+    float *outp = pb.splits == 1 ? dw : ws->part;
+    dim3 grid(K / 32, C / 64, pb.splits);
+    const size_t lds = (size_t)2 * (b.xs_floats + 32 * WC_DPK) * 4;
+    mi_prof_begin(st, MI_FAM_WGRAD, 2.0 * 9 * (double)N * b.Ho * b.Wo * C * K,
+                  4.0 * ((double)N * C * H * H + (double)N * K * b.Ho * b.Wo + 9.0 * C * K));
+    if (stride == 1) hipLaunchKernelGGL((wgradC_kernel<1>), grid, dim3(256), lds, st, x, dy, outp, b);
+    else hipLaunchKernelGGL((wgradC_kernel<2>), grid, dim3(256), lds, st, x, dy, outp, b);
+    mi_prof_end(st);
+    MI_LAUNCH_CHECK(stride == 1 ? "wgradC_kernel<s1>" : "wgradC_kernel<s2>");
+    if (pb.splits > 1) return mi_launch_split_reduce(st, outp, dw, (long)wsz9, pb.splits, wsz9);
+    return 0;
+}
+int mid_direct_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k, int stride) {
+    hipStream_t st = (hipStream_t)s;
     WgPlan p;
-    if (wgrad_plan(N, C, H, K, k, stride, &p) || H % stride) { mi_record_error("mid_conv_wgrad", "unsupported shape"); return -2; }
+    if (wgrad_plan(N, C, H, K, k, stride, &p) || H % stride) { mi_record_error("mid_direct_wgrad", "unsupported shape"); return -2; }
     const size_t wsz = (size_t)K * C * k * k;
-    if (!ws || ws->part_floats < wsz * p.splits) { mi_record_error("mid_conv_wgrad", "workspace too small"); return -3; }
+    if (!ws || ws->part_floats < wsz * p.splits) { mi_record_error("mid_direct_wgrad", "workspace too small"); return -3; }
     WgArgs a;
     a.N = N; a.C = C; a.H = H; a.W = H; a.K = K; a.Ho = H / stride; a.Wo = H / stride; a.pad = k / 2;
     a.RPC = p.rpc; a.RG = p.rg; a.SEGW = p.segw; a.SG = p.sg;

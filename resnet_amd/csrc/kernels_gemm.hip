@@ -234,7 +234,8 @@ static int launch_gemm(hipStream_t st, const float *A, const float *B, float *C,
 int mi_launch_split_reduce(hipStream_t st, const float *part, float *out, long n, int splits, size_t stride);
 
 // Y[n][k][p] = sum_c W[k][c] X[n][c][p]
-int mi_conv1x1_fwd(hipStream_t st, const float *x, const float *w, float *y, int N, int C, int P, int K) {
+extern "C" int mi_conv1x1_fwd(mid_stream s, const float *x, const float *w, float *y, int N, int C, int P, int K) {
+    hipStream_t st = (hipStream_t)s;
     GemmArgs g = {};
     g.M = K; g.N = N * P; g.K = C; g.P = P;
     g.a_sm = C; g.a_sk = 1;
@@ -243,8 +244,9 @@ int mi_conv1x1_fwd(hipStream_t st, const float *x, const float *w, float *y, int
     return launch_gemm<BATCH_N, true, false>(st, w, x, y, nullptr, g, 1, C % 4 == 0, P % 4 == 0) > 0 ? 0 : -1;
 }
 // dX[n][c][p] = sum_k W[k][c] dY[n][k][p] (+ addend)
-int mi_conv1x1_dgrad(hipStream_t st, const float *w, const float *dy, float *dx, const float *addend, int N, int C,
-                     int P, int K) {
+extern "C" int mi_conv1x1_dgrad(mid_stream s, const float *w, const float *dy, float *dx, const float *addend, int N, int C,
+                                int P, int K) {
+    hipStream_t st = (hipStream_t)s;
     GemmArgs g = {};
     g.M = C; g.N = N * P; g.K = K; g.P = P;
     g.a_sm = 1; g.a_sk = C;
@@ -261,12 +263,13 @@ static int wgrad1x1_splits(int N, int C, int P, int K) {
     if (splits < 1) splits = 1;
     return splits;
 }
-size_t mi_conv1x1_wgrad_part_floats(int N, int C, int P, int K) {
+extern "C" size_t mi_conv1x1_wgrad_part_floats(int N, int C, int P, int K) {
     return (size_t)wgrad1x1_splits(N, C, P, K) * K * C;
 }
 // dW[k][c] = sum_(n,p) dY[n][k][p] X[n][c][p]
-int mi_conv1x1_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int P,
-                     int K) {
+extern "C" int mi_conv1x1_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int P,
+                                int K) {
+    hipStream_t st = (hipStream_t)s;
     GemmArgs g = {};
     g.M = K; g.N = C; g.K = N * P; g.P = P;
     g.a_sm = P; g.a_sb = (long)K * P;

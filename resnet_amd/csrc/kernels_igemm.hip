@@ -1,7 +1,7 @@
 // kernels_igemm.hip -- convolutions as an im2col-free implicit GEMM on the CDNA4 matrix cores, fp32
 // (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate).
 //
-// Which layers come here is a policy of mi_igemm_supported() (RESNET_MI_IGEMM, see there).  By default every 3x3 and 1x1
+// Which layers come here is the planner's choice (layer.c: RESNET_MI_IGEMM over mi_igemm_supported()).  By default every 3x3 and 1x1
 // convolution whose channel counts tile, forward / dgrad / wgrad -- among them the reference's PROJECTION shortcuts, which
 // are 3x3 / stride-2 / pad-1 (resnet.cu:884-889, 1693-1700), not the usual 1x1: 256->512 @56, 512->1024 @28,
 // 1024->2048 @14 hold 57% of the network's multiply-adds.  The stem (C = 3), shapes that do not tile and, with
@@ -890,28 +890,15 @@ igemm_wgrad_reduce_t_kernel(const float *__restrict__ part, float *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static int igemm_mode(void) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("RESNET_MI_IGEMM"); on = e ? atoi(e) : 2; }
-    return on;
-}
 enum { IGOP_FWD = 0, IGOP_DGRAD = 1, IGOP_WGRAD = 2 };
-// Policy + shape gate.  RESNET_MI_IGEMM:
-//   0  off: every convolution on the older kernels (direct VALU 3x3/7x7, gemm_mfma_kernel 1x1)
-//   1  1x1 weight gradients and the 3x3/s2 projection shortcuts (K >= 2C) only: the bottleneck's own 3x3 convolutions
-//      stay on the direct VALU kernels, 1x1 forward / dgrad on gemm_mfma_kernel
-//   2  (default) every 3x3 and 1x1 convolution whose channel counts tile.  Measured on MI355X the 3x3 layers are
-//      compute-bound, not HBM-bound (fp32 3x3 at C >= 64: >= 288 flop per byte), and the matrix cores run them at
-//      90-121 TFLOP/s against 60-75 on the vector ALUs.  1x1 forward / dgrad gain nothing from this kernel's staging
-//      pipeline (reductions of 2..64 k-steps: bound by prologue, epilogue and workgroup-count quantisation) but 8 %
-//      from its tile-height choice and sliced tail round (igemm_pick_bm, igemm_tail_plan): 19.0 -> 16.8 ms/step.
-int mi_igemm_supported(int op, int N, int C, int H, int K, int k, int stride) {
-    const int mode = igemm_mode();
-    if (!mode) return 0;
+// Shape and size gate, no policy: which of the shapes that pass come here is the planner's choice (layer.c, RESNET_MI_IGEMM).
+// Measured on MI355X the 3x3 layers are compute-bound, not HBM-bound (fp32 3x3 at C >= 64: >= 288 flop per byte), and the
+// matrix cores run them at 90-121 TFLOP/s against 60-75 on the vector ALUs.  1x1 forward / dgrad gain nothing from this
+// kernel's staging pipeline (reductions of 2..64 k-steps: bound by prologue, epilogue and workgroup-count quantisation) but
+// 8 % from its tile-height choice and sliced tail round (igemm_pick_bm, igemm_tail_plan): 19.0 -> 16.8 ms/step.
+extern "C" int mi_igemm_supported(int op, int N, int C, int H, int K, int k, int stride) {
     if (!((k == 1 && stride == 1) || (k == 3 && (stride == 1 || stride == 2)))) return 0;
     if (H % stride || H / stride < 2) return 0;
-    if (k == 1 && op != IGOP_WGRAD && mode < 2) return 0;
-    if (k == 3 && mode == 1 && !(stride == 2 && K >= 2 * C && C >= 256)) return 0; // projections only
     if ((double)N * C * H * H >= 1073741824.0 || (double)N * K * (H / stride) * (H / stride) >= 1073741824.0) return 0; /* 32-bit byte offsets */
     if (op == IGOP_FWD) return C % 32 == 0 && K % 64 == 0;
     if (op == IGOP_DGRAD) return K % 32 == 0 && C % 64 == 0;
@@ -939,14 +926,13 @@ static int igemm_wgrad_splits(int N, int C, int H, int K, int k, int stride) {
 // 1x1 weight gradient with C % 128 != 0 (the 64-channel layers): dW^T[c][k] = sum X[c] dY[k] -- the same kernel with the two
 // tensors in each other's role (rows = the 64 input channels as a 64-row tile, columns = output channels)
 static bool igemm_wgrad_swapped(int C, int K, int k) { return k == 1 && C % 128 != 0; }
-size_t mi_igemm_part_floats(int N, int C, int H, int K, int k, int stride) {
+extern "C" size_t mi_igemm_part_floats(int N, int C, int H, int K, int k, int stride) {
     if (igemm_wgrad_swapped(C, K, k)) return (size_t)igemm_wgrad_splits(N, K, H, C, k, stride) * K * C;
     return (size_t)igemm_wgrad_splits(N, C, H, K, k, stride) * k * k * K * C;
 }
 
 #define IG_TAIL_FLOATS ((size_t)IG_SLOTS * 128 * 128) /* partial-tile buffer: one slice per slot (768 x 64 x 128 fits too), 33.5 MB */
-size_t mi_igemm_tail_floats(void) { return igemm_mode() ? IG_TAIL_FLOATS : 0; }
-extern "C" int mid_igemm_mode(void) { return igemm_mode(); } /* RESNET_MI_IGEMM: 0 = no matrix cores anywhere */
+extern "C" size_t mi_igemm_tail_floats(void) { return IG_TAIL_FLOATS; }
 // Workgroup-count quantisation: `tiles` equal workgroups on IG_SLOTS resident slots run in ceil(tiles / IG_SLOTS) rounds, so
 // a last round that fills only a fraction of the chip costs a whole round (ResNet-50 at N=256: the 1024->2048 @14
 // projection has 1568 tiles = 3.06 rounds).  The `rem` tiles of that last round are cut into s = IG_SLOTS / rem slices along
@@ -1091,9 +1077,12 @@ static int igemm_launch(hipStream_t st, dim3 grid, const float *A, const float *
 }
 static int igemm_fam(int k) { return k == 1 ? MI_FAM_GEMM : MI_FAM_PCONV; }
 
-int mi_igemm_fwd(hipStream_t st, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K, int k,
-                 int stride, mid_bn_parts *parts) {
+extern "C" int mi_igemm_fwd(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K, int k,
+                            int stride, mid_bn_parts *parts) {
+    hipStream_t st = (hipStream_t)s;
     const int T = k * k;
+    if (parts) parts->nparts = 0;
+    if (!mi_igemm_supported(IGOP_FWD, N, C, H, K, k, stride)) { mi_record_error("mi_igemm_fwd", "shape not supported by the implicit GEMM"); return -2; }
     if (!ws || ws->wt_floats < (size_t)T * C * K) { mi_record_error("mi_igemm_fwd", "workspace too small"); return -3; }
     const float *A = ws->pre_fwd; // re-laid [t][c][k] by mid_conv_prelayout_all, else done here
     if (!A) {
@@ -1125,9 +1114,11 @@ int mi_igemm_fwd(hipStream_t st, mid_workspace *ws, const float *x, const float 
 
 // fz (optional): the reduction pass of the batch-norm backward that consumes dx, fused into this kernel's epilogue (stride 1);
 // fz->nparts > 0 on return says it did (dx then holds the GATED gradient)
-int mi_igemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend, int N,
-                   int C, int H, int K, int k, int stride, mid_bn_bwd_parts *fz) {
+extern "C" int mi_igemm_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend, int N,
+                              int C, int H, int K, int k, int stride, mid_bn_bwd_parts *fz) {
+    hipStream_t st = (hipStream_t)s;
     if (fz) fz->nparts = 0;
+    if (!mi_igemm_supported(IGOP_DGRAD, N, C, H, K, k, stride)) { mi_record_error("mi_igemm_dgrad", "shape not supported by the implicit GEMM"); return -2; }
     const int T = k * k;
     const float *A = w; // 1x1: the KC tensor is already [k][c]
     if (k == 3) {
@@ -1166,8 +1157,10 @@ int mi_igemm_dgrad(hipStream_t st, mid_workspace *ws, const float *w, const floa
     return 0;
 }
 
-int mi_igemm_wgrad(hipStream_t st, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k,
-                   int stride) {
+extern "C" int mi_igemm_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k,
+                              int stride) {
+    hipStream_t st = (hipStream_t)s;
+    if (!mi_igemm_supported(IGOP_WGRAD, N, C, H, K, k, stride)) { mi_record_error("mi_igemm_wgrad", "shape not supported by the implicit GEMM"); return -2; }
     if (igemm_wgrad_swapped(C, K, k)) {
         const int splits = igemm_wgrad_splits(N, K, H, C, 1, 1);
         if (!ws || ws->part_floats < (size_t)splits * K * C) { mi_record_error("mi_igemm_wgrad", "workspace too small"); return -3; }
@@ -1253,8 +1246,4 @@ extern "C" int mid_conv_prelayout_all(mid_stream s, const mid_wt_entry *entries_
     hipLaunchKernelGGL(igemm_wt_all_kernel, dim3(ntiles), dim3(256), 0, (hipStream_t)s, entries_dev, tile_entry_dev);
     MI_LAUNCH_CHECK("igemm_wt_all_kernel");
     return 0;
-}
-extern "C" void mid_conv_prelayout_needs(int N, int C, int H, int K, int k, int stride, int *need_fwd, int *need_dgrad) {
-    *need_fwd = mi_igemm_supported(IGOP_FWD, N, C, H, K, k, stride) ? 1 : 0;
-    *need_dgrad = (k == 3 && mi_igemm_supported(IGOP_DGRAD, N, C, H, K, k, stride)) ? 1 : 0; // 1x1 dgrad reads the KC tensor itself
 }

@@ -1062,7 +1062,7 @@ static int bgemm_wgrad_splits(int N, int C, int H, int K, int k, int stride) {
     }
     return best;
 }
-size_t mi_bgemm_part_floats(int N, int C, int H, int K, int k, int stride) {
+extern "C" size_t mi_bgemm_part_floats(int N, int C, int H, int K, int k, int stride) {
     const int P = (H / stride) * (H / stride);
     int mx = 1;
     for (int vw = 1; vw <= 8; vw *= 2) { // the launch picks its split count on the padded reduction length: take the largest
@@ -1313,8 +1313,11 @@ static int bgemm_plan_wgrad(BgArgs &g, int N, int C, int H, int K, int k, int st
     *used = mi_cdiv(kd, g.klen);
     return bm;
 }
-int mi_bgemm_wgrad(hipStream_t st, mid_workspace *ws, const u16 *x, const u16 *dy, float *dw, int N, int C, int H, int K, int k, int stride) {
+extern "C" int mi_bgemm_wgrad(mid_stream s, mid_workspace *ws, const void *xv, const void *dyv, float *dw, int N, int C, int H, int K, int k, int stride) {
+    hipStream_t st = (hipStream_t)s;
+    const u16 *x = (const u16 *)xv, *dy = (const u16 *)dyv;
     const int T = k * k;
+    if (!mi_bgemm_supported(BGOP_WGRAD, N, C, H, K, k, stride)) { mi_record_error("mi_bgemm_wgrad", "shape not supported by the bf16 kernels"); return -2; }
     BgArgs g = {};
     const bool parity_ok = stride == 2 && ws && ws->s2d && ws->s2d_bytes >= (size_t)N * C * H * H * 2;
     int vw, splits, used;
@@ -1336,16 +1339,6 @@ int mi_bgemm_wgrad(hipStream_t st, mid_workspace *ws, const u16 *x, const u16 *d
 
 extern "C" {
 int mid_bf16_supported(int op, int N, int C, int H, int K, int k, int stride) { return mi_bgemm_supported(op, N, C, H, K, k, stride); }
-static int pw_wgrad_on(void) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("RESNET_MI_BF16_PW_WGRAD"); on = e ? atoi(e) != 0 : 1; }
-    return on;
-}
-size_t mid_bf16_part_floats(int N, int C, int H, int K, int k, int stride) {
-    size_t a = mi_bgemm_part_floats(N, C, H, K, k, stride);
-    if (k == 1 && stride == 1 && pw_wgrad_on() && mid_pw_wgrad_supported(N, C, H, K)) { const size_t b = mid_pw_wgrad_part_floats(N, C, H, K); if (b > a) a = b; }
-    return a;
-}
 /* one layer's weights KCRS fp32 -> the bf16 k-step tiles of the forward pass [t][c/64][K][64] (what mid_conv_prelayout_all_bf16 makes for a table) */
 int mid_bf16_prelayout_fwd(mid_stream s, const float *w, void *out, int K, int C, int k) { return bg_prelayout_one((hipStream_t)s, w, (u16 *)out, nullptr, K, C, k); }
 /* ... and of the dgrad [t][k/64][C][64] */
@@ -1371,14 +1364,6 @@ int mid_conv_dgrad_bn_bf16(mid_stream s, mid_workspace *ws, const float *w, cons
                            int H, int K, int k, int stride, mid_bn_bwd_parts *fz) {
     if (!mi_bgemm_supported(BGOP_DGRAD, N, C, H, K, k, stride)) { mi_record_error("mid_conv_dgrad_bn_bf16", "shape not supported by the bf16 kernels"); return -2; }
     return mi_bgemm_dgrad((hipStream_t)s, ws, w, (const u16 *)dy, (u16 *)dx, (const u16 *)addend, N, C, H, K, k, stride, fz);
-}
-int mid_conv_wgrad_bf16(mid_stream s, mid_workspace *ws, const void *x, const void *dy, float *dw, int N, int C, int H, int K, int k,
-                        int stride) {
-    /* 1x1: both operands staged as they lie by LDS-DMA (kernels_cl_bf16.hip), where the shape and the workspace allow */
-    if (k == 1 && stride == 1 && pw_wgrad_on() && mid_pw_wgrad_supported(N, C, H, K) && ws->part && ws->part_floats >= mid_pw_wgrad_part_floats(N, C, H, K))
-        return mid_pw_wgrad(s, x, dy, dw, ws->part, ws->part_floats, N, C, H, K);
-    if (!mi_bgemm_supported(BGOP_WGRAD, N, C, H, K, k, stride)) { mi_record_error("mid_conv_wgrad_bf16", "shape not supported by the bf16 kernels"); return -2; }
-    return mi_bgemm_wgrad((hipStream_t)s, ws, (const u16 *)x, (const u16 *)dy, dw, N, C, H, K, k, stride);
 }
 /* mi_conv_plan for the NCHW route (resnet_mi.h): the planners of mi_bgemm_fwd / _dgrad / _wgrad with the operator's workspace (parity
  * planes for a stride-2 input).  0 where the route refuses the shape */

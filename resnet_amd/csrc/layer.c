@@ -1,7 +1,7 @@
 /*
  * layer.c -- everything that follows from one MiLayer alone (mi_host.h): the planner that gives a convolution its forward, dgrad and
- * wgrad kernel routes and the sizes of the buffers those routes need, the allocation of exactly those buffers, the layer's share of
- * the workspaces, and the runners that re-lay operands and launch in the routes' order.  The trainer (trainer.c) keeps the network as
+ * wgrad kernel routes, names the kernel of each and sizes the buffers those kernels need, the allocation of exactly those buffers, the
+ * layer's share of the workspaces, and the runners that re-lay operands and call the named kernel's launcher.  The trainer (trainer.c) keeps the network as
  * one table of units (MiUnit: a MiLayer with its batch norm, its tensors and the unit whose channel-last planes it writes), plans every
  * unit's layer with the planner's choices, and owns streams, events and the weight table.  The operator layer (ops.c) plans one layer
  * with forced routes and runs the same runners.  Plain C over mi_device.h.
@@ -36,6 +36,21 @@ static int size_limit_named(const MiLayer *L, int dtype, int N, const int force[
     return 1;
 }
 
+/* The kernel of an MI_*_F32 route.  RESNET_MI_IGEMM (o->igemm) says which shapes may use the implicit GEMM at all: 0 none -- every
+ * convolution on the older kernels; 1 the 1x1 weight gradients and the 3x3 / stride-2 projection shortcuts (K >= 2C) only -- the
+ * bottleneck's own 3x3 convolutions stay on the direct VALU kernels, 1x1 forward / dgrad on gemm_mfma_kernel; 2 (default) every 3x3 and
+ * 1x1.  Among those the kernel's own gate (shape, and tensors below 2^30 elements: so the batch decides too) has the last word; what it
+ * leaves goes to the plain GEMM (1x1) or the direct kernels, whose launchers refuse the shapes nothing takes */
+int mi_layer_f32_kernel(const MiOptions *o, int op, int N, int C, int H, int K, int k, int stride) {
+    int ig = o->igemm != 0;
+    if (k == 1 && op != 2 && o->igemm < 2) ig = 0;
+    if (k == 3 && o->igemm == 1 && !(stride == 2 && K >= 2 * C && C >= 256)) ig = 0;
+    if (ig && mi_igemm_supported(op, N, C, H, K, k, stride)) return MI_K_IGEMM;
+    if (k == 1 && stride == 1) return MI_K_GEMM1X1;
+    if (op != 2) return MI_K_DCONV;
+    return mid_direct_wgradC_supported(N, C, H, K, k, stride) ? MI_K_WGRADC : MI_K_WGRAD;
+}
+
 static int layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int N, int site, const int force[3]);
 int mi_layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int N, int site, const int force[3]) {
     /* every route indexes pixels (columns of the implicit GEMMs, rows of the direct kernels' patches) with 32 bits */
@@ -58,26 +73,29 @@ static int layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int
      * striding convolutions are the spatial one and the projection) */
     if (k3 && (s == 1 ? o->cl_s1 : s == 2 && o->cl_s2) && mid_cl_supported(0, N, C, H, K, s)) fwd = MI_FWD_CL;
     /* fp32 storage: the stem in exact fp32 on the matrix cores (kernels_stem_bf16.hip, st32_*) */
-    if (dtype == MID_F32 && mid_igemm_mode() > 0 && stem_mc && o->stem_mfma) fwd = MI_FWD_STEM_F32;
+    if (dtype == MID_F32 && o->igemm > 0 && stem_mc && o->stem_mfma) fwd = MI_FWD_STEM_F32;
     /* the stem on the bf16 matrix cores (image and weights rounded to bf16 like every other convolution of this mode) */
     if (dtype == MID_BF16 && stem_mc && o->bf16_stem) fwd = MI_FWD_STEM_BF16;
     if (force && force[0] != MI_PLANNED) fwd = force[0];
     switch (fwd) {
-    case MI_NOT_RUN: break;
-    case MI_FWD_F32: if (bf) return -2; break;
-    case MI_FWD_BF16: if (!bf || !mid_bf16_supported(0, N, C, H, K, k, s)) return -2; break;
+    case MI_NOT_RUN: L->kfwd = MI_K_NONE; break;
+    case MI_FWD_F32: if (bf) return -2; L->kfwd = mi_layer_f32_kernel(o, 0, N, C, H, K, k, s); break;
+    case MI_FWD_BF16: if (!bf || !mid_bf16_supported(0, N, C, H, K, k, s)) return -2; L->kfwd = MI_K_BGEMM; break;
     case MI_FWD_CL:
         if (!k3 || !mid_cl_supported(0, N, C, H, K, s)) return -2;
         L->cl_bytes = mid_cl_operand_bytes(0, N, C, H, K, s);
+        L->kfwd = MI_K_CL_CONV;
         break;
     case MI_FWD_PW: /* one tap of the channel-last kernel on a dense channel-last input: both operands reduction-contiguous */
         if (!bf || k != 1 || s != 1 || !mid_cl_pw_supported(N, C, H, K)) return -2;
         L->cl_bytes = (size_t)N * H * H * C * 2 + 4096;
+        L->kfwd = MI_K_CL_CONV;
         break;
     case MI_FWD_STEM_F32: case MI_FWD_STEM_BF16:
         if (!stem_mc) return -2;
         L->xp_bytes = fwd == MI_FWD_STEM_F32 ? mid_stem_f32_xp_bytes(N, H) : mid_stem_bf16_xp_bytes(N, H);
         L->scratch_floats = mid_stem_bf16_part_floats(N, H);
+        L->kfwd = fwd == MI_FWD_STEM_F32 ? MI_K_ST32_FWD : MI_K_ST_FWD;
         break;
     default: return -2;
     }
@@ -92,16 +110,18 @@ static int layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int
     if (k3 && s == 2 && o->cl_dgrad2 && mid_cl_dgrad2_supported(N, C, H, K)) dgrad = MI_DG_CL2;
     if (force && force[1] != MI_PLANNED) dgrad = force[1];
     switch (dgrad) {
-    case MI_NOT_RUN: break;
-    case MI_DG_F32: if (bf) return -2; break;
-    case MI_DG_BF16: if (!bf || !mid_bf16_supported(1, N, C, H, K, k, s)) return -2; break;
+    case MI_NOT_RUN: L->kdgrad = MI_K_NONE; break;
+    case MI_DG_F32: if (bf) return -2; L->kdgrad = mi_layer_f32_kernel(o, 1, N, C, H, K, k, s); break;
+    case MI_DG_BF16: if (!bf || !mid_bf16_supported(1, N, C, H, K, k, s)) return -2; L->kdgrad = MI_K_BGEMM; break;
     case MI_DG_CL:
         if (!k3 || s != 1 || !mid_cl_supported(1, N, C, H, K, 1)) return -2;
         L->dye_bytes = mid_cl_operand_bytes(1, N, C, H, K, 1);
+        L->kdgrad = MI_K_CL_CONV;
         break;
     case MI_DG_CL2:
         if (!k3 || s != 2 || !mid_cl_dgrad2_supported(N, C, H, K)) return -2;
         L->dye_bytes = mid_cl_dgrad2_operand_bytes(N, K, H / 2);
+        L->kdgrad = MI_K_CL_DGRAD2;
         break;
     default: return -2;
     }
@@ -117,13 +137,16 @@ static int layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int
     if (fwd == MI_FWD_STEM_BF16) wgrad = MI_WG_STEM_BF16;
     if (force && force[2] != MI_PLANNED) wgrad = force[2];
     switch (wgrad) {
-    case MI_NOT_RUN: break;
-    case MI_WG_F32: if (bf) return -2; break;
-    case MI_WG_BF16: if (!bf || !mid_bf16_supported(2, N, C, H, K, k, s)) return -2; break;
-    case MI_WG_CL: if (!wg) return -2; break;
-    case MI_WG_CL2: if (!wg2 || !L->dye_bytes) return -2; break;
-    case MI_WG_STEM_F32: if (fwd != MI_FWD_STEM_F32) return -2; break;
-    case MI_WG_STEM_BF16: if (fwd != MI_FWD_STEM_BF16) return -2; break;
+    case MI_NOT_RUN: L->kwgrad = MI_K_NONE; break;
+    case MI_WG_F32: if (bf) return -2; L->kwgrad = mi_layer_f32_kernel(o, 2, N, C, H, K, k, s); break;
+    case MI_WG_BF16: /* 1x1: both operands staged as they lie by LDS-DMA (kernels_cl_bf16.hip), where the shape tiles */
+        if (!bf || !mid_bf16_supported(2, N, C, H, K, k, s)) return -2;
+        L->kwgrad = k == 1 && s == 1 && o->pw_wgrad && mid_pw_wgrad_supported(N, C, H, K) ? MI_K_PW_WGRAD : MI_K_BGEMM;
+        break;
+    case MI_WG_CL: if (!wg) return -2; L->kwgrad = MI_K_CL_WGRAD; break;
+    case MI_WG_CL2: if (!wg2 || !L->dye_bytes) return -2; L->kwgrad = MI_K_CL_WGRAD2; break;
+    case MI_WG_STEM_F32: if (fwd != MI_FWD_STEM_F32) return -2; L->kwgrad = MI_K_ST32_WGRAD; break;
+    case MI_WG_STEM_BF16: if (fwd != MI_FWD_STEM_BF16) return -2; L->kwgrad = MI_K_ST_WGRAD; break;
     default: return -2;
     }
     /* NCHW parity planes of a stride-2 input (kernels_igemm_bf16.hip): the NCHW forward writes them and the weight gradient reads
@@ -133,22 +156,22 @@ static int layer_plan(MiLayer *L, int dtype, int policy, const MiOptions *o, int
     L->fwd = fwd; L->dgrad = dgrad; L->wgrad = wgrad;
 
     /* the forms a weight table re-lays once per forward pass (mid_conv_prelayout_all): every bf16 convolution (k-step tiles, forward
-     * and dgrad forms), the fp32 ones on the implicit-GEMM route (RESNET_MI_PRELAYOUT=0: each re-lays its own) */
-    L->wre_fwd = L->wre_dgrad = 0;
-    if (bf) L->wre_fwd = L->wre_dgrad = 1;
-    else if (dtype == MID_F32 && k <= 3 && o->prelayout) mid_conv_prelayout_needs(N, C, H, K, k, s, &L->wre_fwd, &L->wre_dgrad);
+     * and dgrad forms), the fp32 ones on the implicit GEMM (RESNET_MI_PRELAYOUT=0: each re-lays its own; its 1x1 dgrad reads the KC
+     * tensor as it is) */
+    L->wre_fwd = bf || (o->prelayout && L->kfwd == MI_K_IGEMM);
+    L->wre_dgrad = bf || (o->prelayout && L->kdgrad == MI_K_IGEMM && k == 3);
     L->wre_floats = ((size_t)k * k * C * K) / (bf ? 2 : 1);
 
     /* The dgrad also does the reduction pass of the BN' its output feeds (and gates that output): sites 1 expansion dgrad -> spatial
      * BN', 2 spatial dgrad -> reduction BN', 4 reduction dgrad -> the expansion BN' of the identity block below.  bf16: every site
      * whose dgrad is on the NCHW kernel (RECOMPUTE_BN too: the gating tensors have just been re-derived when the dgrad runs).
-     * fp32: the sites of RESNET_MI_F32_BNFUSE_BWD on the implicit-GEMM route, not with the FULL policy (its derivative mirror keeps
+     * fp32: the sites of RESNET_MI_F32_BNFUSE_BWD where every tiling shape is on the implicit GEMM, not with the FULL policy (its derivative mirror keeps
      * the ungated gradients the dump tree names).  Measured at batch 256 (same box, ms/step): none 108.3-109.5, site 4 alone
      * 108.3-108.9, site 1 alone 109.4-110.2, sites 1+2 111.6-112.8, all 111.7-112.2 -- the fp32 epilogue keeps lane = column, so
      * the fused form reads x / mask / addend with 4-byte accesses (four times the memory instructions of the bf16 kernel's
      * row-major drain) and pays for it wherever the separate reduction pass was only 2 tensors; site 4 replaces a 4-tensor pass
      * and breaks even, so it is the default. */
-    const int f32_sites = mid_igemm_mode() >= 2 ? o->bnfuse_bwd_f32 : 0;
+    const int f32_sites = o->igemm >= 2 ? o->bnfuse_bwd_f32 : 0;
     L->fz = site && o->bnfuse_bwd &&
             (dgrad == MI_DG_BF16 || (dgrad == MI_DG_F32 && (f32_sites & site) && policy != MI_STORE_FULL));
     return 0;
@@ -196,11 +219,20 @@ int mi_layer_own_weights(MiLayer *L, mid_wt_entry *e, mid_stream s) {
 
 /* the workspaces every convolution of a table shares, sized for its largest layer */
 void mi_layer_need(const MiLayer *L, MiLayerNeed *need) {
-    const int N = L->N, C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride, bf = L->dtype == MID_BF16 && k <= 3;
-    size_t a = mid_conv_ws_wt_floats(C, K, k), b = mid_conv_ws_part_floats(N, C, H, K, k, s), e;
-    if (bf && (e = mid_bf16_part_floats(N, C, H, K, k, s)) > b) b = e;
-    if (bf && k == 3 && mid_cl_wgrad_supported(N, C, H, K, s) && (e = mid_cl_wgrad_part_floats(N, C, H, K, s)) > b) b = e;
-    if (bf && k == 3 && mid_cl_wgrad2_supported(N, C, H, K, s) && (e = mid_cl_wgrad2_part_floats(N, C, H, K, s)) > b) b = e;
+    const int N = L->N, C = L->C, H = L->H, K = L->K, k = L->k, s = L->stride;
+    /* re-laid weights; behind them the partial tiles of the implicit GEMM's sliced tail round */
+    size_t a = mid_conv_ws_wt_floats(C, K, k) + (L->kfwd == MI_K_IGEMM || L->kdgrad == MI_K_IGEMM ? mi_igemm_tail_floats() : 0), b = 0, e;
+    switch (L->kwgrad) { /* the split partials of the weight gradient */
+    case MI_K_IGEMM: b = mi_igemm_part_floats(N, C, H, K, k, s); break;
+    case MI_K_GEMM1X1: b = mi_conv1x1_wgrad_part_floats(N, C, H * H, K); break;
+    case MI_K_WGRADC: b = mid_direct_wgradC_part_floats(N, C, H, K, k, s); break;
+    case MI_K_WGRAD: b = mid_direct_wgrad_part_floats(N, C, H, K, k, s); break;
+    case MI_K_BGEMM: b = mi_bgemm_part_floats(N, C, H, K, k, s); break;
+    case MI_K_PW_WGRAD: b = mid_pw_wgrad_part_floats(N, C, H, K); break;
+    case MI_K_CL_WGRAD: b = mid_cl_wgrad_part_floats(N, C, H, K, s); break;
+    case MI_K_CL_WGRAD2: b = mid_cl_wgrad2_part_floats(N, C, H, K, s); break;
+    default: break; /* (the stem's partials are the layer's own scratch) */
+    }
     if (a > need->wt) need->wt = a;
     if (b > need->part) need->part = b;
     /* the statistics partials of the layer's own output; a fusing dgrad leaves the sums of the BN' below in the same table */
@@ -253,7 +285,11 @@ int mi_layer_fwd(MiLayer *L, MiLayerWs *w, mid_stream s, const void *x, void *y,
         rc = mid_conv_fwd_bf16(s, &w->ws, x, L->w, y, N, C, H, K, L->k, L->stride, parts);
         L->par_valid = w->ws.s2d_valid; /* the launch says whether it left the parity planes */
         break;
-    default: rc = mid_conv_fwd_stats(s, &w->ws, (const float *)x, L->w, (float *)y, N, C, H, K, L->k, L->stride, parts);
+    default: /* MI_FWD_F32; only the implicit GEMM leaves statistics partials */
+        if (parts) parts->nparts = 0;
+        if (L->kfwd == MI_K_IGEMM) rc = mi_igemm_fwd(s, &w->ws, (const float *)x, L->w, (float *)y, N, C, H, K, L->k, L->stride, parts);
+        else if (L->kfwd == MI_K_GEMM1X1) rc = mi_conv1x1_fwd(s, (const float *)x, L->w, (float *)y, N, C, H * H, K);
+        else rc = mid_direct_fwd(s, &w->ws, (const float *)x, L->w, (float *)y, N, C, H, K, L->k, L->stride);
     }
     w->ws.pre_fwd = NULL;
     return rc;
@@ -295,7 +331,8 @@ const mid_bn_bwd_parts *mi_layer_fz_request(const MiLayer *L, const MiLayerWs *w
     return r;
 }
 /* req (mi_layer_fz_request): the dgrad also does the reduction pass of the BN' its output feeds; it hands that over in *fz (nparts > 0
- * when the launch could do it, dx then holds the gated gradient) */
+ * when the launch could do it, dx then holds the gated gradient; fp32: the implicit GEMM at stride 1 can, every other kernel runs the
+ * plain dgrad and hands back nparts = 0) */
 int mi_layer_dgrad(const MiLayer *L, MiLayerWs *w, mid_stream s, const void *dy, void *dx, const void *addend, const mid_bn_bwd_parts *req,
                    mid_bn_bwd_parts *fz) {
     const int N = L->N, C = L->C, H = L->H, K = L->K, k = L->k, st = L->stride;
@@ -306,12 +343,13 @@ int mi_layer_dgrad(const MiLayer *L, MiLayerWs *w, mid_stream s, const void *dy,
      * the NCHW kernel's four parity classes).  It writes every element of dx: no addend (the stride-2 layers' dgrads have none) */
     if (L->dgrad == MI_DG_CL2) return mid_cl_dgrad2(s, L->dye, L->we->dgrad, dx, N, C, H, K);
     w->ws.pre_dgrad = L->we ? L->we->dgrad : NULL;
-    if (req) *fz = *req;
+    if (req) { *fz = *req; fz->nparts = 0; }
     if (L->dgrad == MI_DG_BF16 && req) rc = mid_conv_dgrad_bn_bf16(s, &w->ws, L->w, dy, dx, addend, N, C, H, K, k, st, fz);
-    else if (req) /* fp32 storage: the stride-1 layers on the implicit-GEMM route do the same */
-        rc = mid_conv_dgrad_bn_f32(s, &w->ws, L->w, (const float *)dy, (float *)dx, (const float *)addend, N, C, H, K, k, st, fz);
     else if (L->dgrad == MI_DG_BF16) rc = mid_conv_dgrad_bf16(s, &w->ws, L->w, dy, dx, addend, N, C, H, K, k, st);
-    else rc = mid_conv_dgrad(s, &w->ws, L->w, (const float *)dy, (float *)dx, (const float *)addend, N, C, H, K, k, st);
+    else if (L->kdgrad == MI_K_IGEMM)
+        rc = mi_igemm_dgrad(s, &w->ws, L->w, (const float *)dy, (float *)dx, (const float *)addend, N, C, H, K, k, st, req && st == 1 ? fz : NULL);
+    else if (L->kdgrad == MI_K_GEMM1X1) rc = mi_conv1x1_dgrad(s, L->w, (const float *)dy, (float *)dx, (const float *)addend, N, C, H * H, K);
+    else rc = mid_direct_dgrad(s, &w->ws, L->w, (const float *)dy, (float *)dx, (const float *)addend, N, C, H, K, k, st);
     w->ws.pre_dgrad = NULL;
     return rc;
 }
@@ -326,8 +364,16 @@ int mi_layer_wgrad(const MiLayer *L, MiLayerWs *w, mid_stream s, const void *x, 
     case MI_WG_CL2: /* both operands channel-last: the forward's input planes and the dY planes mi_layer_dy_relayout has made */
         return mid_cl_wgrad2(s, L->cl, L->dye, dw, w->ws.part, w->ws.part_floats, N, C, H, K, st);
     case MI_WG_CL: return mid_cl_wgrad(s, L->cl, dy, dw, w->ws.part, w->ws.part_floats, N, C, H, K, st);
-    case MI_WG_BF16: return mid_conv_wgrad_bf16(s, &w->ws, x, dy, dw, N, C, H, K, k, st);
-    default: return mid_conv_wgrad(s, &w->ws, (const float *)x, (const float *)dy, dw, N, C, H, K, k, st);
+    case MI_WG_BF16:
+        if (L->kwgrad == MI_K_PW_WGRAD) return mid_pw_wgrad(s, x, dy, dw, w->ws.part, w->ws.part_floats, N, C, H, K);
+        return mi_bgemm_wgrad(s, &w->ws, x, dy, dw, N, C, H, K, k, st);
+    default: break; /* MI_WG_F32 */
+    }
+    switch (L->kwgrad) {
+    case MI_K_IGEMM: return mi_igemm_wgrad(s, &w->ws, (const float *)x, (const float *)dy, dw, N, C, H, K, k, st);
+    case MI_K_GEMM1X1: return mi_conv1x1_wgrad(s, &w->ws, (const float *)x, (const float *)dy, dw, N, C, H * H, K);
+    case MI_K_WGRADC: return mid_direct_wgradC(s, &w->ws, (const float *)x, (const float *)dy, dw, N, C, H, K, k, st);
+    default: return mid_direct_wgrad(s, &w->ws, (const float *)x, (const float *)dy, dw, N, C, H, K, k, st);
     }
 }
 /* BN' (+fused ReLU') of a unit of C channels over P pixels.  fz: the hand-off of the dgrad that produced dy -- nparts > 0: it gated dy
@@ -344,14 +390,24 @@ int mi_bn_bwd_unit(MiLayerWs *w, mid_stream s, mid_bn_bwd_parts *fz, const void 
 }
 
 /* ---------------------------------------------------------------------------------------------- */
-int mi_layer_routes(int dtype, int policy, int N, int C, int H, int K, int k, int stride, int site, int out[4]) {
+static int planned(MiLayer *L, int dtype, int policy, int N, int C, int H, int K, int k, int stride, int site) {
     MiOptions o;
-    MiLayer L;
-    for (int i = 0; i < 4; i++) out[i] = 0;
     if (policy < MI_STORE_FAST || policy > MI_STORE_FULL || (site != 0 && site != 1 && site != 2 && site != 4)) return -2;
     mi_read_options(&o);
-    mi_layer_init(&L, NULL, C, H, K, k, stride);
-    if (mi_layer_plan(&L, dtype, policy, &o, N, site, NULL)) return -2;
+    mi_layer_init(L, NULL, C, H, K, k, stride);
+    return mi_layer_plan(L, dtype, policy, &o, N, site, NULL) ? -2 : 0;
+}
+int mi_layer_routes(int dtype, int policy, int N, int C, int H, int K, int k, int stride, int site, int out[4]) {
+    MiLayer L;
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (planned(&L, dtype, policy, N, C, H, K, k, stride, site)) return -2;
     out[0] = L.fwd; out[1] = L.dgrad; out[2] = L.wgrad; out[3] = L.fz;
+    return 0;
+}
+int mi_layer_kernels(int dtype, int policy, int N, int C, int H, int K, int k, int stride, int site, int out[3]) {
+    MiLayer L;
+    for (int i = 0; i < 3; i++) out[i] = 0;
+    if (planned(&L, dtype, policy, N, C, H, K, k, stride, site)) return -2;
+    out[0] = L.kfwd; out[1] = L.kdgrad; out[2] = L.kwgrad;
     return 0;
 }

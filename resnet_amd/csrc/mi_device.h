@@ -83,17 +83,13 @@ typedef struct {
     int K, C, T, tile0;
 } mid_wt_entry;
 int mid_conv_prelayout_all(mid_stream s, const mid_wt_entry *entries_dev, const int *tile_entry_dev, int ntiles);
-/* which pre-laid forms the implicit-GEMM route of this layer would use (0/1 each); both 0 = layer not on that route */
-void mid_conv_prelayout_needs(int N, int C, int H, int K, int k, int stride, int *need_fwd, int *need_dgrad);
 
 /* ---- convolution (NCHW activations, KCRS weights), square images/kernels, pad k/2, Ho = H/stride ---- */
-/* Routed by shape and RESNET_MI_IGEMM (kernels_igemm.hip: mi_igemm_supported): MFMA implicit GEMM for the 3x3 / 1x1 shapes
- * that tile, plain MFMA GEMM for other 1x1, direct LDS-tiled VALU kernels for the 7x7 stem and the rest.
- * Returns 0 ok, <0 unsupported shape. */
-int mid_conv_fwd(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K,
-                 int k, int stride);
-/* Batch-norm statistics fused into the producing convolution: when the layer runs on the implicit-GEMM kernel every
- * workgroup also writes per-channel (count, mean, M2) partials of its output tile into parts->buf (three planes of
+/* The fp32 kernels, one launcher each.  Which of them a convolution runs is named once, by the planner (layer.c, MI_K_*): nothing here
+ * chooses.  Every launcher returns 0, or < 0 with the error recorded where it is handed a shape its kernel does not take (-2) or a
+ * workspace smaller than its size function asks for (-3). */
+/* Batch-norm statistics fused into the producing convolution: the implicit-GEMM kernel (and the bf16, channel-last and stem
+ * kernels) has every workgroup also write per-channel (count, mean, M2) partials of its output tile into parts->buf (three planes of
  * [nparts][K]); parts->nparts comes back > 0.  0 = not fused: run the separate statistics pass (mid_bn_fwd). */
 typedef struct {
     float *buf;
@@ -101,49 +97,65 @@ typedef struct {
     int nparts;
 } mid_bn_parts;
 size_t mid_bn_parts_floats(int N, int K, int Ho);
-int mid_conv_fwd_stats(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K,
-                       int k, int stride, mid_bn_parts *parts);
-/* dx = dgrad (+ addend when addend != NULL; addend may alias dx) */
-int mid_conv_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend,
-                   int N, int C, int H, int K, int k, int stride);
-int mid_conv_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H,
-                   int K, int k, int stride);
-/* sizes a workspace must have for the given layer (floats) */
-size_t mid_conv_ws_wt_floats(int C, int K, int k);
-size_t mid_conv_ws_part_floats(int N, int C, int H, int K, int k, int stride);
-
-/* ---- bf16-activation path (kernels_igemm_bf16.hip): x / y / dy / dx are bf16 NCHW, weights fp32 KCRS (rounded to bf16 when
- * re-laid), weight gradients fp32.  ws->pre_fwd / pre_dgrad point at bf16 k-step tiles when mid_conv_prelayout_all_bf16 made
- * them; otherwise the call re-lays the weights itself into ws->wt. ---- */
-int mid_bf16_supported(int op, int N, int C, int H, int K, int k, int stride); /* op 0 fwd, 1 dgrad, 2 wgrad */
-size_t mid_bf16_part_floats(int N, int C, int H, int K, int k, int stride);
-int mid_conv_prelayout_all_bf16(mid_stream s, const mid_wt_entry *entries_dev, const int *tile_entry_dev, int ntiles);
-int mid_conv_fwd_bf16(mid_stream s, mid_workspace *ws, const void *x, const float *w, void *y, int N, int C, int H, int K, int k,
-                      int stride, mid_bn_parts *parts);
-/* The REDUCTION pass of a batch-norm backward fused into the dgrad that produces its dy (bf16 kernels, pixel-major epilogue):
- * the dgrad stores g = (mask > 0 ? dx : 0) instead of dx and leaves per-tile sums of g and g (x - mean) per channel in buf (two
- * planes [nparts][C]); nparts comes back > 0 when the launch could do it.  mid_bn_bwd_parts_t then finishes that batch norm
- * (merge, finalize, apply) without reading dy for the sums. */
+/* The REDUCTION pass of a batch-norm backward fused into the dgrad that produces its dy (bf16 kernels, pixel-major epilogue; fp32
+ * implicit GEMM at stride 1): the dgrad stores g = (mask > 0 ? dx : 0) instead of dx and leaves per-tile sums of g and g (x - mean) per
+ * channel in buf (two planes [nparts][C]); nparts comes back > 0 when the launch could do it.  mid_bn_bwd_parts_t then finishes that
+ * batch norm (merge, finalize, apply) without reading dy for the sums. */
 typedef struct {
-    const void *x;       /* the BN's input (the convolution output it normalised), bf16, the shape of the dgrad output */
+    const void *x;       /* the BN's input (the convolution output it normalised), the shape of the dgrad output */
     const void *mask;    /* the tensor whose sign gates: that BN's activated output, or the block output for the expansion BN */
     const float *means;
     float *buf;
     size_t floats;
     int nparts;
 } mid_bn_bwd_parts;
+/* igemm_kernel (kernels_igemm.hip): MFMA implicit GEMM for the 3x3 / 1x1 shapes that tile.  mi_igemm_supported: its shape and size gate
+ * (op 0 fwd, 1 dgrad, 2 wgrad); the workspace holds the re-laid weights (mid_conv_ws_wt_floats; with mi_igemm_tail_floats more behind
+ * them, the partial tiles of the reduction-sliced tail workgroups, compute stream only) and the weight gradient's split partials.
+ * dx = dgrad (+ addend when addend != NULL; addend may alias dx); fz (optional, stride 1): see mid_bn_bwd_parts */
+int mi_igemm_supported(int op, int N, int C, int H, int K, int k, int stride);
+size_t mi_igemm_tail_floats(void);
+size_t mi_igemm_part_floats(int N, int C, int H, int K, int k, int stride);
+int mi_igemm_fwd(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K, int k, int stride,
+                 mid_bn_parts *parts);
+int mi_igemm_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend, int N, int C, int H,
+                   int K, int k, int stride, mid_bn_bwd_parts *fz);
+int mi_igemm_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k, int stride);
+/* gemm_mfma_kernel (kernels_gemm.hip): a 1x1 stride-1 convolution over P = H * H pixels as a plain MFMA GEMM, any channel counts */
+int mi_conv1x1_fwd(mid_stream s, const float *x, const float *w, float *y, int N, int C, int P, int K);
+int mi_conv1x1_dgrad(mid_stream s, const float *w, const float *dy, float *dx, const float *addend, int N, int C, int P, int K);
+size_t mi_conv1x1_wgrad_part_floats(int N, int C, int P, int K);
+int mi_conv1x1_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int P, int K);
+/* dconv_kernel, wgradC_kernel, wgrad_kernel (kernels_conv.hip): direct LDS-tiled VALU kernels -- forward 3x3 (stride 1 / 2) and the 7x7
+ * stem, dgrad 3x3, weight gradient in the C form (3x3, C % 64 == 0, K % 32 == 0, planes its chunks tile) or the read-lane form
+ * (3x3 and 7x7, K % 64 == 0).  The workspace holds the re-laid weights (mid_conv_ws_wt_floats) and the weight gradient's partials */
+size_t mid_conv_ws_wt_floats(int C, int K, int k);
+int mid_direct_fwd(mid_stream s, mid_workspace *ws, const float *x, const float *w, float *y, int N, int C, int H, int K, int k, int stride);
+int mid_direct_dgrad(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend, int N, int C, int H,
+                     int K, int k, int stride);
+int mid_direct_wgradC_supported(int N, int C, int H, int K, int k, int stride);
+size_t mid_direct_wgradC_part_floats(int N, int C, int H, int K, int k, int stride);
+int mid_direct_wgradC(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k, int stride);
+size_t mid_direct_wgrad_part_floats(int N, int C, int H, int K, int k, int stride);
+int mid_direct_wgrad(mid_stream s, mid_workspace *ws, const float *x, const float *dy, float *dw, int N, int C, int H, int K, int k, int stride);
+
+/* ---- bf16-activation path (kernels_igemm_bf16.hip): x / y / dy / dx are bf16 NCHW, weights fp32 KCRS (rounded to bf16 when
+ * re-laid), weight gradients fp32.  ws->pre_fwd / pre_dgrad point at bf16 k-step tiles when mid_conv_prelayout_all_bf16 made
+ * them; otherwise the call re-lays the weights itself into ws->wt. ---- */
+int mid_bf16_supported(int op, int N, int C, int H, int K, int k, int stride); /* op 0 fwd, 1 dgrad, 2 wgrad */
+int mid_conv_prelayout_all_bf16(mid_stream s, const mid_wt_entry *entries_dev, const int *tile_entry_dev, int ntiles);
+int mid_conv_fwd_bf16(mid_stream s, mid_workspace *ws, const void *x, const float *w, void *y, int N, int C, int H, int K, int k,
+                      int stride, mid_bn_parts *parts);
 int mid_conv_dgrad_bn_bf16(mid_stream s, mid_workspace *ws, const float *w, const void *dy, void *dx, const void *addend, int N, int C,
                            int H, int K, int k, int stride, mid_bn_bwd_parts *fz);
-/* the same for fp32 storage (kernels_igemm.hip): stride-1 layers on the implicit-GEMM route; otherwise a plain dgrad, nparts = 0 */
-int mid_conv_dgrad_bn_f32(mid_stream s, mid_workspace *ws, const float *w, const float *dy, float *dx, const float *addend, int N, int C,
-                          int H, int K, int k, int stride, mid_bn_bwd_parts *fz);
 int mid_bn_bwd_parts_t(mid_stream s, float *stats_ws, const mid_bn_bwd_parts *parts, const void *x, int x_dt, const float *gamma,
                        const float *beta, const float *means, const float *vars, const void *dy_gated, int a_dt, void *dx, float *dgamma,
                        float *dbeta, int N, int C, int P, float eps);
 int mid_conv_dgrad_bf16(mid_stream s, mid_workspace *ws, const float *w, const void *dy, void *dx, const void *addend, int N, int C,
                         int H, int K, int k, int stride);
-int mid_conv_wgrad_bf16(mid_stream s, mid_workspace *ws, const void *x, const void *dy, float *dw, int N, int C, int H, int K, int k,
-                        int stride);
+/* bgemm_kernel's weight gradient and its split partials; a 1x1 the planner puts on pw_wgrad_kernel runs mid_pw_wgrad instead */
+size_t mi_bgemm_part_floats(int N, int C, int H, int K, int k, int stride);
+int mi_bgemm_wgrad(mid_stream s, mid_workspace *ws, const void *x, const void *dy, float *dw, int N, int C, int H, int K, int k, int stride);
 /* ---- 3x3 convolutions of the bf16 path on channel-last, zero-padded operands (kernels_cl_bf16.hip): both operands global -> LDS by
  * LDS-DMA, no transposes, no masks.  op 0 forward (stride 1 or 2), op 1 dgrad (stride 1) ---- */
 int mid_bf16_prelayout_fwd(mid_stream s, const float *w, void *out, int K, int C, int k);
@@ -177,7 +189,6 @@ int mid_cl_dgrad2(mid_stream s, const void *dyp, const void *a_tiles, void *dx, 
 /* the 7x7 stride-2 stem (3 -> 64 channels) on the bf16 matrix cores (kernels_stem_bf16.hip): image and weights rounded to
  * bf16, fp32 accumulation, fp32 output / output gradient.  xp = the image as zero-padded parity planes (written by the
  * forward, read again by the weight gradient); scratch = wave partials + re-laid weights (mid_stem_bf16_part_floats). */
-int mid_igemm_mode(void); /* RESNET_MI_IGEMM (0 = the convolutions stay off the matrix cores) */
 /* ... and in exact fp32 (v_mfma_f32_32x32x2_f32) for the fp32 storage mode; same shape rule, same scratch, fp32 planes */
 size_t mid_stem_f32_xp_bytes(int N, int H);
 int mid_stem_fwd_f32(mid_stream s, const float *x, const float *w, float *y, void *xp, size_t xp_bytes, float *scratch, size_t scratch_floats,
@@ -187,7 +198,7 @@ int mid_stem_bf16_supported(int C, int H, int K, int k, int stride);
 size_t mid_stem_bf16_xp_bytes(int N, int H);
 size_t mid_stem_bf16_part_floats(int N, int H);
 int mid_stem_fwd_bf16(mid_stream s, const float *x, const float *w, void *y, int y_dt, void *xp, size_t xp_bytes, float *scratch, size_t scratch_floats,
-                      int N, int H, mid_bn_parts *parts); /* parts (optional): BN statistics partials of y, as mid_conv_fwd_stats leaves them */
+                      int N, int H, mid_bn_parts *parts); /* parts (optional): BN statistics partials of y, as mi_igemm_fwd leaves them */
 int mid_stem_wgrad_bf16(mid_stream s, const void *xp, const void *dy, int dy_dt, float *dw, float *scratch, size_t scratch_floats, int N, int H);
 int mid_f32_to_bf16(mid_stream s, const float *in, void *out, size_t n);
 int mid_bf16_to_f32(mid_stream s, const void *in, float *out, size_t n);

@@ -53,7 +53,8 @@ typedef struct BatchExt {
 BatchExt *mi_batch_ext(Batch *b);
 void mi_batch_ext_free(Batch *b);
 
-/* the trainer's own switches (environment), read once per trainer by init_trainer; kernel-level switches stay in the .hip files */
+/* the switches (environment) that decide what runs, read once per trainer by init_trainer and once per operator call: the planner is
+ * handed them; the .hip files keep only tuning knobs of a kernel's own geometry (*_BM, *_TAIL, *_VW, ...) */
 typedef struct {
     int cl_s1, cl_s1_dgrad;      /* RESNET_MI_BF16_CL_S1 / _CL_S1_DGRAD (0: stride-1 3x3 forward + wgrad / dgrad on the NCHW kernels) */
     int cl_s2, cl_dgrad2;        /* RESNET_MI_BF16_CL_S2 / _CL_DGRAD2 (0: stride-2 forward + wgrad / dgrad on the NCHW kernels) */
@@ -64,11 +65,13 @@ typedef struct {
     int overlap, overlap_given;  /* RESNET_MI_OVERLAP, and whether it was set at all */
     int bnfuse;                  /* RESNET_MI_BNFUSE (0: fp32 forward BN statistics by a pass of their own) */
     int prelayout;               /* RESNET_MI_PRELAYOUT (0: each fp32 convolution re-lays its own weights) */
+    int igemm;                   /* RESNET_MI_IGEMM: which fp32 convolutions run on the matrix cores (0 none, 1 few, 2 all that tile; layer.c) */
+    int pw_wgrad;                /* RESNET_MI_BF16_PW_WGRAD (0: every bf16 NCHW weight gradient on bgemm_kernel) */
 } MiOptions;
 
 /* One convolution of the network and how it runs (layer.c), decided once per build of the buffers: the kernel routes (MI_FWD_* /
- * MI_DG_* / MI_WG_*, resnet_mi.h) follow from shape, storage type, store policy and options, and the buffers the layer owns and their
- * sizes follow from the routes.  The trainer plans its table with the planner's own choices; an operator (ops.c) forces its routes. */
+ * MI_DG_* / MI_WG_*, resnet_mi.h) and the kernel of each (MI_K_*) follow from shape, storage type, store policy and options, and the
+ * buffers the layer owns and their sizes follow from the kernels.  The trainer plans its table with the planner's own choices; an operator (ops.c) forces its routes. */
 enum { MI_PLANNED = -1, MI_NOT_RUN = -2 }; /* a forced route: the planner's choice / the operation is not run and needs nothing */
 typedef struct {
     const float *w;
@@ -78,7 +81,8 @@ typedef struct {
     int wre_fwd, wre_dgrad;      /* which re-laid forms the routes read from a weight table, */
     size_t wre_floats;           /* and the floats of one */
     int fwd, dgrad, wgrad;       /* MI_FWD_* / MI_DG_* / MI_WG_* */
-    int fz;                      /* the dgrad also does the reduction pass of the BN' its output feeds (mid_conv_dgrad_bn_*) */
+    int kfwd, kdgrad, kwgrad;    /* MI_K_*: the kernel each runner launches */
+    int fz;                      /* the dgrad is asked to do the reduction pass of the BN' its output feeds too (mi_layer_dgrad) */
     /* bf16, channel-last input planes (kernels_cl_bf16.hip) read by the forward and the weight gradient: one zero-padded plane
      * (stride 1) or four parity planes (stride 2); cl_by_bn (set by the trainer, which knows the producer): the producing BN apply
      * writes them (the reduction BN for the 3x3, the expansion BN of the block above for a stride-2 projection), else a re-layout
@@ -130,6 +134,8 @@ int mi_bn_bwd_unit(MiLayerWs *w, mid_stream s, mid_bn_bwd_parts *fz, const void 
                    const float *means, const float *vars, const void *dy, const void *mask_src, int mask_mode, void *gated_out, int a_dt,
                    void *dx, float *dgamma, float *dbeta, int N, int C, int P, float eps);
 void mi_read_options(MiOptions *o); /* the process's switches (trainer.c) */
+/* the kernel an MI_*_F32 route runs operation op (0 fwd, 1 dgrad, 2 wgrad) of a shape on: the planner's rule, for the plan queries too */
+int mi_layer_f32_kernel(const MiOptions *o, int op, int N, int C, int H, int K, int k, int stride);
 
 /* One convolution + batch norm unit of the trainer's network, and everything about it that is fixed until the buffers are rebuilt
  * (trainer.c, build_units).  Forward tensors, parameters and parameter gradients only: nothing here points into the derivative tree,

@@ -27,8 +27,14 @@ static int finish(int rc) {
 /* ---- the convolution operators: plan the layer with the operator's routes, allocate at the planner's sizes, run the module's
  * runners, synchronise, free.  rc: the first failing step's code (later steps are skipped) ---- */
 typedef struct { MiLayer L; MiLayerWs w; mid_wt_entry we; mid_stream s; int rc; } OpConv;
-/* no switch reaches an operator: its routes are forced, and a dgrad + BN' operator fuses wherever its launch can */
-static const MiOptions OP_OPT = {.bnfuse_bwd = 1, .bnfuse_bwd_f32 = 7};
+/* an operator's routes are forced and its dgrad + BN' fuses wherever the launch can; of the environment only the two switches that choose
+ * the kernel inside a route reach it (RESNET_MI_IGEMM, RESNET_MI_BF16_PW_WGRAD) */
+static MiOptions op_options(void) {
+    MiOptions env, o = {.bnfuse_bwd = 1, .bnfuse_bwd_f32 = 7};
+    mi_read_options(&env);
+    o.igemm = env.igemm; o.pw_wgrad = env.pw_wgrad;
+    return o;
+}
 /* -2: a route refuses the shape (nothing was allocated).  No weight table here: the NCHW routes re-lay their own weights into the
  * workspace, the channel-last ones get theirs from mi_layer_own_weights (a weight gradient reads none) */
 static int op_open(OpConv *o, int dt, const MiOptions *opt, const float *w, int N, int C, int H, int K, int k, int stride, int fwd, int dgrad,
@@ -55,7 +61,8 @@ static int op_close(OpConv *o) {
 static int op_conv(int dt, int fwd, int dgrad, int wgrad, const void *x, const float *w, const void *dy, void *out, const void *addend, int N,
                    int C, int H, int K, int k, int stride) {
     OpConv o;
-    if (op_open(&o, dt, &OP_OPT, w, N, C, H, K, k, stride, fwd, dgrad, wgrad, 0)) return -2;
+    const MiOptions opt = op_options();
+    if (op_open(&o, dt, &opt, w, N, C, H, K, k, stride, fwd, dgrad, wgrad, 0)) return -2;
     if (wgrad != MI_NOT_RUN) {
         if (o.L.cl) o.rc = mi_layer_x_relayout(&o.L, o.s, x);
         if (!o.rc) o.rc = mi_layer_dy_relayout(&o.L, o.s, dy);
@@ -250,12 +257,21 @@ int mi_debug_redzone_check(void) { return mid_redzone_check(); }
 void mi_debug_redzone_stats(size_t *allocs_checked, size_t *zone_bytes_checked, size_t *live) { mid_redzone_stats(allocs_checked, zone_bytes_checked, live); }
 int mi_debug_trace_names(char *buf, size_t cap) { return mid_trace_names(buf, cap); }
 void mi_debug_trace_clear(void) { mid_trace_clear(); }
-int mi_debug_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]) { return mid_igemm_plan(op, N, C, H, K, k, stride, out); }
+/* 1: the fp32 operator of this shape runs operation op on the implicit GEMM (the planner's answer under the process's switches) */
+static int on_igemm(int op, int N, int C, int H, int K, int k, int stride) {
+    const MiOptions opt = op_options();
+    return op >= 0 && op <= 2 && mi_layer_f32_kernel(&opt, op, N, C, H, K, k, stride) == MI_K_IGEMM;
+}
+int mi_debug_conv_plan(int op, int N, int C, int H, int K, int k, int stride, int out[9]) {
+    if (on_igemm(op, N, C, H, K, k, stride)) return mid_igemm_plan(op, N, C, H, K, k, stride, out);
+    for (int i = 0; i < 9; i++) out[i] = 0;
+    return 0;
+}
 int mi_conv_plan(int dtype, int route, int op, int N, int C, int H, int K, int k, int stride, int out[7]) {
     for (int i = 0; i < 7; i++) out[i] = 0;
     int ok = 0;
     if (op < 0 || op > 2) ok = 0;
-    else if (dtype == MI_DTYPE_F32 && route == MI_ROUTE_DEFAULT) ok = mid_igemm_conv_plan(op, N, C, H, K, k, stride, out);
+    else if (dtype == MI_DTYPE_F32 && route == MI_ROUTE_DEFAULT) ok = on_igemm(op, N, C, H, K, k, stride) && mid_igemm_conv_plan(op, N, C, H, K, k, stride, out);
     else if (dtype == MI_DTYPE_BF16 && route == MI_ROUTE_DEFAULT) ok = mid_bf16_conv_plan(op, N, C, H, K, k, stride, out);
     else if (dtype == MI_DTYPE_BF16 && route >= MI_ROUTE_CL && route <= MI_ROUTE_PW) ok = mid_cl_conv_plan(route, op, N, C, H, K, k, stride, out);
     if (!ok) { for (int i = 0; i < 7; i++) out[i] = 0; return -2; }
@@ -289,7 +305,8 @@ static int op_dgrad_bn_bwd(int dt, const float *w, const void *dy, const void *a
     const size_t bytes = (size_t)N * C * H * H * (dt == MID_BF16 ? 2 : 4);
     mid_bn_bwd_parts fz = {NULL}, req;
     void *tmp = NULL;
-    if (op_open(&o, dt, &OP_OPT, w, N, C, H, K, k, stride, OFF, dt == MID_BF16 ? MI_DG_BF16 : MI_DG_F32, OFF, 1)) return -2;
+    const MiOptions opt = op_options();
+    if (op_open(&o, dt, &opt, w, N, C, H, K, k, stride, OFF, dt == MID_BF16 ? MI_DG_BF16 : MI_DG_F32, OFF, 1)) return -2;
     if (addend) mid_memcpy_d2d(gated, addend, bytes, o.s);
     if (!o.rc) o.rc = mi_layer_dgrad(&o.L, &o.w, o.s, dy, gated, addend ? gated : NULL, mi_layer_fz_request(&o.L, &o.w, &req, bn_x, mask, means), &fz);
     const int nparts = fz.nparts;
@@ -315,7 +332,7 @@ int mi_op_conv_dgrad_bn_bwd_f32(const float *w, const float *dy, const float *ad
  * RESNET_MI_IGEMM allows the matrix cores), exact = 0 image and weights rounded to bf16 inside (MI_FWD_STEM_BF16).  x fp32; conv_dt =
  * storage type of the stem's own output and of its gradient, a_dt = of the activations behind its BN */
 static int stem_open(OpConv *o, const float *w, int N, int H, int exact, int conv_dt, int a_dt, int wgrad) {
-    MiOptions opt = OP_OPT;
+    MiOptions opt = op_options();
     opt.stem_tensors_f32 = conv_dt == MID_F32;
     if ((exact || a_dt != MID_BF16) && conv_dt != MID_F32) return -2;
     return op_open(o, a_dt, &opt, w, N, 3, H, 64, 7, 2, exact ? MI_FWD_STEM_F32 : MI_FWD_STEM_BF16, OFF,
@@ -361,7 +378,8 @@ static int op_conv_bn_fwd(OpConv *o, const void *x, void *conv_out, const float 
 int mi_op_conv_bn_fwd_t(const void *x, const float *w, void *conv_out, int dt, const float *gamma, const float *beta, float *means,
                         float *vars, void *y, int N, int C, int H, int K, int k, int stride, float eps, int relu) {
     OpConv o;
-    if (op_open(&o, dt, &OP_OPT, w, N, C, H, K, k, stride, dt == MID_BF16 ? MI_FWD_BF16 : MI_FWD_F32, OFF, OFF, 0)) return -2;
+    const MiOptions opt = op_options();
+    if (op_open(&o, dt, &opt, w, N, C, H, K, k, stride, dt == MID_BF16 ? MI_FWD_BF16 : MI_FWD_F32, OFF, OFF, 0)) return -2;
     return op_conv_bn_fwd(&o, x, conv_out, gamma, beta, means, vars, y, eps, relu);
 }
 /* the same pair on a bf16 3x3 layer whose forward takes the channel-last kernel (MI_FWD_CL): weights re-laid, input re-laid into a zeroed
@@ -369,7 +387,8 @@ int mi_op_conv_bn_fwd_t(const void *x, const float *w, void *conv_out, int dt, c
 int mi_op_conv_bn_fwd_bf16_cl(const void *x, const float *w, void *conv_out, const float *gamma, const float *beta, float *means,
                               float *vars, void *y, int N, int C, int H, int K, int stride, float eps, int relu) {
     OpConv o;
-    if (op_open(&o, MID_BF16, &OP_OPT, w, N, C, H, K, 3, stride, MI_FWD_CL, OFF, OFF, 0)) return -2;
+    const MiOptions opt = op_options();
+    if (op_open(&o, MID_BF16, &opt, w, N, C, H, K, 3, stride, MI_FWD_CL, OFF, OFF, 0)) return -2;
     return op_conv_bn_fwd(&o, x, conv_out, gamma, beta, means, vars, y, eps, relu);
 }
 /* the stem and its BN + ReLU as forward_pass runs them on the matrix cores: exact = 1 MI_FWD_STEM_F32 (conv_out fp32), exact = 0

@@ -509,6 +509,8 @@ void mi_read_options(MiOptions *o) {
     o->overlap_given = getenv("RESNET_MI_OVERLAP") != NULL;
     o->bnfuse = ENV_INT("RESNET_MI_BNFUSE", 1);
     o->prelayout = ENV_INT("RESNET_MI_PRELAYOUT", 1);
+    o->igemm = ENV_INT("RESNET_MI_IGEMM", 2);
+    o->pw_wgrad = ENV_INT("RESNET_MI_BF16_PW_WGRAD", 1) != 0;
 #undef ENV_INT
 }
 /* resnet.cu:1157-1194 */

@@ -46,6 +46,13 @@ def layer_routes(lib, dtype, policy, N, Cc, H, K, k, stride, site=0):
     rc = lib.mi_layer_routes(dtype, policy, N, Cc, H, K, k, stride, site, out)
     return tuple(out) if rc == 0 else None
 
+def layer_kernels(lib, dtype, policy, N, Cc, H, K, k, stride, site=0):
+    """mi_layer_kernels (host only): the kernel ids (binding.MI_K_*) of the forward, the dgrad and the weight gradient inside the routes
+    layer_routes answers, or None where the planner refuses (-2)"""
+    out = (C.c_int * 3)()
+    rc = lib.mi_layer_kernels(dtype, policy, N, Cc, H, K, k, stride, site, out)
+    return tuple(out) if rc == 0 else None
+
 
 class Ops:
     def __init__(self):

@@ -303,8 +303,8 @@ BF16_ROUTE_NAMES = ({1: "default", 2: "cl"}, {1: "default", 2: "cl", 3: "cl"}, {
 
 
 def bf16_route(L, op, N, Cn, H, K, k, s):
-    """the route the planner gives a bf16 layer (layer_routes).  The one choice it does not make: on MI_WG_BF16 a 1x1 weight gradient takes
-    the LDS-DMA kernel at launch where that tiles (mid_conv_wgrad_bf16), which mi_conv_plan's route "pw" answers"""
+    """the route the planner gives a bf16 layer (layer_routes).  Inside MI_WG_BF16 a 1x1 weight gradient takes the LDS-DMA kernel where
+    that tiles (the planner's kernel choice, mi_layer_kernels), which mi_conv_plan's route "pw" answers"""
     r = layer_routes(L, 1, 0, N, Cn, H, K, k, s)
     assert r is not None, "the planner refuses the bf16 layer %s at N = %d" % ((Cn, H, K, k, s), N)
     name = BF16_ROUTE_NAMES[OPS[op]][r[OPS[op]]]

@@ -2,11 +2,14 @@
 
   route_worker.py ops OUT.json KEY [KEY ...]       the operator cases of the table entries KEY (tests/routes.py), each case once
   route_worker.py trainer OUT.json f32|bf16|both   two training steps at batch 4: C1S in fp32, C4I in bf16
+  route_worker.py kernels OUT.json CASES.json      per case (dtype, op, C, H, K, k, stride, N, addend): what the planner names, what was launched
 
 ops: per case, clear the launch ring, run the case's perelement.py checker (float64 reference, the checker's own bounds: a failure ends
 the process with a traceback), and record the worst distances and the ring's names.  For the cases of "bitwise" entries the operator is
 run once more on the same operands and its raw outputs go to OUT.json.npz.  trainer: loss, every gradient of both steps and every
-parameter after them go to OUT.json.npz.  OUT.json is written last: it exists only if everything before it passed.
+parameter after them go to OUT.json.npz.  kernels: per case, the planner's routes and kernel ids (mi_layer_routes, mi_layer_kernels), the
+fp32 weight gradient's plan (mi_conv_plan), then the launch ring cleared, the operator of the planned route run once and the ring's names
+(nothing is compared here: the parent asserts).  OUT.json is written last: it exists only if everything before it passed.
 """
 import ctypes
 import json
@@ -98,6 +101,33 @@ def run_ops(out_path, keys):
         json.dump(dict(cases=result, checked=len(result)), f)
 
 
+def run_kernels(out_path, cases_path):
+    from resnet_amd import binding as B
+    from resnet_amd.ops import Ops, layer_kernels, layer_routes
+    ops = Ops()
+    assert ops.L.mi_device_count() >= 1, "no HIP device"
+    with open(cases_path) as f:
+        cases = [tuple(c) for c in json.load(f)]
+    result = []
+    for dt, op, Cn, H, K, k, s, N, addend in cases:
+        i = ("fwd", "dgrad", "wgrad").index(op)
+        dtype = B.MI_DTYPE_BF16 if dt == "bf16" else B.MI_DTYPE_F32
+        route, kernel = layer_routes(ops.L, dtype, B.MI_STORE_FAST, N, Cn, H, K, k, s), layer_kernels(ops.L, dtype, B.MI_STORE_FAST, N, Cn, H, K, k, s)
+        assert route is not None and kernel is not None, "the planner refuses %s" % ((dt, op, Cn, H, K, k, s, N),)
+        plan = R.conv_plan(ops.L, 0, "default", op, N, Cn, H, K, k, s) if dt == "f32" else None
+        ops.L.mi_debug_trace_clear()
+        if route[i] in ((B.MI_FWD_STEM_F32, B.MI_FWD_STEM_BF16) if op == "fwd" else (B.MI_WG_STEM_F32, B.MI_WG_STEM_BF16)) and k == 7:
+            got = P.stem_call(ops, dt, op, P.stem_inputs(dt, op, N, H))
+        else:
+            assert route[i] == (1 if dt == "bf16" else 0), "the planned route of %s is %d: not an operator this worker runs" % ((dt, op, Cn, H, K, k, s, N), route[i])
+            case = (dt, "default", op, Cn, H, K, k, s, "red" if addend else "")
+            got = P.conv_route_call(ops, case, P.conv_route_inputs(case, N))
+        assert got is not None
+        result.append(dict(case=[dt, op, Cn, H, K, k, s, N, addend], route=route[i], kernel=kernel[i], plan=plan, names=ring_names(ops.L)))
+    with open(out_path, "w") as f:
+        json.dump(dict(cases=result), f)
+
+
 HYPER = dict(lr=1e-4, wd=0.0, b1=0.9, b2=0.999, eps=1e-7)
 
 
@@ -139,5 +169,7 @@ if __name__ == "__main__":
     mode, out = sys.argv[1], sys.argv[2]
     if mode == "ops":
         run_ops(out, sys.argv[3:])
+    elif mode == "kernels":
+        run_kernels(out, sys.argv[3])
     else:
         run_trainer(out, sys.argv[3])

@@ -11,6 +11,9 @@ The switches are read once per process, so every (switch, value) runs in a child
   test_store_policies_bit_identical_after_25_steps[f32]; the bf16 switches are parameters of
   test_gpu_bf16.py::test_training_step_bf16_on_the_other_kernel_routes); "bitwise" entries also compare loss, every gradient and every
   parameter of two steps with a default child's, bit for bit.
+* test_planner_names_the_launched_kernel: per RESNET_MI_IGEMM value (and once with RESNET_MI_BF16_PW_WGRAD=0) one child runs the fp32
+  and bf16 operators over shapes that take every kernel of the two NCHW route families; the convolution launch in the ring carries the
+  name of the kernel mi_layer_kernels answered, with exactly the re-layout and reduce launches that kernel implies.
 
 A child that ends by a signal, times out or reports a GPU memory fault is a casualty: every later test of this file then fails at once
 without starting another process on the device.  Nothing is retried.
@@ -232,3 +235,93 @@ def test_trainer_under_switch(key, default_trainer, tmp_path):
         assert len(got.files) > 10
         for name in got.files:
             assert got[name].tobytes() == ref[name].tobytes(), "%s under %s differs from the default trainer's" % (name, key)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# (dtype, op, C, H, K, k, stride, N, addend) of test_planner_names_the_launched_kernel
+def _kernel_cases():
+    from test_gpu_ops import DIRECT
+    f32 = [(64, 8, 96, 3, 1, 2),                                  # the mixed layer: another kernel per operation
+           routes.S_3x3, routes.S_1x1, routes.S_3x3s2, routes.S_49,
+           (48, 8, 96, 1, 1, 4),                                  # a 1x1 no implicit GEMM tiles: gemm_mfma_kernel in every mode
+           (256, 56, 64, 1, 1, 8),                                # the weight gradient's grouped split reduce
+           (3, 32, 64, 7, 2, 4)]                                  # the stem
+    bf16 = [(256, 8, 128, 1, 1, 5), (128, 14, 256, 1, 1, 3),      # pw_wgrad_kernel unless switched off
+            (192, 8, 128, 1, 1, 5)]                               # C % 128 != 0: bgemm_kernel
+    cases = [("f32", c[0]) + tuple(c[1:7]) + (c[7],) for c in DIRECT]
+    cases += [("f32", op) + sh + (False,) for sh in f32 for op in routes.ALL if not (sh[3] == 7 and op == "dgrad")]
+    cases += [("bf16", op) + sh + (False,) for sh in bf16 for op in routes.ALL]
+    return list(dict.fromkeys(cases))
+
+
+# what the issue of this test states outright, (dtype, op, shape) -> kernel name per RESNET_MI_IGEMM value (None: every value)
+KERNEL_FACTS = [
+    (("f32", "fwd", (64, 8, 96, 3, 1, 2)), {"2": "dconv_kernel", "0": "dconv_kernel"}),       # K % 64 != 0
+    (("f32", "dgrad", (64, 8, 96, 3, 1, 2)), {"2": "igemm_kernel", "0": "dconv_kernel"}),
+    (("f32", "wgrad", (64, 8, 96, 3, 1, 2)), {"2": "wgradC_kernel", "0": "wgradC_kernel"}),
+    (("f32", "fwd", (48, 8, 96, 1, 1, 4)), {None: "gemm_mfma_kernel"}),
+    (("f32", "dgrad", (48, 8, 96, 1, 1, 4)), {None: "gemm_mfma_kernel"}),
+    (("f32", "wgrad", (48, 8, 96, 1, 1, 4)), {None: "gemm_mfma_kernel"}),
+    (("f32", "fwd", routes.S_3x3), {"0": "dconv_kernel", "1": "dconv_kernel", "2": "igemm_kernel"}),
+    (("f32", "fwd", routes.S_1x1), {"0": "gemm_mfma_kernel", "1": "gemm_mfma_kernel", "2": "igemm_kernel"}),
+    (("f32", "wgrad", routes.S_1x1), {"0": "gemm_mfma_kernel", "1": "igemm_kernel", "2": "igemm_kernel"}),
+    (("f32", "fwd", (3, 32, 64, 7, 2, 4)), {"0": "dconv_kernel", "2": "st32_fwd_kernel"}),
+    (("f32", "wgrad", (3, 32, 64, 7, 2, 4)), {"0": "wgrad_kernel", "2": "st32_wgrad_kernel"}),
+    (("bf16", "wgrad", (192, 8, 128, 1, 1, 5)), {None: "bgemm_kernel"}),
+    (("bf16", "fwd", (256, 8, 128, 1, 1, 5)), {None: "bgemm_kernel"}),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env_add", [{"RESNET_MI_IGEMM": "0"}, {"RESNET_MI_IGEMM": "1"}, {"RESNET_MI_IGEMM": "2"}, {"RESNET_MI_BF16_PW_WGRAD": "0"}],
+                         ids=["igemm0", "igemm1", "igemm2", "pw_wgrad0"])
+def test_planner_names_the_launched_kernel(env_add, tmp_path):
+    """Per case and operation the child clears the launch ring and runs the operator; here: the one convolution kernel among the ring's
+    names is the kernel mi_layer_kernels named (binding.MI_KERNEL_NAMES), for the cases KERNEL_FACTS lists it is also the kernel the
+    shape rules give, and the launches around it are the ones that kernel implies -- an operator has no pre-laid weights, so
+    igemm_wt_kernel exactly in front of an implicit-GEMM forward or 3x3 dgrad and wt_relayout_kernel exactly in front of dconv_kernel;
+    split_reduce_kernel only behind the kernels that split (wgradC_kernel, wgrad_kernel, gemm_mfma_kernel), the implicit GEMM's own
+    reduce exactly behind its weight gradient, grouped where mi_conv_plan says so.  The RESNET_MI_BF16_PW_WGRAD=0 child runs the bf16
+    cases only."""
+    from resnet_amd import binding as B
+    cases = [c for c in _kernel_cases() if "RESNET_MI_IGEMM" in env_add or c[0] == "bf16"]
+    with open(tmp_path / "cases.json", "w") as f:
+        json.dump(cases, f)
+    out = str(tmp_path / "kernels.json")
+    r = run_child("kernels %s" % env_add, [sys.executable, WORKER, "kernels", out, str(tmp_path / "cases.json")], env_add, 300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    with open(out) as f:
+        got = json.load(f)["cases"]
+    assert len(got) == len(cases)
+    conv_names = set(B.MI_KERNEL_NAMES[1:])
+    mode, pw = env_add.get("RESNET_MI_IGEMM"), env_add.get("RESNET_MI_BF16_PW_WGRAD")
+    seen = set()
+    for g in got:
+        dt, op, Cn, H, K, k, s, N, addend = g["case"]
+        what = "%s under %s" % (g["case"], env_add)
+        want = B.MI_KERNEL_NAMES[g["kernel"]]
+        heads = [n.split("<")[0] for n in g["names"]]
+        print("%-60s %-18s %s" % (g["case"], want, g["names"]))
+        # (the stem's weight-gradient operator runs the forward first: the weight gradient reads the planes it leaves)
+        behind = {"st32_wgrad_kernel": {"st32_fwd_kernel"}, "st_wgrad_kernel": {"st_fwd_kernel"}}.get(want, set())
+        assert want and {h for h in heads if h in conv_names} - behind == {want}, "%s: the planner names %r, launched %s" % (what, want, g["names"])
+        seen.add(want)
+        for (fdt, fop, fshape), by_mode in KERNEL_FACTS:
+            if (fdt, fop, tuple(fshape)) == (dt, op, (Cn, H, K, k, s, N)) and (None in by_mode or mode in by_mode):
+                assert want == by_mode.get(None, by_mode.get(mode)), what
+        if dt == "bf16" and op == "wgrad" and Cn % 128 == 0:
+            assert want == ("bgemm_kernel" if pw == "0" else "pw_wgrad_kernel"), what
+        assert ("igemm_wt_kernel" in heads) == (want == "igemm_kernel" and (op == "fwd" or (op == "dgrad" and k == 3))), what
+        assert ("wt_relayout_kernel" in heads) == (want == "dconv_kernel"), what
+        if "split_reduce_kernel" in heads:
+            assert want in ("wgradC_kernel", "wgrad_kernel", "gemm_mfma_kernel") and op == "wgrad", what
+        ig_reduce = [n for n in g["names"] if n.startswith("igemm_wgrad_reduce")]
+        if dt == "f32":
+            assert (g["plan"] is not None) == (want == "igemm_kernel"), "%s: mi_conv_plan and mi_layer_kernels disagree" % what
+            assert len(ig_reduce) == (1 if want == "igemm_kernel" and op == "wgrad" else 0), what
+            if ig_reduce and not ig_reduce[0].startswith("igemm_wgrad_reduce_t_kernel"):
+                assert ("grouped" in ig_reduce[0]) == bool(g["plan"][6]), what
+    if mode == "2":
+        assert {"igemm_kernel", "gemm_mfma_kernel", "dconv_kernel", "wgradC_kernel", "wgrad_kernel", "bgemm_kernel", "pw_wgrad_kernel",
+                "st32_fwd_kernel", "st32_wgrad_kernel"} <= seen, sorted(seen)
+        assert any("grouped" in n for g in got for n in g["names"]), "no case reached the grouped split reduce"
