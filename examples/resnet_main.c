@@ -29,6 +29,10 @@
  *              min(DECAY, (1 + k) / (10 + k)) for update k.  DECAY is used as given: torchvision's correction for world, batch, N and the
  *              number of epochs is the caller's.  --ema alone implies --bn-momentum 0.1; with --val-u8 every validation is printed twice,
  *              for the raw weights and for the EMA weights
+ *   ./ResNetMI --batch 256 --accum 16 --accum-scale 0.0625
+ *              gradient accumulation (mi_trainer_set_accumulation): one optimizer update per K iterations on the sum of their gradients
+ *              times S (default 1: the sum, what a batch K times as large would give; 1/K: the mean over the micro-batches).  An
+ *              iteration stays one micro-batch: the printout, --iters and --val-every count micro-batches, --ema-every counts updates
  *   ./ResNetMI --labels-file id_to_label_mapping.txt --synsets-file id_to_synset_mapping.txt --counts-file id_to_img_count_mapping.txt
  *              the class metadata of resnet.cu:3236-3242: iterations per epoch = ceil(sum of the class counts / batch) (:3309)
  *              unless --iters says otherwise
@@ -125,6 +129,8 @@ int main(int argc, char **argv) {
     const int EMA_EVERY = atoi(opt(argc, argv, "--ema-every", "1"));
     int ema_warmup = 0;
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--ema-warmup")) ema_warmup = 1;
+    const int ACCUM = atoi(opt(argc, argv, "--accum", "1"));
+    const float ACCUM_SCALE = (float)atof(opt(argc, argv, "--accum-scale", "1"));
     const char *dump_root = opt(argc, argv, "--dump-root", NULL);
     const char *loss_log = opt(argc, argv, "--loss-log", "avg_loss_log.txt");
     const int resume_id = atoi(opt(argc, argv, "--resume", "-1"));           /* LOAD_FROM_DUMP_ID, resnet.cu:3299 */
@@ -167,6 +173,8 @@ int main(int argc, char **argv) {
     }
     /* before a resume: overwrite_model_params then restores the averaged model and its counter from the dump, where it holds them */
     if (ema_arg && mi_trainer_set_ema(trainer, atof(ema_arg), EMA_EVERY, ema_warmup)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    /* before a resume too: a dump made inside a window holds the sum so far */
+    if (ACCUM != 1 && mi_trainer_set_accumulation(trainer, ACCUM, ACCUM_SCALE)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (resume_id != -1) { overwrite_trainer_hyperparams(trainer, resume_id, "my_custom"); overwrite_model_params(trainer, resume_id, "my_custom"); }
 
     FILE *loss_file = fopen(loss_log, "w");

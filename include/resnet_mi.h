@@ -617,6 +617,46 @@ int mi_trainer_ema_get_location(Train_ResNet *t, int i, float *host);
 int mi_trainer_ema_set_location(Train_ResNet *t, int i, const float *host);
 int mi_trainer_ema_get_running_stats(Train_ResNet *t, float *means, float *vars);
 int mi_trainer_ema_set_running_stats(Train_ResNet *t, const float *means, const float *vars);
+/* ---------------- gradient accumulation: k micro-batches per optimizer update ----------------
+ * The large global batches LARS and mixup / CutMix are made for, on the GPUs one has.  Off by default (k = 1); while off every launch,
+ * value and dumped file is what it was, and nothing is allocated before the first k > 1.
+ *
+ * The gradient is a batch SUM (dlogits carries no 1/N), so the sum of k micro-batch gradients is what a batch k times as large would
+ * have handed the optimizer -- batch norm statistics apart, which stay per micro-batch as in every framework.  A backward pass
+ * OVERWRITES the gradient arena, so the sum lives in an accumulator arena of its own (grad_accum_kernel, kernels_optim.hip):
+ *   MI_ACC_FIRST  acc = g                   as 32-bit words: NaN payloads and -0 as they are
+ *   MI_ACC_ADD    acc = acc (+) g
+ *   MI_ACC_FOLD   g = (acc (+) g) (x) scale  acc is not written
+ * fp32, every operation rounded on its own (no fused multiply-add).  Nothing is guarded: a value that is not finite propagates by IEEE
+ * rules, and the optimizer's own guards see a folded gradient that is not finite as they see any other.
+ *
+ * mi_op_grad_accumulate: the kernel on its own, on device arrays of n floats; 16-byte accesses where both pointers are 16-byte aligned,
+ * element-wise otherwise.  -1, mi_last_error set, nothing launched or written: a NULL pointer, a pointer that is not 4-byte aligned,
+ * overlapping ranges, n == 0 or n > 2^40, an unknown mode, in MI_ACC_FOLD a scale that is NaN, infinite or <= 0.
+ *
+ * mi_trainer_set_accumulation(t, k, scale): the main loop stays the reference's -- load_new_batch / forward_pass / backwards_pass /
+ * update_parameters once per micro-batch.  Calls 1 .. k - 1 of a window to update_parameters only collect: one launch on the compute
+ * stream (FIRST, then ADD), no optimizer, no EMA, no NaN-flag copy, no decay advance, the re-laid weights stay valid.  Call k folds
+ * (scale: 1 for the sum, 1.f / k for the mean over micro-batches) and then does everything update_parameters does today, once: the
+ * optimizer on the folded gradient (the LARS trust ratio is taken on it), the decay advance, the EMA (its `every` counts applied
+ * updates), the NaN flag.  No new host synchronisation.  Per micro-batch stay the BN batch statistics and the running-statistics
+ * update, cur_dump_id and the periodic dump, input_reset, the mix plan's step and the loss records.  Data parallel: the collecting
+ * passes cut no bucket and start no collective; on the last pass every bucket is folded on the comm stream in front of its all-reduce
+ * (scale per rank, before the sum), behind the events the all-reduce waits for.
+ * The first call with k > 1 allocates the accumulator (counted in mi_trainer_device_bytes).  -1, mi_last_error set, nothing changed:
+ * k < 1, a scale that is NaN, infinite or <= 0, a call inside a window (pending > 0) or between forward_pass and update_parameters.
+ * mi_trainer_accumulation: k and the micro-batches summed so far in this window.  Like the optimizer, the setting is not dumped.
+ *
+ * Checkpoints: inside a window (k > 1, pending > 0) dump_trainer also writes <dump>/grad_accum.buffer -- k and pending as int32, then the
+ * accumulator's arena floats; any other dump is byte for byte what it was.  overwrite_model_params on a trainer with k > 1 restores the
+ * accumulator and pending where the file exists, holds the same k and fits; otherwise pending = 0, with one note on stderr if a file
+ * was there.  mi_debug_accum_arena: the accumulator on the device (NULL before the first k > 1), laid out as the gradient arena. */
+enum { MI_ACC_FIRST = 0, MI_ACC_ADD = 1, MI_ACC_FOLD = 2 };
+int mi_op_grad_accumulate(float *acc, float *g, size_t n, int mode, float scale);
+void mi_debug_accum_geometry(size_t out[4]); /* as mi_debug_ema_geometry */
+int mi_trainer_set_accumulation(Train_ResNet *t, int k, float scale);
+int mi_trainer_accumulation(const Train_ResNet *t, int *k, int *pending);
+float *mi_debug_accum_arena(const Train_ResNet *t);
 /* the SGD / LARS kernels on their own: p, g, b device arrays of n floats; tensor i starts at offsets_host[i] (n_tensors + 1 entries,
  * multiples of 4, the last <= n) and runs to the next offset; tensor_is_weight_host[i] 1: trust ratio and weight decay (LARS).
  * nan_flag_dev: device int or NULL.  sq_norms_out_host (optional, 2 n_tensors doubles): (|w|^2, |g|^2) per tensor before the update,

@@ -127,6 +127,7 @@ MI_KERNEL_NAMES = ("", "igemm_kernel", "gemm_mfma_kernel", "dconv_kernel", "wgra
 (MI_K_NONE, MI_K_IGEMM, MI_K_GEMM1X1, MI_K_DCONV, MI_K_WGRADC, MI_K_WGRAD, MI_K_BGEMM, MI_K_PW_WGRAD, MI_K_CL_CONV, MI_K_CL_DGRAD2, MI_K_CL_WGRAD,
  MI_K_CL_WGRAD2, MI_K_ST32_FWD, MI_K_ST32_WGRAD, MI_K_ST_FWD, MI_K_ST_WGRAD) = range(16)
 MI_OPT_ADAM, MI_OPT_SGD, MI_OPT_LARS = 0, 1, 2
+MI_ACC_FIRST, MI_ACC_ADD, MI_ACC_FOLD = 0, 1, 2  # modes of mi_op_grad_accumulate
 MI_LOSS_HOST, MI_LOSS_DEVICE, MI_LOSS_NO_PRED_COPY = 0, 1, 2  # flags of mi_trainer_set_loss
 MI_GUARD = 256  # slack bytes mi_malloc leaves on both sides of a tensor (csrc/mi_host.h)
 
@@ -252,6 +253,11 @@ PROTOTYPES = {
     "mi_trainer_ema_set_location": (_i, [_T, _i, _vp]),
     "mi_trainer_ema_get_running_stats": (_i, [_T, _vp, _vp]),
     "mi_trainer_ema_set_running_stats": (_i, [_T, _vp, _vp]),
+    "mi_op_grad_accumulate": (_i, [_vp, _vp, _sz, _i, _f]),
+    "mi_debug_accum_geometry": (None, [C.POINTER(_sz)]),
+    "mi_trainer_set_accumulation": (_i, [_T, _i, _f]),
+    "mi_trainer_accumulation": (_i, [_T, _ip, _ip]),
+    "mi_debug_accum_arena": (_vp, [_T]),
     "mi_op_momentum_update": (_i, [_i, _vp, _vp, _vp, _sz, _vp, _i, _vp, _f, _f, _f, _f, _vp, _vp]),
     "mi_trainer_nan_location": (_i, [_T]),
     "mi_trainer_stem_dtype": (_i, [_T]),

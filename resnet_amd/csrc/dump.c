@@ -263,6 +263,45 @@ static void restore_ema(Train_ResNet *t, int dump_id, const char *special_dir) {
     free(arena); free(stats);
 }
 
+/* grad_accum.buffer, only inside a window of gradient accumulation (mi_trainer_set_accumulation with k > 1, micro-batches pending): k and
+ * the number of micro-batches summed so far as int32, then the accumulator's arena_floats floats, padding words included */
+static char *accum_path(int dump_id, Train_ResNet *t, const char *special_dir) {
+    char *path = NULL;
+    return asprintf(&path, "%s/%s/%08d/grad_accum.buffer", root_of(t), special_dir, dump_id) < 0 ? NULL : path;
+}
+static void dump_accum(int dump_id, Train_ResNet *t, const char *special_dir) {
+    const MiCtx *c = (const MiCtx *)t->backend_ctx;
+    if (c->acc_k <= 1 || c->acc_pending <= 0) return;
+    const int32_t head[2] = {c->acc_k, c->acc_pending};
+    float *host = (float *)malloc(c->arena_floats * sizeof(float));
+    char *path = accum_path(dump_id, t, special_dir);
+    mi_copy_to_host(host, c->acc_arena, c->arena_floats * sizeof(float));
+    FILE *f = path ? fopen(path, "wb") : NULL;
+    if (!f || fwrite(head, sizeof head[0], 2, f) != 2 || fwrite(host, sizeof(float), c->arena_floats, f) != c->arena_floats)
+        fprintf(stderr, "resnet_mi: cannot write %s\n", path ? path : "grad_accum.buffer");
+    if (f) fclose(f);
+    free(path); free(host);
+}
+/* ... and back: a dump made between two windows has no file and the restored trainer starts a window; a file of another k or another
+ * network is left alone, with a note, and the window starts anew */
+static void restore_accum(Train_ResNet *t, int dump_id, const char *special_dir) {
+    MiCtx *c = (MiCtx *)t->backend_ctx;
+    if (c->acc_k <= 1) return;
+    mi_trainer_accum_restore(t, NULL, 0);
+    char *path = accum_path(dump_id, t, special_dir);
+    FILE *f = path ? fopen(path, "rb") : NULL;
+    free(path);
+    if (!f) return;
+    int32_t head[2] = {0, 0};
+    float *host = (float *)malloc(c->arena_floats * sizeof(float));
+    const int ok = fread(head, sizeof head[0], 2, f) == 2 && head[0] == c->acc_k && head[1] > 0 && head[1] < head[0] &&
+                   fread(host, sizeof(float), c->arena_floats, f) == c->arena_floats && fgetc(f) == EOF;
+    fclose(f);
+    if (!ok || mi_trainer_accum_restore(t, host, head[1]))
+        fprintf(stderr, "resnet_mi: grad_accum.buffer of dump %d does not fit this trainer's accumulation (k = %d): the window starts anew\n", dump_id, c->acc_k);
+    free(host);
+}
+
 /* resnet.cu:2755-2772 */
 void dump_trainer(int dump_id, Train_ResNet *t, const char *special_dir) {
     if (!special_dir) special_dir = "default";
@@ -275,6 +314,7 @@ void dump_trainer(int dump_id, Train_ResNet *t, const char *special_dir) {
     dump_meta_and_checkpoint(dump_id, t, special_dir);
     dump_running_stats(dump_id, t, special_dir);
     dump_ema(dump_id, t, special_dir);
+    dump_accum(dump_id, t, special_dir);
 }
 
 /* resnet.cu:2778-2817 */
@@ -314,4 +354,5 @@ void overwrite_model_params(Train_ResNet *t, int dump_id, const char *special_di
     }
     restore_running_stats(t, dump_id, special_dir);
     restore_ema(t, dump_id, special_dir);
+    restore_accum(t, dump_id, special_dir);
 }

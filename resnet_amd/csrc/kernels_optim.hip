@@ -15,7 +15,9 @@
 // finite.  *nan_flag becomes the highest offending tensor index + 1 (atomicMax on an int).
 //
 // Behind them the two kernels of weight averaging ("Weight averaging"), which know no tensors: ema_update_kernel, e <- lerp(e,
-// p, w) over a whole arena, and exchange_kernel, which swaps two arenas word for word around an eval pass on the averaged model.
+// p, w) over a whole arena, and exchange_kernel, which swaps two arenas word for word around an eval pass on the averaged model.  In the
+// same geometry grad_accum_kernel ("Gradient accumulation"): the gradient arenas of k micro-batches summed in a second arena
+// and folded back, scaled, into the gradient arena in front of one optimizer update.
 #include "mi_common.hpp"
 #include "mi_device.h"
 
@@ -254,10 +256,72 @@ exchange_kernel(uint32_t *__restrict__ a, uint32_t *__restrict__ b, size_t n) {
     }
 }
 
-// the grid of both: one workgroup per turn of V-float items, capped (n >= 1)
+// ---- gradient accumulation ("Gradient accumulation"): the sum of k micro-batch gradient arenas, in the geometry above.  acc and
+// g are arenas of n words; MODE first: acc <- g as words (no arithmetic touches a value), add: acc <- acc (+) g, fold: g <- (acc (+) g) (x)
+// scale with acc only read.  Every operation is rounded on its own and nothing is guarded: what IEEE gives for a value that is not finite
+// is what the optimizer behind the fold sees ----
+// the pragma, not __fadd_rn / __fmul_rn (mix_pair, kernels_input.hip): the fold's sum and product must stay two roundings
+template <int MODE>
+__device__ __forceinline__ uint32_t acc_word(uint32_t a, uint32_t q, float scale) {
+#pragma clang fp contract(off)
+    if (MODE == MID_ACC_FIRST) return q;
+    const float sum = __uint_as_float(a) + __uint_as_float(q);
+    if (MODE == MID_ACC_ADD) return __float_as_uint(sum);
+    const float scaled = sum * scale;
+    return __float_as_uint(scaled);
+}
+template <int MODE> __device__ __forceinline__ uint32_t acc_item(uint32_t a, uint32_t q, float scale) { return acc_word<MODE>(a, q, scale); }
+template <int MODE> __device__ __forceinline__ uint4 acc_item(uint4 a, uint4 q, float scale) {
+    return make_uint4(acc_word<MODE>(a.x, q.x, scale), acc_word<MODE>(a.y, q.y, scale), acc_word<MODE>(a.z, q.z, scale), acc_word<MODE>(a.w, q.w, scale));
+}
+
+template <int V, int MODE>
+__global__ void __launch_bounds__(OPT_THREADS)
+grad_accum_kernel(uint32_t *__restrict__ acc, uint32_t *__restrict__ g, size_t n, float scale) {
+    typedef typename ExWord<V>::T T;
+    constexpr bool READS_ACC = MODE != MID_ACC_FIRST;
+    const T *av = (const T *)acc, *gv = (const T *)g;
+    T *out = (T *)(MODE == MID_ACC_FOLD ? g : acc);
+    const size_t items = n / V, stride = (size_t)gridDim.x * EMA_TURN;
+    for (size_t base = (size_t)blockIdx.x * EMA_TURN; base < items; base += stride) {
+        if (base + EMA_TURN <= items) { // a whole turn: every load in flight before the first store
+            T x[EMA_PER_THREAD], y[EMA_PER_THREAD];
+#pragma unroll
+            for (int k = 0; k < EMA_PER_THREAD; k++) {
+                const size_t i = base + threadIdx.x + k * OPT_THREADS;
+                y[k] = gv[i];
+                x[k] = READS_ACC ? av[i] : y[k];
+            }
+#pragma unroll
+            for (int k = 0; k < EMA_PER_THREAD; k++) out[base + threadIdx.x + k * OPT_THREADS] = acc_item<MODE>(x[k], y[k], scale);
+        } else {
+            for (size_t it = base + threadIdx.x; it < items; it += OPT_THREADS) {
+                const T y = gv[it], x = READS_ACC ? av[it] : y;
+                out[it] = acc_item<MODE>(x, y, scale);
+            }
+        }
+    }
+    if (V > 1 && blockIdx.x == 0) {
+        const size_t i = items * V + threadIdx.x;
+        if (i < n) {
+            const uint32_t y = g[i], x = READS_ACC ? acc[i] : y;
+            (MODE == MID_ACC_FOLD ? g : acc)[i] = acc_word<MODE>(x, y, scale);
+        }
+    }
+}
+
+// the grid of all three: one workgroup per turn of V-float items, capped (n >= 1)
 static unsigned ema_grid(size_t n, int V) {
     const size_t turns = (n / V + EMA_TURN - 1) / EMA_TURN;
     return (unsigned)(turns < 1 ? 1 : turns > EMA_MAX_GRID ? EMA_MAX_GRID : turns);
+}
+
+template <int V>
+static void accum_launch(hipStream_t st, uint32_t *acc, uint32_t *g, size_t n, int mode, float scale) {
+    const dim3 grid(ema_grid(n, V)), block(OPT_THREADS);
+    if (mode == MID_ACC_FIRST) hipLaunchKernelGGL((grad_accum_kernel<V, MID_ACC_FIRST>), grid, block, 0, st, acc, g, n, scale);
+    else if (mode == MID_ACC_ADD) hipLaunchKernelGGL((grad_accum_kernel<V, MID_ACC_ADD>), grid, block, 0, st, acc, g, n, scale);
+    else hipLaunchKernelGGL((grad_accum_kernel<V, MID_ACC_FOLD>), grid, block, 0, st, acc, g, n, scale);
 }
 
 extern "C" {
@@ -293,6 +357,26 @@ int mid_exchange(mid_stream s, float *a, float *b, size_t n) {
 /* the launch geometry, for tests and documents: [0] threads, [1] floats of one workgroup's turn in the vector instantiation, [2] in the
  * element-wise one, [3] the grid's cap */
 void mid_ema_geometry(size_t out[4]) { out[0] = OPT_THREADS; out[1] = (size_t)EMA_TURN * 4; out[2] = EMA_TURN; out[3] = EMA_MAX_GRID; }
+int mid_grad_accumulate(mid_stream s, float *acc, float *g, size_t n, int mode, float scale) {
+    static const char *const names[3][2] = {{"grad_accum_kernel<first,element-wise>", "grad_accum_kernel<first,vector>"},
+                                            {"grad_accum_kernel<add,element-wise>", "grad_accum_kernel<add,vector>"},
+                                            {"grad_accum_kernel<fold,element-wise>", "grad_accum_kernel<fold,vector>"}};
+    const char *who = "mid_grad_accumulate";
+    if (!acc || !g) { mi_record_error(who, "a pointer is NULL"); return -1; }
+    if ((((uintptr_t)acc | (uintptr_t)g) & 3) != 0) { mi_record_error(who, "acc / g must be 4-byte aligned"); return -1; }
+    if (n == 0 || n > EMA_MAX_N) { mi_record_error(who, "n lies in [1, 2^40]"); return -1; }
+    const uintptr_t lo = (uintptr_t)acc < (uintptr_t)g ? (uintptr_t)acc : (uintptr_t)g, hi = (uintptr_t)acc < (uintptr_t)g ? (uintptr_t)g : (uintptr_t)acc;
+    if (hi - lo < n * sizeof(float)) { mi_record_error(who, "the two ranges overlap"); return -1; }
+    if (mode != MID_ACC_FIRST && mode != MID_ACC_ADD && mode != MID_ACC_FOLD) { mi_record_error(who, "unknown mode"); return -1; }
+    if (mode == MID_ACC_FOLD && !(scale > 0.f && scale <= 3.402823466e+38f)) { mi_record_error(who, "scale is finite and > 0"); return -1; }
+    const bool vec = (((uintptr_t)acc | (uintptr_t)g) & 15) == 0;
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, (mode == MID_ACC_FIRST ? 8.0 : 12.0) * (double)n); // algorithmic: g (and acc) in, one out
+    if (vec) accum_launch<4>((hipStream_t)s, (uint32_t *)acc, (uint32_t *)g, n, mode, scale);
+    else accum_launch<1>((hipStream_t)s, (uint32_t *)acc, (uint32_t *)g, n, mode, scale);
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK(names[mode][vec]);
+    return 0;
+}
 int mid_optim_norms(mid_stream s, const float *p, const float *g, const mid_chunk *chunks, int c0, int c1, double *part) {
     if (c1 <= c0) return 0;
     hipLaunchKernelGGL(optim_norm_kernel, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, chunks, c0, (double2 *)part);

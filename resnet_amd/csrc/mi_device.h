@@ -318,6 +318,12 @@ int mid_optim_update(mid_stream s, int kind, float *p, float *g, float *b, const
 int mid_ema_update(mid_stream s, float *ema, const float *p, size_t n, float w);
 int mid_exchange(mid_stream s, float *a, float *b, size_t n);
 void mid_ema_geometry(size_t out[4]); /* [0] threads, floats of one workgroup's turn [1] vector [2] element-wise, [3] the grid's cap */
+/* gradient accumulation (kernels_optim.hip), over two arenas of n floats in the geometry of the two above.  FIRST: acc = g as 32-bit words
+ * (NaN payloads and -0 as they are); ADD: acc = acc + g; FOLD: g = (acc + g) * scale, sum and product rounded on their own, acc only read.
+ * Nothing is guarded: a value that is not finite propagates by IEEE rules.  -1, mid_last_error set, nothing launched: a NULL pointer, a
+ * pointer that is not 4-byte aligned, n == 0 or n > 2^40, overlapping ranges, an unknown mode, in FOLD a scale that is NaN, infinite or <= 0 */
+enum { MID_ACC_FIRST = 0, MID_ACC_ADD = 1, MID_ACC_FOLD = 2 };
+int mid_grad_accumulate(mid_stream s, float *acc, float *g, size_t n, int mode, float scale);
 int mid_nhwc_to_nchw(mid_stream s, const float *in, float *out, int N, int H, int W, int C);
 int mid_nchw_to_nhwc(mid_stream s, const float *in, float *out, int N, int C, int H, int W);
 /* uint8 shards (kernels_input.hip): src = n whole images [dim_in][dim_in][3] bytes (B,G,R interleaved), 16-byte aligned; plan = int [n][3]

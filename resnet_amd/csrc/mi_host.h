@@ -251,6 +251,12 @@ typedef struct MiCtx {
     double ema_decay;
     int ema_every, ema_warmup, ema_eval, ema_swapped;
     int64_t ema_updates;
+    /* mi_trainer_set_accumulation (k 1, scale 1, arena NULL before the first k > 1; not tracked in allocs[] either): the sum of the
+     * window's micro-batch gradient arenas [arena_floats], the setting, the micro-batches summed so far in this window; acc_in_step:
+     * between forward_pass and update_parameters (the setter is refused); acc_folded: backwards_pass folded every data-parallel
+     * bucket of this window's last micro-batch, update_parameters does not fold again */
+    float *acc_arena, acc_scale;
+    int acc_k, acc_pending, acc_in_step, acc_folded;
     /* mi_trainer_eval_u8: scratch of its own -- the decoded batch, and bytes / labels / plan on the device and pinned; the event
      * behind the last copies out of the pinned set */
     int ev8_dim_in;
@@ -311,6 +317,9 @@ void mi_trainer_mix_batch(Train_ResNet *t, Batch *b, int rank, int world);
 /* trainer.c, for dump.c's restore: the whole averaged model from host arrays laid out as the two device arenas are (params: arena_floats
  * floats, padding words included; stats: 2 * rs_channels) and the counter; -1 before mi_trainer_set_ema */
 int mi_trainer_ema_restore(Train_ResNet *t, const float *params_arena_host, const float *stats_host, int64_t updates);
+/* trainer.c, for dump.c's restore: the accumulator from a host array laid out as the arena is (read only where pending > 0) and the
+ * window's count; -1 without an accumulator or with a count outside [0, k) */
+int mi_trainer_accum_restore(Train_ResNet *t, const float *arena_host, int pending);
 void mi_trainer_poll_errors(Train_ResNet *t); /* load_new_batch: wait for and read the NaN / Inf flag of the last update */
 void mi_record_host_error(const char *what, const char *detail); /* sets mi_last_error (runtime.hip) */
 int mi_loss_args_ok(const char *who, float smoothing, int topk, int L); /* ops.c: the rules of mi_op_loss_head / mi_trainer_set_loss */

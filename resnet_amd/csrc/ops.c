@@ -232,6 +232,9 @@ float mi_ema_weight(double decay, int warmup, int64_t k) {
 int mi_op_ema_update(float *ema, const float *p, size_t n, float w) { return finish(mid_ema_update(mi_global()->compute, ema, p, n, w)); }
 int mi_op_exchange(float *a, float *b, size_t n) { return finish(mid_exchange(mi_global()->compute, a, b, n)); }
 void mi_debug_ema_geometry(size_t out[4]) { mid_ema_geometry(out); }
+/* gradient accumulation (resnet_mi.h): the kernel on its own; it runs in the geometry of the two above */
+int mi_op_grad_accumulate(float *acc, float *g, size_t n, int mode, float scale) { return finish(mid_grad_accumulate(mi_global()->compute, acc, g, n, mode, scale)); }
+void mi_debug_accum_geometry(size_t out[4]) { mid_ema_geometry(out); }
 int mi_op_nhwc_to_nchw(const float *in,float *out, int N, int H, int W, int C) { return finish(mid_nhwc_to_nchw(mi_global()->compute, in, out, N, H, W, C)); }
 int mi_op_decode_u8(const uint8_t *src_dev, const int *plan_dev, float *out_nchw, int n, int dim_in, int dim_out) {
     return finish(mid_decode_u8(mi_global()->compute, src_dev, plan_dev, out_nchw, n, dim_in, dim_out));

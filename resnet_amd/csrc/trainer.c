@@ -558,6 +558,7 @@ Train_ResNet *init_trainer(ResNet *model, Batch *cur_batch, int batch_size, floa
     }
     c->ev_nan = mid_event_create();
     c->nan_location = -1;
+    c->acc_k = 1; c->acc_scale = 1.f; /* no accumulation: every update_parameters applies its own gradient */
     c->loss_topk = 1; /* with smoothing 0 and MI_LOSS_HOST: the reference's head */
     c->loss_row = falloc(c, (size_t)batch_size);
     c->loss_rank = (int *)mi_ctx_alloc(c, (size_t)batch_size * sizeof(int));
@@ -657,7 +658,8 @@ size_t mi_trainer_activation_bytes(const Train_ResNet *t) { return ((MiCtx *)t->
 size_t mi_trainer_device_bytes(const Train_ResNet *t) {
     const MiCtx *c = (MiCtx *)t->backend_ctx;
     const size_t ema = c->ema_arena ? (c->arena_floats + 2 * (size_t)c->rs_channels) * sizeof(float) : 0; /* mi_trainer_set_ema's two arenas */
-    return c->dev_bytes + c->arena_floats * sizeof(float) + ema; /* + the parameter arena (owned by the model) */
+    const size_t acc = c->acc_arena ? c->arena_floats * sizeof(float) : 0; /* mi_trainer_set_accumulation's arena */
+    return c->dev_bytes + c->arena_floats * sizeof(float) + ema + acc; /* + the parameter arena (owned by the model) */
 }
 void mi_trainer_set_dump_every(Train_ResNet *t, int every) { ctx_of(t)->dump_every = every; }
 void mi_trainer_set_overlap(Train_ResNet *t, int mode) {
@@ -812,6 +814,7 @@ void forward_pass(Train_ResNet *t) {
     mid_event_record(c->ev_t[0], G.compute);
     bind_sync_bn(c);
     c->acts_from_eval = 0;
+    c->acc_in_step = 1; /* until update_parameters: mi_trainer_set_accumulation is refused in between */
     forward_trunk(t, t->cur_batch->images, 0);
     if (c->mix_on && c->mix_last.mode != 0) /* the batch was mixed by load_new_batch: both labels of every row, weighted lam / 1 - lam */
         ck(mid_loss_head_mix(G.compute, a->linear_output, t->cur_batch->correct_classes, c->mix_labels_b, c->mix_last.lam, t->forward_buffer->pred,
@@ -1378,6 +1381,42 @@ int mi_dp_plan_buckets(const Dims *d, size_t bucket_bytes, size_t *from, size_t 
     return n;
 }
 
+/* Gradient accumulation (resnet_mi.h): k micro-batches per optimizer update.  A backward pass overwrites the gradient arena, so the
+ * window's sum lives in an arena of its own: the first k - 1 update_parameters of a window only add the gradient arena into it
+ * (acc_pending counts them), the k-th folds it back -- g = (acc + g) * scale -- in front of the unchanged optimizer path. */
+static int acc_collecting(const MiCtx *c) { return c->acc_k > 1 && c->acc_pending + 1 < c->acc_k; }
+int mi_trainer_set_accumulation(Train_ResNet *t, int k, float scale) {
+    MiCtx *c = ctx_of(t);
+    const char *who = "mi_trainer_set_accumulation";
+    if (k < 1) { mi_record_host_error(who, "k is >= 1 (1: no accumulation)"); return -1; }
+    if (!(scale > 0.f) || isinf(scale)) { mi_record_host_error(who, "scale is finite and > 0"); return -1; }
+    if (c->acc_pending > 0) { mi_record_host_error(who, "a window is open: micro-batches are pending"); return -1; }
+    if (c->acc_in_step) { mi_record_host_error(who, "not between forward_pass and update_parameters"); return -1; }
+    if (k > 1 && !c->acc_arena) { /* the first time: the arena, through the allocator every tensor comes from */
+        c->acc_arena = (float *)mid_malloc(c->arena_floats * sizeof(float));
+        if (!c->acc_arena) { mi_record_host_error(who, "device allocation failed"); return -1; }
+    }
+    c->acc_k = k; c->acc_scale = scale;
+    return 0;
+}
+int mi_trainer_accumulation(const Train_ResNet *t, int *k, int *pending) {
+    const MiCtx *c = (const MiCtx *)t->backend_ctx;
+    if (k) *k = c->acc_k;
+    if (pending) *pending = c->acc_pending;
+    return 0;
+}
+float *mi_debug_accum_arena(const Train_ResNet *t) { return ((const MiCtx *)t->backend_ctx)->acc_arena; }
+int mi_trainer_accum_restore(Train_ResNet *t, const float *arena_host, int pending) {
+    MiCtx *c = ctx_of(t);
+    if (!c->acc_arena || pending < 0 || pending >= c->acc_k) return -1;
+    if (pending) {
+        mid_memcpy_h2d(c->acc_arena, arena_host, c->arena_floats * sizeof(float), G.compute);
+        mid_stream_sync(G.compute);
+    }
+    c->acc_pending = pending;
+    return mid_last_error()[0] ? -1 : 0;
+}
+
 /* data parallel: hand the finished tail [from, cursor) of the gradient arena to RCCL on the comm stream as soon
  * as it is at least one bucket (or `force`).  Gradients become ready FC-first, i.e. from the arena's end
  * (the order update_parameters walks, resnet.cu:2952). */
@@ -1386,6 +1425,7 @@ void mi_dp_reduce_ready(Train_ResNet *t, size_t from, int force) {
     const int pending = c->wgrad_pending;
     if (force) join_wgrad(c); /* end of backward: every weight gradient is on the compute stream's timeline */
     if (!c->comm) return;
+    if (acc_collecting(c)) return; /* this micro-batch's gradients are summed on this rank: no bucket, no collective */
     if (from >= c->dp_cursor) return;
     const size_t n = c->dp_cursor - from;
     if (!force && n * sizeof(float) < c->bucket_bytes) return;
@@ -1395,6 +1435,10 @@ void mi_dp_reduce_ready(Train_ResNet *t, size_t from, int force) {
     /* the bucket also holds weight gradients from the aux stream: the comm stream waits for the latest of them itself,
      * the compute stream does not stall */
     if (pending) mid_stream_wait_event(G.comm, c->ev_wgrad_done);
+    if (c->acc_k > 1) { /* the window's last micro-batch: the bucket's sum, scaled on this rank, is what is reduced */
+        ck(mid_grad_accumulate(G.comm, c->acc_arena + from, c->g_arena + from, c->dp_cursor - from, MID_ACC_FOLD, c->acc_scale), "gradient fold (bucket)");
+        c->acc_folded = 1;
+    }
     ck(mid_rccl_allreduce_sum(c->comm, c->g_arena + from, c->dp_cursor - from, G.comm), "RCCL all-reduce");
     const int b = c->n_buckets++; /* < MI_MAX_BUCKETS by the rule above */
     c->bk_from[b] = from; c->bk_to[b] = c->dp_cursor;
@@ -1524,6 +1568,23 @@ void update_parameters(Train_ResNet *t) {
         dump_trainer(t->cur_dump_id, t, t->dump_dir);
     }
     mid_event_record(c->ev_t[4], G.compute);
+    c->acc_in_step = 0;
+    if (c->acc_k > 1) {
+        if (acc_collecting(c)) { /* behind backward, whose end joined the weight-gradient stream: the sum so far, and nothing else */
+            ck(mid_grad_accumulate(G.compute, c->acc_arena, c->g_arena, c->arena_floats, c->acc_pending ? MID_ACC_ADD : MID_ACC_FIRST, 1.f),
+               "gradient accumulation");
+            c->acc_pending++;
+            if (c->input_reset) { /* :2981-2982 */
+                mid_memset(t->cur_batch->images, 0, (size_t)t->batch_size * t->cur_batch->image_size * sizeof(float), G.compute);
+                mid_memset(t->cur_batch->correct_classes, 0, (size_t)t->batch_size * sizeof(int), G.compute);
+            }
+            mid_event_record(c->ev_t[5], G.compute);
+            return;
+        }
+        /* the window's last micro-batch (data parallel: backwards_pass folded every bucket in front of its all-reduce) */
+        if (!c->acc_folded) ck(mid_grad_accumulate(G.compute, c->acc_arena, c->g_arena, c->arena_floats, MID_ACC_FOLD, c->acc_scale), "gradient fold");
+        c->acc_folded = 0; c->acc_pending = 0;
+    }
     if (c->dp_pending && c->n_buckets > 0) {
         for (int b = 0; b < c->n_buckets; b++) {
             mid_stream_wait_event(G.compute, c->bk_ev[b]);
@@ -1655,6 +1716,7 @@ void destroy_trainer(Train_ResNet *t) {
     mid_free(c->mix_labels_b);
     mid_free(c->rs_arena); mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics);
     mid_free(c->ema_arena); mid_free(c->ema_rs);
+    mid_free(c->acc_arena);
     ev8_free(c);
     if (c->ev8_copied) mid_event_destroy(c->ev8_copied);
     free(c->loc_off);

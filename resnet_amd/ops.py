@@ -302,6 +302,21 @@ class Ops:
         self._chk(self.L.mi_op_exchange(da.ptr + 4 * at, db.ptr + 4 * at, n), "exchange")
         return self._unguard(da, at, n, guard), self._unguard(db, at, n, guard)
 
+    def accum_geometry(self):
+        """(threads, floats of one workgroup's turn in the vector / the element-wise instantiation, grid cap) of grad_accumulate's kernel"""
+        out = (C.c_size_t * 4)()
+        self.L.mi_debug_accum_geometry(out)
+        return tuple(int(v) for v in out)
+
+    def grad_accumulate(self, acc, g, mode, scale=1.0, offset_floats=0, guard=0, fill=0.0):
+        """mi_op_grad_accumulate on float32 (or uint32) arrays of one length: mode MI_ACC_FIRST acc = g, MI_ACC_ADD acc = acc + g, MI_ACC_FOLD
+        g = (acc + g) * scale.  Operands placed and returned as ema_update's: (acc, g)"""
+        n = int(np.size(acc))
+        da, at = self._guarded(acc, offset_floats, guard, fill)
+        dg, _ = self._guarded(g, offset_floats, guard, fill)
+        self._chk(self.L.mi_op_grad_accumulate(da.ptr + 4 * at, dg.ptr + 4 * at, n, int(mode), float(scale)), "grad_accumulate")
+        return self._unguard(da, at, n, guard), self._unguard(dg, at, n, guard)
+
     @staticmethod
     def _unguard(d, at, n, guard):
         out = d.get()

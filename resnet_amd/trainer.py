@@ -232,6 +232,21 @@ class Trainer:
         if self.L.mi_trainer_eval_use_ema(self.t, int(bool(on))) != 0:
             self._refused("mi_trainer_eval_use_ema")
 
+    # ---- gradient accumulation (include/resnet_mi.h, "gradient accumulation") ----
+    def set_accumulation(self, k, scale=1.0):
+        """k micro-batches per optimizer update: of every k update() calls the first k - 1 only sum the gradient arena on the device, the
+        k-th applies (sum * scale) through the optimizer once (scale 1 / k: the mean over micro-batches).  step() stays one micro-batch.
+        Between windows only; k = 1: off"""
+        if self.L.mi_trainer_set_accumulation(self.t, int(k), float(scale)) != 0:
+            self._refused("mi_trainer_set_accumulation")
+
+    def accumulation(self):
+        """(k, pending): the setting and the micro-batches summed so far in this window"""
+        k, pending = C.c_int(0), C.c_int(0)
+        if self.L.mi_trainer_accumulation(self.t, C.byref(k), C.byref(pending)) != 0:
+            self._refused("mi_trainer_accumulation")
+        return k.value, pending.value
+
     def set_lr(self, lr):
         """learning_rate for the next update_parameters and on (read at every update)"""
         self.t.contents.learning_rate = lr

@@ -1,0 +1,60 @@
+"""Gradient accumulation in numpy float32 (include/resnet_mi.h, "gradient accumulation"): the model of grad_accum_kernel and of a window
+of k micro-batches.  Every operation is one IEEE float32 operation rounded on its own -- a sum, then a product, never a fused
+multiply-add; values that are not finite propagate as IEEE has them.  tests/test_accum_model.py pins it against torch on the CPU.
+"""
+import numpy as np
+
+FIRST, ADD, FOLD = 0, 1, 2
+
+
+def _f32(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.float32) if a.dtype == np.uint32 else a.astype(np.float32, copy=False)
+
+
+def first(g):
+    """acc = g: the words of g (NaN payloads and -0 as they are)"""
+    return _f32(g).copy()
+
+
+def add(acc, g):
+    """acc = acc (+) g"""
+    with np.errstate(all="ignore"):
+        return (_f32(acc) + _f32(g)).astype(np.float32)
+
+
+def fold(acc, g, scale):
+    """g = (acc (+) g) (x) scale; float32 times a float32 scalar stays float32 in numpy, one rounding each"""
+    with np.errstate(all="ignore"):
+        s = (_f32(acc) + _f32(g)).astype(np.float32)
+        return (s * np.float32(scale)).astype(np.float32)
+
+
+def window(gs, scale):
+    """what the optimizer is handed after a window over the micro-batch gradients gs[0 .. k): first, add ..., and the last one folded in.
+    (k = 1 is the product alone; the trainer runs no window at k = 1 and applies no scale)"""
+    gs = [_f32(g) for g in gs]
+    if len(gs) == 1:
+        with np.errstate(all="ignore"):
+            return (gs[0] * np.float32(scale)).astype(np.float32)
+    acc = first(gs[0])
+    for g in gs[1:-1]:
+        acc = add(acc, g)
+    return fold(acc, gs[-1], scale)
+
+
+def accumulator(gs):
+    """the accumulator after the collecting calls over gs (at least one)"""
+    acc = first(gs[0])
+    for g in gs[1:]:
+        acc = add(acc, g)
+    return acc
+
+
+def same(got, want):
+    """bit for bit, except that a NaN matches any NaN: IEEE 754 leaves the sign and payload of a NaN that an operation produces or passes
+    on to the implementation (x86 and the GPU differ), and only `first`, which does no arithmetic, promises them"""
+    got, want = _f32(got), _f32(want)
+    if got.shape != want.shape:
+        return False
+    return bool(np.all((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))))
