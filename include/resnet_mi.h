@@ -786,6 +786,9 @@ int mi_mix_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, dou
  * Returns 0, or -1 with mi_last_error set and nothing launched: n outside [1, 65535], image_size != 3 dim^2, dim outside [1, 16384], a NULL
  * pointer, images not 4-byte aligned, an unknown mode, mode 1 with lam outside [0, 1]. */
 int mi_op_mix_batch(float *images_nchw, int n, int image_size /* 3 dim^2 */, int dim, const MiMixPlan *plan_host);
+/* host only, launches nothing: [0] threads of a workgroup, [1] the cap on grid.x, [2] waves of a workgroup.  One sweep of the capped grid
+ * covers [0] [1] work items of a pair in mode 1 (16-byte groups, or elements) and [1] [2] row segments of a box in mode 2 */
+void mi_debug_mix_geometry(size_t out[3]);
 /* the two-label head: mi_op_loss_head with labels a (the image's own) and b (its partner's) per row and one weight lam in [0, 1].  With
  * u = eps / (float)L, wa = (1.f - eps) (x) lam, wb = (1.f - eps) (x) (1.f - lam), each product rounded once:
  *   pred      the bits of mi_op_softmax

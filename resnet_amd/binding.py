@@ -278,6 +278,7 @@ PROTOTYPES = {
     "mi_op_resample_u8": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "mi_mix_plan": (_i, [_u64, _i, C.c_int64, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _i, C.POINTER(MiMixPlan)]),
     "mi_op_mix_batch": (_i, [_vp, _i, _i, _i, C.POINTER(MiMixPlan)]),
+    "mi_debug_mix_geometry": (None, [C.POINTER(_sz)]),
     "mi_op_loss_head_mix": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
     "mi_trainer_set_mix": (_i, [_T, C.c_double, C.c_double, C.c_double, C.c_double, _u64]),
     "mi_trainer_last_mix": (_i, [_T, C.POINTER(MiMixPlan)]),

@@ -346,3 +346,6 @@ int mid_mix_labels(mid_stream s, const int *labels, int *labels_b, int n) {
     MI_LAUNCH_CHECK("mix_labels_kernel");
     return 0;
 }
+/* the launch geometry of mixup_kernel and cutmix_kernel, for tests and documents: [0] threads, [1] the cap on grid.x, [2] waves of a
+ * workgroup.  One sweep of the capped grid: [0] [1] work items of mixup_kernel, [1] [2] row segments of cutmix_kernel */
+void mid_mix_geometry(size_t out[3]) { out[0] = MIX_THREADS; out[1] = MIX_MAX_BLOCKS_X; out[2] = MIX_THREADS / 64; }

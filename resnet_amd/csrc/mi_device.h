@@ -339,6 +339,7 @@ int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *o
 int mid_mix_batch(mid_stream s, float *images, int n, size_t image_size, int dim, int mode, float lam, int y0, int x0, int y1, int x1);
 /* labels_b[i] = labels[n - 1 - i] */
 int mid_mix_labels(mid_stream s, const int *labels, int *labels_b, int n);
+void mid_mix_geometry(size_t out[3]); /* [0] threads, [1] the cap on grid.x, [2] waves of a workgroup (a wave takes one row segment of a CutMix box) */
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */
 int mid_fill_uniform(mid_stream s, float *out, size_t n, uint64_t seed, uint64_t offset, float lo, float hi);
 /* test aids (kernels_misc.hip; callers serialise): `word` into every LDS word of every CU between two device synchronises, and a read-only

@@ -248,6 +248,7 @@ int mi_op_mix_batch(float *images_nchw, int n, int image_size, int dim, const Mi
     return finish(mid_mix_batch(mi_global()->compute, images_nchw, n, (size_t)image_size, dim, plan_host->mode, plan_host->lam, plan_host->y0,
                                 plan_host->x0, plan_host->y1, plan_host->x1));
 }
+void mi_debug_mix_geometry(size_t out[3]) { mid_mix_geometry(out); }
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_lds_fill(uint32_t word) { return finish(mid_debug_lds_fill(word)); }
 int mi_debug_poison_lds(void) { return mi_debug_lds_fill(0xFFFFFFFFu); }

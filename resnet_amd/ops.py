@@ -235,6 +235,13 @@ class Ops:
         self._chk(self.L.mi_op_mix_batch(d.ptr + 4 * offset_floats, n, 3 * D * D, D, C.byref(plan)), "mix_batch")
         return d.get()[offset_floats:].reshape(images.shape)
 
+    def mix_geometry(self):
+        """(threads, cap on grid.x, waves of a workgroup) of the two mix kernels: one sweep is threads * cap work items (mixup), cap * waves
+        row segments (CutMix)"""
+        out = (C.c_size_t * 3)()
+        self.L.mi_debug_mix_geometry(out)
+        return tuple(int(v) for v in out)
+
     def loss_head_mix(self, x, labels_a, labels_b, lam, smoothing=0.0, topk=5, total=None):
         """mi_op_loss_head_mix on logits x (N, L) with two labels per row and the weight lam: returns what loss_head returns"""
         N, L = x.shape

@@ -30,6 +30,28 @@ def fold(acc, g, scale):
         return (s * np.float32(scale)).astype(np.float32)
 
 
+def fold_once(acc, g, scale):
+    """what the fold must NOT compute: (acc + g) scale evaluated in double and rounded to float32 at the end (what a fused
+    multiply-add, or arithmetic kept in a wider type, would give)"""
+    with np.errstate(all="ignore"):
+        return ((_f32(acc).astype(np.float64) + _f32(g).astype(np.float64)) * np.float64(np.float32(scale))).astype(np.float32)
+
+
+def separating_pair(n, scale, seed):
+    """(acc, g) of n float32, acc ~ N(0, 1) and g ~ 1e-4 N(0, 1), in which EVERY element tells fold from fold_once at this scale, and
+    acc != g everywhere: candidates are drawn and the ones the model separates are kept, in the order drawn"""
+    rng = np.random.RandomState(seed)
+    accs, gs, have = [], [], 0
+    while have < n:
+        m = 16 * (n - have) + 4096
+        acc, g = rng.randn(m).astype(np.float32), (rng.randn(m) * 1e-4).astype(np.float32)
+        keep = (fold(acc, g, scale).view(np.uint32) != fold_once(acc, g, scale).view(np.uint32)) & (acc != g)
+        accs.append(acc[keep])
+        gs.append(g[keep])
+        have += int(keep.sum())
+    return np.concatenate(accs)[:n].copy(), np.concatenate(gs)[:n].copy()
+
+
 def window(gs, scale):
     """what the optimizer is handed after a window over the micro-batch gradients gs[0 .. k): first, add ..., and the last one folded in.
     (k = 1 is the product alone; the trainer runs no window at k = 1 and applies no scale)"""

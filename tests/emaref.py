@@ -3,6 +3,9 @@
 weight(decay, warmup, k)      the weight of EMA update k in Python doubles, rounded to float32 once
 fma32(a, b, c)                an exact float32 fused multiply-add
 lerp32(e, p, w)               torch.lerp's float32 bits with the library's rule for results that are not finite
+unfused32, other_branch32     the two slightly wrong kernels; alternative32(e, p, w) is the one the weight w is there to catch
+separating_pair(n, w, seed)   inputs in which every element tells lerp32 from alternative32
+tail_and_partial_turn(...)    the positions the streaming kernels handle outside a whole unrolled turn
 ema_run(params_per_step, ...) a whole run: the counter, `every`, the warm-up
 
 fma32 is exact.  The product of two float32 values is exact in float64 (48 bits).  Its sum with a float32 value is not, and rounding it
@@ -41,6 +44,58 @@ def lerp32(e, p, w):
         d = (p - e).astype(np.float32)
         r = fma32(w, d, e) if w < np.float32(0.5) else fma32(-(np.float32(1.0) - w), d, p)
     return np.where(np.isfinite(r), r, e).astype(np.float32)
+
+
+def unfused32(e, p, w):
+    """what the kernel must NOT compute: the same branch with the product and the sum rounded one after the other"""
+    e, p = np.asarray(e, np.float32), np.asarray(p, np.float32)
+    w = np.float32(w)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = (p - e).astype(np.float32)
+        r = (e + (w * d).astype(np.float32)) if w < np.float32(0.5) else (p + (-(np.float32(1.0) - w) * d).astype(np.float32))
+        r = r.astype(np.float32)
+    return np.where(np.isfinite(r), r, e).astype(np.float32)
+
+
+def other_branch32(e, p, w):
+    """the fused branch that w does NOT select (w < 0.5 read as w >= 0.5 and the other way round)"""
+    e, p = np.asarray(e, np.float32), np.asarray(p, np.float32)
+    w = np.float32(w)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = (p - e).astype(np.float32)
+        r = fma32(-(np.float32(1.0) - w), d, p) if w < np.float32(0.5) else fma32(w, d, e)
+    return np.where(np.isfinite(r), r, e).astype(np.float32)
+
+
+def alternative32(e, p, w):
+    """the wrong kernel a weight is there to catch: the other branch at w = 0.5 (the comparison written <=), the unfused update elsewhere"""
+    return other_branch32(e, p, w) if np.float32(w) == np.float32(0.5) else unfused32(e, p, w)
+
+
+def separating_pair(n, w, seed):
+    """(e, p) of n float32 in the distribution of the operator tests (e ~ 0.1 N(0, 1), p - e ~ 0.01 N(0, 1)) in which EVERY element tells
+    lerp32 from alternative32 at the weight w: candidates are drawn and the ones the model separates are kept, in the order drawn"""
+    rng = np.random.RandomState(seed)
+    es, ps, have = [], [], 0
+    while have < n:
+        m = 64 * (n - have) + 4096
+        e = (0.1 * rng.randn(m)).astype(np.float32)
+        p = (e + 0.01 * rng.randn(m)).astype(np.float32)
+        keep = lerp32(e, p, w).view(np.uint32) != alternative32(e, p, w).view(np.uint32)
+        es.append(e[keep])
+        ps.append(p[keep])
+        have += int(keep.sum())
+    return np.concatenate(es)[:n].copy(), np.concatenate(ps)[:n].copy()
+
+
+def tail_and_partial_turn(n, turn_floats, vector):
+    """the positions of an arena of n floats that the streaming kernels (ema_update, exchange, grad_accum) do not handle in a whole unrolled
+    turn: the floats of the last, partial turn (turn_floats per workgroup turn in this instantiation) and, in the vector instantiation, the
+    n % 4 floats behind the last 16-byte group"""
+    at = np.zeros(n, bool)
+    body = n - n % 4 if vector else n
+    at[body // turn_floats * turn_floats:] = True
+    return at
 
 
 def ema_run(params_per_step, start, decay, every=1, warmup=False, counter=0, updates_before=0):

@@ -88,6 +88,51 @@ def make_inputs(N, L):
     return np.ascontiguousarray(x, np.float32), lab
 
 
+RANKED_SHAPE = (130, 10)  # 130 rows: the 64 lanes of loss_reduce_kernel take three passes, the last with rows 128 and 129 only
+
+
+def ranked_inputs():
+    """(x, labels, ranks) for the batch totals: row r of RANKED_SHAPE holds a permutation (seed 53) of the logits 0 .. L - 1 and its
+    label is the class with the (r mod L)-th largest logit, so row_rank[r] == r mod L by construction -- every value of the rank
+    occurs, in the rows below 64 and in the rows past them.  Distinct integers: no ties, nothing underflows (the smallest p is e^-9 / s)"""
+    N, L = RANKED_SHAPE
+    rng = np.random.RandomState(53)
+    x = np.empty((N, L), np.float32)
+    lab = np.empty(N, np.int32)
+    for r in range(N):
+        x[r] = rng.permutation(L)
+        lab[r] = int(np.argsort(-x[r])[r % L])
+    return x, lab, np.arange(N) % L
+
+
+RANKED_COUNTS = {1: (117, 117), 5: (117, 65), 10: (117, 0)}  # topk -> (wrong_top1, wrong_topk) of ranked_inputs; rows past 64: 60 and 35
+
+
+def check_batch_totals(head, new_total, topk):
+    """the batch totals (loss_reduce_kernel) on ranked_inputs, for the one-label and the two-label operator alike: 130 rows -- three
+    passes of the 64 lanes, the last with two rows -- whose ranks are arange(130) % 10 by construction, so that rows with rank == topk
+    exist and the rows past 64 hold 60 and 35 of the counts.  head(x, labels, total) launches the operator with this topk and returns what
+    Ops.loss_head returns; new_total() is a zeroed record on the device.  Asserts row_rank, the counts, loss_sum against the float64 sum
+    of the device's own row_loss (1e-12 relative: a lane that adds its rows in float is 5e-9 off), and that a second launch doubles total"""
+    x, lab, ranks = ranked_inputs()
+    N = len(lab)
+    total = new_total()
+    pred, dl, rl, rr, last, tot = head(x, lab, total)
+    assert np.array_equal(rr, ranks), "row_rank is not the constructed vector: rows %s" % np.flatnonzero(rr != ranks)[:8]
+    w1, wk = RANKED_COUNTS[topk]
+    assert (w1, wk) == (int(np.sum(ranks >= 1)), int(np.sum(ranks >= topk)))
+    assert (last["rows"], last["wrong_top1"], last["wrong_topk"], last["batches"]) == (N, w1, wk, 1), last
+    assert np.all(np.isfinite(rl))
+    want = float(np.sum(rl.astype(np.float64)))
+    assert abs(last["loss_sum"] - want) <= 1e-12 * abs(want), (last["loss_sum"], want)
+    assert tot == last
+    again = head(x, lab, total)
+    assert again[4] == last and np.float64(again[4]["loss_sum"]).tobytes() == np.float64(last["loss_sum"]).tobytes()
+    assert again[5]["loss_sum"] == 2 * last["loss_sum"] and again[5]["batches"] == 2
+    assert all(again[5][f] == 2 * last[f] for f in ("rows", "wrong_top1", "wrong_topk")), again[5]
+    return pred, dl, rl
+
+
 def loss_bound(ref):
     """|device row_loss - ref| allowed per row: 2^-19 (2 + ref) (derivation: DESIGN.md, "Loss head")"""
     return 2.0 ** -19 * (2.0 + np.asarray(ref, np.float64))

@@ -185,3 +185,30 @@ def loss_head_mix_f32(x, a, b, lam, eps=0.0):
 
 
 LAMS = [0.0, 0.3, 1.0]  # the operator tests' weights; 0.3 is no float32: np.float32(0.3) is what both sides see
+# At lam = 0.3 with eps 0 or 0.1 every way of forming wb gives the same float32 ((1 - eps) (1 - lam), (1 - eps) - wa, 1 - (eps + wa), ...):
+# those cases cannot tell how the kernel rounds it.  At lam = 0.7, eps = 0.1 the product (1 - eps) (x) (1 - lam) and the difference
+# (1 - eps) (-) wa are neighbouring floats (tests/test_mix_model.py)
+WB_LAM, WB_EPS = 0.7, 0.1
+
+
+def wb_as_difference(lam, eps):
+    """what the kernel must NOT compute: wb = (1 - eps) (-) wa"""
+    f = np.float32
+    return (f(1) - f(eps)) - (f(1) - f(eps)) * f(lam)
+
+
+def targets_reassociated_f32(L, a, b, lam, eps):
+    """targets_f32 with the sum associated the other way, t_j = wa_j + (wb_j + u): differs from targets_f32 only in rows with a == b"""
+    f = np.float32
+    lam, eps = f(lam), f(eps)
+    u = eps / f(L)
+    wa, wb = (f(1) - eps) * lam, (f(1) - eps) * (f(1) - lam)
+    t = np.empty((len(a), L), f)
+    for r in range(len(a)):
+        w, w2 = np.zeros(L, f), np.zeros(L, f)
+        if 0 <= a[r] < L:
+            w[a[r]] = wa
+        if wb > 0 and 0 <= b[r] < L:
+            w2[b[r]] = wb
+        t[r] = w + (w2 + u)
+    return t

@@ -18,6 +18,10 @@ killers  pytest node ids, one to three, the smallest cases that reach the branch
 RAG = "tests/test_gpu_ragged.py::"
 OPS = "tests/test_gpu_ops.py::"
 BF = "tests/test_gpu_bf16.py::"
+MIX = "tests/test_gpu_mix.py::"
+EMA = "tests/test_gpu_ema.py::"
+ACC = "tests/test_gpu_accum.py::"
+LOSS = "tests/test_gpu_loss_head.py::"
 
 MUTANTS = []
 
@@ -300,7 +304,126 @@ _m("optim_scalar_tail_no_momentum", "kernels_optim.hip",
    "tensors whose length is no multiple of 4",
    ["tests/test_gpu_optim.py::test_operator_scalar_tail[sgd]", "tests/test_gpu_optim.py::test_operator_scalar_tail[lars]"])
 
+_m("ema_unfused", "kernels_optim.hip",
+   "    const float r = w < 0.5f ? fmaf(w, d, e) : fmaf(-omw, d, pv);",
+   "    float r;\n    {\n#pragma clang fp contract(off)\n        const float t = w < 0.5f ? w * d : -omw * d;\n        r = w < 0.5f ? t + e : t + pv;\n    }",
+   "ema_elem rounds the product and the sum one after the other instead of one fma: 47 to 65 of about 1024 elements at w = 0.1",
+   "every element of ema_update_kernel",
+   [EMA + "test_ema_kernel_is_the_model[vector-w=0.1]", EMA + "test_ema_kernel_is_the_model[element-wise-w=0.8]"])
+_m("ema_branch_le_half", "kernels_optim.hip",
+   "    const float r = w < 0.5f ? fmaf(w, d, e)",
+   "    const float r = w <= 0.5f ? fmaf(w, d, e)",
+   "ema_elem takes the branch around e at w = 0.5 (torch.lerp takes the one around p there): about 40 of 1024 elements",
+   "w == 0.5",
+   # CPU pre-check (emaref.other_branch32 on _pair's inputs): 39 / 41 / 42 elements at n = 1023 / 1024 / 1025
+   [EMA + "test_ema_kernel_is_the_model[vector-w=0.5]"])
+_m("ema_no_finite_guard", "kernels_optim.hip",
+   "    return fin(r) ? r : e;",
+   "    return r;",
+   "ema_elem stores a result that is not finite instead of keeping e",
+   "elements whose p, e or difference is not finite",
+   [EMA + "test_ema_kernel_keeps_elements_that_would_not_be_finite[vector-p]"])
+_m("ema_tail_unfused", "kernels_optim.hip",
+   "        if (i < n) ema[i] = ema_elem(ema[i], p[i], w, omw);",
+   "        if (i < n) {\n#pragma clang fp contract(off)\n            const float e0 = ema[i], p0 = p[i], d0 = p0 - e0, t0 = w < 0.5f ? w * d0 : -omw * d0;\n"
+   "            const float r0 = w < 0.5f ? t0 + e0 : t0 + p0;\n            ema[i] = fin(r0) ? r0 : e0;\n        }",
+   "the n % 4 elements behind the last float4 of ema_update_kernel<4> are updated without the fma (1 to 3 elements of an arena)",
+   "the vector tail line of ema_update_kernel",
+   # CPU pre-check: _pair's inputs separate none of these elements at n <= 5 and few beyond; emaref.separating_pair separates all
+   [EMA + "test_ema_tails_and_partial_turns_on_inputs_that_separate_the_alternatives[vector-w=0.1]",
+    EMA + "test_ema_tails_and_partial_turns_on_inputs_that_separate_the_alternatives[vector-w=0.8]"])
+_m("exchange_tail_one_way", "kernels_optim.hip",
+   "if (i < n) { const uint32_t x = a[i], y = b[i]; a[i] = y; b[i] = x; }",
+   "if (i < n) { const uint32_t x = a[i], y = b[i]; a[i] = y; b[i] = y; }",
+   "the n % 4 words behind the last uint4 of exchange_kernel<4> go from b to a only: b keeps its words",
+   "the vector tail line of exchange_kernel",
+   [EMA + "test_exchange_kernel_swaps_words[vector]"])
+_m("exchange_turn_item2_one_way", "kernels_optim.hip",
+   "                av[i] = y[k]; bv[i] = x[k];",
+   "                av[i] = y[k]; bv[i] = k == 2 ? y[k] : x[k];",
+   "the third of the four items a thread moves in a whole turn of exchange_kernel goes from b to a only",
+   "whole (unrolled) turns of exchange_kernel",
+   [EMA + "test_exchange_kernel_swaps_words[vector]", EMA + "test_exchange_kernel_swaps_words[element-wise]"])
+_m("accum_first_adds_zero", "kernels_optim.hip",
+   "    if (MODE == MID_ACC_FIRST) return q;",
+   "    if (MODE == MID_ACC_FIRST) return __float_as_uint(__uint_as_float(q) + 0.f);",
+   "grad_accum FIRST passes the gradient through an addition of 0: -0 becomes +0 (and a signalling NaN quiet)",
+   "grad_accum_kernel<first>, words that arithmetic changes",
+   [ACC + "test_kernel_is_the_model[first-vector]", ACC + "test_kernel_propagates_what_is_not_finite[first-element-wise]"])
+_m("accum_fold_rounded_once", "kernels_optim.hip",
+   "    const float scaled = sum * scale;",
+   "    const float scaled = (float)(((double)__uint_as_float(a) + (double)__uint_as_float(q)) * (double)scale);",
+   "grad_accum FOLD evaluates (acc + g) scale in double and rounds once: about a quarter of the elements at scale 1 / 3",
+   "grad_accum_kernel<fold>, every element",
+   [ACC + "test_fold_rounds_the_sum_and_the_product_separately", ACC + "test_kernel_is_the_model[fold-element-wise]"])
+_m("accum_partial_turn_reads_g_twice", "kernels_optim.hip",
+   "                out[it] = acc_item<MODE>(x, y, scale);",
+   "                out[it] = acc_item<MODE>(y, y, scale);",
+   "the partial turn of grad_accum_kernel takes the gradient for the accumulator's value as well (g + g); whole turns and the tail do not",
+   "the partial-turn branch of grad_accum_kernel (ADD and FOLD)",
+   [ACC + "test_tails_and_partial_turns_on_inputs_that_separate_the_alternatives[add-vector]",
+    ACC + "test_tails_and_partial_turns_on_inputs_that_separate_the_alternatives[fold-element-wise]"])
+_m("accum_tail_fold_rounded_once", "kernels_optim.hip",
+   "            (MODE == MID_ACC_FOLD ? g : acc)[i] = acc_word<MODE>(x, y, scale);",
+   "            (MODE == MID_ACC_FOLD ? g : acc)[i] = MODE == MID_ACC_FOLD\n"
+   "                ? __float_as_uint((float)(((double)__uint_as_float(x) + (double)__uint_as_float(y)) * (double)scale)) : acc_word<MODE>(x, y, scale);",
+   "the n % 4 elements behind the last uint4 of grad_accum_kernel<4, fold> are rounded once, through double",
+   "the vector tail line of grad_accum_kernel<fold>",
+   [ACC + "test_tails_and_partial_turns_on_inputs_that_separate_the_alternatives[fold-vector]"])
+
 # kernels_input.hip
+_m("mix_pair_fma", "kernels_input.hip",
+   "    const float na = la + mb, nb = lb + ma;",
+   "    const float na = fmaf(lam, a, mb), nb = fmaf(lam, b, ma);",
+   "mix_pair contracts lam a + (mu b) into one fma: one rounding fewer in both results",
+   "every element of mixup_kernel",
+   [MIX + "test_mixup[2-8-0.3]", MIX + "test_mixup[2-7-0.3]"])
+_m("mixup_elem_partner_weight", "kernels_input.hip",
+   "            mix_pair(va, vb, lam, mu);\n            a[e] = va; b[e] = vb;",
+   "            mix_pair(va, vb, lam, lam);\n            a[e] = va; b[e] = vb;",
+   "the element-wise branch of mixup_kernel weighs the partner with lam instead of 1 - lam",
+   "the element-wise branch of mixup_kernel",
+   [MIX + "test_mixup[2-7-0.3]", MIX + "test_mixup_on_an_unaligned_batch"])
+_m("mixup_second_turn_keeps", "kernels_input.hip",
+   "i < items; i += step) {\n        if (i < quads) {",
+   "i < items; i += step) {\n        lam = i >= step ? 1.f : lam; mu = i >= step ? 0.f : mu;\n        if (i < quads) {",
+   "work items a thread of mixup_kernel reaches after its first (i >= step) are mixed with lam = 1, mu = 0: they keep their values",
+   "the second and later grid-stride turns of mixup_kernel",
+   [MIX + "test_mixup_takes_a_second_grid_stride_turn[vec]", MIX + "test_mixup_takes_a_second_grid_stride_turn[elem]"])
+_m("cutmix_groups_second_lane_turn_keep_b", "kernels_input.hip",
+   "for (int q = lane; q < nq; q += 64) { const uint4 t = qa[q]; qa[q] = qb[q]; qb[q] = t; }",
+   "for (int q = lane; q < nq; q += 64) { const uint4 t = qa[q], o = qb[q]; qa[q] = o; qb[q] = q >= 64 ? o : t; }",
+   "the 16-byte groups q >= 64 of a row segment (a lane's second turn) go from b to a only: b keeps its words",
+   "cutmix_kernel, 16-byte path, boxes more than 64 groups wide",
+   [MIX + "test_cutmix_wide_and_tall_boxes[vec-x3_inner]", MIX + "test_cutmix_wide_and_tall_boxes[vec-whole]"])
+_m("cutmix_elems_from_64_keep_b", "kernels_input.hip",
+   "for (int e = 64 + lane; e < w; e += 64) { const uint32_t t = pa[e]; pa[e] = pb[e]; pb[e] = t; }",
+   "for (int e = 64 + lane; e < w; e += 64) { const uint32_t o = pb[e]; pa[e] = o; pb[e] = o; }",
+   "the elements e >= 64 of a row segment on the element-wise path go from b to a only: b keeps its words",
+   "cutmix_kernel, element-wise path, boxes more than 64 columns wide",
+   [MIX + "test_cutmix_wide_and_tall_boxes[elem-x3_inner]"])
+_m("cutmix_second_sweep_keep_b", "kernels_input.hip",
+   "        if (lane < head) { const uint32_t t = pa[lane]; pa[lane] = pb[lane]; pb[lane] = t; }\n"
+   "        if (!vec) for (int e = 64 + lane; e < w; e += 64) { const uint32_t t = pa[e]; pa[e] = pb[e]; pb[e] = t; }\n"
+   "        else {\n"
+   "            uint4 *qa = (uint4 *)(pa + head), *qb = (uint4 *)(pb + head);\n"
+   "            for (int q = lane; q < nq; q += 64) { const uint4 t = qa[q]; qa[q] = qb[q]; qb[q] = t; }\n",
+   "        const bool late = sgm >= (int)gridDim.x * waves;\n"
+   "        if (lane < head) { const uint32_t t = pa[lane], o = pb[lane]; pa[lane] = o; pb[lane] = late ? o : t; }\n"
+   "        if (!vec) for (int e = 64 + lane; e < w; e += 64) { const uint32_t t = pa[e], o = pb[e]; pa[e] = o; pb[e] = late ? o : t; }\n"
+   "        else {\n"
+   "            uint4 *qa = (uint4 *)(pa + head), *qb = (uint4 *)(pb + head);\n"
+   "            for (int q = lane; q < nq; q += 64) { const uint4 t = qa[q], o = qb[q]; qa[q] = o; qb[q] = late ? o : t; }\n",
+   "row segments a wave of cutmix_kernel reaches after its first (sgm >= gridDim.x * waves) go from b to a only, on both paths",
+   "the second sweep of the segment loop of cutmix_kernel (3 h > 512 segments)",
+   [MIX + "test_cutmix_wide_and_tall_boxes[elem-from_1_1]", MIX + "test_cutmix_wide_and_tall_boxes[vec-from_1_1]"])
+_m("cutmix_tail_behind_groups_keep_b", "kernels_input.hip",
+   "            if (e < w) { const uint32_t t = pa[e]; pa[e] = pb[e]; pb[e] = t; }",
+   "            if (e < w) { const uint32_t o = pb[e]; pa[e] = o; pb[e] = o; }",
+   "the elements behind the last 16-byte group of a row segment go from b to a only",
+   "cutmix_kernel, 16-byte path, the one-lane-each tail",
+   # D = 30, columns 3 .. 28: rows whose segment starts 1 word past a 16-byte boundary have 3 + 5 x 4 + 3 elements
+   [MIX + "test_cutmix[2-30-x3_w26]"])
 _m("decode_r_plane_b_mean", "kernels_input.hip",
    "{123.68, 116.78, 103.94}; // subtracted from source byte 0",
    "{123.68, 116.78, 123.68}; // subtracted from source byte 0",
@@ -339,6 +462,46 @@ _m("loss_long_row_float_sum", "kernels_loss.hip",
    "rows longer than LOSS_REG_COLS add z per lane in float instead of double",
    "loss_head_kernel<mem> (L > 1024)",
    ["tests/test_gpu_loss_head.py::test_long_row_sums_z_in_double"])
+_m("loss_mix_wb_as_difference", "kernels_loss.hip",
+   "wb = MIX ? loss_mul_rn(1.f - eps, 1.f - lam) : 0.f;",
+   "wb = MIX ? loss_add_rn(1.f - eps, -wa) : 0.f;",
+   "the two-label head forms the second weight as (1 - eps) - wa instead of the product (1 - eps)(1 - lam): the neighbouring float at some lam",
+   "loss_head_kernel<*, MIX>, t_b of every row",
+   # CPU pre-check (tests/test_mix_model.py): the same float32 at lam = 0.3 with eps 0 and 0.1 -- test_loss_head_mix cannot see it --, the
+   # neighbouring one at lam = 0.7, eps = 0.1
+   [MIX + "test_second_weight_is_one_rounded_product"])
+_m("loss_mix_drops_wb_zb", "kernels_loss.hip",
+   "logf(s) - wa * zc - wb * zb - u * sz",
+   "logf(s) - wa * zc - u * sz",
+   "the two-label row loss lacks the second label's term wb z_b",
+   "loss_head_kernel<*, MIX>, row_loss with wb > 0",
+   [MIX + "test_loss_head_mix[shape1-0.3-0.0]"])
+_m("loss_mix_target_sum_reassociated", "kernels_loss.hip",
+   "loss_add_rn(loss_add_rn(valid && (j_) == c ? wa : 0.f, valid_b && (j_) == cb ? wb : 0.f), u)",
+   "loss_add_rn(valid && (j_) == c ? wa : 0.f, loss_add_rn(valid_b && (j_) == cb ? wb : 0.f, u))",
+   "the two-label target is summed as wa + (wb + u): another float32 where both labels are one class and the roundings fall that way",
+   "loss_head_kernel<*, MIX>, rows with a == b",
+   # CPU pre-check (tests/test_mix_model.py): of lossref.SHAPES at lam 0.3, eps 0.1 only L = 65 separates (all 4 rows); a != b never does
+   [MIX + "test_loss_head_mix[shape3-0.3-0.1]"])
+_m("loss_reduce_topk_strict", "kernels_loss.hip",
+   "wk += row_rank[r] >= topk ? 1 : 0;",
+   "wk += row_rank[r] > topk ? 1 : 0;",
+   "the batch totals count a row as top-k wrong only where rank > k: rows whose rank is exactly k are missed",
+   "loss_reduce_kernel, rows with rank == topk",
+   [LOSS + "test_batch_totals_past_64_rows_and_at_the_topk_threshold[5-0.0]", MIX + "test_batch_totals_past_64_rows_and_at_the_topk_threshold[1-0.1]"])
+_m("loss_reduce_rows_past_64_zero", "kernels_loss.hip",
+   "        sum += (double)row_loss[r];\n        w1 += row_rank[r] >= 1 ? 1 : 0;\n        wk += row_rank[r] >= topk ? 1 : 0;",
+   "        sum += (r >= 64 ? 0.0 : 1.0) * (double)row_loss[r];\n        w1 += (r >= 64 ? 0 : 1) * (row_rank[r] >= 1 ? 1 : 0);\n"
+   "        wk += (r >= 64 ? 0 : 1) * (row_rank[r] >= topk ? 1 : 0);",
+   "the batch totals multiply the rows a lane reaches after its first (r >= 64) by 0: the loss sum and both counts lack them",
+   "loss_reduce_kernel, the second and later passes of the lanes (N > 64)",
+   [LOSS + "test_batch_totals_past_64_rows_and_at_the_topk_threshold[10-0.0]"])
+_m("loss_reduce_float_lane_sum", "kernels_loss.hip",
+   "sum += (double)row_loss[r];",
+   "sum = (double)(float)((float)sum + row_loss[r]);",
+   "the lanes of loss_reduce_kernel add their rows in float: loss_sum is about 5e-9 off (relative) at two or three rows per lane",
+   "loss_reduce_kernel, lanes with more than one row (N > 64)",
+   [LOSS + "test_batch_totals_past_64_rows_and_at_the_topk_threshold[10-0.1]"])
 
 # mi_common.hpp (one header mutant: it recompiles every .hip file)
 _m("pack_bf2_truncates", "mi_common.hpp",

@@ -90,6 +90,32 @@ def test_the_fold_is_a_sum_then_a_product_not_a_fused_multiply_add():
     assert M.same(two, _torch_window([a, b], s))
 
 
+@pytest.mark.parametrize("vector", [True, False], ids=["vector", "element-wise"])
+def test_separating_inputs_separate_every_tail_and_partial_turn_position(vector):
+    """a condition, not a measurement: at every length of tests/test_gpu_accum.py, every position of the n % 4 tail and of the partial turn
+    (and every other one) tells the two-rounding fold from the fold rounded once, at the operator test's scale 1 / 3; acc != g everywhere,
+    so a launch that reads one operand twice shows in ADD as well"""
+    import ctypes as C
+    import emaref
+    from resnet_amd import binding as B
+    geo = (C.c_size_t * 4)()
+    B.load().mi_debug_accum_geometry(geo)  # host only
+    turn = int(geo[1] if vector else geo[2])
+    scale = SCALES[2]
+    for n in sorted({1, 3, 4, 5, 1023, 1024, 1025, turn - 1, turn, turn + 1}):
+        acc, g = M.separating_pair(n, scale, n)
+        assert acc.size == g.size == n and acc.dtype == g.dtype == np.float32
+        differ = _bits(M.fold(acc, g, scale)) != _bits(M.fold_once(acc, g, scale))
+        at = emaref.tail_and_partial_turn(n, turn, vector)
+        assert differ[at].all() and differ.all(), "n = %d: %d positions do not separate" % (n, int((~differ).sum()))
+        assert np.all(acc != g) and np.all(_bits(M.add(acc, g)) != _bits(M.add(g, g)))
+    # fold_once is the expression of the test above
+    rng = np.random.RandomState(7)
+    a, b = rng.randn(4096).astype(np.float32), (rng.randn(4096) * 1e-4).astype(np.float32)
+    once = ((a.astype(np.float64) + b.astype(np.float64)) * np.float64(scale)).astype(np.float32)
+    assert np.array_equal(_bits(M.fold_once(a, b, scale)), _bits(once))
+
+
 def test_special_values_follow_ieee():
     inf, nan = np.float32(np.inf), np.float32(np.nan)
     a = np.array([inf, inf, -0.0, 0.0, DENORMAL, HUGE, 1.5, nan], np.float32)

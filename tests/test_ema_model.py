@@ -110,6 +110,51 @@ def test_exact_properties_and_the_non_finite_rule():
         assert np.array_equal(_bits(got)[keep], _bits(clean)[keep])
 
 
+def _kernel_lengths(vector):
+    """the length set of tests/test_gpu_ema.py, from the launcher's own constants (host only)"""
+    from resnet_amd import binding as B
+    geo = (C.c_size_t * 4)()
+    B.load().mi_debug_ema_geometry(geo)
+    turn = int(geo[1] if vector else geo[2])
+    return sorted({1, 3, 4, 5, 1023, 1024, 1025, turn - 1, turn, turn + 1}), turn
+
+
+@pytest.mark.parametrize("w", [np.float32(0.1), np.float32(0.8), np.float32(0.5)], ids=["0.1", "0.8", "0.5"])
+@pytest.mark.parametrize("vector", [True, False], ids=["vector", "element-wise"])
+def test_separating_inputs_separate_every_tail_and_partial_turn_position(vector, w):
+    """a condition, not a measurement: at every length of the operator test, every position of the n % 4 tail and of the partial turn
+    (and every other one) tells the model from the alternative -- unfused at w = 0.1 and 0.8, the other branch at 0.5.  The operator
+    test's older inputs do so in 2 to 6 % of the positions, and in none at n <= 5"""
+    lengths, turn = _kernel_lengths(vector)
+    covered = 0
+    for n in lengths:
+        e, p = M.separating_pair(n, w, n)
+        assert e.size == p.size == n and e.dtype == p.dtype == np.float32
+        differ = _bits(M.lerp32(e, p, w)) != _bits(M.alternative32(e, p, w))
+        at = M.tail_and_partial_turn(n, turn, vector)
+        assert at.any() or n % turn == 0
+        assert differ[at].all() and differ.all(), "n = %d: %d of %d tail / partial-turn positions do not separate" % (n, int((~differ[at]).sum()), int(at.sum()))
+        assert np.all(np.isfinite(e)) and np.all(np.isfinite(p))
+        covered += int(at.sum())
+    assert covered > turn
+    # the positions: a vector arena of one turn + 7 floats has its last 4 + 3 outside the whole turn; an element-wise one its last 7
+    assert list(np.flatnonzero(M.tail_and_partial_turn(turn + 7, turn, vector))) == list(range(turn, turn + 7))
+    assert not M.tail_and_partial_turn(turn, turn, vector).any() and M.tail_and_partial_turn(turn - 1, turn, vector).all()
+
+
+def test_alternatives_are_what_their_names_say():
+    e, p = _inputs()
+    e, p = e[:4096], p[:4096]
+    for w in WEIGHTS[:3]:
+        unfused = (e + (w * (p - e)).astype(np.float32)).astype(np.float32) if w < 0.5 else \
+            (p - ((p - e) * (np.float32(1) - w)).astype(np.float32)).astype(np.float32)
+        assert np.array_equal(_bits(M.unfused32(e, p, w)), _bits(unfused))
+    half = np.float32(0.5)
+    assert np.array_equal(_bits(M.other_branch32(e, p, half)), _bits(M.fma32(half, p - e, e)))
+    assert np.array_equal(_bits(M.alternative32(e, p, half)), _bits(M.other_branch32(e, p, half)))
+    assert np.array_equal(_bits(M.alternative32(e, p, np.float32(0.8))), _bits(M.unfused32(e, p, np.float32(0.8))))
+
+
 def test_ema_run_counts_and_skips():
     rng = np.random.RandomState(3)
     start = [rng.randn(7).astype(np.float32)]

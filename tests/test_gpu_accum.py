@@ -99,6 +99,22 @@ def test_kernel_is_the_model(ops, mode, offset):
 
 @pytest.mark.parametrize("offset", [0, 1], ids=["vector", "element-wise"])
 @pytest.mark.parametrize("mode", [m for m, _ in MODES], ids=[n for _, n in MODES])
+def test_tails_and_partial_turns_on_inputs_that_separate_the_alternatives(ops, mode, offset):
+    """the lengths above on accumref.separating_pair: EVERY element tells the fold (a sum, then a product) from the fold rounded once,
+    and acc != g everywhere, so that the n % 4 tail and the partial turn, which have their own lines in the kernel, cannot round
+    differently or read an operand twice unnoticed.  _pair's inputs separate about a quarter of the elements (tests/test_accum_model.py
+    holds the 100 % as a condition, without a GPU)"""
+    import emaref
+    _, turn_v, turn_e, _ = ops.accum_geometry()
+    for n in _lengths(ops, offset)[0]:
+        acc, g = M.separating_pair(n, SCALE, n)
+        at = emaref.tail_and_partial_turn(n, turn_e if offset else turn_v, not offset)
+        assert np.all(_bits(M.fold(acc, g, SCALE))[at] != _bits(M.fold_once(acc, g, SCALE))[at]) and np.all(acc[at] != g[at])
+        _check_launch(ops, mode, offset, acc, g, SCALE, "n = %d" % n)
+
+
+@pytest.mark.parametrize("offset", [0, 1], ids=["vector", "element-wise"])
+@pytest.mark.parametrize("mode", [m for m, _ in MODES], ids=[n for _, n in MODES])
 def test_kernel_propagates_what_is_not_finite(ops, mode, offset):
     """NaN (with a payload), +-inf, -0 and a denormal in the vector body, in the n % 4 tail and in the second grid-stride turn, in either
     operand: IEEE results, no guard; FIRST keeps every bit"""

@@ -83,6 +83,25 @@ def test_ema_kernel_is_the_model(ops, offset, w):
         assert np.array_equal(got_e[0][same], e[same]), "p == e: the value stays"
 
 
+@pytest.mark.parametrize("w", [np.float32(0.1), np.float32(0.8), np.float32(0.5)], ids=["w=0.1", "w=0.8", "w=0.5"])
+@pytest.mark.parametrize("offset", [0, 1], ids=["vector", "element-wise"])
+def test_ema_tails_and_partial_turns_on_inputs_that_separate_the_alternatives(ops, offset, w):
+    """the lengths above on emaref.separating_pair: EVERY element tells the model from the wrong kernel this weight is there to catch
+    (the unfused update at 0.1 and 0.8, the other branch at 0.5), so that the n % 4 tail (1 to 3 elements) and the partial turn, which
+    have their own lines in the kernel, cannot be written with another rounding unnoticed.  _pair's inputs separate 2 to 6 % of the
+    elements, and none at n <= 5 (tests/test_ema_model.py holds the 100 % as a condition, without a GPU)"""
+    _, turn_v, turn_e, _ = ops.ema_geometry()
+    for n in _lengths(ops, offset):
+        e, p = M.separating_pair(n, w, n)
+        want = M.lerp32(e, p, w)
+        at = M.tail_and_partial_turn(n, turn_e if offset else turn_v, not offset)
+        assert np.all(_bits(want)[at] != _bits(M.alternative32(e, p, w))[at])
+        got_e, got_p = ops.ema_update(e, p, w, offset_floats=offset, guard=GUARD, fill=FILL)
+        bad = _bits(got_e[0]) != _bits(want)
+        assert not bad.any(), "n = %d: %d elements differ from the model, %d of them in the tail or the partial turn" % (n, int(bad.sum()), int(bad[at].sum()))
+        assert _same(got_p[0], p) and _guards_ok(got_e) and _guards_ok(got_p), "n = %d: p or a guard word was written" % n
+
+
 @pytest.mark.parametrize("offset", [0, 1], ids=["vector", "element-wise"])
 def test_ema_and_exchange_take_a_second_grid_stride_turn(ops, offset):
     n = _second_turn_length(ops, offset)

@@ -87,6 +87,17 @@ def test_loss_head(ops, shape, eps):
     assert last1["wrong_topk"] == last1["wrong_top1"] == last["wrong_top1"] and last1["loss_sum"] == last["loss_sum"]
 
 
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+@pytest.mark.parametrize("topk", [1, 5, 10])
+def test_batch_totals_past_64_rows_and_at_the_topk_threshold(ops, topk, eps):
+    """loss_reduce_kernel: lossref.check_batch_totals says what is built and asserted"""
+    pred, dl, rl = R.check_batch_totals(lambda x, lab, total: ops.loss_head(x, lab, eps, topk, total=total), lambda: ops.dev(_record()), topk)
+    x, lab, _ = R.ranked_inputs()
+    assert _same(pred, ops.softmax(x))
+    ref = R.loss_head(x, lab, eps)[2]
+    assert np.all(np.abs(rl.astype(np.float64) - ref) <= R.loss_bound(ref))
+
+
 def test_long_row_sums_z_in_double(ops):
     """loss_head_kernel<mem> (rows of more than 1024 columns) adds z per lane in double.  lossref.long_row_corner builds the corner that
     needs it: label at the maximum, every other logit 90 .. 240 below it, smoothing 0.5 (u sum z is nearly all of the loss), the logits

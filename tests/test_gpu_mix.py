@@ -5,8 +5,11 @@ mixup: n 1, 2, 5, 8 (no pair; one pair; a middle row; more than one pair) x D 7 
 8 (16-byte path), 30 (image_size 2700, a multiple of 4) x lam 0, 1, 0.5, 0.3, and a batch that starts 4 bytes into its buffer.
 CutMix at D 30 and 7: empty, whole image, one pixel, x0 = 1 width 5, x0 = 3 width 26, x0 = 4 width 26 (D 30: to the right edge), a box
 out of range, an inverted one.
+Behind one sweep of the capped grid (mi_debug_mix_geometry: 32768 work items, 512 row segments): mixup at the smallest D whose pair has
+more items, CutMix at the smallest D whose boxes have more segments, more than 64 columns and more than 64 16-byte groups per row.
 The head on lossref.SHAPES: pred = mi_op_softmax's bits, dlogits = the float32 model's bits on that pred, lam = 1 = mi_op_loss_head's bits,
-row_loss inside the bound DESIGN.md ("Loss head") derives, the records, an invalid second label.
+row_loss inside the bound DESIGN.md ("Loss head") derives, the records, an invalid second label; the batch totals on 130 rows of known
+rank (lossref.check_batch_totals); the second weight at a lam where its rounding shows.
 """
 import ctypes as C
 
@@ -93,6 +96,83 @@ def test_cutmix(ops, n, D, box):
         assert _same(got, x)
     if box in ("whole", "out_of_range"):
         assert _same(got[0], x[n - 1]) and _same(got[n - 1], x[0])
+
+
+LANES = 64  # a wave takes one row segment of a CutMix box: lane-strided over its elements, or over its 16-byte groups
+
+
+def _sweeps(ops):
+    """what one sweep of the capped grid covers, from the launcher's own constants: work items of a pair (mixup_kernel: 32768), row
+    segments of a box (cutmix_kernel: 512).  Everything below them is done before a thread strides on"""
+    threads, cap, waves = ops.mix_geometry()
+    return threads * cap, cap * waves
+
+
+def _second_turn_dim(ops, path):
+    """the smallest D whose pair has more work items than one sweep: 16-byte groups (3 D^2 / 4 of them, D even) or elements (3 D^2, D odd).
+    With 128 workgroups of 256 threads: 210 and 105, 33075 items both"""
+    items, _ = _sweeps(ops)
+    D = 2 if path != "elem" else 1
+    while (3 * D * D // 4 if path != "elem" else 3 * D * D) <= items:
+        D += 2
+    return D
+
+
+@pytest.mark.parametrize("path", ["vec", "elem", "vec_unaligned"])
+def test_mixup_takes_a_second_grid_stride_turn(ops, path):
+    """n = 2 at the smallest D at which the threads of the capped grid stride on (`i += step`), on the 16-byte path, on the element-wise
+    path of an odd D, and on the element-wise path of the even D through a batch that starts 4 bytes into its buffer (4 sweeps)"""
+    items, _ = _sweeps(ops)
+    D = _second_turn_dim(ops, path)
+    work = 3 * D * D // 4 if path == "vec" else 3 * D * D
+    assert work > items and (3 * D * D) % 4 == (0 if path != "elem" else 3)
+    x = _images(2, D)
+    p = _plan(1, 0.3)
+    got = ops.mix_batch(x, p, offset_floats=1 if path == "vec_unaligned" else 0)
+    want = R.mix(x, p)
+    bad = _bits(got) != _bits(want)
+    assert not bad.any(), "%d elements differ, the first at flat index %d of %d" % (int(bad.sum()), int(np.flatnonzero(bad.ravel())[0]), bad.size // 2)
+    assert np.mean(_bits(got) != _bits(x)) > 0.99  # the comparison is not vacuous: the mix moved (nearly) every element
+
+
+def _cutmix_dim(ops, path):
+    """the smallest D at which the boxes below run every loop of cutmix_kernel more than once.  Both paths: 3 (D - 1) row segments are
+    more than one sweep (the segment loop strides on).  elem (D odd): then w >= D - 5 > 2 x 64, three lane turns.  vec (D a multiple of
+    16): the narrowest box (w = D - 5, one element in front of the first 16-byte boundary) has more than 64 groups.  With 128 workgroups
+    of 4 waves: 173 and 272"""
+    _, segments = _sweeps(ops)
+    D = 1 if path == "elem" else 16
+    while 3 * (D - 1) <= segments or D - 5 <= 2 * LANES or (path == "vec" and (D - 6) // 4 <= LANES):
+        D += 2 if path == "elem" else 16
+    return D
+
+
+def _big_boxes(D):
+    return {"whole": (0, 0, D, D), "from_1_1": (1, 1, D, D), "x3_inner": (0, 3, D - 1, D - 2)}
+
+
+@pytest.mark.parametrize("box", ["whole", "from_1_1", "x3_inner"])
+@pytest.mark.parametrize("path", ["elem", "vec"])
+def test_cutmix_wide_and_tall_boxes(ops, path, box):
+    """n = 3 (a middle row).  elem: image_size % 4 != 0, every element on its own, the lanes of a wave take three turns over a row.  vec:
+    up to 68 16-byte groups per row (the lanes take a second turn), with 0, 3 and 1 elements in front of them and 0, 0 and 2 behind.
+    Every box has more row segments than one sweep of the grid"""
+    _, segments = _sweeps(ops)
+    D = _cutmix_dim(ops, path)
+    assert (3 * D * D) % 4 == (0 if path == "vec" else 3)
+    y0, x0, y1, x1 = _big_boxes(D)[box]
+    assert 3 * (y1 - y0) > segments and x1 - x0 > 2 * LANES
+    x = _images(3, D)
+    p = _plan(2, 0.5, (y0, x0, y1, x1))
+    got = ops.mix_batch(x, p)
+    want = R.mix(x, p)
+    inside = np.zeros((D, D), bool)
+    inside[y0:y1, x0:x1] = True
+    bad = _bits(got[:, :, inside]) != _bits(want[:, :, inside])
+    assert not bad.any(), "%d elements inside the box differ from the model" % int(bad.sum())
+    assert _same(got[:, :, ~inside], x[:, :, ~inside]), "an element outside the box was written"
+    assert _same(got[0][:, inside], x[2][:, inside]) and _same(got[2][:, inside], x[0][:, inside]) and _same(got[1], x[1])
+    assert np.mean(_bits(x[0][:, inside]) != _bits(x[2][:, inside])) > 0.99  # not vacuous: the partners differ (nearly) everywhere
 
 
 def test_mode_0_launches_nothing(ops):
@@ -195,6 +275,37 @@ def test_loss_head_mix(ops, shape, lam, eps):
         again = ops.loss_head_mix(x, a, b, lam32, eps, k, total=total)
         assert _same(again[0], pred) and _same(again[1], dl) and _same(again[2], rl) and again[4] == last
         assert again[5]["loss_sum"] == 2 * last["loss_sum"] and again[5]["batches"] == 2
+
+
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+@pytest.mark.parametrize("topk", [1, 5, 10])
+def test_batch_totals_past_64_rows_and_at_the_topk_threshold(ops, topk, eps):
+    """loss_reduce_kernel behind the two-label head (lossref.check_batch_totals says what is built and asserted); the rank is label a's"""
+    from resnet_amd import binding as B
+    lam = np.float32(0.3)
+    new_total = lambda: ops.dev(np.zeros(C.sizeof(B.MiLossMetrics), np.uint8))
+    pred, dl, rl = lossref.check_batch_totals(lambda x, a, total: ops.loss_head_mix(x, a, R.labels_b(a), lam, eps, topk, total=total), new_total, topk)
+    x, a, _ = lossref.ranked_inputs()
+    assert _same(pred, ops.softmax(x)) and _same(dl, pred - R.targets_f32(x.shape[1], a, R.labels_b(a), lam, eps))
+    ref = R.loss_head_mix(x, a, R.labels_b(a), lam, eps)[2]
+    assert np.all(np.abs(rl.astype(np.float64) - ref) <= lossref.loss_bound(ref))
+
+
+def test_second_weight_is_one_rounded_product(ops):
+    """wb = (1.f - eps) (x) (1.f - lam), rounded once.  At the weights of test_loss_head_mix every other way of forming it gives the same
+    float32 (mixref.WB_LAM says so); at lam = 0.7, eps = 0.1 the difference (1.f - eps) - wa is the neighbouring float, and every row's
+    t_b -- and t_a where a == b -- shows it"""
+    shape = (3, 10)
+    x, a, rev, sm = _head_case(ops, shape)
+    lam, eps = np.float32(R.WB_LAM), R.WB_EPS
+    assert R.wb_as_difference(lam, eps) != (np.float32(1) - np.float32(eps)) * (np.float32(1) - lam)
+    for b in (rev, a):
+        pred, dl, rl, rr, _, _ = ops.loss_head_mix(x, a, b, lam, eps, 5)
+        want = pred - R.targets_f32(shape[1], a, b, lam, eps)
+        assert _same(pred, sm)
+        assert _same(dl, want), "dlogits: %d elements differ from the float32 model" % int(np.sum(_bits(dl) != _bits(want)))
+        ref = R.loss_head_mix(x, a, b, lam, eps)[2]
+        assert np.all(np.abs(rl.astype(np.float64) - ref) <= lossref.loss_bound(ref))
 
 
 @pytest.mark.parametrize("eps", [0.0, 0.1])

@@ -43,6 +43,36 @@ def test_rank_rule(shape):
     assert R.rank_of(nan, lab)[0] == 0 and not R.host_rule_wrong(nan, lab)[0]
 
 
+def test_ranked_inputs_have_the_ranks_they_are_built_for():
+    """lossref.ranked_inputs (the batch-totals test): with the float32 soft-max the ranks are arange(N) % L; the counts the operator test
+    asserts follow, and the rows past the 64 lanes carry a share of each, so that a reduction that loses them shows.  None of
+    lossref.SHAPES has a row whose rank equals its top-k: `rank >= k` written `> k` gives the same counts there"""
+    x, lab, ranks = R.ranked_inputs()
+    N, L = R.RANKED_SHAPE
+    assert x.shape == (N, L) and N > 128 and np.array_equal(ranks, np.arange(N) % L)
+    assert all(sorted(row) == list(range(L)) for row in x)
+    e = np.exp(x - x.max(axis=1, keepdims=True))  # float32 throughout
+    p32 = e / e.sum(axis=1, keepdims=True)
+    assert p32.dtype == np.float32 and np.array_equal(R.rank_of(p32, lab), ranks)
+    assert np.array_equal(R.loss_head(x, lab)[3], ranks)
+    assert [int(np.sum(ranks >= k)) for k in (1, 5, 10)] == [117, 65, 0]
+    assert [int(np.sum(ranks[64:] >= k)) for k in (1, 5)] == [60, 35]
+    for k in (1, 5):
+        assert int(np.sum(ranks > k)) != int(np.sum(ranks >= k))
+    for shape in R.SHAPES:
+        xs, ls = R.make_inputs(*shape)
+        pr = R.softmax(xs).astype(np.float32)
+        assert not np.any(R.rank_of(pr, ls) == min(5, shape[1])), shape
+    # a lane that adds its two or three rows in float is off by far more than the 1e-12 the operator test allows
+    for eps in (0.0, 0.1):
+        rl = R.loss_head_f32(x, lab, eps)
+        lanes = np.zeros(64, np.float32)
+        for r in range(N):
+            lanes[r % 64] += rl[r]
+        want = float(np.sum(rl.astype(np.float64)))
+        assert abs(float(np.sum(lanes.astype(np.float64))) - want) > 1e-10 * want
+
+
 def test_labels_outside_the_row():
     x, lab = R.make_inputs(3, 10)
     bad = lab.copy()

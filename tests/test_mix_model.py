@@ -194,8 +194,30 @@ def test_f32_targets_at_lam_one_are_the_one_label_targets():
         assert np.array_equal(t.view(np.uint32), want.view(np.uint32))
 
 
+def test_the_inputs_of_the_rounding_mutants_separate_them():
+    """the mutant table's pre-check (tests/mutants.py, loss_mix_wb_as_difference and loss_mix_target_sum_reassociated): the operator
+    cases named as their killers see other float32 targets under the fault.  wb: not at the operator tests' lam = 0.3, but at WB_LAM,
+    WB_EPS.  The association: only with a == b, and of lossref.SHAPES at eps 0.1, lam 0.3 only where L = 65"""
+    f = np.float32
+    for eps in (0.0, 0.1):
+        assert R.wb_as_difference(0.3, eps) == (f(1) - f(eps)) * (f(1) - f(0.3)), "lam = 0.3 has begun to separate: name it as a killer"
+    wb = (f(1) - f(R.WB_EPS)) * (f(1) - f(R.WB_LAM))
+    assert R.wb_as_difference(R.WB_LAM, R.WB_EPS) in (np.nextafter(wb, f(0)), np.nextafter(wb, f(1)))
+    seen = {}
+    for shape in lossref.SHAPES:
+        _, a = lossref.make_inputs(*shape)
+        b = R.labels_b(a)
+        assert np.array_equal(R.targets_f32(shape[1], a, b, 0.3, 0.1)[a != b], R.targets_reassociated_f32(shape[1], a, b, 0.3, 0.1)[a != b])
+        t, t2 = R.targets_f32(shape[1], a, a, 0.3, 0.1), R.targets_reassociated_f32(shape[1], a, a, 0.3, 0.1)
+        seen[shape] = int(np.sum(np.any(t != t2, axis=1)))
+    assert seen[(4, 65)] == 4 and sum(seen.values()) == 4, seen
+
+
 def test_library_exports_the_mix_entry_points(lib):
     from resnet_amd import binding
-    for name in ("mi_mix_plan", "mi_op_mix_batch", "mi_op_loss_head_mix", "mi_trainer_set_mix", "mi_trainer_last_mix"):
+    for name in ("mi_mix_plan", "mi_op_mix_batch", "mi_op_loss_head_mix", "mi_trainer_set_mix", "mi_trainer_last_mix", "mi_debug_mix_geometry"):
         assert hasattr(lib, name) and name in binding.PROTOTYPES, name
     assert C.sizeof(binding.MiMixPlan) == 24
+    geo = (C.c_size_t * 3)()
+    lib.mi_debug_mix_geometry(geo)  # host only
+    assert geo[0] % 64 == 0 and geo[2] == geo[0] // 64 and geo[1] >= 1
