@@ -12,7 +12,8 @@
  *              draw per epoch; --augment fixed (default: the shard's own crops, the reference's pixels) | center | random | rrc, --no-flip
  *   ./ResNetMI --shards-u8 /data/train_data_shards/u8 --augment rrc --rrc-scale 0.08,1 --rrc-ratio 0.75,1.3333333333333333 --batch 256
  *              random-resized crop: a box of LO .. HI of the image's area and of aspect ratio LO .. HI (the defaults shown), resampled
- *              to the input size on the device
+ *              to the input size on the device; --rrc-antialias: scaled as Pillow's BILINEAR scales bytes (the filter widened by the
+ *              scale factor, mi_batch_set_antialias), not by the two-tap gather
  *   ./ResNetMI --label-smoothing 0.1 --topk 5 --device-loss
  *              the loss head on the device (mi_trainer_set_loss): label-smoothed cross entropy, loss and top-1 / top-K error counted
  *              there, one line of totals per epoch; --device-loss also drops forward_pass's blocking copy of the predictions
@@ -22,7 +23,8 @@
  *   ./ResNetMI --bn-momentum 0.1 --val-u8 /data/val_shards/u8 --val-dim-in 256 --val-every 5000
  *              evaluation: running statistics of every batch norm (mi_trainer_track_running_stats; --val-u8 alone implies momentum 0.1) and,
  *              every STEPS iterations and at the end of every epoch, the eval pass over every %03d.images_u8 / %03d.labels under DIR
- *              (whole dim-in^2 images, centre crop): loss per image, top-1 and top-K error of the set
+ *              (whole dim-in^2 images, centre crop): loss per image, top-1 and top-K error of the set; --val-resize N: every image is
+ *              first scaled to N x N (antialiased, as Pillow) and the centre crop is taken from that: torchvision's --val-resize-size
  *   ./ResNetMI --ema 0.99998 --ema-every 32 --ema-warmup --val-u8 /data/val_shards/u8
  *              weight averaging (mi_trainer_set_ema): an exponential moving average of the parameters and the batch-norm running statistics,
  *              updated on the device behind every N-th update_parameters (default 1) with e <- e + (1 - DECAY) (p - e); --ema-warmup: timm's
@@ -48,8 +50,9 @@ static const char *opt(int argc, char **argv, const char *name, const char *def)
     return def;
 }
 
-/* the whole validation set, shard by shard through mi_trainer_eval_u8 (each call returns its own total); 0, or -1 with a message printed */
-static int validate_one(Train_ResNet *trainer, const char *dir, int dim_in, int topk, const char *when) {
+/* the whole validation set, shard by shard through mi_trainer_eval_u8 (resize > 0: mi_trainer_eval_u8_resized; each call returns its own
+ * total); 0, or -1 with a message printed */
+static int validate_one(Train_ResNet *trainer, const char *dir, int dim_in, int resize, int topk, const char *when) {
     MiLossMetrics sum = {0};
     const size_t img = (size_t)dim_in * dim_in * 3;
     for (int id = 0;; id++) {
@@ -68,7 +71,8 @@ static int validate_one(Train_ResNet *trainer, const char *dir, int dim_in, int 
         int ok = fi && n > 0 && labels && images && fread(labels, sizeof(int), (size_t)n, fl) == (size_t)n &&
                  fread(images, img, (size_t)n, fi) == (size_t)n;
         if (!ok) fprintf(stderr, "validation shard %03d under %s is missing, empty or short\n", id, dir);
-        else if (mi_trainer_eval_u8(trainer, images, labels, n, dim_in, topk, &m)) { fprintf(stderr, "%s\n", mi_last_error()); ok = 0; }
+        else if (resize > 0 ? mi_trainer_eval_u8_resized(trainer, images, labels, n, dim_in, resize, topk, &m)
+                            : mi_trainer_eval_u8(trainer, images, labels, n, dim_in, topk, &m)) { fprintf(stderr, "%s\n", mi_last_error()); ok = 0; }
         fclose(fl);
         if (fi) fclose(fi);
         free(labels); free(images);
@@ -81,14 +85,14 @@ static int validate_one(Train_ResNet *trainer, const char *dir, int dim_in, int 
     return 0;
 }
 /* with --ema: the set twice, scored with the raw weights and with the averaged ones (mi_trainer_eval_use_ema) */
-static int validate(Train_ResNet *trainer, const char *dir, int dim_in, int topk, const char *when, int ema) {
+static int validate(Train_ResNet *trainer, const char *dir, int dim_in, int resize, int topk, const char *when, int ema) {
     char label[64];
-    if (!ema) return validate_one(trainer, dir, dim_in, topk, when);
+    if (!ema) return validate_one(trainer, dir, dim_in, resize, topk, when);
     snprintf(label, sizeof label, "%s, raw weights", when);
-    if (validate_one(trainer, dir, dim_in, topk, label)) return -1;
+    if (validate_one(trainer, dir, dim_in, resize, topk, label)) return -1;
     snprintf(label, sizeof label, "%s, EMA weights", when);
     if (mi_trainer_eval_use_ema(trainer, 1)) { fprintf(stderr, "%s\n", mi_last_error()); return -1; }
-    const int rc = validate_one(trainer, dir, dim_in, topk, label);
+    const int rc = validate_one(trainer, dir, dim_in, resize, topk, label);
     mi_trainer_eval_use_ema(trainer, 0);
     return rc;
 }
@@ -125,6 +129,9 @@ int main(int argc, char **argv) {
     const int TOPK = atoi(topk_arg ? topk_arg : "5");
     const char *bn_momentum_arg = opt(argc, argv, "--bn-momentum", NULL), *val_u8 = opt(argc, argv, "--val-u8", NULL);
     const int VAL_DIM_IN = atoi(opt(argc, argv, "--val-dim-in", "256")), VAL_EVERY = atoi(opt(argc, argv, "--val-every", "0"));
+    const int VAL_RESIZE = atoi(opt(argc, argv, "--val-resize", "0"));
+    int rrc_antialias = 0;
+    for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--rrc-antialias")) rrc_antialias = 1;
     const char *ema_arg = opt(argc, argv, "--ema", NULL);
     const int EMA_EVERY = atoi(opt(argc, argv, "--ema-every", "1"));
     int ema_warmup = 0;
@@ -160,6 +167,7 @@ int main(int argc, char **argv) {
         const int mode = !strcmp(augment, "random") ? MI_AUG_RANDOM : !strcmp(augment, "center") ? MI_AUG_CENTER : MI_AUG_FIXED;
         if (!strcmp(augment, "rrc") ? mi_batch_set_augment_rrc(batch, flip, aug_seed, rrc_scale[0], rrc_scale[1], rrc_ratio[0], rrc_ratio[1])
                                     : mi_batch_set_augment(batch, mode, flip, aug_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+        if (rrc_antialias && mi_batch_set_antialias(batch, 1)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     } else if (shards) mi_batch_source_shards(batch, shards, !strcmp(layout, "nhwc") ? MI_LAYOUT_NHWC : MI_LAYOUT_NCHW);
     else mi_batch_source_synthetic(batch, 1234, 1235, N_CLASSES, 4);
     if (shards || shards_u8) mi_batch_set_prefetch(batch, 1);
@@ -213,7 +221,7 @@ int main(int argc, char **argv) {
             update_parameters(trainer);
             if (mi_last_error()[0]) { fprintf(stderr, "device error: %s\n", mi_last_error()); return 2; }
             steps_done++;
-            if (val_u8 && VAL_EVERY > 0 && steps_done % VAL_EVERY == 0 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "step", ema_arg != NULL)) return 1;
+            if (val_u8 && VAL_EVERY > 0 && steps_done % VAL_EVERY == 0 && validate(trainer, val_u8, VAL_DIM_IN, VAL_RESIZE, TOPK, "step", ema_arg != NULL)) return 1;
         }
         if (stop) break;
         if (loss_on_device) {
@@ -224,7 +232,7 @@ int main(int argc, char **argv) {
                        total.loss_sum / (double)total.rows, 100.0 * (double)total.wrong_top1 / (double)total.rows, TOPK,
                        100.0 * (double)total.wrong_topk / (double)total.rows);
         }
-        if (val_u8 && validate(trainer, val_u8, VAL_DIM_IN, TOPK, "epoch", ema_arg != NULL)) return 1;
+        if (val_u8 && validate(trainer, val_u8, VAL_DIM_IN, VAL_RESIZE, TOPK, "epoch", ema_arg != NULL)) return 1;
         /* resnet.cu:3410-3421: per-epoch loss (a SUM over the epoch) and accuracy, rewind the data source */
         mi_trainer_end_epoch(trainer, epoch_loss, epoch_n_wrong, total_images_per_epoch);
         cur_iter_in_epoch = 0;

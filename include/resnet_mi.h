@@ -755,6 +755,51 @@ int mi_batch_set_augment_rrc(Batch *b, int flip, uint64_t seed, double scale_lo,
 /* the boxes of the last load, int [n_images][5]; returns n_images, or -1 (another source or mode, or nothing loaded yet) */
 int mi_batch_last_boxes(const Batch *b, int *out);
 
+/* ---------------- antialiased resize: Pillow's bilinear bits for the random-resized crop and the validation resize ----------------
+ * mi_op_resample_u8 reads two source pixels per axis whatever the scale: a box larger than the output is point-sampled.  Pillow's
+ * Image.resize(size, BILINEAR) -- what torchvision's RandomResizedCrop and Resize run on PIL images -- widens the triangle filter by the
+ * scale factor instead, in fixed-point arithmetic on bytes with a stated rounding; the kernel below reproduces it bit for bit on the box
+ * cut out first: img.crop(box).resize((V, V), BILINEAR).  tests/aaref.py restates it and is compared with Pillow itself.
+ *
+ * One axis scales `in` source pixels (the box's) to V output pixels.  In double, every operation rounded on its own (no fused
+ * multiply-add, host or device):  scale = in / V, fs = max(scale, 1.0), support = fs, ss = 1.0 / fs.  Output index o:
+ *   center = (o + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in), the cast
+ *   truncating toward zero;  taps j = 0 .. xmax - xmin - 1:  a = fabs((j + xmin - center + 0.5) ss), w_j = a < 1.0 ? 1.0 - a : 0.0,
+ *   ww = sum of w_j in order of j, k_j = w_j / ww, K_j = (int)(0.5 + k_j 4194304.0) -- 22 fractional bits;
+ *   pixel = clip((2097152 + sum_j byte[xmin + j] K_j) >> 22, 0, 255), exact in int32 (at most 16384 taps of weights that sum to 2^22 +- taps / 2).
+ * Two dimensions: the horizontal pass first, its result ROUNDED TO BYTES, the vertical pass on those bytes.  Pillow skips a pass whose
+ * in == V; its table is K = (2^22, 0), which hands every byte through unchanged, so the kernel does not branch.  The filter never reads
+ * outside the box.  The written value is the decode's: out[n][2 - p][oy][ox] = (float)((double)(float)byte - mean[p]).
+ *
+ * mi_aa_coeffs: host-only, no GPU: xmin and K_0 .. K_{min(taps, cap) - 1} of output index o, returns the tap count xmax - xmin (-1:
+ * in or V < 1, o outside [0, V)).  It is compiled from the text the kernel compiles (csrc/mi_aa.h).
+ *
+ * mi_op_resample_aa_u8: src_dev, boxes_dev and out_nchw as mi_op_resample_u8, the boxes clamped the same way.  Every box is scaled to
+ * virt x virt; of that the window of rows [win_row, win_row + dim_out) x columns [win_col, win_col + dim_out) is written, output column ox
+ * taking window column flip ? dim_out - 1 - ox : ox.  The RRC uses virt = dim_out and window (0, 0); a validation resize the whole image
+ * as box, virt = the resize size and the centre window.  A box with h = w = virt = dim_out gives mi_op_decode_u8's bits; an upscale does
+ * NOT give mi_op_resample_u8's (another convention).  A workgroup owns R window rows of one image (16, fewer where needed): it builds
+ * the tap tables of its rows and of the window's columns from the box, stages the source rows and columns those need (16-byte loads
+ * that stay inside the n images), filters them horizontally into bytes in LDS and vertically from there.  LDS, sized for a box as
+ * large as the image, with ks = 2 max(ceil(dim_in / virt), 1) + 1 the most taps of an output index and S the most source rows of R
+ * output rows (dim_in >= virt: ceil((R + 1) dim_in / virt) + 1, else ceil((R - 1) dim_in / virt) + 3; at most dim_in):
+ * 4 (dim_out + R)(ks + 2) bytes of tables rounded up to 16, + S (16 ceil((3 dim_in + 15) / 16) + 3 dim_out rounded up to 4) in 64 KB.
+ * Returns 0; -2 where R = 1 does not fit; -1 with mi_last_error set and nothing launched: n outside [1, 65535], dim_in, dim_out or
+ * virt outside [1, 16384], src not 16-byte aligned, out or boxes not 4-byte aligned, a window that leaves [0, virt]. */
+int mi_aa_coeffs(int in, int V, int o, int *xmin, int *K, int cap);
+int mi_op_resample_aa_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_nchw, int n, int dim_in, int dim_out, int virt, int win_row,
+                         int win_col);
+/* MI_SRC_SHARDS_U8 only (else -1, mi_last_error set).  While on, a load in MI_AUG_RRC mode launches the antialiased kernel (virt = the
+ * input size, window 0) in place of the bilinear one: same plan, same stream, under prefetch and rank slices alike; every other mode is
+ * untouched.  Off by default, and then every launch and bit is what it was.  A batch prefetched under the other choice is dropped.  Not dumped. */
+int mi_batch_set_antialias(Batch *b, int on);
+/* mi_trainer_eval_u8 with the centre crop replaced by torchvision's Resize(resize) + CenterCrop(input) on bytes: every whole image scaled
+ * to resize x resize by the antialiased kernel, of which the window at offset (resize - input) / 2 (integer quotient) on both axes is
+ * scored.  dim_in may be smaller than the input (an upscale).  resize == dim_in gives mi_trainer_eval_u8's records bit for bit.
+ * -1 as mi_trainer_eval_u8 and for resize < input; it shares that call's scratch and honours mi_trainer_eval_use_ema alike. */
+int mi_trainer_eval_u8_resized(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int resize, int topk,
+                               MiLossMetrics *out);
+
 /* ---------------- mixing: mixup and CutMix in place, a two-label loss head ----------------
  * mixup (Zhang et al. 2018) blends every image of a batch with a partner, CutMix (Yun et al. 2019) pastes a box of the partner into it;
  * the loss weighs both images' labels.  The partner of row i is row n - 1 - i (timm's x.flip(0)), one weight lam and one box per batch.

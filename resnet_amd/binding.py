@@ -284,6 +284,10 @@ PROTOTYPES = {
     "mi_trainer_last_mix": (_i, [_T, C.POINTER(MiMixPlan)]),
     "mi_batch_set_augment_rrc": (_i, [_B, _i, _u64, C.c_double, C.c_double, C.c_double, C.c_double]),
     "mi_batch_last_boxes": (_i, [_B, _vp]),
+    "mi_aa_coeffs": (_i, [_i, _i, _i, _vp, _vp, _i]),
+    "mi_op_resample_aa_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+    "mi_batch_set_antialias": (_i, [_B, _i]),
+    "mi_trainer_eval_u8_resized": (_i, [_T, _vp, _vp, C.c_int64, _i, _i, _i, C.POINTER(MiLossMetrics)]),
     "mi_op_convert": (_i, [_vp, _i, _vp, _i, _sz]),
     "mi_bf16_conv_supported": (_i, [_i] * 7),
     "mi_bf16_pw_wgrad_supported": (_i, [_i] * 4),

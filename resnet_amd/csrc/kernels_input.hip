@@ -6,6 +6,7 @@
 // possible values are a table the compiler evaluates in double; every workgroup keeps a copy in LDS.
 #include "mi_common.hpp"
 #include "mi_device.h"
+#include "mi_aa.h"
 
 #define DEC_ROWS 16     // output rows of one image per workgroup
 #define DEC_THREADS 256
@@ -235,6 +236,169 @@ int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *o
                        total, R, rs_src_rows(R, dim_in, dim_out), CH, vec, make_fastdiv((uint32_t)(dim_out >> 2)), make_fastdiv((uint32_t)(dim_out & 3)));
     mi_prof_end((hipStream_t)s);
     MI_LAUNCH_CHECK("resample_u8_kernel");
+    return 0;
+}
+
+// ---- antialiased resize: the box scaled to virt x virt as Pillow's Image.resize(BILINEAR) does it on bytes, a window of it written ----
+// The arithmetic is written down in include/resnet_mi.h ("antialiased resize") and restated in tests/aaref.py; the tap table is mi_aa.h's,
+// the text mi_aa_coeffs compiles for the host.  Two passes, the first rounded to bytes: columns, then rows.
+#define AA_ROWS 16      // output rows of one image per workgroup (fewer where the worst case does not fit into LDS)
+#define AA_THREADS 256
+#define AA_LDS_MAX 65536
+
+// source rows `rows` consecutive output rows can touch on an axis in -> V: the first row's lo > c0 - s - 0.5 and the last row's
+// hi <= c1 + s + 0.5 with c1 - c0 = (rows - 1) in / V and s = max(in / V, 1), so hi - lo < (rows - 1) in / V + 2 s + 1; never more than `in`.
+// It grows with `in`: the launcher sizes for a box as high as the image
+static inline int aa_src_rows(int rows, int in, int V) {
+    const int s = in >= V ? mi_cdiv((long)(rows + 1) * in, V) + 1 : mi_cdiv((long)(rows - 1) * in, V) + 3;
+    return s < in ? s : in;
+}
+// the decode table's conversion of a byte at source position p
+__device__ __forceinline__ float aa_value(int b, int p) {
+    const double mean_of_src[3] = {123.68, 116.78, 103.94}; // as g_decode_table
+    return (float)((double)(float)b - mean_of_src[p]);
+}
+
+// grid (ceil(D / R), n), R rows of the window per workgroup; the window is rows [win_row, + D) x columns [win_col, + D) of the virt x virt
+// image.  LDS: ctab[D] and rtab[R], entries of TS = ks + 2 ints (first tap - first staged column / row, taps, the coefficients); S raw row
+// buffers of CH 16-byte pieces -- box rows lo(first output row) .. hi(last), of each the byte span of columns lo(first window column) ..
+// hi(last), staged from its 16-byte-aligned start as in resample_u8_kernel; S rows of MP bytes of the horizontally filtered window
+// columns (flip folded in), 3 bytes a pixel.  lo and hi never decrease with the output index, so every tap lies in what was staged.
+// R, S, CH and ks come from the launcher, sized for h = w = dim_in; the box is clamped here, so no plan reads outside its image.
+__global__ void __launch_bounds__(AA_THREADS)
+resample_aa_u8_kernel(const uint8_t *__restrict__ src, const int *__restrict__ boxes, float *__restrict__ out, int dim_in, int D, int virt,
+                      int win_row, int win_col, size_t total_bytes, int R, int S, int CH, int ks, int vec, FastDiv fdD, FastDiv fdQ, FastDiv fdT) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char aa_smem[];
+    const int TS = ks + 2, MP = (D * 3 + 3) & ~3;
+    int *ctab = (int *)aa_smem;
+    int *rtab = ctab + (size_t)D * TS;
+    unsigned char *raw = aa_smem + ((((size_t)D + R) * TS * 4 + 15) & ~(size_t)15);
+    unsigned char *mid = raw + (size_t)S * CH * 16;
+    const int tid = threadIdx.x, n = blockIdx.y, h0 = blockIdx.x * R;
+    const int nrows = min(R, D - h0);
+    const int *bx = boxes + 5 * (size_t)n;
+    const int h = min(max(bx[2], 1), dim_in), w = min(max(bx[3], 1), dim_in);
+    const int r0 = min(max(bx[0], 0), dim_in - h), c0 = min(max(bx[1], 0), dim_in - w), flip = bx[4] != 0;
+
+    int ya, yb, xa, xb, unused;
+    mi_aa_bounds(h, virt, win_row + h0, &ya, &unused);
+    mi_aa_bounds(h, virt, win_row + h0 + nrows - 1, &unused, &yb);
+    mi_aa_bounds(w, virt, win_col, &xa, &unused);
+    mi_aa_bounds(w, virt, win_col + D - 1, &unused, &xb);
+    const int nsrc = min(yb - ya, S); // <= S by aa_src_rows; the min keeps LDS addressing safe whatever the arithmetic
+    for (int i = tid; i < D; i += AA_THREADS) {
+        int *e = ctab + (size_t)i * TS, lo;
+        const int taps = mi_aa_taps(w, virt, win_col + (flip ? D - 1 - i : i), &lo, e + 2, ks);
+        e[0] = lo - xa; e[1] = min(taps, ks);
+    }
+    for (int i = tid; i < nrows; i += AA_THREADS) {
+        int *e = rtab + (size_t)i * TS, lo;
+        const int taps = mi_aa_taps(h, virt, win_row + h0 + i, &lo, e + 2, ks);
+        e[0] = lo - ya; e[1] = min(taps, ks);
+    }
+    const int span = (xb - xa) * 3;
+    const size_t g0 = (((size_t)n * dim_in + r0 + ya) * dim_in + c0 + xa) * 3; // first byte of the first staged span
+    const size_t row_pitch = (size_t)dim_in * 3;
+    const int pieces = min((span + 30) >> 4, CH);
+    for (int r = tid >> 6; r < nsrc; r += AA_THREADS / 64) {
+        const size_t g = g0 + (size_t)r * row_pitch;
+        for (int c = tid & 63; c < pieces; c += 64) {
+            const size_t a = (g & ~(size_t)15) + (size_t)c * 16;
+            if (a < g + span) *(uint4 *)(raw + ((size_t)r * CH + c) * 16) = load16_in_batch(src, a, total_bytes);
+        }
+    }
+    __syncthreads();
+
+    // columns: every staged row to the D window columns, rounded to bytes
+    for (int i = tid; i < nsrc * D; i += AA_THREADS) {
+        const int r = (int)fd_div((uint32_t)i, fdD), ox = i - r * D;
+        const int *e = ctab + (size_t)ox * TS;
+        const int taps = e[1];
+        const unsigned char *L = raw + (size_t)r * CH * 16 + ((g0 + (size_t)r * row_pitch) & 15) + e[0] * 3;
+        int s0 = 1 << (MI_AA_BITS - 1), s1 = s0, s2 = s0;
+        for (int j = 0; j < taps; j++) {
+            const int k = e[2 + j];
+            s0 += L[3 * j] * k; s1 += L[3 * j + 1] * k; s2 += L[3 * j + 2] * k;
+        }
+        unsigned char *m = mid + (size_t)r * MP + ox * 3;
+        m[0] = (unsigned char)min(s0 >> MI_AA_BITS, 255); m[1] = (unsigned char)min(s1 >> MI_AA_BITS, 255); m[2] = (unsigned char)min(s2 >> MI_AA_BITS, 255);
+    }
+    __syncthreads();
+
+    // rows: a lane takes 4 consecutive output pixels, 12 bytes = 3 aligned dwords of every tap's row (MP and 3 ox are multiples of 4)
+    const int Q = D >> 2;
+    const size_t plane = (size_t)D * D;
+    float *const out_n = out + (size_t)n * 3 * plane;
+    for (int i = tid; i < nrows * Q; i += AA_THREADS) {
+        const int r = (int)fd_div((uint32_t)i, fdQ), ox = (i - r * Q) * 4;
+        const int *e = rtab + (size_t)r * TS;
+        const int taps = min(e[1], nsrc - e[0]);
+        const unsigned char *M = mid + (size_t)e[0] * MP + ox * 3;
+        int acc[12];
+#pragma unroll
+        for (int t = 0; t < 12; t++) acc[t] = 1 << (MI_AA_BITS - 1);
+        for (int j = 0; j < taps; j++) {
+            const int k = e[2 + j];
+            const uint32_t *m4 = (const uint32_t *)(M + (size_t)j * MP);
+            const uint32_t d[3] = {m4[0], m4[1], m4[2]};
+#pragma unroll
+            for (int t = 0; t < 12; t++) acc[t] += (int)((d[t >> 2] >> (8 * (t & 3))) & 255u) * k;
+        }
+        float v[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+#pragma unroll
+            for (int p = 0; p < 3; p++) v[p][j] = aa_value(min(acc[3 * j + p] >> MI_AA_BITS, 255), p);
+        }
+        float *o = out_n + (size_t)(h0 + r) * D + ox;
+#pragma unroll
+        for (int d3 = 0; d3 < 3; d3++) { // plane d3 (0 = R) holds source position 2 - d3
+            if (vec) *(float4 *)(o + d3 * plane) = make_float4(v[2 - d3][0], v[2 - d3][1], v[2 - d3][2], v[2 - d3][3]);
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; j++) o[d3 * plane + j] = v[2 - d3][j];
+            }
+        }
+    }
+    const int T = D & 3;
+    for (int i = tid; i < nrows * T * 3; i += AA_THREADS) {
+        const int rd = (int)fd_div((uint32_t)i, fdT), ox = 4 * Q + (i - rd * T);
+        const int r = rd / 3, p = 2 - (rd - 3 * r);
+        const int *e = rtab + (size_t)r * TS;
+        const int taps = min(e[1], nsrc - e[0]);
+        const unsigned char *M = mid + (size_t)e[0] * MP + ox * 3 + p;
+        int s = 1 << (MI_AA_BITS - 1);
+        for (int j = 0; j < taps; j++) s += M[(size_t)j * MP] * e[2 + j];
+        out_n[(2 - p) * plane + (size_t)(h0 + r) * D + ox] = aa_value(min(s >> MI_AA_BITS, 255), p);
+    }
+}
+
+int mid_resample_aa_u8(mid_stream s, const uint8_t *src, const int *boxes, float *out, int n, int dim_in, int dim_out, int virt, int win_row,
+                       int win_col) {
+    const char *who = "mid_resample_aa_u8";
+    if (n < 1 || n > 65535 || dim_out < 1 || dim_out > 16384 || dim_in < 1 || dim_in > 16384 || virt < 1 || virt > 16384) {
+        mi_record_error(who, "need 1 <= n <= 65535 and 1 <= dim_in, dim_out, virt <= 16384"); return -1;
+    }
+    if (win_row < 0 || win_col < 0 || win_row > virt - dim_out || win_col > virt - dim_out) { mi_record_error(who, "the window leaves [0, virt]"); return -1; }
+    if (((uintptr_t)src & 15) != 0) { mi_record_error(who, "src must be 16-byte aligned"); return -1; }
+    if (((uintptr_t)out & 3) != 0 || ((uintptr_t)boxes & 3) != 0) { mi_record_error(who, "out / boxes must be 4-byte aligned"); return -1; }
+    const int CH = (dim_in * 3 + 15 + 15) / 16; // 16-byte pieces the widest span can touch once its start is rounded down
+    const int ks = mi_aa_ksize(dim_in, virt), MP = (dim_out * 3 + 3) & ~3;
+    int R = dim_out < AA_ROWS ? dim_out : AA_ROWS;
+    size_t lds;
+    for (;; R--) { // LDS for the worst case h = w = dim_in: the box is known on the device only
+        lds = ((((size_t)dim_out + R) * (ks + 2) * 4 + 15) & ~(size_t)15) + (size_t)aa_src_rows(R, dim_in, virt) * ((size_t)CH * 16 + MP);
+        if (lds <= AA_LDS_MAX || R == 1) break;
+    }
+    if (lds > AA_LDS_MAX) { mi_record_error(who, "dim_in too large: tables and source rows of one output row do not fit into LDS"); return -2; }
+    const int vec = (dim_out & 3) == 0 && ((uintptr_t)out & 15) == 0;
+    const size_t total = (size_t)n * dim_in * dim_in * 3;
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 15.0 * n * dim_out * dim_out); // algorithmic, as the decode: 3 bytes in, 12 out per output pixel
+    hipLaunchKernelGGL(resample_aa_u8_kernel, dim3(mi_cdiv(dim_out, R), n), dim3(AA_THREADS), lds, (hipStream_t)s, src, boxes, out, dim_in, dim_out,
+                       virt, win_row, win_col, total, R, aa_src_rows(R, dim_in, virt), CH, ks, vec, make_fastdiv((uint32_t)dim_out),
+                       make_fastdiv((uint32_t)(dim_out >> 2)), make_fastdiv((uint32_t)(dim_out & 3)));
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK("resample_aa_u8_kernel");
     return 0;
 }
 

@@ -7,7 +7,8 @@
  * stays resident in HBM) because the reference's /mnt/storage paths are literals.
  * MI_SRC_SHARDS_U8 (new work, no counterpart in the reference): the shard holds whole uint8 images; the crop is drawn per load by
  * mi_augment_plan and made, with the flip and the float conversion, by the decode kernel (kernels_input.hip).  MI_AUG_RRC: the plan
- * is a box per image (mi_augment_plan_rrc) and the resample kernel scales it to the input size.
+ * is a box per image (mi_augment_plan_rrc) and the resample kernel scales it to the input size -- the two-tap bilinear one, or with
+ * mi_batch_set_antialias the one that filters as Pillow does.
  */
 #define _GNU_SOURCE
 #include <math.h>
@@ -15,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "mi_host.h"
+#include "mi_aa.h"
 
 static BatchExt *g_ext = NULL;
 BatchExt *mi_batch_ext(Batch *b) {
@@ -117,6 +119,19 @@ int mi_batch_set_augment_rrc(Batch *b, int flip, uint64_t seed, double scale_lo,
     e->rrc_scale[0] = scale_lo; e->rrc_scale[1] = scale_hi; e->rrc_ratio[0] = ratio_lo; e->rrc_ratio[1] = ratio_hi;
     e->have_next = 0; e->have_plan = 0; /* a batch prefetched under the old choice; a plan of the other shape */
     return 0;
+}
+int mi_batch_set_antialias(Batch *b, int on) {
+    BatchExt *e = mi_batch_ext(b);
+    if (e->source != MI_SRC_SHARDS_U8) { mi_record_host_error("mi_batch_set_antialias", "the data source is not MI_SRC_SHARDS_U8"); return -1; }
+    if (e->have_next) mid_event_sync(e->ev_next); /* the batch prefetched under the old choice still reads the pinned set */
+    e->rrc_antialias = on != 0;
+    e->have_next = 0;
+    return 0;
+}
+/* the host's copy of the kernel's tap table (mi_aa.h: the same text) */
+int mi_aa_coeffs(int in, int V, int o, int *xmin, int *K, int cap) {
+    if (in < 1 || V < 1 || o < 0 || o >= V || !xmin || (!K && cap > 0)) { mi_record_host_error("mi_aa_coeffs", "need in, V >= 1, 0 <= o < V and the two outputs"); return -1; }
+    return mi_aa_taps(in, V, o, xmin, K, cap < 0 ? 0 : cap);
 }
 int mi_batch_last_plan(const Batch *b, int *out) {
     BatchExt *e = mi_batch_ext((Batch *)b);
@@ -281,7 +296,8 @@ static void u8_enqueue(Batch *b, BatchExt *e, int bi, int k, mid_stream s, float
     mid_memcpy_h2d(labels_dev, labels_host, (size_t)N * sizeof(int), s);
     const int rrc = e->aug_mode == MI_AUG_RRC;
     mid_memcpy_h2d(e->plan_dev[k], e->plan_pinned[k], (size_t)N * (rrc ? 5 : 3) * sizeof(int), s);
-    if (rrc) mid_resample_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim);
+    if (rrc && e->rrc_antialias) mid_resample_aa_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim, b->image_dim, 0, 0);
+    else if (rrc) mid_resample_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim);
     else mid_decode_u8(s, e->u8_dev[k], e->plan_dev[k], images, N, e->u8_dim_in, b->image_dim);
 }
 /* the plan of this rank's batch bi of the resident shard at `epoch` into plan_pinned[k]; 0, or -1 with a message */

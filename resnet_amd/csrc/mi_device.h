@@ -332,6 +332,10 @@ int mid_nchw_to_nhwc(mid_stream s, const float *in, float *out, int N, int C, in
 int mid_decode_u8(mid_stream s, const uint8_t *src, const int *plan, float *out, int n, int dim_in, int dim_out);
 /* boxes [n][5] (row0, col0, h, w, flip), clamped into the image; each box resampled to dim_out^2.  -2: dim_in too large for LDS */
 int mid_resample_u8(mid_stream s, const uint8_t *src, const int *boxes, float *out, int n, int dim_in, int dim_out);
+/* the same boxes scaled to virt^2 as Pillow's Image.resize(BILINEAR) scales bytes (antialiased; include/resnet_mi.h), of which the window of
+ * rows [win_row, + dim_out) x columns [win_col, + dim_out) is written.  -1: sizes, alignment, a window that leaves [0, virt]; -2: LDS */
+int mid_resample_aa_u8(mid_stream s, const uint8_t *src, const int *boxes, float *out, int n, int dim_in, int dim_out, int virt, int win_row,
+                       int win_col);
 /* mixup / CutMix in place on fp32 NCHW images [n][3][dim][dim], row i paired with row n - 1 - i (the middle row of an odd n is not touched).
  * mode 0: nothing is launched.  1: a' = lam a + (1.f - lam) b and b' likewise, every operation rounded on its own.  2: the box rows
  * [y0, y1) x columns [x0, x1) of every plane changes places, clamped into the image on the device; an empty box launches nothing.

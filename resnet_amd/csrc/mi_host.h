@@ -42,6 +42,7 @@ typedef struct BatchExt {
      * buffer set (0: the blocking load / the batch in use, 1: the prefetched next batch; swapped with the images) a pinned and a
      * device staging buffer for the batch's bytes and for its plan */
     int u8_dim_in, aug_mode, aug_flip, u8_have_crops, have_plan, next_epoch;
+    int rrc_antialias;           /* MI_AUG_RRC: the boxes go through the antialiased kernel (mi_batch_set_antialias) */
     uint64_t aug_seed;
     double rrc_scale[2], rrc_ratio[2]; /* MI_AUG_RRC: area share and aspect ratio, (lo, hi) each */
     uint8_t *u8_shard;           /* host, shard_n_images * dim_in^2 * 3 */

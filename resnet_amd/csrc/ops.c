@@ -242,6 +242,10 @@ int mi_op_decode_u8(const uint8_t *src_dev, const int *plan_dev, float *out_nchw
 int mi_op_resample_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_nchw, int n, int dim_in, int dim_out) {
     return finish(mid_resample_u8(mi_global()->compute, src_dev, boxes_dev, out_nchw, n, dim_in, dim_out));
 }
+int mi_op_resample_aa_u8(const uint8_t *src_dev, const int *boxes_dev, float *out_nchw, int n, int dim_in, int dim_out, int virt, int win_row,
+                         int win_col) {
+    return finish(mid_resample_aa_u8(mi_global()->compute, src_dev, boxes_dev, out_nchw, n, dim_in, dim_out, virt, win_row, win_col));
+}
 int mi_op_mix_batch(float *images_nchw, int n, int image_size, int dim, const MiMixPlan *plan_host) {
     if (!plan_host) { mi_record_host_error("mi_op_mix_batch", "plan_host is NULL"); return -1; }
     if (image_size < 1) { mi_record_host_error("mi_op_mix_batch", "image_size = 3 dim^2"); return -1; }

@@ -1047,33 +1047,37 @@ static void ev8_free(MiCtx *c) {
     c->ev8_images = NULL; c->ev8_bytes_dev = NULL; c->ev8_labels_dev = NULL; c->ev8_plan_dev = NULL;
     c->ev8_bytes_pinned = NULL; c->ev8_labels_pinned = NULL; c->ev8_plan_pinned = NULL; c->ev8_dim_in = 0;
 }
-static int eval_u8_batches(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk) {
+/* resize 0: the centre crop through the decode kernel; else the whole image scaled to resize^2 (antialiased), the centre window of that */
+static int eval_u8_batches(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int resize, int topk) {
     MiCtx *c = ctx_of(t);
     const int N = t->batch_size, D = t->model->dims->input;
     const size_t img = (size_t)dim_in * dim_in * 3, out_img = (size_t)D * D * 3;
     for (int64_t at = 0; at < n; at += N) {
         const int nv = n - at < N ? (int)(n - at) : N;
         if (at) mid_event_sync(c->ev8_copied); /* the pinned set is free again once the last batch's copies have left it */
-        if (mi_augment_plan(MI_AUG_CENTER, 0, 0, 0, at, nv, dim_in, D, NULL, c->ev8_plan_pinned)) return -1;
+        if (resize) for (int i = 0; i < nv; i++) { int *bx = c->ev8_plan_pinned + 5 * i; bx[0] = bx[1] = bx[4] = 0; bx[2] = bx[3] = dim_in; }
+        else if (mi_augment_plan(MI_AUG_CENTER, 0, 0, 0, at, nv, dim_in, D, NULL, c->ev8_plan_pinned)) return -1;
         memcpy(c->ev8_bytes_pinned, images_host + (size_t)at * img, (size_t)nv * img);
         memcpy(c->ev8_labels_pinned, labels_host + at, (size_t)nv * sizeof(int));
         mid_memcpy_h2d(c->ev8_bytes_dev, c->ev8_bytes_pinned, (size_t)nv * img, G.compute);
         mid_memcpy_h2d(c->ev8_labels_dev, c->ev8_labels_pinned, (size_t)nv * sizeof(int), G.compute);
-        mid_memcpy_h2d(c->ev8_plan_dev, c->ev8_plan_pinned, (size_t)nv * 3 * sizeof(int), G.compute);
+        mid_memcpy_h2d(c->ev8_plan_dev, c->ev8_plan_pinned, (size_t)nv * (resize ? 5 : 3) * sizeof(int), G.compute);
         mid_event_record(c->ev8_copied, G.compute);
-        if (mid_decode_u8(G.compute, c->ev8_bytes_dev, c->ev8_plan_dev, c->ev8_images, nv, dim_in, D)) return -1;
+        if (resize ? mid_resample_aa_u8(G.compute, c->ev8_bytes_dev, c->ev8_plan_dev, c->ev8_images, nv, dim_in, D, resize, (resize - D) / 2, (resize - D) / 2) :
+            mid_decode_u8(G.compute, c->ev8_bytes_dev, c->ev8_plan_dev, c->ev8_images, nv, dim_in, D)) return -1;
         if (nv < N) mid_memset(c->ev8_images + (size_t)nv * out_img, 0, (size_t)(N - nv) * out_img * sizeof(float), G.compute);
         if (mi_trainer_eval_forward(t, c->ev8_images, c->ev8_labels_dev, nv, topk)) return -1;
     }
     return 0;
 }
-int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk, MiLossMetrics *out) {
+static int eval_u8(Train_ResNet *t, const char *who, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int resize, int topk,
+                   MiLossMetrics *out) {
     MiCtx *c = ctx_of(t);
-    const char *who = "mi_trainer_eval_u8";
     const int N = t->batch_size, D = t->model->dims->input;
     if (eval_args_ok(t, who, 1, topk)) return -1;
     if (!images_host || !labels_host || n < 1) { mi_record_host_error(who, "images, labels and n >= 1 are needed"); return -1; }
-    if (dim_in < D) { mi_record_host_error(who, "dim_in is smaller than the network's input"); return -1; }
+    if (!resize && dim_in < D) { mi_record_host_error(who, "dim_in is smaller than the network's input"); return -1; }
+    if (dim_in < 1) { mi_record_host_error(who, "dim_in >= 1 is needed"); return -1; }
     const size_t img = (size_t)dim_in * dim_in * 3, out_img = (size_t)D * D * 3;
     if (c->ev8_dim_in != dim_in) {
         mid_device_sync();
@@ -1081,10 +1085,10 @@ int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *l
         c->ev8_images = (float *)mid_malloc((size_t)N * out_img * sizeof(float));
         c->ev8_bytes_dev = (uint8_t *)mid_malloc((size_t)N * img);
         c->ev8_labels_dev = (int *)mid_malloc((size_t)N * sizeof(int));
-        c->ev8_plan_dev = (int *)mid_malloc((size_t)N * 3 * sizeof(int));
+        c->ev8_plan_dev = (int *)mid_malloc((size_t)N * 5 * sizeof(int)); /* a box plan at most */
         c->ev8_bytes_pinned = (uint8_t *)mid_malloc_host((size_t)N * img);
         c->ev8_labels_pinned = (int *)mid_malloc_host((size_t)N * sizeof(int));
-        c->ev8_plan_pinned = (int *)mid_malloc_host((size_t)N * 3 * sizeof(int));
+        c->ev8_plan_pinned = (int *)mid_malloc_host((size_t)N * 5 * sizeof(int));
         if (!c->ev8_images || !c->ev8_bytes_dev || !c->ev8_labels_dev || !c->ev8_plan_dev || !c->ev8_bytes_pinned || !c->ev8_labels_pinned ||
             !c->ev8_plan_pinned) { ev8_free(c); mi_record_host_error(who, "allocation of the staging buffers failed"); return -1; }
         if (!c->ev8_copied) c->ev8_copied = mid_event_create();
@@ -1092,13 +1096,21 @@ int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *l
     }
     mid_memset(c->eval_metrics + 1, 0, sizeof(mid_loss_metrics), G.compute);
     c->ema_swapped = ema_exchange(t); /* the averaged model: one exchange around the whole loop, not one per batch */
-    const int rc = eval_u8_batches(t, images_host, labels_host, n, dim_in, topk);
+    const int rc = eval_u8_batches(t, images_host, labels_host, n, dim_in, resize, topk);
     if (c->ema_swapped) { c->ema_swapped = 0; ema_exchange(t); }
     if (rc) return -1;
     MiLossMetrics total;
     if (mi_trainer_eval_metrics(t, NULL, &total, 0)) return -1; /* the one synchronise */
     if (out) *out = total;
     return 0;
+}
+int mi_trainer_eval_u8(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int topk, MiLossMetrics *out) {
+    return eval_u8(t, "mi_trainer_eval_u8", images_host, labels_host, n, dim_in, 0, topk, out);
+}
+int mi_trainer_eval_u8_resized(Train_ResNet *t, const uint8_t *images_host, const int *labels_host, int64_t n, int dim_in, int resize, int topk,
+                               MiLossMetrics *out) {
+    if (resize < t->model->dims->input) { mi_record_host_error("mi_trainer_eval_u8_resized", "resize is smaller than the network's input"); return -1; }
+    return eval_u8(t, "mi_trainer_eval_u8_resized", images_host, labels_host, n, dim_in, resize, topk, out);
 }
 
 /* ---------------------------------------------------------------------------------------------- */

@@ -144,6 +144,22 @@ class Ops:
         img = out[:total].reshape(n, 3, dim_out, dim_out)
         return (img, out[total:]) if pad_floats else img
 
+    def resample_aa_u8(self, src, boxes, dim_out, virt=None, win=(0, 0), pad_floats=0, fill=0.0):
+        """as resample_u8, antialiased (mi_op_resample_aa_u8): every box is scaled to virt x virt (default dim_out) as Pillow's
+        Image.resize(BILINEAR) scales bytes, and the window of dim_out rows and columns at win = (row, column), or one int for both, is
+        written.  pad_floats, fill: as decode_u8"""
+        src = np.ascontiguousarray(src, np.uint8)
+        n, dim_in = src.shape[0], src.shape[1]
+        virt = dim_out if virt is None else virt
+        win_row, win_col = (win, win) if np.isscalar(win) else win
+        total = n * 3 * dim_out * dim_out
+        dsrc, dbox = self.dev(src), self.dev(np.ascontiguousarray(boxes, np.int32))
+        dout = self.dev(np.full(total + pad_floats, fill, np.float32))
+        self._chk(self.L.mi_op_resample_aa_u8(dsrc.ptr, dbox.ptr, dout.ptr, n, dim_in, dim_out, int(virt), int(win_row), int(win_col)), "resample_aa_u8")
+        out = dout.get()
+        img = out[:total].reshape(n, 3, dim_out, dim_out)
+        return (img, out[total:]) if pad_floats else img
+
     def maxpool_fwd(self, x, k, stride):
         N, Cc, H, _ = x.shape
         Ho = H // stride

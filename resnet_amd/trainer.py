@@ -169,16 +169,21 @@ class Trainer:
             self._refused("mi_trainer_eval_metrics")
         return last.as_dict(), total.as_dict()
 
-    def evaluate_u8(self, images_u8, labels, dim_in, topk=5):
+    def evaluate_u8(self, images_u8, labels, dim_in, topk=5, resize=None):
         """a whole array of dim_in x dim_in x 3 (B,G,R) byte images: centre crop, decode and eval pass per batch on the device; the
-        totals as a dict (loss_sum, rows, wrong_top1, wrong_topk, batches)"""
+        totals as a dict (loss_sum, rows, wrong_top1, wrong_topk, batches).  resize: every image is first scaled to resize x resize as
+        Pillow's BILINEAR does (antialiased) and the centre crop is taken from that (mi_trainer_eval_u8_resized)"""
         images_u8 = np.ascontiguousarray(images_u8, np.uint8)
         labels = np.ascontiguousarray(labels, np.int32)
         n = labels.size
         if images_u8.size != n * dim_in * dim_in * 3:
             raise ValueError("images_u8 does not hold %d images of %d x %d x 3 bytes" % (n, dim_in, dim_in))
         out = B.MiLossMetrics()
-        if self.L.mi_trainer_eval_u8(self.t, images_u8.ctypes.data, labels.ctypes.data, n, int(dim_in), int(topk), C.byref(out)) != 0:
+        if resize is not None:
+            if self.L.mi_trainer_eval_u8_resized(self.t, images_u8.ctypes.data, labels.ctypes.data, n, int(dim_in), int(resize), int(topk),
+                                                 C.byref(out)) != 0:
+                self._refused("mi_trainer_eval_u8_resized")
+        elif self.L.mi_trainer_eval_u8(self.t, images_u8.ctypes.data, labels.ctypes.data, n, int(dim_in), int(topk), C.byref(out)) != 0:
             self._refused("mi_trainer_eval_u8")
         return out.as_dict()
 
@@ -339,10 +344,13 @@ class Trainer:
 
     AUGMENTS = {"fixed": B.MI_AUG_FIXED, "center": B.MI_AUG_CENTER, "random": B.MI_AUG_RANDOM, "rrc": B.MI_AUG_RRC}
 
-    def source_shards_u8(self, shard_dir, dim_in, augment="fixed", flip=True, seed=0, prefetch=False, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3)):
+    def source_shards_u8(self, shard_dir, dim_in, augment="fixed", flip=True, seed=0, prefetch=False, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3),
+                         antialias=False):
         """uint8 shards of whole dim_in x dim_in images (mi_build_shard_u8); crop, flip and float conversion on the device at
         every load.  augment: "fixed" (the shard's .crops, the reference's pixels), "center", "random" (a new draw per epoch) or "rrc"
-        (random-resized crop: a box of `scale` of the image's area and aspect `ratio`, resampled to the input size; a new draw per epoch)"""
+        (random-resized crop: a box of `scale` of the image's area and aspect `ratio`, resampled to the input size; a new draw per epoch).
+        antialias: the "rrc" boxes are scaled as Pillow's BILINEAR scales them (the filter widened by the scale factor), not by the
+        two-tap gather"""
         self.L.mi_batch_source_shards_u8(self.c_batch, shard_dir.encode(), int(dim_in))
         if self.AUGMENTS[augment] == B.MI_AUG_RRC:
             rc, what = self.L.mi_batch_set_augment_rrc(self.c_batch, int(bool(flip)), int(seed), float(scale[0]), float(scale[1]),
@@ -353,6 +361,7 @@ class Trainer:
             e = self.error()
             self.L.mi_clear_error()
             raise RuntimeError(what + e)
+        self.L.mi_batch_set_antialias(self.c_batch, int(bool(antialias)))
         if prefetch:
             self.L.mi_batch_set_prefetch(self.c_batch, 1)
         self.check()

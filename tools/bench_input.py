@@ -7,11 +7,14 @@
    --runs launches after warm-up.  GB/s over the algorithmic bytes: decode N dim_out^2 (3 + 12), re-layout N dim_out^2 3 (4 + 4).
    Beside them the resample kernel of the random-resized crop (mi_op_resample_u8) on the boxes mi_augment_plan_rrc draws with the
    default bounds (scale 0.08 .. 1, ratio 3/4 .. 4/3): its bytes are the boxes' 3 h w in and the same 12 N dim_out^2 out.
+   Then the antialiased kernel (mi_op_resample_aa_u8) beside the bilinear one, alternating, at 256 -> 224 and 256 -> 176, on
+   whole-image boxes (the strongest downscale) and on the RRC plan's boxes: same bytes, so the ratio of the two is the price of the filter.
 2. The whole training step on the real data path: ResNet-50 at batch 256, fp32 and bf16 storage, from (a) the synthetic pool resident
    in HBM, (b) fp32 NCHW shards with prefetch, (c) uint8 shards, RANDOM crops with flips, with prefetch, (d) the same uint8 shard
-   with random-resized crops (u8 rrc).  Both shards are built from the same seeded class files in a temporary directory; one shard
-   holds every timed step, so no step reads a file.  Legs (b), (c) and (d) run three times each, alternating, which gives every leg
-   the run-to-run spread the comparisons are read against: (c) against (b), (d) against (c).
+   with random-resized crops (u8 rrc), (e) the same with antialias on (u8 rrc aa).  Both shards are built from the same seeded class
+   files in a temporary directory; one shard holds every timed step, so no step reads a file.  Legs (b) to (e) run three times each,
+   alternating, which gives every leg the run-to-run spread the comparisons are read against: (c) against (b), (d) against (c); (e) is
+   reported beside (d), no threshold is set for it.
 3. Host and device bytes of the two shard sources.
   python tools/bench_input.py [--runs 30] [--steps 16] [--warmup 3] [--skip-steps]
 Exit status 1 if the decode is slower than the re-layout, the uint8 leg slower than the fp32-shard leg by more than that spread, or
@@ -90,6 +93,46 @@ def bench_kernels(runs, warmup=3):
     return res
 
 
+def bench_resample(runs, warmup=3):
+    """the bilinear and the antialiased resample side by side: dim_out 224 and 176, whole-image and RRC-plan boxes"""
+    ops = Ops()
+    L = ops.L
+    src = ops.dev(np.random.default_rng(0).integers(0, 256, size=(N, DIM_IN, DIM_IN, 3), dtype=np.uint8))
+    rrc = np.empty((N, 5), np.int32)
+    assert L.mi_augment_plan_rrc(1, 7, 0, 0, N, DIM_IN, 0.08, 1.0, 3 / 4, 4 / 3, rrc.ctypes.data) == 0
+    whole = np.tile(np.array([0, 0, DIM_IN, DIM_IN, 0], np.int32), (N, 1))
+    whole[::2, 4] = 1
+    res = {}
+    L.mi_prof_enable(1 << FAMILY)
+    for D in (224, 176):
+        out = ops.dev(shape=(N, 3, D, D))
+        for name, boxes in (("whole", whole), ("rrc", rrc)):
+            dbox = ops.dev(boxes)
+            legs = {"resample_u8": lambda: L.mi_op_resample_u8(src.ptr, dbox.ptr, out.ptr, N, DIM_IN, D),
+                    "resample_aa_u8": lambda: L.mi_op_resample_aa_u8(src.ptr, dbox.ptr, out.ptr, N, DIM_IN, D, D, 0, 0)}
+            ms = {k: [] for k in legs}
+            for i in range(warmup + runs):
+                for k, fn in legs.items():
+                    L.mi_prof_reset()
+                    assert fn() == 0, L.mi_last_error().decode()
+                    t = family_ms(L)
+                    if i >= warmup:
+                        ms[k].append(t)
+            byt = int(3 * (boxes[:, 2].astype(np.int64) * boxes[:, 3]).sum()) + N * D * D * 12
+            r = {}
+            for k in legs:
+                med = float(np.median(ms[k]))
+                r[k] = dict(ms=round(med, 4), ms_min=round(float(np.min(ms[k])), 4), ms_max=round(float(np.max(ms[k])), 4),
+                            gb_per_s=round(byt / (med * 1e-3) / 1e9, 1))
+                print("%-15s 256 -> %d, %-5s boxes %8.4f ms (min %.4f, max %.4f; %d runs)  %7.1f GB/s" %
+                      (k, D, name, med, r[k]["ms_min"], r[k]["ms_max"], len(ms[k]), r[k]["gb_per_s"]))
+            r["algorithmic_bytes"] = byt
+            r["aa_over_bilinear"] = round(r["resample_aa_u8"]["ms"] / r["resample_u8"]["ms"], 3)
+            res["%d_%s" % (D, name)] = r
+    L.mi_prof_enable(0)
+    return res
+
+
 def build_shards(root, per_shard):
     """seeded class files -> one fp32 NCHW shard and one uint8 shard of the same images (the library's two writers)"""
     L = B.load()
@@ -122,6 +165,8 @@ def time_leg(kind, dtype, dirs, per_shard, steps, warmup):
             tr.source_synthetic(1234, 1235, pool_batches=2)
         elif kind == "f32_shards":
             tr.source_shards(dirs[0], B.MI_LAYOUT_NCHW, prefetch=True)
+        elif kind == "u8_rrc_aa":
+            tr.source_shards_u8(dirs[1], DIM_IN, augment="rrc", flip=True, seed=7, prefetch=True, antialias=True)
         elif kind == "u8_rrc":
             tr.source_shards_u8(dirs[1], DIM_IN, augment="rrc", flip=True, seed=7, prefetch=True)
         else:
@@ -149,7 +194,7 @@ def bench_steps(steps, warmup):
     try:
         f32, u8, sizes = build_shards(root, per_shard)
         for dtype in ("f32", "bf16"):
-            kinds = ("f32_shards", "u8_shards", "u8_rrc")
+            kinds = ("f32_shards", "u8_shards", "u8_rrc", "u8_rrc_aa")
             r = {k: [] for k in kinds}
             r["synthetic"], dev = time_leg("synthetic", dtype, (f32, u8), per_shard, steps, warmup)
             for _ in range(3):
@@ -163,9 +208,10 @@ def bench_steps(steps, warmup):
                               gap_to_synthetic={k: round(1 - best[k] / r["synthetic"], 4) for k in best},
                               u8_ge_f32_shards=best["u8_shards"] >= best["f32_shards"] - spread,
                               rrc_ge_random=best["u8_rrc"] >= best["u8_shards"] - spreads["u8_shards"], trainer_device_bytes=dev)
-            print("%-4s synthetic %.1f img/s, fp32 shards %s, uint8 shards %s, uint8 rrc %s (spread of repeats %.1f, of the uint8 leg %.1f)" %
+            print("%-4s synthetic %.1f img/s, fp32 shards %s, uint8 shards %s, uint8 rrc %s, uint8 rrc antialiased %s (spread of repeats %.1f, of "
+                  "the uint8 leg %.1f)" %
                   (dtype, r["synthetic"], ["%.1f" % x for x in r["f32_shards"]], ["%.1f" % x for x in r["u8_shards"]],
-                   ["%.1f" % x for x in r["u8_rrc"]], spread, spreads["u8_shards"]))
+                   ["%.1f" % x for x in r["u8_rrc"]], ["%.1f" % x for x in r["u8_rrc_aa"]], spread, spreads["u8_shards"]))
         img_in, img_out = DIM_IN * DIM_IN * 3, DIM_OUT * DIM_OUT * 3 * 4
         res["bytes"] = dict(
             shard_files=sizes, images_per_shard=per_shard,
@@ -188,6 +234,7 @@ def main():
     if B.load().mi_device_count() < 1:
         raise RuntimeError("bench_input needs a HIP device")
     out = {"kernels": bench_kernels(max(a.runs, 20))}
+    out["resample"] = bench_resample(max(a.runs, 20))
     ok = out["kernels"]["decode_le_nhwc"]
     if not a.skip_steps:
         out["steps"] = bench_steps(max(a.steps, 16), a.warmup)
