@@ -22,6 +22,7 @@ MIX = "tests/test_gpu_mix.py::"
 EMA = "tests/test_gpu_ema.py::"
 ACC = "tests/test_gpu_accum.py::"
 LOSS = "tests/test_gpu_loss_head.py::"
+AA = "tests/test_gpu_input_aa.py::"
 
 MUTANTS = []
 
@@ -442,6 +443,99 @@ _m("resample_tail_no_row_weight", "kernels_input.hip",
    "the scalar tail columns of the resample (dim_out % 4 of them) ignore the vertical weight",
    "the last dim_out % 4 columns of a row",
    ["tests/test_gpu_input_rrc.py::test_resample_sweep[37-30-1]"])
+
+# resample_aa_u8_kernel.  mi_aa.h takes no mutant (the one header slot is mi_common.hpp's, and loader.c compiles the same text): a fault
+# in the table's arithmetic is planted where the kernel stores the table.  e[0] (first tap) and e[1] (tap count) are an address and a
+# bound and are never touched; the coefficients e[2 ...] are values.  The cases are (dim_in, virt, dim_out, window) of AA + CASES;
+# tests/test_input_aa.py restates every entry in the numpy model and holds, without a GPU, that each killer's own inputs separate it.
+_m("aa_col_truncates", "kernels_input.hip",
+   "int s0 = 1 << (MI_AA_BITS - 1), s1 = s0, s2 = s0;",
+   "int s0 = 0, s1 = s0, s2 = s0;",
+   "the column pass of the antialiased resize starts its three sums at 0 instead of 2^21: it truncates where Pillow rounds",
+   "resample_aa_u8_kernel, the column pass, every element",
+   [AA + "test_sweep[9-4-4-0]"])
+_m("aa_row_truncates", "kernels_input.hip",
+   "for (int t = 0; t < 12; t++) acc[t] = 1 << (MI_AA_BITS - 1);",
+   "for (int t = 0; t < 12; t++) acc[t] = 0;",
+   "the row pass starts the twelve sums of a quad at 0 instead of 2^21: every column but the last dim_out % 4",
+   "resample_aa_u8_kernel, the row pass over quads",
+   [AA + "test_sweep[9-4-4-0]"])
+_m("aa_tail_truncates", "kernels_input.hip",
+   "int s = 1 << (MI_AA_BITS - 1);",
+   "int s = 0;",
+   "the scalar tail of the row pass starts its sum at 0 instead of 2^21: the last dim_out % 4 columns",
+   "resample_aa_u8_kernel, the row pass over the last dim_out % 4 columns",
+   [AA + "test_sweep[33-7-7-0]"])
+_m("aa_value_r_plane_b_mean", "kernels_input.hip",
+   "103.94}; // as g_decode_table\n    return (float)((double)(float)b - mean_of_src[p]);",
+   "123.68}; // as g_decode_table\n    return (float)((double)(float)b - mean_of_src[p]);",
+   "aa_value's own mean table takes the B mean for source position 2: the R plane of every image",
+   "aa_value, one of three planes",
+   [AA + "test_sweep[8-1-1-0]"])
+_m("aa_scalar_store_lane3", "kernels_input.hip",
+   "for (int j = 0; j < 4; j++) o[d3 * plane + j] = v[2 - d3][j];",
+   "for (int j = 0; j < 4; j++) o[d3 * plane + j] = v[2 - d3][j] + (j == 3 ? 0.0625f : 0.f);",
+   "the element-wise store of a quad (vec == 0) adds 2^-4 to its fourth value: every fourth column where out is off a 16-byte boundary or "
+   "dim_out % 4 != 0",
+   "resample_aa_u8_kernel, the row pass over quads, the element-wise stores",
+   [AA + "test_sweep[33-7-7-0]", AA + "test_into_an_output_one_float_off_alignment[32-8-8-0]"])
+_m("aa_ctab_first_coeff_low", "kernels_input.hip",
+   "e[0] = lo - xa; e[1] = min(taps, ks);",
+   "e[0] = lo - xa; e[1] = min(taps, ks); e[2] -= (e[1] > 1);",
+   "the first coefficient of every column-table entry with more than one tap is one unit of 2^-22 low: only outputs whose column sum lies "
+   "within one byte value of a rounding boundary change, so only tie-prone ratios see it",
+   "resample_aa_u8_kernel, the column table as stored",
+   # CPU pre-check (tests/test_input_aa.py), elements of the three whole+corner images that change: 340 / 357 / 75 of 1728 each at
+   # 16 -> 24, 250 / 222 / 133 of 8112 at 64 -> 58; none in the whole images at 9 -> 4 and 33 -> 7
+   [AA + "test_sweep[16-24-24-0]", AA + "test_sweep[64-58-52-3]"])
+_m("aa_rtab_last_coeff_high", "kernels_input.hip",
+   "e[0] = lo - ya; e[1] = min(taps, ks);",
+   "e[0] = lo - ya; e[1] = min(taps, ks); e[2 + e[1] - 1] += (e[1] > 1);",
+   "the last coefficient of every row-table entry with more than one tap is one unit of 2^-22 high (e[1] >= 1 is the count of coefficients "
+   "the entry holds: the store stays inside it): as aa_ctab_first_coeff_low, vertical",
+   "resample_aa_u8_kernel, the row table as stored",
+   # CPU pre-check: 86 / 86 / 21 elements at 16 -> 24, 85 / 94 / 50 at 64 -> 58
+   [AA + "test_sweep[16-24-24-0]", AA + "test_sweep[64-58-52-3]"])
+_m("aa_col_blue_first_tap_zero", "kernels_input.hip",
+   "s0 += L[3 * j] * k;",
+   "s0 += L[3 * j] * (j == 0 ? 0 : k);",
+   "the column pass multiplies the first tap of source channel 0 by 0: the B plane",
+   "resample_aa_u8_kernel, the column pass, one source channel",
+   [AA + "test_sweep[9-4-4-0]"])
+_m("aa_row_second_turn_plus_one", "kernels_input.hip",
+   "v[p][j] = aa_value(min(acc[3 * j + p] >> MI_AA_BITS, 255), p);",
+   "v[p][j] = aa_value(min(acc[3 * j + p] >> MI_AA_BITS, 255) + (i >= AA_THREADS ? 1 : 0), p);",
+   "quads a thread of the row pass reaches after its first (i >= 256) come out one byte value high: rows and quads past item 255 of a "
+   "workgroup",
+   "the second and later grid-stride turns of the row pass (R (dim_out / 4) > 256: dim_out >= 68)",
+   # 16 x 17 = 272 items: the last 16 quads of row 15 of every full workgroup; 15 x 25 = 375 items under R = 15
+   [AA + "test_sweep[100-68-68-0]", AA + "test_sweep[294-100-100-0]"])
+_m("aa_ctab_past_256_first_tap_zero", "kernels_input.hip",
+   "e[0] = lo - xa; e[1] = min(taps, ks);",
+   "e[0] = lo - xa; e[1] = min(taps, ks); e[2] = i >= AA_THREADS ? 0 : e[2];",
+   "column-table entries a thread fills after its first (i >= 256) get first coefficient 0: window columns 256 and up, or columns "
+   "0 .. dim_out - 257 of a flipped image",
+   "the second grid-stride turn of the column-table fill (dim_out > 256)",
+   [AA + "test_sweep[300-260-260-0]"])
+_m("aa_stage_pieces_past_64_zero", "kernels_input.hip",
+   "*(uint4 *)(raw + ((size_t)r * CH + c) * 16) = load16_in_batch(src, a, total_bytes);",
+   "*(uint4 *)(raw + ((size_t)r * CH + c) * 16) = c >= 64 ? make_uint4(0u, 0u, 0u, 0u) : load16_in_batch(src, a, total_bytes);",
+   "the 16-byte pieces of a source row that a lane stages after its first (c >= 64) are stored as zeros: source bytes from 1024 on, "
+   "counted from the row span's start rounded down to 16",
+   "the second lane turn of the staging loop (boxes of 337 columns and more)",
+   # no case of the sweep is that wide; the image one pixel under the LDS limit is (468 columns, 89 pieces, R = 1).  CPU pre-check: 569 of
+   # its 1728 elements change
+   [AA + "test_refuses_an_image_too_wide_for_lds"])
+_m("aa_rtab_row9_first_tap_zero", "kernels_input.hip",
+   "e[0] = lo - ya; e[1] = min(taps, ks);",
+   "e[0] = lo - ya; e[1] = min(taps, ks); e[2] = i == 9 ? 0 : e[2];",
+   "row-table entry 9 of every workgroup gets first coefficient 0: window rows = 9 mod R where a workgroup has at least 10 rows, none "
+   "where R <= 9.  The pair of killers says that the row tables are per workgroup: 16 -> 24 (R = 16) fails in row 9 (and no other); "
+   "200 -> 24 (R = 9, workgroups of 9, 9 and 6 rows) must NOT show the fault in any row and alone does not kill it -- it passes, and "
+   "would fail if the table were indexed by the window row",
+   "resample_aa_u8_kernel, the row table as stored, one entry of a workgroup",
+   # the R = 9 case stands first: the child stops at its first failure (-x), so this order is the one in which both run
+   [AA + "test_sweep[200-24-24-0]", AA + "test_sweep[16-24-24-0]"])
 
 # kernels_loss.hip
 _m("loss_u_over_l_minus_1", "kernels_loss.hip",

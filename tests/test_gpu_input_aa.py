@@ -14,8 +14,25 @@ pytestmark = pytest.mark.gpu
 
 # (dim_in, virt, dim_out, window): one output pixel; odd sizes with a scalar tail; dim_out % 4 == 0; an upscale; no scaling at all;
 # a window inside the resized image, square and not
-CASES = [(8, 1, 1, 0), (9, 4, 4, 0), (33, 7, 7, 0), (32, 8, 8, 0), (16, 24, 24, 0), (40, 40, 40, 0), (64, 58, 52, 3), (64, 29, 22, (0, 7))]
+OLD_CASES = [(8, 1, 1, 0), (9, 4, 4, 0), (33, 7, 7, 0), (32, 8, 8, 0), (16, 24, 24, 0), (40, 40, 40, 0), (64, 58, 52, 3), (64, 29, 22, (0, 7))]
+# the loop turns and launcher branches that OLD_CASES never take, each at the smallest shape that takes it ("Suite
+# sensitivity"); the numbers are the launcher's, from aaref.launch_rows / aaref.lds_bytes, and test_new_cases_are_on_their_branches
+# holds them so that a launcher change which moves a case off its branch fails loudly.  AA_THREADS = 256, Q = dim_out / 4:
+# (100, 68, 68, 0)    the row pass `for (i = tid; i < nrows * Q; i += 256)` takes a second turn: R = 16, 16 x 17 = 272 items; D = 64
+#                     gives exactly 256
+# (300, 260, 260, 0)  the table fill `for (i = tid; i < D; i += 256)` takes a second turn (the smallest D % 4 == 0 past 256); 1040 row
+#                     items: 5 turns
+# (200, 24, 24, 0)    1 < R < 16 with a ragged last workgroup: R = 9, workgroups of 9, 9 and 6 rows; 19-tap rows
+# (294, 100, 100, 0)  1 < R < 16 together with a second row-pass turn: R = 15, 15 x 25 = 375 items; the smallest dim_in for D = 100
+# No case stages a row of more than 64 16-byte pieces (the lanes' second turn `for (c = tid & 63; c < pieces; c += 64)`, boxes of 337
+# columns and more): test_refuses_an_image_too_wide_for_lds does, with 89 pieces, and is the killer of that turn's mutant
+NEW_CASES = {(100, 68, 68, 0): dict(R=16, items=272, ks=5, lds=15976, second_turn=True),
+             (300, 260, 260, 0): dict(R=16, items=1040, ks=5, lds=43596, second_turn=True, wide_table=True),
+             (200, 24, 24, 0): dict(R=9, items=54, ks=19, lds=61944, groups=[9, 9, 6], lower_R=True),
+             (294, 100, 100, 0): dict(R=15, items=375, ks=7, lds=63532, second_turn=True, lower_R=True)}
+CASES = OLD_CASES + list(NEW_CASES)
 N = 3
+AA_THREADS = 256
 
 
 def corner_box(d):
@@ -55,6 +72,27 @@ def run_aa(ops, src, boxes, D, virt, win, front=1024, back=1024, rc_want=0):
     assert rc == rc_want, ops.L.mi_last_error().decode()
     out = dout.get()
     return out[front:front + total].reshape(n, 3, D, D), out[:front], out[front + total:]
+
+
+def test_new_cases_are_on_their_branches():
+    """host arithmetic only (tests/test_input_aa.py runs it without a device as well): the launcher's answer for every new case is the
+    one it was chosen for, and no old case reaches any of these branches"""
+    for (dim_in, virt, D, win), want in NEW_CASES.items():
+        R = aaref.launch_rows(dim_in, D, virt)
+        assert (R, R * (D // 4), aaref.ksize(dim_in, virt), aaref.lds_bytes(R, dim_in, D, virt)) == (want["R"], want["items"], want["ks"], want["lds"])
+        assert aaref.lds_bytes(R, dim_in, D, virt) <= aaref.AA_LDS_MAX
+        assert (R * (D // 4) > AA_THREADS) == bool(want.get("second_turn")) and (D > AA_THREADS) == bool(want.get("wide_table"))
+        assert (1 < R < aaref.AA_ROWS) == bool(want.get("lower_R"))
+        if want.get("lower_R"):  # R is lowered because R + 1 does not fit, not because dim_out is small
+            assert D > R and aaref.lds_bytes(R + 1, dim_in, D, virt) > aaref.AA_LDS_MAX
+        if "groups" in want:
+            assert [min(R, D - h0) for h0 in range(0, D, R)] == want["groups"]
+    assert aaref.launch_rows(100, 64, 64) * (64 // 4) == AA_THREADS  # D = 64: exactly one turn; 68 is the next multiple of 4
+    assert all(aaref.launch_rows(d, 100, 100) == 16 for d in range(100, 294))  # 294: the smallest dim_in with R < 16 at D = 100
+    for dim_in, virt, D, win in OLD_CASES:
+        R = aaref.launch_rows(dim_in, D, virt)
+        assert R == min(16, D) and R * (D // 4) <= AA_THREADS and D <= AA_THREADS
+    assert all((3 * c[0] + 30) >> 4 <= 64 for c in CASES) and (3 * (lds_limit_inputs()[1] - 1) + 30) >> 4 > 64
 
 
 # ---------------------------------------------------------------- the kernel on its own
@@ -163,11 +201,18 @@ def test_refusals_write_nothing(ops):
     assert not np.any(out.get() == SENTINEL)
 
 
+def lds_limit_inputs():
+    """(D, the smallest dim_in the launcher refuses at D, one image a pixel smaller, its whole box flipped)"""
+    D = 24
+    dim_in = next(d for d in range(D, 16385) if aaref.launch_rows(d, D, D) == 0)
+    img = np.random.RandomState(5).randint(0, 256, size=(1, dim_in - 1, dim_in - 1, 3), dtype=np.uint8)
+    return D, dim_in, img, np.array([[0, 0, dim_in - 1, dim_in - 1, 1]], np.int32)
+
+
 def test_refuses_an_image_too_wide_for_lds(ops):
     """the smallest dim_in at which the tables and source rows of ONE output row exceed 64 KB, from the launcher's formula: -2 with a
     message, nothing launched; one pixel less runs"""
-    D = 24
-    dim_in = next(d for d in range(D, 16385) if aaref.launch_rows(d, D, D) == 0)
+    D, dim_in, img, whole = lds_limit_inputs()
     assert aaref.launch_rows(dim_in - 1, D, D) == 1 and aaref.lds_bytes(1, dim_in, D, D) > 65536 >= aaref.lds_bytes(1, dim_in - 1, D, D)
     src = ops.dev(shape=(1, dim_in, dim_in, 3), dtype=np.uint8)
     bx = ops.dev(np.array([[0, 0, 1, 1, 0]], np.int32))
@@ -176,8 +221,6 @@ def test_refuses_an_image_too_wide_for_lds(ops):
     assert "LDS" in ops.L.mi_last_error().decode()
     ops.L.mi_clear_error()
     assert np.all(out.get() == SENTINEL)
-    img = np.random.RandomState(5).randint(0, 256, size=(1, dim_in - 1, dim_in - 1, 3), dtype=np.uint8)
-    whole = np.array([[0, 0, dim_in - 1, dim_in - 1, 1]], np.int32)
     check(ops.resample_aa_u8(img, whole, D), aaref.resample(img, whole, D))  # R = 1, the most taps that fit
 
 

@@ -19,7 +19,7 @@ CSRC = os.path.join(ROOT, "resnet_amd", "csrc")
 # starts child processes of its own
 ALLOWED_FILES = {"tests/test_gpu_ops.py", "tests/test_gpu_bf16.py", "tests/test_gpu_ragged.py", "tests/test_gpu_optim.py", "tests/test_gpu_loss_head.py",
                  "tests/test_gpu_eval.py", "tests/test_gpu_dp.py", "tests/test_gpu_input_u8.py", "tests/test_gpu_input_rrc.py", "tests/test_gpu_mix.py",
-                 "tests/test_gpu_ema.py", "tests/test_gpu_accum.py"}
+                 "tests/test_gpu_ema.py", "tests/test_gpu_accum.py", "tests/test_gpu_input_aa.py"}
 SPAWNING = ("test_conv_parity_on_the_other_kernel_routes", "test_training_step_bf16_on_the_other_kernel_routes", "test_two_ranks_over_rccl",
             "test_bench_", "test_rccl_one_rank")
 
@@ -34,7 +34,7 @@ def _builder():
 def test_entries_are_well_formed():
     names = [m["name"] for m in mutants.MUTANTS]
     assert len(names) == len(set(names)), "names are not unique"
-    assert len(names) >= 67
+    assert len(names) >= 79
     for m in mutants.MUTANTS:
         assert re.fullmatch(r"[a-z0-9_]+", m["name"]), m["name"]
         assert m["what"] and m["branch"], m["name"]
