@@ -436,3 +436,112 @@ def trainer_bn_sites(L, dims=None, N=None):
             out.add((dt, b["red"], Ho, "bwd", "parts" if fuses(1, b["red"], Ho, b["ex"], 1, 1) else 1))
             out.add((dt, b["red"], H, "bwd", "parts" if fuses(2, b["red"], H, b["red"], 3, s) else 1))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The loop turns of the batch-norm reductions (kernels_bn.hip), restated from the launchers: which turn a shape takes.
+BN_SPLIT_MAX, BN_THREADS = 64, 256
+
+
+def bn_nsplit(N, Cn):
+    """bn_nsplit: the blocks per channel, min(ceil(2048 / C), N, 64), at least 1"""
+    return max(1, min(-(-2048 // Cn), N, BN_SPLIT_MAX))
+
+
+def bn_vec(pair, P):
+    """bn_vec: elements per unit of the reductions -- fp32 / fp32: 4 where the plane allows it, else 1; bf16 storage on either side: 8, 4 or 1"""
+    if pair == "f32":
+        return 4 if P % 4 == 0 else 1
+    return 8 if P % 8 == 0 else 4 if P % 4 == 0 else 1
+
+
+def bn_reach(pair, Cn, H, N, in_flight=4):
+    """what the blocks of bn_stats_kernel (in_flight 4) or bn_bwd_reduce_kernel (4; the external-mask modes 2) run at this shape:
+    dict(nsplit, V, units = the largest block's unit count, whole = whole turns of its thread 0, remainder = units left to the remainder
+    loop over all threads, crosses = a whole turn holds units of two images)"""
+    P = H * H
+    ns, V = bn_nsplit(N, Cn), bn_vec(pair, P)
+    cnt = -(-N // ns)
+    PV = P // V
+    total = cnt * PV
+    turn = in_flight * BN_THREADS
+    # thread t takes whole turn k while k turn + t + (in_flight - 1) 256 < total
+    turns_of = [max(0, -(-(total - t - (in_flight - 1) * BN_THREADS) // turn)) for t in range(BN_THREADS)]
+    whole = turns_of[0]
+    return dict(nsplit=ns, V=V, units=total, whole=whole, remainder=total - in_flight * sum(turns_of),
+                crosses=whole > 0 and cnt > 1 and PV < turn * whole)
+
+
+# (pair, C, H, N): N = 1, H = 66 -- one image per split, 1089 float4 units: a whole turn and a remainder; C = 2048, H = 48 -- one split, a
+# whole turn that crosses from one image into the next (bf16: 8 elements per unit, so N = 4 for 1152 units); C = 2048, H = 7, N = 21 -- 1029
+# scalar units, the V == 1 whole turn; C = 64, H = 4, N = 33 -- 32 splits (finalize lanes 16 .. 31), the first with two images
+LOOP_TURN_SHAPES = [("f32", 64, 66, 1), ("bf16", 64, 66, 1), ("f32", 2048, 48, 2), ("bf16", 2048, 48, 4), ("f32", 2048, 7, 21),
+                    ("bf16", 2048, 7, 21), ("f32", 64, 4, 33), ("bf16", 64, 4, 33)]
+
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# soft-max / loss head: rows whose maximum a lane meets only after its first turn
+DOMINANT_L = (65, 1000, 1537)
+DOMINANT_GAP = 95.0   # > 89: expf of the gap overflows float32
+
+
+def dominant_columns(L):
+    """per row of dominant_rows(L) the column of its dominant logit: the first column past a lane's first turn, the last column, one of the
+    last register slot of loss_head_kernel<reg> (960 .. 1023) where the row has it, and a row without a dominant logit (-1)"""
+    cols = [64, L - 1, min(L - 1, 64 + (L - 65) // 2)]
+    if L > 960:
+        cols.append(min(L - 1, 990))
+    return cols + [-1]
+
+
+def dominant_rows(L, seed=73):
+    """N(0, 9) logits; row r has x[r, dominant_columns(L)[r]] = max of the row + DOMINANT_GAP"""
+    cols = dominant_columns(L)
+    rng = np.random.default_rng(seed + L)
+    x = (rng.standard_normal((len(cols), L)) * 3.0).astype(np.float32)
+    for r, c in enumerate(cols):
+        if c >= 0:
+            x[r, c] = x[r].max() + np.float32(DOMINANT_GAP)
+    return x
+
+
+ADAM_GRID_CAP = 16384   # ew_blocks (kernels_misc.hip): workgroups of 256 threads; a thread takes a second turn past 16384 x 256 elements
+
+
+def adam_second_turn_inputs():
+    """((p, g, m, v), indices of the planted NaN / Inf gradients, hyper-parameters) of test_gpu_ops.py::test_adam_second_grid_stride_turn:
+    n = 16384 x 256 + 257, step 500 (1 - b1^t = 1, 1 - b2^t = 0.39), wd 5e-4; non-finite gradients in the first turn and in the second"""
+    n = ADAM_GRID_CAP * 256 + 257
+    rng = np.random.default_rng(83)
+    p = rng.standard_normal(n, dtype=np.float32) * np.float32(0.05)
+    g = rng.standard_normal(n, dtype=np.float32) * np.exp(rng.uniform(-8, 2, n)).astype(np.float32)
+    m = rng.standard_normal(n, dtype=np.float32) * np.float32(1e-2)
+    v = np.abs(rng.standard_normal(n, dtype=np.float32)) * np.float32(1e-4)
+    bad_g = np.array([3, 12345, ADAM_GRID_CAP * 256, ADAM_GRID_CAP * 256 + 200, n - 1])
+    g[bad_g] = [np.nan, np.inf, -np.inf, np.nan, np.inf]
+    cb1 = cb2 = np.float32(1)
+    for _ in range(500):
+        cb1, cb2 = np.float32(cb1 * np.float32(0.9)), np.float32(cb2 * np.float32(0.999))
+    return (p, g, m, v), bad_g, dict(lr=1e-3, wd=5e-4, b1=0.9, b2=0.999, cb1=cb1, cb2=cb2, eps=1e-7)
+
+
+def adam_violations(got, inputs, hp, first=0):
+    """elements of got = (p', m', v') outside the bounds of adam_ref on inputs = (p, g, m, v), in blocks (host memory), and the worst
+    distance; first: the index the comparison starts at"""
+    p, g, m, v = inputs
+    bad, worst = 0, 0.0
+    for i in range(first, p.size, 1 << 21):
+        sl = slice(i, i + (1 << 21))
+        for a, (ref, A) in zip(got, adam_ref(p[sl], g[sl], m[sl], v[sl], **hp)):
+            w, b = R.dist_f32(a[sl], ref, A)
+            bad, worst = bad + b, max(worst, w)
+    return bad, worst
+
+
+def dominant_labels(L):
+    """labels for dominant_rows(L): the dominant column, a column past 63 that is not it, column 0, ... -- every row's label is valid and
+    some lie past column 63"""
+    cols = dominant_columns(L)
+    lab = [cols[0], 64 if L > 65 else 0, 0] + [cols[3]] * (len(cols) - 4) + [L - 1]
+    return np.asarray(lab[:len(cols)], np.int32)

@@ -88,6 +88,30 @@ def make_inputs(N, L):
     return np.ascontiguousarray(x, np.float32), lab
 
 
+def dominant_inputs(L):
+    """(x, labels) of test_gpu_loss_head.py::test_dominant_logit_past_column_63: ewref.dominant_rows / dominant_labels -- per row one
+    logit 95 above every other at a column past 63 (the last row has none); labels on it, past column 63 off it, at column 0"""
+    import ewref
+    return ewref.dominant_rows(L), ewref.dominant_labels(L)
+
+
+def loss_head_f32_max_of(x, labels, eps, cols):
+    """loss_head_f32's row_loss with the row maximum taken over the first `cols` columns only (the planted faults of tests/mutants.py that
+    leave a lane's later turns out of the maximum): float32 throughout, so a logit far above that maximum overflows exp"""
+    f = np.float32
+    x = np.asarray(x, f)
+    N, L = x.shape
+    u = f(eps) / f(L)
+    out = np.empty(N, f)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for r in range(N):
+            c = int(labels[r])
+            z = x[r] - x[r, :cols].max()
+            s = np.exp(z).sum(dtype=f)
+            out[r] = np.log(s) - (f(1) - f(eps)) * z[c] - u * z.sum(dtype=f)
+    return out
+
+
 RANKED_SHAPE = (130, 10)  # 130 rows: the 64 lanes of loss_reduce_kernel take three passes, the last with rows 128 and 129 only
 
 

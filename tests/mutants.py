@@ -597,6 +597,349 @@ _m("loss_reduce_float_lane_sum", "kernels_loss.hip",
    "loss_reduce_kernel, lanes with more than one row (N > 64)",
    [LOSS + "test_batch_totals_past_64_rows_and_at_the_topk_threshold[10-0.1]"])
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# The loop turns of the first-generation element-wise kernels ("Suite sensitivity", "Loop turns of the
+# first-generation element-wise kernels"): one entry per whole turn, remainder, inter-wave merge, straddle, second grid-stride turn and second lane turn.  The reach
+# of every killer is worked out from the launchers' formulas in the "reach" table there; tests/test_loop_turns_model.py holds, without a
+# GPU, that the killers' own inputs separate the restated fault.
+LT = RAG + "test_bn_loop_turns"
+OPT = "tests/test_gpu_optim.py::"
+U8 = "tests/test_gpu_input_u8.py::"
+RRC = "tests/test_gpu_input_rrc.py::"
+
+# kernels_bn.hip
+_m("bn_stats_turn_unit3_m2_zero", "kernels_bn.hip",
+   "                    m2 += (a * a + b * b) + (cc * cc + d * d);",
+   "                    m2 += (u == 3 ? 0.f : 1.f) * ((a * a + b * b) + (cc * cc + d * d));",
+   "the whole turn of bn_stats_kernel (four units in flight, V > 1) multiplies the squared deviations of its fourth unit by 0: the variance "
+   "of every channel whose block has 1024 units or more",
+   "bn_stats_kernel, the four-in-flight loop, V > 1 (cnt P / V >= 1024)",
+   # of the nets' planes only the 112^2 stem reaches it (8 splits of one image, 3136 float4 units); test_bn_loop_turns has the small
+   # shapes with a whole turn and a remainder (N = 1, C = 64, H = 66: 1089 units)
+   [RAG + "test_bn_fwd_ragged[r50_N8-f32_C64_H112]"])
+_m("bn_stats_turn_scalar_fourth_deviation", "kernels_bn.hip",
+   "wel_add_batch(w, 4.f, bm, (a * a + b * b) + (cc * cc + d * d));",
+   "wel_add_batch(w, 4.f, bm, (a * a + b * b) + (cc * cc + 0.f * d * d));",
+   "the whole turn of bn_stats_kernel<V = 1> drops the fourth squared deviation of a batch of four",
+   "bn_stats_kernel, the four-in-flight loop, V == 1 (planes of 49: cnt >= 21)",
+   # C = 2048: one split; N = 21 x 49 = 1029 scalar units: one whole turn, 5 units of remainder
+   [LT + "[f32_C2048_H7_N21]"])
+_m("bn_stats_remainder_add4_fourth_deviation", "kernels_bn.hip",
+   "t.m2 = (da * da + db * db) + (dc * dc + dd * dd);",
+   "t.m2 = (da * da + db * db) + (dc * dc + 0.f * dd * dd);",
+   "wel_add4 (called by the remainder loop of bn_stats_kernel only) drops the fourth squared deviation",
+   "bn_stats_kernel, the remainder loop, V > 1",
+   [RAG + "test_bn_fwd_ragged[c1s_N4-f32_C64_H8]"])
+_m("bn_stats_remainder_add1_half_mean", "kernels_bn.hip",
+   "Wel t; t.n = 1.f; t.mean = a; t.m2 = 0.f;",
+   "Wel t; t.n = 1.f; t.mean = 0.5f * a; t.m2 = 0.f;",
+   "wel_add1 (called by the remainder loop of bn_stats_kernel<V = 1> only) enters every value at half its size",
+   "bn_stats_kernel, the remainder loop, V == 1",
+   [RAG + "test_bn_fwd_ragged[r50_N8-f32_C512_H7]"])
+_m("bn_stats_interwave_wave3_count_zero", "kernels_bn.hip",
+   "for (int i = 1; i < (int)(blockDim.x >> 6); i++) r = wel_merge(r, sh[i]);",
+   "for (int i = 1; i < (int)(blockDim.x >> 6); i++) { Wel t_ = sh[i]; t_.n = i == 3 ? 0.f : t_.n; r = wel_merge(r, t_); }",
+   "the inter-wave merge of bn_stats_kernel takes the fourth wave's partial with n = 0: its mean is ignored and the total count is short",
+   "bn_stats_kernel, the merge of the four waves (the fourth wave holds data from 193 units on)",
+   # c1s_N4-f32_C64_H8 has 16 units per block: wave 3 holds n = 0 there anyway.  r50_N8-f32_C64_H56: 784 units
+   [RAG + "test_bn_fwd_ragged[r50_N8-f32_C64_H56]"])
+_m("bn_parts_merge_turn_item7_m2_zero", "kernels_bn.hip",
+   "for (int u = 0; u < 8; u++) w = wel_merge(w, b[u]);",
+   "for (int u = 0; u < 8; u++) { Wel t_ = b[u]; t_.m2 = u == 7 ? 0.f : t_.m2; w = wel_merge(w, t_); }",
+   "the eight-in-flight loop of bn_parts_merge_kernel takes the eighth partial's M2 as 0",
+   "bn_parts_merge_kernel, whole turns (more than 28 partials per chunk)",
+   # plan (64, 128, 52, 52, 1, 1, 0): 13 column tiles x 4 = 52 partials, one chunk: one whole turn per sub-group, then 5 partials
+   [RAG + "test_conv_bn_fwd_ragged[r50_N8-bf16_C1024_H14_K256_k1_s1]"])
+_m("bn_parts_merge_remainder_m2_zero", "kernels_bn.hip",
+   "Wel b = {parts[o], parts[plane + o], parts[2 * plane + o]};",
+   "Wel b = {parts[o], parts[plane + o], 0.f * parts[2 * plane + o]};",
+   "the remainder loop of bn_parts_merge_kernel takes every partial's M2 as 0",
+   "bn_parts_merge_kernel, the remainder loop",
+   [RAG + "test_conv_bn_fwd_ragged[c1s_N4-f32_C64_H8_K64_k1_s1]"])
+_m("bn_parts_merge_subgroup3_dropped", "kernels_bn.hip",
+   "for (int i = 1; i < 4; i++) r = wel_merge(r, sh[i][cx]);",
+   "for (int i = 1; i < 4; i++) { Wel t_ = sh[i][cx]; if (i == 3) { t_.n = 0.f; t_.mean = 0.f; t_.m2 = 0.f; } r = wel_merge(r, t_); }",
+   "the merge of the four sub-groups of bn_parts_merge_kernel leaves the fourth out: a quarter of the partials",
+   "bn_parts_merge_kernel, the merge of the sub-groups",
+   [RAG + "test_conv_bn_fwd_ragged[c1s_N4-f32_C64_H8_K64_k1_s1]"])
+_m("bn_finalize_lanes_from_16_m2_zero", "kernels_bn.hip",
+   "if (lane < nsplit) { w.n = p[lane * 3]; w.mean = p[lane * 3 + 1]; w.m2 = p[lane * 3 + 2]; }",
+   "if (lane < nsplit) { w.n = p[lane * 3]; w.mean = p[lane * 3 + 1]; w.m2 = (lane >= 16 ? 0.f : 1.f) * p[lane * 3 + 2]; }",
+   "bn_finalize_kernel takes the M2 of the partials in lanes 16 and up as 0",
+   "bn_finalize_kernel, lanes 16 .. 63 (more than 16 splits: N > 16 and C <= 120)",
+   # N = 33, C = 64: 32 splits, the first with two images
+   [LT + "[f32_C64_H4_N33]"])
+_m("bn_bwd_finalize_lanes_from_16_s2_zero", "kernels_bn.hip",
+   "if (lane < nsplit) { s1 = p[lane * 3]; s2 = p[lane * 3 + 1]; }",
+   "if (lane < nsplit) { s1 = p[lane * 3]; s2 = (lane >= 16 ? 0.f : 1.f) * p[lane * 3 + 1]; }",
+   "bn_bwd_finalize_kernel takes the second sum of the partials in lanes 16 and up as 0: dgamma, and dx through it",
+   "bn_bwd_finalize_kernel, lanes 16 .. 63",
+   # N = 33, C = 64: 32 splits of bn_bwd_reduce_kernel's own grid (at most 8 at N = 8: r50_N8-f32_C64_H56_mode1 passes under this fault).
+   # Of the suite as it was, the fused dgrad of r50_N8-bf16_C64_H56_K256_k1_s1 killed it: 784 partials, 64 chunks
+   [RAG + "test_bn_bwd_loop_turns[f32_C64_H4_N33_mode0]", RAG + "test_dgrad_bn_bwd_ragged[r50_N8-bf16_C64_H56_K256_k1_s1]"])
+_m("bn_apply_straddle_sd", "kernels_bn.hip",
+   "sd1 = sqrtf(vars[c1] + eps); g1 = gamma[c1]; b1 = beta[c1];\n        }",
+   "sd1 = sd0; g1 = gamma[c1]; b1 = beta[c1];\n        }",
+   "in a vector that straddles two channel planes the second channel's elements are divided by the first channel's standard deviation",
+   "bn_apply_kernel, the straddling vectors of 7 x 7 planes (STR)",
+   [RAG + "test_bn_fwd_ragged[r50_N8-f32_C512_H7]"])
+_m("bn_apply_norm_out_after_relu", "kernels_bn.hip",
+   "if (norm_out) VecIO<float, V>::store(norm_out + e, nv);",
+   "if (norm_out) VecIO<float, V>::store(norm_out + e, v);",
+   "bn_apply_kernel stores the value after the ReLU (and the residual) as norm_out, the BN output the FULL store policy keeps",
+   "bn_apply_kernel, the xhat_out / norm_out stores (the trainer's FULL store policy; no operator passes them)",
+   [OPS + "test_full_store_policy_tensors_per_element"])
+_m("bn_apply_cl_short_piece_last_residual_zero", "kernels_bn.hip",
+   "r[q] = (residual && q < nv) ? mi_bf2f(residual[e + q]) : 0.f;",
+   "r[q] = (residual && q < nv) ? (q == nv - 1 ? 0.f : 1.f) * mi_bf2f(residual[e + q]) : 0.f;",
+   "bn_apply_cl_kernel reads the residual of the last element of a plane's short last piece (P % 8 != 0) as 0",
+   "bn_apply_cl_kernel, the nv < 8 branch with a residual",
+   # 14 x 14 = 196 = 24 x 8 + 4; "cl par add_relu" is the expansion BN's form
+   [RAG + "test_bn_fwd_ragged[r50_N8-bf16_C1024_H14]"])
+_m("bn_apply_cl_tile_odd_pixel_takes_even", "kernels_bn.hip",
+   "tile[(part * 8 + 2 * q + 1) * 72 + cc] = (bf16_t)(o[q] >> 16);",
+   "tile[(part * 8 + 2 * q + 1) * 72 + cc] = (bf16_t)(o[q] & 0xffffu);",
+   "the tile fill of bn_apply_cl_kernel gives the odd pixel of a pair the even pixel's half-word: every second pixel of the channel-last copy",
+   "bn_apply_cl_kernel, the LDS tile as filled",
+   [RAG + "test_bn_fwd_ragged[c1s_N4-bf16_C64_H8]"])
+_m("bn_bwd_reduce_turn_last_unit_s2", "kernels_bn.hip",
+   "for (int q = 0; q < V; q++) gq[q] = one(xv[u][q], dv[u][q], mv[u][q]);",
+   "for (int q = 0; q < V; q++) { const float keep_ = s2; gq[q] = one(xv[u][q], dv[u][q], mv[u][q]); s2 = u == U - 1 ? keep_ : s2; }",
+   "the whole turn of bn_bwd_reduce_kernel leaves its last unit in flight out of the second sum: dgamma, and dx through it",
+   "bn_bwd_reduce_kernel, the U-in-flight loop (U = 4: 1024 units; the external-mask modes U = 2: 512)",
+   [RAG + "test_bn_bwd_ragged[r50_N8-f32_C64_H112_mode1]"])
+_m("bn_bwd_reduce_remainder_last_element_s1", "kernels_bn.hip",
+   "for (int q = 0; q < V; q++) gq[q] = one(xv[q], dv[q], mv[q]);",
+   "for (int q = 0; q < V; q++) { const float keep_ = s1; gq[q] = one(xv[q], dv[q], mv[q]); s1 = q == V - 1 ? keep_ : s1; }",
+   "the remainder loop of bn_bwd_reduce_kernel leaves the last element of every unit out of the first sum: dbeta, and dx through it",
+   "bn_bwd_reduce_kernel, the remainder loop",
+   [RAG + "test_bn_bwd_ragged[c1s_N4-f32_C256_H8_mode0]"])
+_m("bn_bwd_reduce_remainder_gated_ungated", "kernels_bn.hip",
+   "if (MASK == 3) VecIO<TA, V>::store(gated + o, gq);",
+   "if (MASK == 3) VecIO<TA, V>::store(gated + o, dv);",
+   "the remainder loop of bn_bwd_reduce_kernel<3> writes the ungated dy as the gated gradient",
+   "bn_bwd_reduce_kernel, MASK == 3, the remainder loop's store",
+   [RAG + "test_bn_bwd_ragged[c1s_N4-f32_C256_H8_mode3]"])
+_m("bn_bwd_parts_merge_turn_item7_dropped", "kernels_bn.hip",
+   "for (int u = 0; u < 8; u++) { a1 += u1[u]; a2 += u2[u]; }",
+   "for (int u = 0; u < 8; u++) { a1 += u == 7 ? 0.f : u1[u]; a2 += u == 7 ? 0.f : u2[u]; }",
+   "the eight-in-flight loop of bn_bwd_parts_merge_kernel leaves the eighth partial out of both sums",
+   "bn_bwd_parts_merge_kernel, whole turns (more than 28 partials per chunk)",
+   # plan (64, 128, 208, 208, 1, 1, 0): 13 column tiles x 4 = 52 partials, one chunk
+   [RAG + "test_dgrad_bn_bwd_ragged[r50_N8-f32_C1024_H14_K256_k1_s1]"])
+_m("bn_bwd_parts_merge_remainder_s2_zero", "kernels_bn.hip",
+   "a1 += parts[o]; a2 += parts[plane + o];",
+   "a1 += parts[o]; a2 += 0.f * parts[plane + o];",
+   "the remainder loop of bn_bwd_parts_merge_kernel multiplies the second sum's partials by 0",
+   "bn_bwd_parts_merge_kernel, the remainder loop",
+   [RAG + "test_dgrad_bn_bwd_ragged[c1s_N4-bf16_C64_H8_K256_k1_s1]"])
+_m("bn_bwd_parts_merge_no_eps", "kernels_bn.hip",
+   "o[0] = s1; o[1] = s2 / sqrtf(vars[c] + eps);",
+   "o[0] = s1; o[1] = s2 / sqrtf(vars[c]);",
+   "bn_bwd_parts_merge_kernel divides the second sum by sqrtf(var) without eps: channels of small variance",
+   "bn_bwd_parts_merge_kernel, the final division",
+   # the fused-dgrad cases normalise N(0.3, 1.5^2) tensors: var = 2.25 against eps = 1e-7, and the fault survived both of them
+   [RAG + "test_dgrad_bn_bwd_small_variance[f32]", RAG + "test_dgrad_bn_bwd_small_variance[bf16]"])
+_m("bn_bwd_apply_straddle_k2", "kernels_bn.hip",
+   "k11 = dbeta[c1] * inv_m; k21 = dgamma[c1] * inv_m; scale1 = g1 / sd1;",
+   "k11 = dbeta[c1] * inv_m; k21 = k20; scale1 = g1 / sd1;",
+   "in a vector that straddles two channel planes the second channel's dx takes the first channel's dgamma / M",
+   "bn_bwd_apply_kernel, the straddling vectors of 7 x 7 planes (STR)",
+   [RAG + "test_bn_bwd_ragged[r50_N8-f32_C2048_H7_mode0]"])
+_m("bn_bwd_apply_gate_y_ge", "kernels_bn.hip",
+   "if (MASK == 1) on = bn_y(xh, g, b) > 0.f;\n            if (MASK == 2) on = mv[q] > 0.f;",
+   "if (MASK == 1) on = bn_y(xh, g, b) >= 0.f;\n            if (MASK == 2) on = mv[q] > 0.f;",
+   "the recomputed gate of bn_bwd_apply_kernel is y >= 0: dx passes dy where y is exactly 0",
+   "bn_bwd_apply_kernel, MASK == 1, elements with y == 0",
+   [RAG + "test_bn_bwd_ragged[c1s_N4-f32_C64_H8_mode1]"])
+
+# kernels_misc.hip
+_m("maxpool_left_tap_never_wins", "kernels_misc.hip",
+   "const float e = v[2 * j + c];",
+   "const float e = (j == 0 && c == 0) ? -2048.f : v[2 * j + c];",
+   "the left-neighbour tap of a cell of maxpool_fwd_3x3s2_kernel (the element in front of the 8-element vector) never wins: value and "
+   "index of every fourth output whose maximum sits there",
+   "maxpool_fwd_3x3s2_kernel, the has_left tap",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-maxpool_f32]"])
+_m("maxpool_last_tap_never_wins", "kernels_misc.hip",
+   "const float e = v[2 * j + c];",
+   "const float e = (r == 1 && j == 3 && c == 2) ? -2048.f : v[2 * j + c];",
+   "the last tap of a cell of maxpool_fwd_3x3s2_kernel (lower row, last of the nine columns) never wins",
+   "maxpool_fwd_3x3s2_kernel, tap (r = 1, j = 3, c = 2)",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-maxpool_f32]"])
+_m("maxpool_bwd_v11_first_writer", "kernels_misc.hip",
+   "if (i11 == e11) v11 = d11;",
+   "if (i11 == e11) v11 = (i00 == e11) ? d00 : d11;",
+   "maxpool_bwd_3x3s2_kernel lets window (a, b) win over window (a + 1, b + 1) for the cell's last element",
+   "maxpool_bwd_3x3s2_kernel, elements that are the arg-max of both diagonal windows",
+   [RAG + "test_pools_softmax_fc_ragged[c1s_N4-maxpool_f32]"])
+_m("maxpool_generic_last_of_equal_maxima", "kernels_misc.hip",
+   "if (v > mv) { mv = v; mi = (int)pbase + ih * H + iw; }",
+   "if (v >= mv) { mv = v; mi = (int)pbase + ih * H + iw; }",
+   "the generic max-pool takes the last of equal maxima inside a window (the index stays in the window)",
+   "maxpool_fwd_kernel (planes whose rows are no multiple of 8 elements)",
+   [OPS + "test_maxpool[64-12-3]"])
+_m("maxpool_generic_bwd_first_writer", "kernels_misc.hip",
+   "if (idx[o] == (int)e) v = ldf<T>(dy + o);",
+   "if (idx[o] == (int)e) v = v != 0.f ? v : ldf<T>(dy + o);",
+   "the generic max-pool backward keeps the first window (with a dy other than 0) whose arg-max an element is, not the last",
+   "maxpool_bwd_kernel (odd planes: every even plane takes maxpool_bwd_3x3s2_kernel)",
+   [OPS + "test_maxpool[64-13-3]"])
+_m("avgpool_second_lane_turn_zero", "kernels_misc.hip",
+   "for (int i = lane; i < P; i += 64) s += ldf<T>(xp + i);",
+   "for (int i = lane; i < P; i += 64) s += (i >= 64 ? 0.f : 1.f) * ldf<T>(xp + i);",
+   "avgpool_fwd_kernel multiplies the elements a lane reaches after its first (i >= 64) by 0",
+   "avgpool_fwd_kernel, the second lane turn (P > 64)",
+   [RAG + "test_avgpool_second_lane_turn[f32]", RAG + "test_avgpool_second_lane_turn[bf16]"])
+_m("softmax_max_of_first_64", "kernels_misc.hip",
+   "for (int j = lane; j < L; j += 64) mx = fmaxf(mx, xr[j]);",
+   "for (int j = lane; j < L; j += 64) mx = j >= 64 ? mx : fmaxf(mx, xr[j]);",
+   "the row maximum of softmax_kernel ignores the columns from 64 on: the same function up to rounding unless a dominant logit sits there",
+   "softmax_kernel, the maximum's second lane turn (L > 64)",
+   [RAG + "test_softmax_dominant_logit_past_column_63[65]", RAG + "test_softmax_dominant_logit_past_column_63[1000]"])
+_m("softmax_sum_second_turn_scaled", "kernels_misc.hip",
+   "float s = 0.f;\n    for (int j = lane; j < L; j += 64) s += expf(xr[j] - mx);",
+   "float s = 0.f;\n    for (int j = lane; j < L; j += 64) s += (j >= 64 ? 1.0009765625f : 1.f) * expf(xr[j] - mx);",
+   "the sum of softmax_kernel scales the terms a lane adds after its first by 1 + 2^-10",
+   "softmax_kernel, the sum's second lane turn (L > 64)",
+   [RAG + "test_pools_softmax_fc_ragged[r50_N8-softmax_ce_deriv]"])
+_m("adam_second_turn_v_corrected_with_beta1", "kernels_misc.hip",
+   "const float ma = mi / (1.f - cur_b1), va = vi / (1.f - cur_b2);",
+   "const float ma = mi / (1.f - cur_b1), va = vi / (1.f - (i >= (size_t)gridDim.x * blockDim.x ? cur_b1 : cur_b2));",
+   "elements a thread of adam_kernel reaches after its first (i >= 16384 x 256) have the second moment corrected with beta1^t",
+   "adam_kernel, the second grid-stride turn (n > 4 194 304)",
+   [OPS + "test_adam_second_grid_stride_turn"])
+_m("adam_no_decoupled_decay", "kernels_misc.hip",
+   "float np = old - (lr * (ma / (sqrtf(va) + eps)) + wd * old);",
+   "float np = old - (lr * (ma / (sqrtf(va) + eps)) + 0.f * wd * old);",
+   "the parameter update of adam_kernel lacks the decoupled wd * old term",
+   "adam_kernel, wd > 0",
+   [OPS + "test_softmax_ce_adam"])
+
+_m("relu_deriv_gate_ge", "kernels_misc.hip",
+   "a.x > 0.f ? u.x : 0.f",
+   "a.x >= 0.f ? u.x : 0.f",
+   "relu_deriv_kernel passes the upstream gradient where the activation is exactly 0, in the first element of every float4",
+   "relu_deriv_kernel (mi_op_relu_deriv), the float4 body",
+   [OPS + "test_bn_add_relu_and_external_mask[256-8-4]"])
+
+_m("add_relu_activation_without_addend", "kernels_misc.hip",
+   "act_out[i] = fmaxf(0.f, s);",
+   "act_out[i] = fmaxf(0.f, a[i]);",
+   "add_relu_kernel's activation is max(a, 0): the shortcut is missing from the block output (the stored sum keeps it)",
+   "add_relu_kernel (the expansion's add + ReLU as a pass of its own: the trainer's FULL store policy)",
+   [OPS + "test_full_store_policy_tensors_per_element"])
+
+# kernels_optim.hip, the optimizer half
+_m("optim_norm_whole_chunk_last_quad_g_zero", "kernels_optim.hip",
+   "q[k] = ((const float4 *)pg)[threadIdx.x + k * OPT_THREADS];",
+   "q[k] = k == MID_OPT_CHUNK / 4 / OPT_THREADS - 1 ? make_float4(0.f, 0.f, 0.f, 0.f) : ((const float4 *)pg)[threadIdx.x + k * OPT_THREADS];",
+   "the whole-chunk branch of optim_norm_kernel takes the gradients of its last load per thread (k == K - 1) as 0: an eighth of sum g^2",
+   "optim_norm_kernel, whole chunks of 8192 floats",
+   [OPT + "test_operator_scalar_tail[lars]"])
+_m("optim_norm_partial_second_turn_zero", "kernels_optim.hip",
+   "const float4 w = ((const float4 *)pw)[i], q = ((const float4 *)pg)[i];",
+   "const float4 z_ = make_float4(0.f, 0.f, 0.f, 0.f), w = i >= OPT_THREADS ? z_ : ((const float4 *)pw)[i], q = i >= OPT_THREADS ? z_ : ((const float4 *)pg)[i];",
+   "the float4 loop of a partial chunk of optim_norm_kernel takes the quads a thread reaches after its first (i >= 256) as 0",
+   "optim_norm_kernel, partial chunks of more than 1024 floats",
+   [OPT + "test_operator_scalar_tail[lars]"])
+_m("optim_norm_interwave_wave3_dropped", "kernels_optim.hip",
+   "for (int k = 0; k < OPT_THREADS / 64; k++) { a += red[0][k]; b += red[1][k]; }",
+   "for (int k = 0; k < OPT_THREADS / 64; k++) { a += k == 3 ? 0.0 : red[0][k]; b += k == 3 ? 0.0 : red[1][k]; }",
+   "the inter-wave sum of optim_norm_kernel leaves the fourth wave out",
+   "optim_norm_kernel, the sum over the four waves",
+   [OPT + "test_operator_scalar_tail[lars]"])
+_m("optim_trust_second_lane_turn_zero", "kernels_optim.hip",
+   "{ sw += part[c].x; sg += part[c].y; }",
+   "{ sw += c - first_chunk[t] >= 64 ? 0.0 : part[c].x; sg += c - first_chunk[t] >= 64 ? 0.0 : part[c].y; }",
+   "optim_trust_kernel takes the partials a lane reaches after its first (chunk 64 and up of a tensor) as 0",
+   "optim_trust_kernel, the second lane turn (tensors of more than 64 chunks: more than 524 288 floats)",
+   [OPT + "test_operator_per_element_at_resnet50_geometry[lars-5e-05]"])
+_m("optim_trust_guard_gn_only", "kernels_optim.hip",
+   "if (wn > 0.f && gn > 0.f) tr",
+   "if (gn > 0.f) tr",
+   "the trust-1 guard of optim_trust_kernel looks at the gradient norm alone: an all-zero weight tensor gets trust ratio 0 and never moves",
+   "optim_trust_kernel, wn == 0 with gn > 0",
+   [OPT + "test_lars_loop_turns_and_an_all_zero_weight_tensor"])
+_m("optim_update_whole_chunk_last_w_no_decay", "kernels_optim.hip",
+   "opt_elem<KIND>(w[k].w, q[k].w, b[k].w, s, wdt, lr, mu, skip, bad);",
+   "opt_elem<KIND>(w[k].w, q[k].w, b[k].w, s, k == K - 1 ? 0.f : wdt, lr, mu, skip, bad);",
+   "the whole-chunk path of optim_update_kernel runs the .w element of a thread's last quad without weight decay: one element in 32",
+   "optim_update_kernel, whole chunks, wd > 0",
+   [OPT + "test_operator_scalar_tail[sgd]", OPT + "test_operator_per_element_at_resnet50_geometry[sgd-5e-05]"])
+_m("optim_update_partial_second_turn_no_momentum", "kernels_optim.hip",
+   "float4 w = ((float4 *)pw)[i], q = ((float4 *)pg)[i], b = ((float4 *)pb)[i];",
+   "float4 w = ((float4 *)pw)[i], q = ((float4 *)pg)[i], b = ((float4 *)pb)[i];\n            if (i >= OPT_THREADS) b = make_float4(0.f, 0.f, 0.f, 0.f);",
+   "the partial-chunk path of optim_update_kernel reads the momentum of the quads a thread reaches after its first as 0 (mu b = 0)",
+   "optim_update_kernel, partial chunks of more than 1024 floats",
+   [OPT + "test_operator_scalar_tail[sgd]"])
+
+# kernels_loss.hip
+_m("loss_reg_max_of_first_slot", "kernels_loss.hip",
+   "if (j < L) { v[k] = xr[j]; mx = fmaxf(mx, v[k]); }",
+   "if (j < L) { v[k] = xr[j]; mx = k >= 1 ? mx : fmaxf(mx, v[k]); }",
+   "the row maximum of loss_head_kernel<reg> ignores the register slots k >= 1 (columns from 64 on)",
+   "loss_head_kernel<reg>, the maximum over the slots (64 < L <= 1024)",
+   # pred must have the soft-max operator's bits: another maximum is another rounding
+   [LOSS + "test_loss_head[shape4-0.1]"])
+_m("loss_mem_max_of_first_64", "kernels_loss.hip",
+   "for (int j = lane; j < L; j += 64) mx = fmaxf(mx, xr[j]);",
+   "for (int j = lane; j < L; j += 64) mx = j >= 64 ? mx : fmaxf(mx, xr[j]);",
+   "the row maximum of loss_head_kernel<mem> ignores the columns from 64 on",
+   "loss_head_kernel<mem>, the maximum loop (L > 1024)",
+   [LOSS + "test_loss_head[shape5-0.1]"])
+_m("loss_reg_rank_last_slot_left_out", "kernels_loss.hip",
+   "if (j < L) LOSS_COLUMN(j, v[k]);",
+   "if (j < L) { const int keep_ = above; LOSS_COLUMN(j, v[k]); above = k == NV - 1 ? keep_ : above; }",
+   "the rank of loss_head_kernel<reg> does not count the columns of the last register slot (960 .. 1023)",
+   "loss_head_kernel<reg>, slot k == NV - 1 (L > 960)",
+   [LOSS + "test_loss_head[shape4-0.0]"])
+
+# kernels_input.hip: the decode and the plain resample (resample_aa_u8_kernel's turns have their entries above)
+_m("decode_stage_second_turn_zero", "kernels_input.hip",
+   "        if (a < g + span) *(uint4 *)(rows + ((size_t)r * CH + c) * 16) = load16_in_batch(src, a, total_bytes);\n    }\n    __syncthreads();",
+   "        if (a < g + span) *(uint4 *)(rows + ((size_t)r * CH + c) * 16) = i >= DEC_THREADS ? make_uint4(0u, 0u, 0u, 0u) : load16_in_batch(src, a, total_bytes);\n    }\n    __syncthreads();",
+   "the 16-byte pieces a thread of decode_u8_kernel stages after its first (i >= 256) are stored as zeros",
+   "decode_u8_kernel, the second turn of the staging loop (16 CH > 256: dim_out >= 81)",
+   [U8 + "test_decode_sweep[256-224-1]"])
+_m("decode_second_quad_turn_plus_one", "kernels_input.hip",
+   "for (int p = 0; p < 3; p++) v[p][j] = tab[p * 256 + L[px * 3 + p]];",
+   "for (int p = 0; p < 3; p++) v[p][j] = tab[p * 256 + L[px * 3 + p]] + (i >= DEC_THREADS ? 1.f : 0.f);",
+   "quads a thread of decode_u8_kernel reaches after its first (i >= 256) come out 1.0 high",
+   "decode_u8_kernel, the second turn of the quad loop (16 (dim_out / 4) > 256: dim_out >= 68)",
+   [U8 + "test_decode_sweep[256-224-1]"])
+_m("decode_scalar_store_lane3", "kernels_input.hip",
+   "                for (int j = 0; j < 4; j++) o[d * plane + j] = v[2 - d][j];\n            }\n        }\n    }\n    const int T = dim_out & 3;",
+   "                for (int j = 0; j < 4; j++) o[d * plane + j] = v[2 - d][j] + (j == 3 ? 0.0625f : 0.f);\n            }\n        }\n    }\n    const int T = dim_out & 3;",
+   "the element-wise store of a quad of decode_u8_kernel (vec == 0) adds 2^-4 to its fourth value",
+   "decode_u8_kernel, the element-wise quad stores (dim_out % 4 != 0 or an unaligned out)",
+   [U8 + "test_decode_sweep[40-33-1]"])
+_m("resample_ctab_past_256_no_weight", "kernels_input.hip",
+   "ctab[i] = (uint32_t)(fx >> 8) | (uint32_t)(fx & 255) << 16;",
+   "ctab[i] = (uint32_t)(fx >> 8) | (uint32_t)(i >= RS_THREADS ? 0 : fx & 255) << 16;",
+   "column-table entries a thread of resample_u8_kernel fills after its first (i >= 256) get horizontal weight 0",
+   "resample_u8_kernel, the second turn of the column-table fill (dim_out > 256)",
+   [RRC + "test_resample_wide_output_and_wide_box"])
+_m("resample_stage_pieces_past_64_zero", "kernels_input.hip",
+   "*(uint4 *)(rows + ((size_t)r * CH + c) * 16) = load16_in_batch(src, a, total_bytes);\n        }\n    }",
+   "*(uint4 *)(rows + ((size_t)r * CH + c) * 16) = c >= 64 ? make_uint4(0u, 0u, 0u, 0u) : load16_in_batch(src, a, total_bytes);\n        }\n    }",
+   "the 16-byte pieces of a source row that a lane of resample_u8_kernel stages after its first (c >= 64) are stored as zeros: source "
+   "bytes from 1024 on, counted from the span's start rounded down to 16",
+   "resample_u8_kernel, the second lane turn of the staging loop (boxes of 337 columns and more)",
+   [RRC + "test_resample_wide_output_and_wide_box"])
+_m("resample_scalar_store_lane3", "kernels_input.hip",
+   "                for (int j = 0; j < 4; j++) o[d * plane + j] = v[2 - d][j];\n            }\n        }\n    }\n    const int T = D & 3;",
+   "                for (int j = 0; j < 4; j++) o[d * plane + j] = v[2 - d][j] + (j == 3 ? 0.0625f : 0.f);\n            }\n        }\n    }\n    const int T = D & 3;",
+   "the element-wise store of a quad of resample_u8_kernel (vec == 0) adds 2^-4 to its fourth value",
+   "resample_u8_kernel, the element-wise quad stores",
+   [RRC + "test_resample_sweep[40-33-1]", RRC + "test_resample_into_an_unaligned_output"])
+_m("resample_second_quad_turn_plus_one", "kernels_input.hip",
+   "for (int p = 0; p < 3; p++) v[p][j] = rs_value(L0, L1, x0, x1, wx, wy, p);",
+   "for (int p = 0; p < 3; p++) v[p][j] = rs_value(L0, L1, x0, x1, wx, wy, p) + (i >= RS_THREADS ? 1.f : 0.f);",
+   "quads a thread of resample_u8_kernel reaches after its first (i >= 256) come out 1.0 high",
+   "resample_u8_kernel, the second turn of the quad loop (R (dim_out / 4) > 256)",
+   [RRC + "test_resample_sweep[256-224-1]"])
+
 # mi_common.hpp (one header mutant: it recompiles every .hip file)
 _m("pack_bf2_truncates", "mi_common.hpp",
    "    bf2_ r = __builtin_convertvector(v, bf2_);\n    return *(uint32_t *)&r;",

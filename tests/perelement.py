@@ -268,7 +268,12 @@ def stem_bn_fwd(ops, variant, N, H, record):
     print("stem + BN %s: conv worst %.3g, statistics worst %.3g x 2^-24 (bound scale), y worst %.3g" % ((variant,) + w3))
 
 
-def dgrad_bn_bwd_inputs(case, N, gen=normal):
+SMALL_VAR_EVERY, SMALL_VAR_SCALE = 8, 2e-4
+
+
+def dgrad_bn_bwd_inputs(case, N, gen=normal, small_var=False):
+    """small_var: every 8th channel of the normalised tensor varies by 1.5 x 2e-4 about 0.3 -- a variance of 9e-8, the size of eps (in
+    bf16 storage the channel keeps two or three levels about 0.3: a variance of about 7e-7)"""
     dt, Cn, H, K, k, s, where = case
     rnd = _rnd_bf(dt == "bf16")
     seed = hash((Cn, H, K, k, s)) % 1000 + 700
@@ -276,7 +281,10 @@ def dgrad_bn_bwd_inputs(case, N, gen=normal):
     w = rnd(gen((K, Cn, k, k), seed + 1, _wscale(Cn, K, k)))
     dy = rnd(gen((N, K, H // s, H // s), seed + 2))
     addend = rnd(gen((N, Cn, H, H), seed + 3)) if "red" in where else None
-    bn_x = rnd(gen((N, Cn, H, H), seed + 4, 1.5) + np.float32(0.3))    # the convolution output the batch norm normalised
+    bn_x = gen((N, Cn, H, H), seed + 4, 1.5)
+    if small_var:
+        bn_x[:, ::SMALL_VAR_EVERY] *= np.float32(SMALL_VAR_SCALE)
+    bn_x = rnd(bn_x + np.float32(0.3))    # the convolution output the batch norm normalised
     gamma, beta = bn_params_conv(Cn, seed + 5, gen)
     means = bn_x.mean((0, 2, 3), dtype=np.float64).astype(np.float32)
     vars_ = bn_x.var((0, 2, 3), dtype=np.float64).astype(np.float32)
@@ -293,14 +301,14 @@ def dgrad_bn_bwd_call(ops, case, inp):
               addend=inp["addend"])
 
 
-def dgrad_bn_bwd(ops, case, N, record):
+def dgrad_bn_bwd(ops, case, N, record, small_var=False):
     """mi_op_conv_dgrad_bn_bwd_{f32,bf16} at the trainer's BN'-fusion sites: the gated dgrad (mask > 0 ? dgrad (+ addend) : 0) on the
     slabs against the convolution reference; dbeta and dgamma against float64 sums of the product's own gated output as it is stored
     (the kernels' contract: kernels_igemm_bf16.hip sums the rounded gradient), to C_FACTOR 2^-24 sum |terms|"""
     dt, Cn, H, K, k, s, where = case
     bf = dt == "bf16"
     seed = hash((Cn, H, K, k, s)) % 1000 + 700
-    inp = dgrad_bn_bwd_inputs(case, N)
+    inp = dgrad_bn_bwd_inputs(case, N, small_var=small_var)
     w, dy, addend, bn_x, gamma, means, vars_, mask, eps = (inp[n] for n in ("w", "dy", "addend", "bn_x", "gamma", "means", "vars_", "mask", "eps"))
     gated, bdx, dg, db, fused = dgrad_bn_bwd_call(ops, case, inp)
     plan = R.conv_plan(ops.L, 1 if bf else 0, "default", "dgrad", N, Cn, H, K, k, s)

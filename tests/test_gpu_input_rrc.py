@@ -85,6 +85,28 @@ def test_resample_into_an_unaligned_output(ops):
     assert np.all(front == SENTINEL) and np.all(back == SENTINEL)
 
 
+WIDE_IN, WIDE_OUT = 344, 260
+
+
+def wide_boxes():
+    """the boxes of test_resample_wide_output_and_wide_box: 340 columns from column 0 and from column 3 (another residue of the span's
+    first byte), flipped and not; the whole image; a narrow box for comparison"""
+    return np.array([(2, 0, 340, 340, 0), (0, 3, 300, 340, 1), (0, 0, WIDE_IN, WIDE_IN, 1), (5, 7, 60, 50, 0)], np.int32)
+
+
+def test_resample_wide_output_and_wide_box(ops):
+    """the two turns of resample_u8_kernel that 256 -> 224 does not take: the column table's second turn (dim_out = 260 > 256 threads:
+    columns 256 .. 259) and the lanes' second turn over a staged row's 16-byte pieces (a box 340 columns wide spans 1020 bytes and, with
+    its start rounded down to 16, up to 65 pieces; the whole 344-column image 66).  Bits of the model; rrcref.launch_rows: 16 rows"""
+    rng = np.random.RandomState(344260)
+    boxes = wide_boxes()
+    src = rng.randint(0, 256, size=(len(boxes), WIDE_IN, WIDE_IN, 3), dtype=np.uint8)
+    assert rrcref.launch_rows(WIDE_IN, WIDE_OUT) == 16
+    out, front, back = run_resample(ops, src, boxes, WIDE_OUT)
+    check(out, rrcref.resample(src, boxes, WIDE_OUT))
+    assert np.all(front == SENTINEL) and np.all(back == SENTINEL)
+
+
 @pytest.mark.parametrize("dim_in,dim_out", [(256, 224), (37, 30), (32, 32)])
 def test_a_dim_out_box_is_the_decode(ops, dim_in, dim_out):
     """h == w == dim_out: all weights are 0 and the output is mi_op_decode_u8's on (row0, col0, flip), bit for bit, on the device"""

@@ -14,6 +14,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import convref
+import ewref
 import lossref as R
 from util import ACT_MAX_ABS, ACT_REL_L2, check_act
 
@@ -96,6 +98,30 @@ def test_batch_totals_past_64_rows_and_at_the_topk_threshold(ops, topk, eps):
     assert _same(pred, ops.softmax(x))
     ref = R.loss_head(x, lab, eps)[2]
     assert np.all(np.abs(rl.astype(np.float64) - ref) <= R.loss_bound(ref))
+
+
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+@pytest.mark.parametrize("L", ewref.DOMINANT_L)
+def test_dominant_logit_past_column_63(ops, L, eps):
+    """the row maximum is taken over j = lane, lane + 64, ...: make_inputs' large logit sits at column 17, in every lane's first turn, and
+    a maximum that stops after it is the same function up to rounding.  lossref.dominant_inputs: rows whose only large logit -- 95 above
+    every other one, so that expf overflows without it -- sits at column 64, at the last column, in between and (L > 960) in the last
+    register slot of loss_head_kernel<reg>, with labels on it, past column 63 off it, and at column 0.  L = 65 and 1000 run <reg>, 1537
+    <mem>.  Checks as test_loss_head: pred is the soft-max operator's bits and within the soft-max bound of float64, the rank is the rule
+    on pred, row_loss inside loss_bound"""
+    x, lab = R.dominant_inputs(L)
+    pred, dl, rl, rr, last, _ = ops.loss_head(x, lab, eps, min(5, L))
+    assert _same(pred, ops.softmax(x))
+    ref_sm, A = ewref.softmax_ref(x)
+    w, bad = convref.dist_f32(pred, ref_sm, A)
+    assert bad == 0, "pred: %d out of the soft-max bound (worst %.3g)" % (bad, w)
+    assert np.array_equal(rr, R.rank_of(pred, lab))
+    assert rr[0] == 0 and rr[1] >= 1, "row 0's label is its dominant column, row 1's is not"
+    ref_pred, ref_dl, ref_loss, _ = R.loss_head(x, lab, eps)
+    check_act(dl, ref_dl, "dlogits L %d eps %g" % (L, eps), ACT_REL_L2, ACT_MAX_ABS)
+    err = np.abs(rl.astype(np.float64) - ref_loss)
+    assert np.all(np.isfinite(rl))
+    assert np.all(err <= R.loss_bound(ref_loss)), (err, R.loss_bound(ref_loss))
 
 
 def test_long_row_sums_z_in_double(ops):

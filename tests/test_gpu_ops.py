@@ -5,6 +5,8 @@ tensors are permuted on the way.  Tolerances: util.py (fp32, reduction order dif
 import numpy as np
 import pytest
 
+import convref as R
+import ewref as E
 from util import check_act, check_grad, nchw, nhwc, rand, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -142,7 +144,9 @@ def test_bn_add_relu_and_external_mask(ops, oracle, C, H, N):
     assert np.array_equal(hdx, gdx) and np.array_equal(hdg, gdg) and np.array_equal(hdb, gdb)
 
 
-@pytest.mark.parametrize("C,H,N", [(64, 112, 2), (64, 16, 4), (64, 12, 3)])  # 12: rows that are not whole 8-element vectors -> the generic kernel
+# 12: rows that are not whole 8-element vectors -> the generic forward kernel; 13: an odd plane (6 x 6 outputs, the last row and column in no
+# window) -> the generic backward kernel as well, which every even plane leaves to maxpool_bwd_3x3s2_kernel
+@pytest.mark.parametrize("C,H,N", [(64, 112, 2), (64, 16, 4), (64, 12, 3), (64, 13, 3)])
 def test_maxpool(ops, oracle, C, H, N):
     x = np.maximum(rand((N, H, H, C), 21), 0)  # post-ReLU input: ties at 0 exercise "first max wins"
     y, idx = oracle.maxpool_fwd(x, 3, 2)
@@ -213,6 +217,89 @@ def test_softmax_ce_adam(ops, oracle):
     assert flag == 1  # NaN/Inf gradient seen (check_errors semantics, resnet.cu:2879-2907)
     assert rel_l2(gp, rp) < 1e-6 and rel_l2(gm, rm) < 1e-6 and rel_l2(gv, rv) < 1e-6
     assert gm[5] == m[5] and gv[6] == v[6]  # guards keep the old moments (resnet.cu:610-617)
+
+
+def test_adam_second_grid_stride_turn(ops):
+    """adam_kernel's grid is capped at 16384 workgroups of 256: past 4 194 304 elements a thread takes a second turn (ResNet-50's arena
+    takes six).  n = 16384 x 256 + 257 (one whole workgroup and one thread of the second turn), t = 500 so that the two bias corrections
+    differ widely, wd > 0, NaN / Inf gradients planted in the first turn and in the second; every element against the float64 formula
+    (ewref.adam_ref, the bounds of test_gpu_batch256_ew.py)"""
+    x, bad_g, hp = E.adam_second_turn_inputs()
+    p, g, m, v = x
+    n = p.size
+    assert n == E.ADAM_GRID_CAP * 256 + 257
+    gp, gm, gv, flag = ops.adam(p, g, m, v, hp["lr"], hp["wd"], hp["b1"], hp["b2"], hp["cb1"], hp["cb2"], hp["eps"])
+    assert flag == 1
+    bad, worst = E.adam_violations((gp, gm, gv), x, hp)
+    assert bad == 0, "Adam: %d values out of bounds (worst %.3g x 2^-24 A)" % (bad, worst)
+    assert np.array_equal(gm[bad_g], m[bad_g]) and np.array_equal(gv[bad_g], v[bad_g]), "a NaN / Inf gradient must keep m and v"
+    assert np.all(np.isfinite(gp)), "p must stay finite"
+
+
+def _full_store_forward(dims, batch):
+    """one forward pass of a trainer under the FULL store policy (fp32); the caller closes it"""
+    import synth
+    from resnet_amd import Trainer
+    from resnet_amd import binding as B
+    tr = Trainer(dims, batch)
+    if tr.L.mi_device_count() < 1:
+        pytest.fail("no HIP device: this test must run on the MI355X box")
+    tr.set_store_policy(B.MI_STORE_FULL)
+    params = synth.make_params(dims, perturb_bn=True)
+    tr.set_params(params)
+    tr.source_host(B.MI_LAYOUT_NHWC)
+    im, lab = synth.make_batch(dims, batch, step=0)
+    tr.fill_host_batch(im, lab)
+    tr.load_new_batch()
+    tr.forward()
+    tr.check()
+    return tr, params
+
+
+def test_full_store_policy_tensors_per_element():
+    """the tensors only the FULL store policy writes, which no operator exposes: bn_apply_kernel's xhat_out and norm_out (every batch
+    norm's x-hat and its output BEFORE the ReLU) and add_relu_kernel's sum and activation (the expansion's BN output + shortcut, kept
+    as a pass of its own).  C1S at batch 4, one forward: x-hat and the BN output of the stem and of every expansion against
+    ewref.apply_ref from the kernel's own statistics (x-hat: gamma 1, beta 0), the stem's activation = max(BN output, 0) bit for bit;
+    per block sum = BN output + shortcut and activation = max(sum, 0) bit for bit"""
+    import synth
+    dims, batch = synth.C1S_DIMS, 4
+    tr, params = _full_store_forward(dims, batch)
+    try:
+        a = tr.t.contents.forward_buffer.contents.activations.contents
+        eps = float(tr.t.contents.eps)
+
+        def held(what, cache, x, gamma, beta, out):
+            means, vars_ = tr._to_host(cache.means, cache.feature_size), tr._to_host(cache.vars, cache.feature_size)
+            xhat = tr._to_host(cache.normalized_temp, cache.input_size).reshape(x.shape)
+            norm = tr._to_host(cache.normalized, cache.input_size).reshape(x.shape)
+            for name, got, g, b in (("x-hat", xhat, np.ones_like(gamma), np.zeros_like(beta)), ("BN output", norm, gamma, beta)):
+                ref, A = E.apply_ref(x, g, b, means, vars_, eps, False)
+                w, bad = R.dist_f32(got, ref, A)
+                assert bad == 0, "%s %s: %d out of bounds (worst %.3g)" % (what, name, bad, w)
+            assert (norm < 0).any()
+            if out is not None:
+                assert np.array_equal(norm.view(np.uint32), out.view(np.uint32)), "%s: the stored BN output differs from the unit's output" % what
+            return norm
+
+        norm = held("stem", a.norm_init_conv.contents, tr.activation("init_conv_applied"), params[1], params[2], None)
+        act = tr.activation("init_conv_activated")
+        assert np.array_equal(np.maximum(norm, np.float32(0)).view(np.uint32), act.view(np.uint32)), "stem: activation != max(BN output, 0)"
+        loc, prev = 3, tr.activation("init_convblock_input")
+        for i in range(dims["n_conv_blocks"]):
+            k = a.activation_conv_blocks[i].contents
+            pre = "conv_blocks/%d/" % i
+            bn_out = tr.activation(pre + "expanded_post_norm")
+            held("block %d expansion" % i, k.norm_post_expanded.contents, tr.activation(pre + "expanded_applied"), params[loc + 7], params[loc + 8], bn_out)
+            proj = bool(k.norm_post_projection)
+            short = tr.activation(pre + "post_projection_norm_vals") if proj else prev
+            s, out = tr.activation(pre + "combined_output"), tr.activation(pre + "output_activated")
+            assert np.array_equal((bn_out + short).view(np.uint32), s.view(np.uint32)), "block %d: sum != BN output + shortcut" % i
+            assert np.array_equal(np.maximum(s, np.float32(0)).view(np.uint32), out.view(np.uint32)), "block %d: activation != max(sum, 0)" % i
+            assert (s < 0).any() and np.any(short)
+            loc, prev = loc + (12 if proj else 9), out
+    finally:
+        tr.close()
 
 
 def test_layout(ops):

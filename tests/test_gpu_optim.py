@@ -192,6 +192,34 @@ def test_lars_all_zero_gradient_takes_the_trust_one_path(ops):
     assert rel_l2(nw[sl], w[sl].astype(np.float64) - want_b) <= UPD_REL
 
 
+def test_lars_loop_turns_and_an_all_zero_weight_tensor(ops):
+    """the turns of the LARS passes that the ResNet-50 geometry does not isolate, and the other half of the trust-1 guard
+    (optim_ref.LOOP_TURN_OFFSETS): tensor 1 is an all-zero WEIGHT tensor with a gradient (|w| = 0, |g| > 0: trust ratio 1, the tensor
+    moves; test_lars_all_zero_gradient_takes_the_trust_one_path has the |g| = 0 half); tensor 2 has 65 x 8192 + 4 floats -- 66 chunks:
+    lane 0 and lane 1 of optim_trust_kernel take a second turn; tensor 3 has 1024 + 256 x 4 + 4 floats: one partial chunk whose float4
+    loops take two whole turns and one more quad.  Three calls; bounds as test_operator_per_element_at_resnet50_geometry"""
+    offs, is_w = R.LOOP_TURN_OFFSETS, R.LOOP_TURN_IS_WEIGHT
+    w, g, b = _spread_state(offs, 51)
+    z = slice(offs[1], offs[2])
+    w[z] = 0
+    b[z] = 0
+    lr, wd = 0.5, float(np.float32(5e-5))
+    for call in range(3):
+        if call:
+            g = _spread_state(offs, 150 + call)[1]
+        nw, ng, nb, flag, sq = ops.momentum_update(R.LARS, w, g, b, offs, is_w, lr, wd, MU, TAU)
+        assert flag == 0 and not np.any(ng)
+        if call == 0:
+            assert sq[1, 0] == 0 and sq[1, 1] > 0 and np.any(nw[z]), "the all-zero weight tensor must move with trust ratio 1"
+        ref_sq = R.sq_norms(_split(w, offs), _split(g, offs))
+        e = np.abs(sq - ref_sq) / np.maximum(ref_sq, 1e-300)
+        assert e.max() <= NORM_REL, "call %d: squared norm of tensor %d off by %.3e relative" % (call, int(np.argmax(e) // 2), e.max())
+        ref_w, _, ref_b, rflag = R.step(R.LARS, _split(w, offs), _split(g, offs), _split(b, offs), is_w, float(np.float32(lr)), wd, MU, TAU)
+        assert rflag == 0
+        _check_update("lars loop turns call %d" % call, _split(nw, offs), _split(nb, offs), ref_w, ref_b)
+        w, b = nw, nb
+
+
 # ---- the trainer ----
 def _trainer(dims, batch, params, kind, lr, wd, dtype=0, **kw):
     from resnet_amd import Trainer

@@ -127,6 +127,57 @@ def test_bn_bwd_ragged(ops, run):
     P.bn_bwd(ops, case, N, _recorder(net, N))
 
 
+# The loop turns of the batch-norm reductions that no plane of the three nets takes at N <= 8 (ewref.LOOP_TURN_SHAPES says which
+# shape takes which turn; tests/test_loop_turns_model.py holds the reach from the launchers' formulas without a GPU).  Checkers, references
+# and bounds are those of the lists above.
+LT_FWD = [((pair, Cn, H, ("relu",)), N) for pair, Cn, H, N in E.LOOP_TURN_SHAPES]
+LT_BWD = [((pair, Cn, H, mode), N) for pair, Cn, H, N in E.LOOP_TURN_SHAPES for mode in E.MODE_ORDER]
+
+
+@pytest.mark.parametrize("run", LT_FWD, ids=["%s_C%d_H%d_N%d" % (c[0], c[1], c[2], n) for c, n in LT_FWD])
+def test_bn_loop_turns(ops, run):
+    case, N = run
+    P.bn_fwd(ops, case, N, _recorder("turns", N))
+
+
+@pytest.mark.parametrize("run", LT_BWD, ids=["%s_C%d_H%d_N%d_mode%d" % (c[0], c[1], c[2], n, c[3]) for c, n in LT_BWD])
+def test_bn_bwd_loop_turns(ops, run):
+    case, N = run
+    P.bn_bwd(ops, case, N, _recorder("turns", N))
+
+
+SMALL_VAR = {"f32": ("c4i_N4", "f32_C256_H8_K128_k1_s1"), "bf16": ("c1s_N4", "bf16_C64_H8_K256_k1_s1")}
+
+
+@pytest.mark.parametrize("dt", list(SMALL_VAR))
+def test_dgrad_bn_bwd_small_variance(ops, dt):
+    """the fused dgrad + BN' cases normalise tensors of variance 2.25, where eps = 1e-7 cannot be seen; here every 8th channel has a
+    variance of the size of eps (perelement.dgrad_bn_bwd_inputs, small_var), so that bn_bwd_parts_merge_kernel's s2 / sqrt(var + eps)
+    is held to it"""
+    run = [r for r, i in zip(DGRAD_BN, DGRAD_BN_IDS) if i == "%s-%s" % SMALL_VAR[dt]]
+    assert len(run) == 1, "the case list no longer holds %s-%s" % SMALL_VAR[dt]
+    net, N, case = run[0]
+    P.dgrad_bn_bwd(ops, case, N, _recorder(net + " small var", N), small_var=True)
+
+
+@pytest.mark.parametrize("dt", [P.F32, P.BF16], ids=["f32", "bf16"])
+def test_avgpool_second_lane_turn(ops, dt):
+    """9 x 9 planes: lanes 0 .. 16 of avgpool_fwd_kernel add a second element (the nets' last planes have 49 or fewer)"""
+    P.avgpool(ops, dt, 2, 64, 9, _recorder("turns", 2))
+
+
+@pytest.mark.parametrize("Ln", E.DOMINANT_L)
+def test_softmax_dominant_logit_past_column_63(ops, Ln):
+    """rows whose maximum sits past column 63, more than 89 above every other logit: a maximum taken over the lanes' first turn alone
+    overflows expf (ewref.dominant_rows)"""
+    x = E.dominant_rows(Ln)
+    got = ops.softmax(x)
+    ref, A = E.softmax_ref(x)
+    w, bad = R.dist_f32(got, ref, A)
+    assert bad == 0, "soft-max: %d out of bounds (worst %.3g)" % (bad, w)
+    _recorder("turns", len(x))(("softmax dominant", "L=%d" % Ln), w)
+
+
 @pytest.mark.parametrize("run", EW, ids=EW_IDS)
 def test_pools_softmax_fc_ragged(ops, run):
     net, N, (what, arg) = run

@@ -34,7 +34,7 @@ def _builder():
 def test_entries_are_well_formed():
     names = [m["name"] for m in mutants.MUTANTS]
     assert len(names) == len(set(names)), "names are not unique"
-    assert len(names) >= 79
+    assert len(names) >= 130
     for m in mutants.MUTANTS:
         assert re.fullmatch(r"[a-z0-9_]+", m["name"]), m["name"]
         assert m["what"] and m["branch"], m["name"]
