@@ -20,6 +20,10 @@
  *   ./ResNetMI --label-smoothing 0.1 --mixup 0.2 --cutmix 1.0 --mix-prob 1.0 --mix-seed 7
  *              mixup / CutMix on the device at every load (mi_trainer_set_mix; implies the device loss head): Beta(A, A) weights with A in
  *              (0, 1], 0 = that mode off; with both on each step draws one of them with equal odds; --mix-prob P: the share of steps mixed
+ *   ./ResNetMI --random-erase 0.1 --erase-mode noise --erase-seed 7
+ *              random erasing on the device at every load, in front of the mix step (mi_trainer_set_erase): with probability P a row gets
+ *              one box of 0.02 .. 0.33 of its area, aspect 0.3 .. 3.3 (torchvision's --random-erase), filled with the mean pixel (the
+ *              default, --erase-mode const) or with noise of ImageNet's per-channel deviation around it (timm's pixel mode)
  *   ./ResNetMI --bn-momentum 0.1 --val-u8 /data/val_shards/u8 --val-dim-in 256 --val-every 5000
  *              evaluation: running statistics of every batch norm (mi_trainer_track_running_stats; --val-u8 alone implies momentum 0.1) and,
  *              every STEPS iterations and at the end of every epoch, the eval pass over every %03d.images_u8 / %03d.labels under DIR
@@ -126,6 +130,9 @@ int main(int argc, char **argv) {
     const unsigned long long mix_seed = strtoull(opt(argc, argv, "--mix-seed", "0"), NULL, 10);
     const int mixing = MIXUP != 0 || CUTMIX != 0;
     const int loss_on_device = smoothing_arg || topk_arg || device_loss || mixing;
+    const double ERASE_PROB = atof(opt(argc, argv, "--random-erase", "0"));
+    const char *erase_mode = opt(argc, argv, "--erase-mode", "const");
+    const unsigned long long erase_seed = strtoull(opt(argc, argv, "--erase-seed", "0"), NULL, 10);
     const int TOPK = atoi(topk_arg ? topk_arg : "5");
     const char *bn_momentum_arg = opt(argc, argv, "--bn-momentum", NULL), *val_u8 = opt(argc, argv, "--val-u8", NULL);
     const int VAL_DIM_IN = atoi(opt(argc, argv, "--val-dim-in", "256")), VAL_EVERY = atoi(opt(argc, argv, "--val-every", "0"));
@@ -176,6 +183,11 @@ int main(int argc, char **argv) {
     if (loss_on_device && mi_trainer_set_loss(trainer, (float)atof(smoothing_arg ? smoothing_arg : "0"), TOPK,
                                               MI_LOSS_DEVICE | (device_loss ? MI_LOSS_NO_PRED_COPY : 0))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (mixing && mi_trainer_set_mix(trainer, MIXUP, CUTMIX, MIX_PROB, 0.5, mix_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    if (ERASE_PROB != 0) { /* value 0 = the mean pixel (the images are mean-subtracted, not divided); std = ImageNet's in byte units */
+        if (strcmp(erase_mode, "const") && strcmp(erase_mode, "noise")) { fprintf(stderr, "--erase-mode const|noise\n"); return 1; }
+        const MiEraseFill fill = {!strcmp(erase_mode, "noise") ? MI_ERASE_NOISE : MI_ERASE_CONST, {0.f, 0.f, 0.f}, {58.395f, 57.12f, 57.375f}, 0};
+        if (mi_trainer_set_erase(trainer, ERASE_PROB, 0.02, 0.33, 0.3, 3.3, &fill, erase_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    }
     if ((bn_momentum_arg || val_u8 || ema_arg) && mi_trainer_track_running_stats(trainer, 1, (float)atof(bn_momentum_arg ? bn_momentum_arg : "0.1"))) {
         fprintf(stderr, "%s\n", mi_last_error()); return 1;
     }

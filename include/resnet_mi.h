@@ -861,6 +861,59 @@ int mi_op_loss_head_mix(const float *logits, const int *labels_a, const int *lab
 int mi_trainer_set_mix(Train_ResNet *t, double mixup_alpha, double cutmix_alpha, double prob, double switch_prob, uint64_t seed);
 int mi_trainer_last_mix(const Train_ResNet *t, MiMixPlan *out);
 
+/* ---------------- random erasing: a box per image, filled in place with a constant or with noise ----------------
+ * Random erasing (Zhong et al. 2017; torchvision's RandomErasing, timm's --reprob) overwrites one box of an image.  It is a per-sample
+ * transform: every row of the batch has its own draw, and the labels do not change.  Off by default; with it off every launch, value and
+ * dumped file is what it was.
+ *
+ * mi_erase_plan: host-only and deterministic, a pure function of its arguments.  out[4 i ..] = (y0, x0, h, w) of row i, all 0 for a row
+ * that is not erased; h == 0 or w == 0 means no box.  s = splitmix64_at(seed, epoch), k = splitmix64_at(s, step world + rank) (modulo
+ * 2^64: mi_mix_plan's step key), e = splitmix64_at(k, 1000) (the mix plan draws indices up to 131 from k: equal seeds share no draw),
+ * k_i = splitmix64_at(e, i), d(j) = splitmix64_at(k_i, j), U(x) = (x >> 11) 2^-53.  torchvision's RandomErasing.forward + get_params
+ * on a D x D image, D = dim:
+ *   U(d(0)) >= prob: no box.  Else try t = 0 .. 9: target = D D (scale_lo + U(d(1 + 4t)) (scale_hi - scale_lo)), ratio = exp(log(ratio_lo) +
+ *   U(d(2 + 4t)) (log(ratio_hi) - log(ratio_lo))), h = lrint(sqrt(target ratio)), w = lrint(sqrt(target / ratio)) (half to even; h takes the
+ *   product, the other way round than the RRC plan: torchvision's own asymmetry); the first try with h < D and w < D (strict) is taken:
+ *   y0 = ((d(3 + 4t) >> 32) (D - h + 1)) >> 32, x0 = ((d(4 + 4t) >> 32) (D - w + 1)) >> 32.  No try taken: no box (torchvision returns the
+ *   image).  At tiny D a taken try may have h == 0 or w == 0: a legal, empty box, stored as drawn.
+ * Plain double arithmetic, every operation rounded on its own.  Returns 0, or -1 with mi_last_error set: n < 0, dim outside [1, 16384],
+ * prob outside [0, 1], scale_lo or ratio_lo not positive, scale_hi < scale_lo, ratio_hi < ratio_lo, rank outside [0, world). */
+int mi_erase_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, int n, int dim, double prob, double scale_lo, double scale_hi,
+                  double ratio_lo, double ratio_hi, int *out);
+/* the erase kernel on its own (kernels_input.hip): images_nchw fp32 [n][3][dim][dim] in device memory, IN PLACE; boxes_host int [n][4]
+ * (y0, x0, h, w) and fill_host in host memory, both read before the call returns.  Every box is clamped (y0 into [0, dim], h into
+ * [0, dim - y0], x likewise; on the host and again on the device); nothing outside a row's box is read or written, and every word
+ * outside the boxes keeps its bits.  A row without a box writes nothing; a launch none of whose rows has a box is skipped.
+ *   MI_ERASE_CONST: every element of plane c in the box becomes value[c].
+ *   MI_ERASE_NOISE: element (c, y, x) of row i becomes value[c] (+) std[c] (x) z, product and sum fp32 operations rounded one by one.  z
+ *     depends on the element's POSITION only, not on the box or the launch: q = splitmix64_at(noise_seed, first_row + i), el = (c dim + y)
+ *     dim + x, g_m = splitmix64_at(q, 64 + 3 el + m) for m = 0, 1, 2, S = the sum of the twelve 16-bit fields (g_m >> 16 f) & 0xFFFF,
+ *     f = 0 .. 3, z = (float)(S - 393210) 2^-16 (exact).  That is the Irwin-Hall approximation of a unit normal: mean 0, variance
+ *     1 - 2^-32, |z| < 6 -- NOT Gaussian in the tails.  It is integer arithmetic, so device, numpy model and any port agree bit for bit.
+ * The boxes reach the device as kernel arguments, four uint16 a row, 256 rows a launch: no staging buffer, no copy, no event.  16-byte
+ * stores where image_size % 4 == 0 and images is 16-byte aligned.  Returns 0, or -1 with mi_last_error set and nothing launched: a NULL
+ * pointer, n outside [1, 65535], dim outside [1, 16384], image_size != 3 dim^2, images not 4-byte aligned, an unknown mode, a value or std
+ * that is not finite, a negative std. */
+enum { MI_ERASE_CONST = 0, MI_ERASE_NOISE = 1 };
+typedef struct { int mode; float value[3]; float std[3]; uint64_t noise_seed; } MiEraseFill;
+int mi_op_erase_batch(float *images_nchw, int n, int image_size /* 3 dim^2 */, int dim, const int *boxes_host /* [n][4] */,
+                      const MiEraseFill *fill_host, int64_t first_row /* row i uses noise key index first_row + i */);
+/* host only, launches nothing: [0] threads of a workgroup, [1] the cap on grid.x, [2] waves of a workgroup, [3] rows of a launch.  One
+ * sweep of the capped grid covers [1] [2] row segments of a row's box */
+void mi_debug_erase_geometry(size_t out[4]);
+/* The trainer.  While erasing is on load_new_batch ends, for every data source and behind the prefetch swap, on the compute stream and IN
+ * FRONT OF the mix step (erasing is a per-sample transform, mixing the collate step), with: the plan of (seed, cur_epoch, cur_dump_id
+ * before its increment, the Batch's rank and world) for batch_size rows at dim = the network's input -- the values the mix step uses, so
+ * a resumed run and a prefetching run see the same boxes --, and the erase launch on Batch.images with noise_seed = the plan's e and
+ * first_row = 0 (fill->noise_seed is ignored).  Either loss head; no label changes; the eval entry points never erase.  prob == 0
+ * switches it off; with it off nothing is launched and nothing allocated.  May be called between steps.  Like the optimizer and the mix
+ * setting it is not dumped: a resumed run sets it again.  Refused (-1, mi_last_error set) for arguments mi_erase_plan or
+ * mi_op_erase_batch refuses.  mi_trainer_last_erase: the boxes of the last load_new_batch into out [batch_size][4]; returns the rows
+ * written (0 before the first load), -1 while erasing is off. */
+int mi_trainer_set_erase(Train_ResNet *t, double prob, double scale_lo, double scale_hi, double ratio_lo, double ratio_hi,
+                         const MiEraseFill *fill /* noise_seed ignored */, uint64_t seed);
+int mi_trainer_last_erase(const Train_ResNet *t, int *out /* [batch_size][4] */);
+
 /* typed operator layer: x_dt = storage type of the convolution-side tensors (x, dx), a_dt = of the activation-side tensors
  * (y, residual, dy, mask_src, gated_out).  Supported pairs: (F32,F32), (BF16,BF16), (F32,BF16). */
 int mi_op_convert(const void *in, int in_dt, void *out, int out_dt, size_t n);

@@ -101,6 +101,19 @@ class MiMixPlan(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+MI_ERASE_CONST, MI_ERASE_NOISE = 0, 1
+
+
+class MiEraseFill(C.Structure):
+    _fields_ = [("mode", C.c_int), ("value", C.c_float * 3), ("std", C.c_float * 3), ("noise_seed", C.c_uint64)]
+
+
+def erase_fill_struct(mode="const", value=(0, 0, 0), std=(1, 1, 1), noise_seed=0):
+    """a MiEraseFill; mode "const" / "noise" or the integer itself (an unknown one is the library's to refuse)"""
+    m = {"const": MI_ERASE_CONST, "noise": MI_ERASE_NOISE}.get(mode, mode)
+    return MiEraseFill(int(m), (C.c_float * 3)(*[float(v) for v in value]), (C.c_float * 3)(*[float(v) for v in std]), int(noise_seed) & (2 ** 64 - 1))
+
+
 class MiLossMetrics(C.Structure):
     _fields_ = [("loss_sum", C.c_double), ("rows", C.c_int64), ("wrong_top1", C.c_int64), ("wrong_topk", C.c_int64),
                 ("batches", C.c_int64)]
@@ -282,6 +295,11 @@ PROTOTYPES = {
     "mi_op_loss_head_mix": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
     "mi_trainer_set_mix": (_i, [_T, C.c_double, C.c_double, C.c_double, C.c_double, _u64]),
     "mi_trainer_last_mix": (_i, [_T, C.POINTER(MiMixPlan)]),
+    "mi_erase_plan": (_i, [_u64, _i, C.c_int64, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    "mi_op_erase_batch": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(MiEraseFill), C.c_int64]),
+    "mi_debug_erase_geometry": (None, [C.POINTER(_sz)]),
+    "mi_trainer_set_erase": (_i, [_T, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(MiEraseFill), _u64]),
+    "mi_trainer_last_erase": (_i, [_T, _vp]),
     "mi_batch_set_augment_rrc": (_i, [_B, _i, _u64, C.c_double, C.c_double, C.c_double, C.c_double]),
     "mi_batch_last_boxes": (_i, [_B, _vp]),
     "mi_aa_coeffs": (_i, [_i, _i, _i, _vp, _vp, _i]),

@@ -513,3 +513,133 @@ int mid_mix_labels(mid_stream s, const int *labels, int *labels_b, int n) {
 /* the launch geometry of mixup_kernel and cutmix_kernel, for tests and documents: [0] threads, [1] the cap on grid.x, [2] waves of a
  * workgroup.  One sweep of the capped grid: [0] [1] work items of mixup_kernel, [1] [2] row segments of cutmix_kernel */
 void mid_mix_geometry(size_t out[3]) { out[0] = MIX_THREADS; out[1] = MIX_MAX_BLOCKS_X; out[2] = MIX_THREADS / 64; }
+
+// ---- random erasing: a box per image filled in place with a constant or with noise (include/resnet_mi.h, "random erasing"; tests/eraseref.py) ----
+// The boxes travel by value, as kernel arguments: four uint16 a row, ER_ROWS rows a launch (2 KB of the 4 KB a launch may carry), so there
+// is no staging buffer, no copy and nothing the host has to keep alive behind the launch.
+#define ER_THREADS 256
+#define ER_MAX_BLOCKS_X 128
+#define ER_ROWS 256
+struct EraseBoxes { uint16_t v[ER_ROWS][4]; };                 // (y0, x0, h, w) of the launch's rows, clamped by the launcher
+struct EraseFill { float value[3], std[3]; uint64_t seed; uint64_t first; }; // first: the noise key index of the launch's row 0
+
+// as kernels_misc.hip, synth.c and tests/synth.py define the counter streams
+__device__ __forceinline__ uint64_t er_splitmix64_at(uint64_t seed, uint64_t i) {
+    uint64_t z = seed + (i + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// Irwin-Hall: twelve 16-bit fields of three draws, their sum less its mean 12 * 65535 / 2, in units of 2^-16.  |S - 393210| < 2^20, so the
+// conversion and the product with a power of two are exact: integer arithmetic up to the two roundings of er_noise
+__device__ __forceinline__ float er_z(uint64_t q, uint32_t el) {
+    int S = 0;
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+        const uint64_t g = er_splitmix64_at(q, 64 + 3 * (uint64_t)el + m);
+        S += (int)(g & 0xFFFF) + (int)((g >> 16) & 0xFFFF) + (int)((g >> 32) & 0xFFFF) + (int)(g >> 48);
+    }
+    return (float)(S - 393210) * 0x1p-16f;
+}
+// value (+) std (x) z: the product and the sum rounded one by one (the pragma: see mix_pair)
+__device__ __forceinline__ float er_noise(float value, float std, float z) {
+#pragma clang fp contract(off)
+    const float sz = std * z;
+    const float r = value + sz;
+    return r;
+}
+// grid (x, rows of the launch), a wave per row segment of the row's box; a row without a box leaves at once.  The box is clamped here
+// too (y0 into [0, D], h into [0, D - y0], x likewise): no argument addresses outside the row's image.  NOISE 0: plane c's word
+// everywhere; 1: a value per element from its position el = (c D + y) D + x alone.  VEC (image_size % 4 == 0, a 16-byte aligned batch):
+// the elements up to the segment's first 16-byte boundary one lane each, whole 16-byte groups lane-strided, the rest one lane each;
+// else every element on its own, lane-strided.  Stores only: nothing is read from the batch
+template <int NOISE, int VEC>
+__global__ void __launch_bounds__(ER_THREADS)
+erase_kernel(float *__restrict__ images, int D, EraseBoxes boxes, EraseFill fill) {
+    const uint16_t *bx = boxes.v[blockIdx.y];
+    const int y0 = min((int)bx[0], D), x0 = min((int)bx[1], D);
+    const int h = min((int)bx[2], D - y0), w = min((int)bx[3], D - x0);
+    if (h == 0 || w == 0) return;
+    const int lane = threadIdx.x & 63, waves = ER_THREADS / 64;
+    const size_t plane = (size_t)D * D;
+    float *const img = images + (size_t)blockIdx.y * 3 * plane;
+    const uint64_t q = NOISE ? er_splitmix64_at(fill.seed, fill.first + blockIdx.y) : 0;
+    for (int sgm = blockIdx.x * waves + (threadIdx.x >> 6); sgm < 3 * h; sgm += gridDim.x * waves) {
+        const int c = sgm / h, y = y0 + (sgm - c * h);
+        const uint32_t el0 = ((uint32_t)c * D + y) * D + x0; // < 3 * 16384^2 < 2^32
+        float *const p = img + el0;
+        const float val = fill.value[c], sd = fill.std[c];
+        int head = 0, groups = 0;
+        if (VEC) {
+            head = min((int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2), w);
+            groups = (w - head) >> 2;
+            if (lane < head) p[lane] = NOISE ? er_noise(val, sd, er_z(q, el0 + lane)) : val;
+            float4 *const p4 = (float4 *)(p + head);
+            for (int k = lane; k < groups; k += 64) {
+                const uint32_t el = el0 + head + 4 * k;
+                p4[k] = NOISE ? make_float4(er_noise(val, sd, er_z(q, el)), er_noise(val, sd, er_z(q, el + 1)), er_noise(val, sd, er_z(q, el + 2)),
+                                            er_noise(val, sd, er_z(q, el + 3)))
+                              : make_float4(val, val, val, val);
+            }
+        }
+        // VEC: the at most 3 elements behind the last group; else all w of them
+        for (int i = head + 4 * groups + lane; i < w; i += 64) p[i] = NOISE ? er_noise(val, sd, er_z(q, el0 + i)) : val;
+    }
+}
+
+int mid_erase_fill_ok(const char *who, int mode, const float *value, const float *std) {
+    if (!value || !std) { mi_record_error(who, "value / std is NULL"); return 0; }
+    if (mode != 0 && mode != 1) { mi_record_error(who, "mode is 0 (MI_ERASE_CONST) or 1 (MI_ERASE_NOISE)"); return 0; }
+    for (int c = 0; c < 3; c++) {
+        if (!isfinite(value[c]) || !isfinite(std[c])) { mi_record_error(who, "value and std must be finite"); return 0; }
+        if (std[c] < 0.f) { mi_record_error(who, "std must not be negative"); return 0; }
+    }
+    return 1;
+}
+int mid_erase_batch(mid_stream s, float *images, int n, size_t image_size, int dim, const int *boxes_host, int mode, const float *value,
+                    const float *std, uint64_t noise_seed, int64_t first_row) {
+    const char *who = "mid_erase_batch";
+    if (!images || !boxes_host || n < 1 || n > 65535 || dim < 1 || dim > 16384 || image_size != (size_t)3 * dim * dim) {
+        mi_record_error(who, "need images, boxes, 1 <= n <= 65535, 1 <= dim <= 16384 and image_size = 3 dim^2"); return -1;
+    }
+    if (((uintptr_t)images & 3) != 0) { mi_record_error(who, "images must be 4-byte aligned"); return -1; }
+    if (!mid_erase_fill_ok(who, mode, value, std)) return -1;
+    const int vec = (image_size & 3) == 0 && ((uintptr_t)images & 15) == 0;
+    EraseFill fill;
+    for (int c = 0; c < 3; c++) { fill.value[c] = value[c]; fill.std[c] = std[c]; }
+    fill.seed = noise_seed;
+    for (int r0 = 0; r0 < n; r0 += ER_ROWS) {
+        const int rows = n - r0 < ER_ROWS ? n - r0 : ER_ROWS;
+        EraseBoxes bx = {};
+        int hmax = 0;
+        double cells = 0;
+        for (int i = 0; i < rows; i++) { // the kernel's clamp, so that every field fits 16 bits
+            const int *b = boxes_host + 4 * (size_t)(r0 + i);
+            const int y0 = min(max(b[0], 0), dim), x0 = min(max(b[1], 0), dim);
+            const int h = min(max(b[2], 0), dim - y0), w = min(max(b[3], 0), dim - x0);
+            if (h == 0 || w == 0) continue;
+            bx.v[i][0] = (uint16_t)y0; bx.v[i][1] = (uint16_t)x0; bx.v[i][2] = (uint16_t)h; bx.v[i][3] = (uint16_t)w;
+            hmax = max(hmax, h);
+            cells += (double)h * w;
+        }
+        if (hmax == 0) continue; // no row of this launch has a box
+        fill.first = (uint64_t)first_row + (uint64_t)r0;
+        const int gx = mi_cdiv(3 * hmax, ER_THREADS / 64);
+        const dim3 grid(gx < ER_MAX_BLOCKS_X ? gx : ER_MAX_BLOCKS_X, rows), block(ER_THREADS);
+        float *const base = images + (size_t)r0 * image_size;
+        mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 12.0 * cells); // algorithmic: three words written per cell of a box
+        if (mode == 0) {
+            if (vec) hipLaunchKernelGGL((erase_kernel<0, 1>), grid, block, 0, (hipStream_t)s, base, dim, bx, fill);
+            else hipLaunchKernelGGL((erase_kernel<0, 0>), grid, block, 0, (hipStream_t)s, base, dim, bx, fill);
+        } else {
+            if (vec) hipLaunchKernelGGL((erase_kernel<1, 1>), grid, block, 0, (hipStream_t)s, base, dim, bx, fill);
+            else hipLaunchKernelGGL((erase_kernel<1, 0>), grid, block, 0, (hipStream_t)s, base, dim, bx, fill);
+        }
+        mi_prof_end((hipStream_t)s);
+        MI_LAUNCH_CHECK(mode == 0 ? (vec ? "erase_kernel<const,vec>" : "erase_kernel<const,elem>") : (vec ? "erase_kernel<noise,vec>" : "erase_kernel<noise,elem>"));
+    }
+    return 0;
+}
+/* [0] threads, [1] the cap on grid.x, [2] waves of a workgroup, [3] rows of a launch.  One sweep of the capped grid: [1] [2] row segments
+ * of a row's box */
+void mid_erase_geometry(size_t out[4]) { out[0] = ER_THREADS; out[1] = ER_MAX_BLOCKS_X; out[2] = ER_THREADS / 64; out[3] = ER_ROWS; }

@@ -245,6 +245,46 @@ int mi_mix_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, dou
     out->lam = (float)lam;
     return 0;
 }
+/* random erasing: the boxes of one step's rows (include/resnet_mi.h, "random erasing"; tests/eraseref.py restates it with math.log / exp /
+ * sqrt / round).  mi_erase_key: e of that text, the key of the rows' draws and the trainer's noise seed */
+uint64_t mi_erase_key(uint64_t seed, int epoch, int64_t step, int rank, int world) {
+    const uint64_t s = mi_splitmix64_at(seed, (uint64_t)(int64_t)epoch);
+    const uint64_t k = mi_splitmix64_at(s, (uint64_t)step * (uint64_t)world + (uint64_t)rank); /* mi_mix_plan's step key */
+    return mi_splitmix64_at(k, 1000);
+}
+int mi_erase_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, int n, int dim, double prob, double scale_lo, double scale_hi,
+                  double ratio_lo, double ratio_hi, int *out) {
+    const char *who = "mi_erase_plan";
+    if (n < 0 || (n > 0 && !out)) { mi_record_host_error(who, "need n >= 0 and out"); return -1; }
+    if (dim < 1 || dim > 16384) { mi_record_host_error(who, "need 1 <= dim <= 16384"); return -1; }
+    if (!(prob >= 0 && prob <= 1)) { mi_record_host_error(who, "prob lies in [0, 1]"); return -1; }
+    if (!(scale_lo > 0) || !(ratio_lo > 0) || !(scale_hi >= scale_lo) || !(ratio_hi >= ratio_lo)) {
+        mi_record_host_error(who, "need 0 < scale_lo <= scale_hi and 0 < ratio_lo <= ratio_hi"); return -1;
+    }
+    if (world < 1 || rank < 0 || rank >= world) { mi_record_host_error(who, "need 0 <= rank < world"); return -1; }
+    const uint64_t e = mi_erase_key(seed, epoch, step, rank, world);
+    const int D = dim;
+    const double area = (double)D * (double)D, log_lo = log(ratio_lo), log_hi = log(ratio_hi);
+    for (int i = 0; i < n; i++) {
+        int *o = out + 4 * (size_t)i;
+        o[0] = o[1] = o[2] = o[3] = 0;
+        const uint64_t k = mi_splitmix64_at(e, (uint64_t)i);
+        if (rrc_unit(mi_splitmix64_at(k, 0)) >= prob) continue;
+        for (int t = 0; t < 10; t++) {
+            const double target = area * (scale_lo + rrc_unit(mi_splitmix64_at(k, 1 + 4 * t)) * (scale_hi - scale_lo));
+            const double ratio = exp(log_lo + rrc_unit(mi_splitmix64_at(k, 2 + 4 * t)) * (log_hi - log_lo));
+            const double fh = sqrt(target * ratio), fw = sqrt(target / ratio);
+            if (!(fh < D + 1.0 && fw < D + 1.0)) continue; /* rounds to D or more (or is no number): lrint stays in range below */
+            const long lh = lrint(fh), lw = lrint(fw); /* half to even */
+            if (!(lh < D && lw < D)) continue;
+            o[2] = (int)lh; o[3] = (int)lw;
+            o[0] = (int)(((mi_splitmix64_at(k, 3 + 4 * t) >> 32) * (uint64_t)(D - o[2] + 1)) >> 32);
+            o[1] = (int)(((mi_splitmix64_at(k, 4 + 4 * t) >> 32) * (uint64_t)(D - o[3] + 1)) >> 32);
+            break;
+        }
+    }
+    return 0;
+}
 /* double-buffered H2D: while step t runs, batch t+1 of the resident shard goes pinned -> device on the copy stream
  * (the reference copies synchronously at the top of every step, resnet.cu:1315-1316) */
 void mi_batch_set_prefetch(Batch *b, int on) {
@@ -503,7 +543,9 @@ void load_new_batch(Train_ResNet *trainer, Class_Metadata *class_metadata, Batch
         memcpy(b->correct_classes_cpu, e->pool_labels_host + (size_t)j * N, (size_t)N * sizeof(int));
         e->pool_next = (j + 1) % e->pool_batches;
     }
-    /* mixup / CutMix, every source: behind the load (or the prefetch swap) on the compute stream, drawn at the step the dump saves */
+    /* random erasing, then mixup / CutMix (the per-sample transform in front of the collate step), every source: behind the load (or the
+     * prefetch swap) on the compute stream, drawn at the step the dump saves */
+    if (e->status == 0) mi_trainer_erase_batch(trainer, b, e->rank, e->world);
     if (e->status == 0) mi_trainer_mix_batch(trainer, b, e->rank, e->world);
     b->cur_batch_in_shard += 1;
     trainer->cur_dump_id += 1;

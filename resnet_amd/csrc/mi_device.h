@@ -344,6 +344,14 @@ int mid_mix_batch(mid_stream s, float *images, int n, size_t image_size, int dim
 /* labels_b[i] = labels[n - 1 - i] */
 int mid_mix_labels(mid_stream s, const int *labels, int *labels_b, int n);
 void mid_mix_geometry(size_t out[3]); /* [0] threads, [1] the cap on grid.x, [2] waves of a workgroup (a wave takes one row segment of a CutMix box) */
+/* random erasing in place on fp32 NCHW images [n][3][dim][dim]: row i's box boxes_host[4 i ..] = (y0, x0, h, w) (host memory, read before
+ * the call returns; clamped into the image) filled with value[c] (mode 0) or value[c] + std[c] z (mode 1; z from noise_seed, first_row + i
+ * and the element's position; include/resnet_mi.h).  The boxes travel as kernel arguments, 256 rows a launch; a launch without a box is
+ * skipped.  -1: n outside [1, 65535], image_size != 3 dim^2, a NULL pointer, misaligned images, and what mid_erase_fill_ok refuses */
+int mid_erase_batch(mid_stream s, float *images, int n, size_t image_size, int dim, const int *boxes_host, int mode, const float *value,
+                    const float *std, uint64_t noise_seed, int64_t first_row);
+int mid_erase_fill_ok(const char *who, int mode, const float *value, const float *std); /* 0 with the error recorded: unknown mode, a value or std not finite, a negative std */
+void mid_erase_geometry(size_t out[4]); /* [0] threads, [1] the cap on grid.x, [2] waves of a workgroup (a wave takes one row segment of a box), [3] rows of a launch */
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */
 int mid_fill_uniform(mid_stream s, float *out, size_t n, uint64_t seed, uint64_t offset, float lo, float hi);
 /* test aids (kernels_misc.hip; callers serialise): `word` into every LDS word of every CU between two device synchronises, and a read-only

@@ -232,6 +232,13 @@ typedef struct MiCtx {
     uint64_t mix_seed;
     MiMixPlan mix_last;
     int *mix_labels_b;
+    /* mi_trainer_set_erase (all 0 / NULL while it was never on): the settings, and the boxes [batch][4] of the last load_new_batch in
+     * host memory with the number of rows they hold */
+    int erase_on, erase_rows;
+    double erase_prob, erase_scale[2], erase_ratio[2];
+    MiEraseFill erase_fill;
+    uint64_t erase_seed;
+    int *erase_last;
     /* mi_trainer_track_running_stats (all NULL / 0 while off; none of it is tracked in allocs[]: it survives a rebuild of the
      * buffers): the arena [2][rs_channels] (running means, then running variances, units in the table's order at MiUnit.rs_off),
      * the per-unit table of bn_running_update_kernel on the device, the number of forward_pass updates so far; the eval pass's
@@ -315,6 +322,10 @@ void mi_dp_reduce_ready(Train_ResNet *t, size_t from_float_offset, int force);
 /* trainer.c, the last steps of load_new_batch while mixing is on: the plan of this load, the mix launch on Batch.images and the
  * partners' labels, on the compute stream */
 void mi_trainer_mix_batch(Train_ResNet *t, Batch *b, int rank, int world);
+/* trainer.c, in front of it while erasing is on: the boxes of this load and the erase launch on Batch.images, on the compute stream */
+void mi_trainer_erase_batch(Train_ResNet *t, Batch *b, int rank, int world);
+/* loader.c: e of mi_erase_plan (resnet_mi.h), the key of a step's rows and the noise seed the trainer passes */
+uint64_t mi_erase_key(uint64_t seed, int epoch, int64_t step, int rank, int world);
 /* trainer.c, for dump.c's restore: the whole averaged model from host arrays laid out as the two device arenas are (params: arena_floats
  * floats, padding words included; stats: 2 * rs_channels) and the counter; -1 before mi_trainer_set_ema */
 int mi_trainer_ema_restore(Train_ResNet *t, const float *params_arena_host, const float *stats_host, int64_t updates);

@@ -253,6 +253,13 @@ int mi_op_mix_batch(float *images_nchw, int n, int image_size, int dim, const Mi
                                 plan_host->x0, plan_host->y1, plan_host->x1));
 }
 void mi_debug_mix_geometry(size_t out[3]) { mid_mix_geometry(out); }
+int mi_op_erase_batch(float *images_nchw, int n, int image_size, int dim, const int *boxes_host, const MiEraseFill *fill_host, int64_t first_row) {
+    if (!boxes_host || !fill_host) { mi_record_host_error("mi_op_erase_batch", "boxes_host / fill_host is NULL"); return -1; }
+    if (image_size < 1) { mi_record_host_error("mi_op_erase_batch", "image_size = 3 dim^2"); return -1; }
+    return finish(mid_erase_batch(mi_global()->compute, images_nchw, n, (size_t)image_size, dim, boxes_host, fill_host->mode, fill_host->value,
+                                  fill_host->std, fill_host->noise_seed, first_row));
+}
+void mi_debug_erase_geometry(size_t out[4]) { mid_erase_geometry(out); }
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_lds_fill(uint32_t word) { return finish(mid_debug_lds_fill(word)); }
 int mi_debug_poison_lds(void) { return mi_debug_lds_fill(0xFFFFFFFFu); }

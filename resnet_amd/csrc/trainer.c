@@ -887,6 +887,40 @@ void mi_trainer_mix_batch(Train_ResNet *t, Batch *b, int rank, int world) {
     ck(mid_mix_batch(G.compute, b->images, b->n_images, (size_t)b->image_size, b->image_dim, p->mode, p->lam, p->y0, p->x0, p->y1, p->x1), "mix");
     ck(mid_mix_labels(G.compute, b->correct_classes, c->mix_labels_b, b->n_images), "mix labels");
 }
+/* random erasing (resnet_mi.h, "random erasing") */
+int mi_trainer_set_erase(Train_ResNet *t, double prob, double scale_lo, double scale_hi, double ratio_lo, double ratio_hi,
+                         const MiEraseFill *fill, uint64_t seed) {
+    MiCtx *c = ctx_of(t);
+    if (prob == 0) { c->erase_on = 0; c->erase_rows = 0; return 0; }
+    if (!fill) { mi_record_host_error("mi_trainer_set_erase", "fill is NULL"); return -1; }
+    /* the argument rules are mi_erase_plan's and the kernel's */
+    if (mi_erase_plan(seed, 0, 0, 0, 1, 0, t->model->dims->input, prob, scale_lo, scale_hi, ratio_lo, ratio_hi, NULL)) return -1;
+    if (!mid_erase_fill_ok("mi_trainer_set_erase", fill->mode, fill->value, fill->std)) return -1;
+    if (!c->erase_last) c->erase_last = (int *)calloc((size_t)t->batch_size * 4, sizeof(int));
+    if (!c->erase_last) { mi_record_host_error("mi_trainer_set_erase", "no memory for the boxes"); return -1; }
+    c->erase_prob = prob; c->erase_scale[0] = scale_lo; c->erase_scale[1] = scale_hi; c->erase_ratio[0] = ratio_lo; c->erase_ratio[1] = ratio_hi;
+    c->erase_fill = *fill; c->erase_fill.noise_seed = 0; c->erase_seed = seed;
+    c->erase_rows = 0;
+    c->erase_on = 1;
+    return 0;
+}
+int mi_trainer_last_erase(const Train_ResNet *t, int *out) {
+    const MiCtx *c = ctx_of((Train_ResNet *)t);
+    if (!c->erase_on || !out) { mi_record_host_error("mi_trainer_last_erase", "erasing is off (mi_trainer_set_erase)"); return -1; }
+    memcpy(out, c->erase_last, (size_t)c->erase_rows * 4 * sizeof(int));
+    return c->erase_rows;
+}
+void mi_trainer_erase_batch(Train_ResNet *t, Batch *b, int rank, int world) {
+    MiCtx *c = ctx_of(t);
+    if (!c->erase_on) return;
+    const int n = b->n_images < t->batch_size ? b->n_images : t->batch_size;
+    c->erase_rows = 0;
+    if (mi_erase_plan(c->erase_seed, t->cur_epoch, t->cur_dump_id, rank, world, n, b->image_dim, c->erase_prob, c->erase_scale[0], c->erase_scale[1],
+                      c->erase_ratio[0], c->erase_ratio[1], c->erase_last)) return;
+    c->erase_rows = n;
+    ck(mid_erase_batch(G.compute, b->images, n, (size_t)b->image_size, b->image_dim, c->erase_last, c->erase_fill.mode, c->erase_fill.value,
+                       c->erase_fill.std, mi_erase_key(c->erase_seed, t->cur_epoch, t->cur_dump_id, rank, world), 0), "erase");
+}
 /* the two records (last, total) a loss head keeps on the device */
 static int read_metrics(mid_loss_metrics *rec, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
     if (last) mid_memcpy_d2h(last, rec, sizeof *last, G.compute);
@@ -1726,6 +1760,7 @@ void destroy_trainer(Train_ResNet *t) {
     free(t->loss_per_epoch); free(t->accuracy_per_epoch);
     mi_optim_free(&c->optim);
     mid_free(c->mix_labels_b);
+    free(c->erase_last);
     mid_free(c->rs_arena); mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics);
     mid_free(c->ema_arena); mid_free(c->ema_rs);
     mid_free(c->acc_arena);

@@ -258,6 +258,27 @@ class Ops:
         self.L.mi_debug_mix_geometry(out)
         return tuple(int(v) for v in out)
 
+    def erase_batch(self, images, boxes, mode="const", value=(0, 0, 0), std=(1, 1, 1), noise_seed=0, first_row=0, offset_floats=0):
+        """mi_op_erase_batch: fp32 images (n, 3, D, D) erased in place on the device, row i inside boxes[i] = (y0, x0, h, w); mode "const"
+        fills plane c with value[c], "noise" with value[c] + std[c] z (z from noise_seed, first_row + i and the element's position); returns
+        the erased batch.  offset_floats: as mix_batch"""
+        images = np.ascontiguousarray(images, np.float32)
+        n, _, D, _ = images.shape
+        boxes = np.ascontiguousarray(boxes, np.int32).reshape(n, 4)
+        fill = B.erase_fill_struct(mode, value, std, noise_seed)
+        buf = np.zeros(offset_floats + images.size, np.float32)
+        buf[offset_floats:] = images.ravel()
+        d = self.dev(buf)
+        self._chk(self.L.mi_op_erase_batch(d.ptr + 4 * offset_floats, n, 3 * D * D, D, boxes.ctypes.data, C.byref(fill), int(first_row)), "erase_batch")
+        return d.get()[offset_floats:].reshape(images.shape)
+
+    def erase_geometry(self):
+        """(threads, cap on grid.x, waves of a workgroup, rows of a launch) of erase_kernel: one sweep of the capped grid is cap * waves row
+        segments of a row's box; a batch of more rows than a launch carries takes several launches"""
+        out = (C.c_size_t * 4)()
+        self.L.mi_debug_erase_geometry(out)
+        return tuple(int(v) for v in out)
+
     def loss_head_mix(self, x, labels_a, labels_b, lam, smoothing=0.0, topk=5, total=None):
         """mi_op_loss_head_mix on logits x (N, L) with two labels per row and the weight lam: returns what loss_head returns"""
         N, L = x.shape

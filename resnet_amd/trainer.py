@@ -103,6 +103,26 @@ class Trainer:
             self._refused("mi_trainer_last_mix")
         return p.as_dict()
 
+    # ---- random erasing (include/resnet_mi.h, "random erasing") ----
+    def set_erase(self, prob=0.1, scale=(0.02, 0.33), ratio=(0.3, 3.3), mode="const", value=(0, 0, 0), std=(58.395, 57.12, 57.375), seed=0):
+        """random erasing on the device at every load_new_batch, in front of the mix step: with probability prob a row gets one box of
+        scale[0] .. scale[1] of the image's area and aspect ratio[0] .. ratio[1] (torchvision's RandomErasing), filled with value per
+        plane (mode "const") or with value + std z, z nearly normal (mode "noise", timm's pixel mode).  The images are mean-subtracted
+        but not divided: value 0 is the mean pixel, as it is behind torchvision's Normalize, and the default std is ImageNet's in byte
+        units.  prob 0: off"""
+        fill = B.erase_fill_struct(mode, value, std)
+        if self.L.mi_trainer_set_erase(self.t, float(prob), float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1]), C.byref(fill),
+                                       int(seed) & (2 ** 64 - 1)) != 0:
+            self._refused("mi_trainer_set_erase")
+
+    def last_erase(self):
+        """the boxes of the last load_new_batch: int32 (rows, 4), a row (y0, x0, h, w); h == 0 or w == 0: that row was not erased"""
+        out = np.zeros((self.batch, 4), np.int32)
+        rows = self.L.mi_trainer_last_erase(self.t, out.ctypes.data)
+        if rows < 0:
+            self._refused("mi_trainer_last_erase")
+        return out[:rows]
+
     def track_running_stats(self, momentum=0.1, on=True):
         """keep torch.nn.BatchNorm2d's running statistics of every batch norm: one extra launch per forward(); after set_dtype, before
         the first forward()"""
