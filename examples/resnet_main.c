@@ -24,6 +24,9 @@
  *              random erasing on the device at every load, in front of the mix step (mi_trainer_set_erase): with probability P a row gets
  *              one box of 0.02 .. 0.33 of its area, aspect 0.3 .. 3.3 (torchvision's --random-erase), filled with the mean pixel (the
  *              default, --erase-mode const) or with noise of ImageNet's per-channel deviation around it (timm's pixel mode)
+ *   ./ResNetMI --auto-augment ta_wide --ta-seed 7
+ *              TrivialAugmentWide on the device at every load, in front of erasing and mixing (mi_trainer_set_trivial_augment): per row one of
+ *              14 Pillow operations at one of 31 strengths, Pillow's bytes bit for bit (torchvision's --auto-augment ta_wide)
  *   ./ResNetMI --bn-momentum 0.1 --val-u8 /data/val_shards/u8 --val-dim-in 256 --val-every 5000
  *              evaluation: running statistics of every batch norm (mi_trainer_track_running_stats; --val-u8 alone implies momentum 0.1) and,
  *              every STEPS iterations and at the end of every epoch, the eval pass over every %03d.images_u8 / %03d.labels under DIR
@@ -133,6 +136,8 @@ int main(int argc, char **argv) {
     const double ERASE_PROB = atof(opt(argc, argv, "--random-erase", "0"));
     const char *erase_mode = opt(argc, argv, "--erase-mode", "const");
     const unsigned long long erase_seed = strtoull(opt(argc, argv, "--erase-seed", "0"), NULL, 10);
+    const char *auto_augment = opt(argc, argv, "--auto-augment", NULL);
+    const unsigned long long ta_seed = strtoull(opt(argc, argv, "--ta-seed", "0"), NULL, 10);
     const int TOPK = atoi(topk_arg ? topk_arg : "5");
     const char *bn_momentum_arg = opt(argc, argv, "--bn-momentum", NULL), *val_u8 = opt(argc, argv, "--val-u8", NULL);
     const int VAL_DIM_IN = atoi(opt(argc, argv, "--val-dim-in", "256")), VAL_EVERY = atoi(opt(argc, argv, "--val-every", "0"));
@@ -183,6 +188,10 @@ int main(int argc, char **argv) {
     if (loss_on_device && mi_trainer_set_loss(trainer, (float)atof(smoothing_arg ? smoothing_arg : "0"), TOPK,
                                               MI_LOSS_DEVICE | (device_loss ? MI_LOSS_NO_PRED_COPY : 0))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (mixing && mi_trainer_set_mix(trainer, MIXUP, CUTMIX, MIX_PROB, 0.5, mix_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    if (auto_augment) {
+        if (strcmp(auto_augment, "ta_wide")) { fprintf(stderr, "--auto-augment ta_wide\n"); return 1; }
+        if (mi_trainer_set_trivial_augment(trainer, 1, ta_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    }
     if (ERASE_PROB != 0) { /* value 0 = the mean pixel (the images are mean-subtracted, not divided); std = ImageNet's in byte units */
         if (strcmp(erase_mode, "const") && strcmp(erase_mode, "noise")) { fprintf(stderr, "--erase-mode const|noise\n"); return 1; }
         const MiEraseFill fill = {!strcmp(erase_mode, "noise") ? MI_ERASE_NOISE : MI_ERASE_CONST, {0.f, 0.f, 0.f}, {58.395f, 57.12f, 57.375f}, 0};

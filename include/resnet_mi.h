@@ -914,6 +914,91 @@ int mi_trainer_set_erase(Train_ResNet *t, double prob, double scale_lo, double s
                          const MiEraseFill *fill /* noise_seed ignored */, uint64_t seed);
 int mi_trainer_last_erase(const Train_ResNet *t, int *out /* [batch_size][4] */);
 
+/* ---------------- TrivialAugmentWide: one of 14 Pillow operations per image, at one of 31 strengths, in place ----------------
+ * TrivialAugmentWide (Mueller & Hutter 2021; torchvision's --auto-augment ta_wide) draws, per image, one operation uniformly and one of
+ * 31 strength bins uniformly, and a sign for the signed operations.  torchvision applies it to the PIL image (bytes) in front of the
+ * normalisation; here it runs on the fp32 batch behind the decode: per pixel the contract is decode o Pillow-op o quantise, and the
+ * result is, bit for bit, what applying Pillow's operation to the cropped bytes and decoding them gives (tests/taref.py restates the
+ * arithmetic and is pinned to Pillow itself).  Off by default; with it off every launch, value and dumped file is what it was.
+ *
+ * The operations, in torchvision's dictionary order, and their magnitudes at bin b (torchvision's _augmentation_space(31): float32
+ * torch.linspace values widened to double, committed as tables in loader.c):
+ *   SHEAR_X, SHEAR_Y, BRIGHTNESS, COLOR, CONTRAST, SHARPNESS   linspace(0, 0.99, 31)[b], signed
+ *   TRANSLATE_X, TRANSLATE_Y                                   linspace(0, 32, 31)[b], signed (not b 32 / 30: int() of it is 0 .. 15, 17 .. 30, 32)
+ *   ROTATE                                                     4.5 b degrees, signed
+ *   POSTERIZE                                                  8 - round(b / 5) bits (8 .. 2), unsigned
+ *   SOLARIZE                                                   255 - 8.5 b, unsigned
+ *   IDENTITY, AUTOCONTRAST, EQUALIZE                           none
+ *
+ * mi_ta_row: host-only, a pure function; fills the record of (op, bin, neg) on a dim x dim image in double arithmetic, every operation
+ * rounded on its own.  neg is ignored (stored as 0) by the unsigned operations.
+ *   magnitude  the signed magnitude m (the bits for POSTERIZE, the threshold for SOLARIZE, 0 where there is none)
+ *   factor     (float)(1.0 + m) for BRIGHTNESS, COLOR, CONTRAST, SHARPNESS: Pillow's ImageEnhance factor, a C float in Image.blend; else 0
+ *   arg        POSTERIZE: the mask ~(2^(8 - bits) - 1) & 255; SOLARIZE: ceil(threshold), since i < threshold on integers; else 0
+ *   A[6]       the five geometric operations: Pillow's 16.16 fixed-point coefficients of the inverse matrix (a0 .. a5), FIX(v) = floor(v 65536
+ *              + 0.5): A0 = FIX(a0), A1 = FIX(a1), A3 = FIX(a3), A4 = FIX(a4), A2 = FIX(a2 + a0 / 2 + a1 / 2), A5 = FIX(a5 + a3 / 2 + a4 / 2);
+ *              else 0.  The matrices are torchvision's for PIL images:
+ *                SHEAR_X (1, t, 0, 0, 1, 0), SHEAR_Y (1, 0, 0, t, 1, 0), t = tan(radians(degrees(atan(m)))) (centre: the top-left corner);
+ *                TRANSLATE_X a2 = -int(m), TRANSLATE_Y a5 = -int(m) (int truncates toward zero), the rest of the identity;
+ *                ROTATE by m degrees, Pillow's Image.rotate(m, NEAREST) about (dim / 2, dim / 2): r = -radians(m mod 360) (the sign of
+ *                the divisor, as Python's %), a0 = a4 = round(cos r, 15), a1 = round(sin r, 15), a3 = round(-sin r, 15) (decimal
+ *                places, half to even on the exact value), a2 = a0 (-dim / 2) + a1 (-dim / 2) + dim / 2, a5 likewise from a3, a4.
+ *                +-90 degrees comes out of this route as Pillow's transpose: there is no special case.
+ * Returns 0, or -1 with mi_last_error set: out NULL, op outside [0, 14), bin outside [0, 31), neg not 0 or 1, dim outside [1, 4096]
+ * (every 32-bit sum of the gather below then stays under 2^31: DESIGN.md, "Size limits").
+ *
+ * mi_ta_plan: host-only and deterministic, the erase plan's scheme under a key of its own.  s = splitmix64_at(seed, epoch), k =
+ * splitmix64_at(s, step world + rank) (modulo 2^64: mi_mix_plan's step key), a = splitmix64_at(k, 2000) (the mix plan draws indices up to
+ * 131 from k, the erase plan index 1000: equal seeds share no draw), k_i = splitmix64_at(a, i), d(j) = splitmix64_at(k_i, j):
+ * op = ((d(0) >> 32) 14) >> 32, bin = ((d(1) >> 32) 31) >> 32, neg = d(2) >> 63; out[i] = mi_ta_row(op, bin, neg, dim).  Returns 0, or -1
+ * with mi_last_error set: n < 0, out NULL with n > 0, dim outside [1, 4096], rank outside [0, world).
+ *
+ * mi_op_trivial_augment (kernels_input.hip): images_nchw fp32 [n][3][dim][dim] in device memory, IN PLACE; rows_host [n] in host memory,
+ * read before the call returns; workspace_dev: mi_ta_workspace_bytes(n, dim) bytes of device memory, 16-byte aligned, contents
+ * arbitrary (the integer statistics [n][4][256] are zeroed on the stream, then a planar uint8 staging area [n][3][dim][dim]).  No
+ * synchronisation and no host round trip: the records travel as kernel arguments, 128 rows a launch, two launches per 128 rows.
+ *   quantise  b = (int)rint(clamp(v (+) mean_plane, 0, 255)): one fp32 addition, NaN gives 0, half to even.  mean_plane is the fp32 of
+ *             the mean the decode table subtracts on that plane (plane d holds source position 2 - d: the R plane carries 103.94).  For
+ *             every byte-valued source -- fp32 shards, uint8 shards under fixed / centre / random crops, the antialiased random-resized
+ *             crop -- this recovers the byte exactly; other sources (the 8-bit bilinear resample, synthetic batches) are ROUNDED to the
+ *             nearest byte, as conversion to a PIL image would do.
+ *   decode    the decode table's value of the result byte: (float)((double)(float)b - mean).
+ *   Rows with MI_TA_IDENTITY are neither read nor written: every word keeps its bits.  Draws that happen to be numerically neutral
+ *   (POSTERIZE at 8 bits, a zero shear) are not special-cased: they quantise and decode.
+ *   blend(d, x, f) = d (+) f (x) (x (-) d) in fp32, every operation rounded on its own (no FMA); for 0 <= f <= 1 the result is (int)t, else 0
+ *   where t <= 0, 255 where t >= 255, (int)t elsewhere: Pillow's ImagingBlend.  L = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16.
+ *   BRIGHTNESS blend(0, i, f).  CONTRAST blend(M, i, f), M = (2 sum(L) + D^2) / (2 D^2) in 64-bit integers (Pillow's int(mean + 0.5)).
+ *   COLOR blend(L, x, f).  SHARPNESS blend(S, x, f), S = ImageFilter.SMOOTH of the channel: 0.5f plus the nine products with (float)(1 /
+ *   13.) (centre (float)(5 / 13.)) added in row-major order, one rounding each, clipped as above; the outermost rows and columns are
+ *   the source.  POSTERIZE i & arg.  SOLARIZE i < arg ? i : 255 - i.  AUTOCONTRAST per channel from the lowest and highest occupied
+ *   bin: hi <= lo leaves the channel; else scale = 255.0 / (hi - lo), off = -lo scale, clamp((int)(i scale + off), 0, 255) in double,
+ *   product and sum rounded separately, truncation toward zero.  EQUALIZE per channel: step = (D^2 - h[last occupied]) / 255; fewer than
+ *   two occupied bins or step == 0: the identity; else n = step / 2, and for i = 0 .. 255 the entry is min(255, n / step), then n += h[i].
+ *   The geometric operations: xin = (A2 + A1 y + A0 x) >> 16, yin = (A5 + A4 y + A3 x) >> 16 (arithmetic shifts); the source byte where
+ *   both lie inside the image, byte 0 elsewhere (torchvision's fill = None).
+ * Returns 0, or -1 with mi_last_error set and nothing launched: a NULL pointer, n outside [1, 65535], dim outside [1, 4096], image_size
+ * != 3 dim^2, images not 4-byte aligned or workspace not 16-byte aligned, an op or bin out of range. */
+enum { MI_TA_IDENTITY = 0, MI_TA_SHEAR_X, MI_TA_SHEAR_Y, MI_TA_TRANSLATE_X, MI_TA_TRANSLATE_Y, MI_TA_ROTATE, MI_TA_BRIGHTNESS, MI_TA_COLOR,
+       MI_TA_CONTRAST, MI_TA_SHARPNESS, MI_TA_POSTERIZE, MI_TA_SOLARIZE, MI_TA_AUTOCONTRAST, MI_TA_EQUALIZE, MI_TA_OPS = 14, MI_TA_BINS = 31 };
+typedef struct { int op, bin, neg, arg; double magnitude; float factor; int A[6]; } MiTaRow;
+int mi_ta_row(int op, int bin, int neg, int dim, MiTaRow *out);
+int mi_ta_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, int n, int dim, MiTaRow *out);
+size_t mi_ta_workspace_bytes(int n, int dim);
+int mi_op_trivial_augment(float *images_nchw, int n, int image_size /* 3 dim^2 */, int dim, const MiTaRow *rows_host, void *workspace_dev);
+/* host only, launches nothing: [0] threads of a workgroup, [1] the cap on grid.x, [2] rows of a launch, [3] pixels a thread takes per
+ * turn on the 16-byte path (1 on the other).  One sweep of the capped grid covers [0] [1] ([3]) pixels of an image */
+void mi_debug_ta_geometry(size_t out[4]);
+/* The trainer.  While it is on load_new_batch runs, for every data source and behind the prefetch swap, on the compute stream and IN
+ * FRONT OF the erase step (the order is augment, erase, mix): the plan of (seed, cur_epoch, cur_dump_id before its increment, the Batch's
+ * rank and world) for batch_size rows at dim = the network's input -- the step key the erase and mix plans use --, and the launches
+ * of mi_op_trivial_augment on Batch.images.  The workspace is allocated at the first call with on != 0; with it off nothing is
+ * launched and nothing allocated.  The eval entry points never augment.  May be called between steps.  Like the erase and mix
+ * settings it is not dumped: a resumed run sets it again.  Refused (-1, mi_last_error set): an input above 4096.
+ * mi_trainer_last_trivial_augment: the records of the last load_new_batch into out [batch_size]; returns the rows written (0 before
+ * the first load), -1 while it is off. */
+int mi_trainer_set_trivial_augment(Train_ResNet *t, int on, uint64_t seed);
+int mi_trainer_last_trivial_augment(const Train_ResNet *t, MiTaRow *out /* [batch_size] */);
+
 /* typed operator layer: x_dt = storage type of the convolution-side tensors (x, dx), a_dt = of the activation-side tensors
  * (y, residual, dy, mask_src, gated_out).  Supported pairs: (F32,F32), (BF16,BF16), (F32,BF16). */
 int mi_op_convert(const void *in, int in_dt, void *out, int out_dt, size_t n);

@@ -114,6 +114,29 @@ def erase_fill_struct(mode="const", value=(0, 0, 0), std=(1, 1, 1), noise_seed=0
     return MiEraseFill(int(m), (C.c_float * 3)(*[float(v) for v in value]), (C.c_float * 3)(*[float(v) for v in std]), int(noise_seed) & (2 ** 64 - 1))
 
 
+MI_TA_OPS, MI_TA_BINS = 14, 31
+MI_TA_NAMES = ("identity", "shear_x", "shear_y", "translate_x", "translate_y", "rotate", "brightness", "color", "contrast", "sharpness",
+               "posterize", "solarize", "autocontrast", "equalize")
+
+
+class MiTaRow(C.Structure):
+    _fields_ = [("op", C.c_int), ("bin", C.c_int), ("neg", C.c_int), ("arg", C.c_int), ("magnitude", C.c_double), ("factor", C.c_float),
+                ("A", C.c_int * 6)]
+
+    def as_dict(self):
+        return dict(op=self.op, bin=self.bin, neg=self.neg, arg=self.arg, magnitude=self.magnitude, factor=self.factor, A=list(self.A))
+
+
+def ta_rows_struct(rows):
+    """an array of MiTaRow from dicts (as MiTaRow.as_dict gives them; missing fields are 0)"""
+    arr = (MiTaRow * max(len(rows), 1))()
+    for r, d in zip(arr, rows):
+        r.op, r.bin, r.neg, r.arg = int(d["op"]), int(d.get("bin", 0)), int(d.get("neg", 0)), int(d.get("arg", 0))
+        r.magnitude, r.factor = float(d.get("magnitude", 0.0)), float(d.get("factor", 0.0))
+        r.A = (C.c_int * 6)(*[int(v) for v in d.get("A", [0] * 6)])
+    return arr
+
+
 class MiLossMetrics(C.Structure):
     _fields_ = [("loss_sum", C.c_double), ("rows", C.c_int64), ("wrong_top1", C.c_int64), ("wrong_topk", C.c_int64),
                 ("batches", C.c_int64)]
@@ -300,6 +323,13 @@ PROTOTYPES = {
     "mi_debug_erase_geometry": (None, [C.POINTER(_sz)]),
     "mi_trainer_set_erase": (_i, [_T, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(MiEraseFill), _u64]),
     "mi_trainer_last_erase": (_i, [_T, _vp]),
+    "mi_ta_row": (_i, [_i, _i, _i, _i, C.POINTER(MiTaRow)]),
+    "mi_ta_plan": (_i, [_u64, _i, C.c_int64, _i, _i, _i, _i, C.POINTER(MiTaRow)]),
+    "mi_ta_workspace_bytes": (_sz, [_i, _i]),
+    "mi_op_trivial_augment": (_i, [_vp, _i, _i, _i, C.POINTER(MiTaRow), _vp]),
+    "mi_debug_ta_geometry": (None, [C.POINTER(_sz)]),
+    "mi_trainer_set_trivial_augment": (_i, [_T, _i, _u64]),
+    "mi_trainer_last_trivial_augment": (_i, [_T, C.POINTER(MiTaRow)]),
     "mi_batch_set_augment_rrc": (_i, [_B, _i, _u64, C.c_double, C.c_double, C.c_double, C.c_double]),
     "mi_batch_last_boxes": (_i, [_B, _vp]),
     "mi_aa_coeffs": (_i, [_i, _i, _i, _vp, _vp, _i]),

@@ -643,3 +643,305 @@ int mid_erase_batch(mid_stream s, float *images, int n, size_t image_size, int d
 /* [0] threads, [1] the cap on grid.x, [2] waves of a workgroup, [3] rows of a launch.  One sweep of the capped grid: [1] [2] row segments
  * of a row's box */
 void mid_erase_geometry(size_t out[4]) { out[0] = ER_THREADS; out[1] = ER_MAX_BLOCKS_X; out[2] = ER_THREADS / 64; out[3] = ER_ROWS; }
+
+// ---- TrivialAugmentWide: one Pillow operation per image on the fp32 batch, in place (include/resnet_mi.h, "TrivialAugmentWide"; tests/taref.py) ----
+// Per pixel: decode o Pillow-op o quantise.  Two kernels over a planar uint8 staging area [n][3][D][D] and integer statistics [n][4][256]
+// (histograms of R, G, B and of L) in the workspace: ta_stage_kernel quantises the rows that have an operation and counts where the
+// operation needs statistics; ta_apply_kernel reads the staging area and writes the batch through the decode table.  The records travel
+// by value, as kernel arguments (erase_kernel's way): six words and the op a row, TA_ROWS rows a launch.  Rows with MID_TA_IDENTITY leave
+// both kernels at once: nothing of theirs is read or written.
+// hipcc contracts a * b + c into an FMA by default; Pillow rounds each operation.  The blend, the smooth filter's multiply-add and the
+// AutoContrast entry are small functions under `#pragma clang fp contract(off)` (not __fmul_rn / __fadd_rn: see mix_pair).
+#define TA_THREADS 256
+#define TA_MAX_BLOCKS_X 32
+#define TA_ROWS 128
+struct TaOps { uint8_t op[TA_ROWS]; };
+// u: A[6] for the geometric operations; u[0] the bits of `factor` for the four blends; u[0] = arg for Posterize and Solarize
+struct TaRows { int32_t u[TA_ROWS][6]; uint8_t op[TA_ROWS]; };
+
+struct TaRecip { double v[256]; };
+static constexpr TaRecip make_ta_recip() { // 255.0 / k, rounded once, by the compiler
+    TaRecip t{};
+    for (int k = 1; k < 256; k++) t.v[k] = 255.0 / (double)k;
+    return t;
+}
+__device__ const TaRecip g_ta_recip = make_ta_recip();
+
+// the fp32 of the mean g_decode_table subtracts on plane d (plane d holds source position 2 - d)
+__device__ __forceinline__ float ta_mean_plane(int d) { return d == 0 ? 103.94f : d == 1 ? 116.78f : 123.68f; }
+// (int)rint(clamp(v (+) mean, 0, 255)); the comparisons send a NaN to 0
+__device__ __forceinline__ uint32_t ta_quantise(float v, float mean) {
+    float s = v + mean;
+    s = s > 0.f ? s : 0.f;
+    s = s < 255.f ? s : 255.f;
+    return (uint32_t)(int)rintf(s);
+}
+__device__ __forceinline__ uint32_t ta_luma(uint32_t r, uint32_t g, uint32_t b) { return (r * 19595u + g * 38470u + b * 7471u + 0x8000u) >> 16; }
+// Pillow's ImagingBlend on bytes: t = d (+) f (x) (x (-) d); inside (0 <= f <= 1): (int)t, else clipped first
+__device__ __forceinline__ uint32_t ta_blend(float d, float x, float f, bool inside) {
+#pragma clang fp contract(off)
+    const float diff = x - d;
+    const float prod = f * diff;
+    const float t = d + prod;
+    if (inside) return (uint32_t)(int)t & 255u;
+    return t <= 0.f ? 0u : t >= 255.f ? 255u : (uint32_t)(int)t & 255u;
+}
+// acc (+) v (x) k, two roundings: one tap of the smooth filter
+__device__ __forceinline__ float ta_tap(float acc, float v, float k) {
+#pragma clang fp contract(off)
+    const float prod = v * k;
+    const float r = acc + prod;
+    return r;
+}
+// (int)(i scale + off) in double, product and sum rounded separately, truncation toward zero: Pillow's autocontrast entry
+__device__ __forceinline__ int ta_stretch(int i, double scale, double off) {
+#pragma clang fp contract(off)
+    const double prod = (double)i * scale;
+    const double r = prod + off;
+    return (int)r;
+}
+template <int V> __device__ __forceinline__ void ta_load_bytes(const uint8_t *p, uint32_t *b) {
+    if (V == 4) {
+        const uint32_t w = *(const uint32_t *)p;
+#pragma unroll
+        for (int j = 0; j < V; j++) b[j] = (w >> (8 * j)) & 255u;
+    } else b[0] = p[0];
+}
+
+template <int V> __device__ __forceinline__ void ta_store_bytes(uint8_t *p, const uint32_t *b) {
+    if (V == 4) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int j = 0; j < V; j++) w |= b[j] << (8 * j);
+        *(uint32_t *)p = w;
+    } else p[0] = (uint8_t)b[0];
+}
+
+// grid (x <= TA_MAX_BLOCKS_X, rows of the launch); a thread takes V consecutive pixels of the row's image per turn, all three planes.
+// V = 4 (D^2 % 4 == 0 and a 16-byte aligned batch): 16-byte loads, 4-byte stores; else V = 1.  Histograms: in LDS with integer atomics,
+// the occupied bins merged into the statistics with integer atomics -- sums of integers, so the order does not matter
+template <int V>
+__global__ void __launch_bounds__(TA_THREADS)
+ta_stage_kernel(const float *__restrict__ images, uint8_t *__restrict__ stage, uint32_t *__restrict__ stats, int D, TaOps ops) {
+    __shared__ uint32_t hist[4 * 256];
+    const int row = blockIdx.y, op = ops.op[row], tid = threadIdx.x;
+    if (op == MID_TA_IDENTITY) return;
+    const bool counted = op == MID_TA_CONTRAST || op == MID_TA_AUTOCONTRAST || op == MID_TA_EQUALIZE; // uniform in the workgroup
+    if (counted) {
+        for (int i = tid; i < 4 * 256; i += TA_THREADS) hist[i] = 0;
+        __syncthreads();
+    }
+    const uint32_t plane = (uint32_t)D * D, items = plane / V; // D <= 4096: plane <= 2^24
+    const float *const img = images + (size_t)row * 3 * plane;
+    uint8_t *const out = stage + (size_t)row * 3 * plane;
+    for (uint32_t it = blockIdx.x * TA_THREADS + tid; it < items; it += gridDim.x * TA_THREADS) {
+        const uint32_t p = it * V;
+        uint32_t b[3][V];
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            float v[V];
+            VecIO<float, V>::load(img + (size_t)d * plane + p, v);
+#pragma unroll
+            for (int j = 0; j < V; j++) b[d][j] = ta_quantise(v[j], ta_mean_plane(d));
+            ta_store_bytes<V>(out + (size_t)d * plane + p, b[d]);
+        }
+        if (counted) {
+#pragma unroll
+            for (int j = 0; j < V; j++) {
+                atomicAdd(&hist[b[0][j]], 1u);
+                atomicAdd(&hist[256 + b[1][j]], 1u);
+                atomicAdd(&hist[512 + b[2][j]], 1u);
+                atomicAdd(&hist[768 + ta_luma(b[0][j], b[1][j], b[2][j])], 1u);
+            }
+        }
+    }
+    if (counted) {
+        __syncthreads();
+        for (int i = tid; i < 4 * 256; i += TA_THREADS)
+            if (hist[i]) atomicAdd(&stats[(size_t)row * 1024 + i], hist[i]);
+    }
+}
+
+// grid and traversal as ta_stage_kernel; the operation is uniform in the workgroup.  LDS: the decode table plane by plane, and for the
+// table operations a 3 x 256 byte table built here from the record and the row's statistics (thread i builds entry i of each channel:
+// TA_THREADS == 256; a scan of the channel's histogram, every lane reading the same word, gives it the lowest and highest occupied bin,
+// their number and the count below i).  Three families: the table operations, the per-pixel blends (Color, Sharpness), the gather
+template <int V>
+__global__ void __launch_bounds__(TA_THREADS)
+ta_apply_kernel(float *__restrict__ images, const uint8_t *__restrict__ stage, const uint32_t *__restrict__ stats, int D, FastDiv fdD, TaRows rows) {
+    __shared__ float dec[3 * 256];
+    __shared__ uint32_t h[4 * 256];
+    __shared__ uint8_t lut[3 * 256];
+    const int row = blockIdx.y, op = rows.op[row], tid = threadIdx.x;
+    if (op == MID_TA_IDENTITY) return;
+    for (int i = tid; i < 3 * 256; i += TA_THREADS) dec[i] = g_decode_table.v[(2 - (i >> 8)) * 256 + (i & 255)];
+    const float f = __int_as_float(rows.u[row][0]);
+    const bool inside = f >= 0.f && f <= 1.f;
+    const bool table = op == MID_TA_BRIGHTNESS || op == MID_TA_CONTRAST || op == MID_TA_POSTERIZE || op == MID_TA_SOLARIZE ||
+                       op == MID_TA_AUTOCONTRAST || op == MID_TA_EQUALIZE;
+    const uint32_t plane = (uint32_t)D * D, items = plane / V;
+    if (table) {
+        const uint32_t i = (uint32_t)tid; // the entry this thread builds
+        if (op == MID_TA_BRIGHTNESS) {
+            const uint32_t e = ta_blend(0.f, (float)i, f, inside);
+            lut[i] = lut[256 + i] = lut[512 + i] = (uint8_t)e;
+        } else if (op == MID_TA_POSTERIZE) {
+            lut[i] = lut[256 + i] = lut[512 + i] = (uint8_t)(i & (uint32_t)rows.u[row][0]);
+        } else if (op == MID_TA_SOLARIZE) {
+            lut[i] = lut[256 + i] = lut[512 + i] = (uint8_t)((int)i < rows.u[row][0] ? i : 255u - i);
+        } else {
+            for (int k = tid; k < 4 * 256; k += TA_THREADS) h[k] = stats[(size_t)row * 1024 + k];
+            __syncthreads();
+            if (op == MID_TA_CONTRAST) { // M = int(mean of L + 0.5) = (2 sum + D^2) / (2 D^2)
+                uint64_t sum = 0;
+                for (int j = 0; j < 256; j++) sum += (uint64_t)j * h[768 + j];
+                const uint32_t M = (uint32_t)((2 * sum + plane) / (2 * (uint64_t)plane));
+                const uint32_t e = ta_blend((float)M, (float)i, f, inside);
+                lut[i] = lut[256 + i] = lut[512 + i] = (uint8_t)e;
+            } else {
+                for (int c = 0; c < 3; c++) {
+                    int lo = -1, hi = -1, occupied = 0;
+                    uint32_t below = 0;
+                    for (int j = 0; j < 256; j++) {
+                        const uint32_t hj = h[c * 256 + j];
+                        if (hj) { if (lo < 0) lo = j; hi = j; occupied++; }
+                        if (j < (int)i) below += hj;
+                    }
+                    uint32_t e = i;
+                    if (op == MID_TA_AUTOCONTRAST) {
+                        if (hi > lo && lo >= 0) {
+                            const double scale = g_ta_recip.v[hi - lo], off = -(double)lo * scale;
+                            e = (uint32_t)min(max(ta_stretch((int)i, scale, off), 0), 255);
+                        }
+                    } else {
+                        const uint32_t step = occupied >= 2 ? (plane - h[c * 256 + hi]) / 255u : 0u;
+                        if (step) e = min(255u, (step / 2 + below) / step);
+                    }
+                    lut[c * 256 + i] = (uint8_t)e;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float *const img = images + (size_t)row * 3 * plane;
+    const uint8_t *const in = stage + (size_t)row * 3 * plane;
+    const uint32_t A0 = (uint32_t)rows.u[row][0], A1 = (uint32_t)rows.u[row][1], A2 = (uint32_t)rows.u[row][2];
+    const uint32_t A3 = (uint32_t)rows.u[row][3], A4 = (uint32_t)rows.u[row][4], A5 = (uint32_t)rows.u[row][5];
+    const float k1 = (float)(1.0 / 13.0), k5 = (float)(5.0 / 13.0); // ImageFilter.SMOOTH: (1 1 1; 1 5 1; 1 1 1) / 13 as C floats
+    for (uint32_t it = blockIdx.x * TA_THREADS + tid; it < items; it += gridDim.x * TA_THREADS) {
+        const uint32_t p = it * V;
+        uint32_t o[3][V];
+        if (table || op == MID_TA_COLOR) {
+            uint32_t b[3][V];
+#pragma unroll
+            for (int d = 0; d < 3; d++) ta_load_bytes<V>(in + (size_t)d * plane + p, b[d]);
+#pragma unroll
+            for (int j = 0; j < V; j++) {
+                if (table) {
+#pragma unroll
+                    for (int d = 0; d < 3; d++) o[d][j] = lut[d * 256 + b[d][j]];
+                } else {
+                    const float L = (float)ta_luma(b[0][j], b[1][j], b[2][j]);
+#pragma unroll
+                    for (int d = 0; d < 3; d++) o[d][j] = ta_blend(L, (float)b[d][j], f, inside);
+                }
+            }
+        } else {
+            uint32_t y = fd_div(p, fdD), x = p - y * D;
+#pragma unroll
+            for (int j = 0; j < V; j++) {
+                if (op == MID_TA_SHARPNESS) {
+                    const bool border = y == 0 || x == 0 || y + 1 >= (uint32_t)D || x + 1 >= (uint32_t)D;
+#pragma unroll
+                    for (int d = 0; d < 3; d++) {
+                        const uint8_t *const c = in + (size_t)d * plane + p + j;
+                        float s = (float)c[0];
+                        if (!border) { // 0.5f, then the nine products in row-major order, one rounding each
+                            float acc = 0.5f;
+#pragma unroll
+                            for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+                                for (int dx = -1; dx <= 1; dx++)
+                                    acc = ta_tap(acc, (float)c[dy * D + dx], dy == 0 && dx == 0 ? k5 : k1);
+                            s = acc <= 0.f ? 0.f : acc >= 255.f ? 255.f : (float)(int)acc;
+                        }
+                        o[d][j] = ta_blend(s, (float)c[0], f, inside);
+                    }
+                } else { // Pillow's 16.16 nearest affine; sums modulo 2^32 (below 2^31 for every record of mi_ta_row), arithmetic shifts
+                    const int xin = (int)(A2 + A1 * y + A0 * x) >> 16, yin = (int)(A5 + A4 * y + A3 * x) >> 16;
+                    const bool ok = xin >= 0 && xin < D && yin >= 0 && yin < D;
+                    const uint32_t at = ok ? (uint32_t)yin * D + xin : 0u;
+#pragma unroll
+                    for (int d = 0; d < 3; d++) o[d][j] = ok ? in[(size_t)d * plane + at] : 0u;
+                }
+                if (++x == (uint32_t)D) { x = 0; y++; }
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            float v[V];
+#pragma unroll
+            for (int j = 0; j < V; j++) v[j] = dec[d * 256 + o[d][j]];
+            VecIO<float, V>::store(img + (size_t)d * plane + p, v);
+        }
+    }
+}
+
+size_t mid_ta_workspace_bytes(int n, int dim) {
+    if (n < 1 || dim < 1) return 0;
+    return (size_t)n * 4096 + (((size_t)n * 3 * dim * dim + 15) & ~(size_t)15);
+}
+int mid_trivial_augment(mid_stream s, float *images, int n, size_t image_size, int dim, const mid_ta_row *rows_host, void *workspace) {
+    const char *who = "mid_trivial_augment";
+    if (!images || !rows_host || !workspace || n < 1 || n > 65535 || dim < 1 || dim > 4096 || image_size != (size_t)3 * dim * dim) {
+        mi_record_error(who, "need images, rows, workspace, 1 <= n <= 65535, 1 <= dim <= 4096 and image_size = 3 dim^2"); return -1;
+    }
+    if (((uintptr_t)images & 3) != 0) { mi_record_error(who, "images must be 4-byte aligned"); return -1; }
+    if (((uintptr_t)workspace & 15) != 0) { mi_record_error(who, "workspace must be 16-byte aligned"); return -1; }
+    int counted = 0;
+    for (int i = 0; i < n; i++) {
+        const int op = rows_host[i].op, bin = rows_host[i].bin;
+        if (op < 0 || op >= MID_TA_OPS || bin < 0 || bin >= MID_TA_BINS) { mi_record_error(who, "a row's op lies in [0, 14) and its bin in [0, 31)"); return -1; }
+        counted |= op == MID_TA_CONTRAST || op == MID_TA_AUTOCONTRAST || op == MID_TA_EQUALIZE;
+    }
+    uint32_t *const stats = (uint32_t *)workspace;
+    uint8_t *const stage = (uint8_t *)workspace + (size_t)n * 4096;
+    const size_t plane = (size_t)dim * dim;
+    const int vec = (plane & 3) == 0 && ((uintptr_t)images & 15) == 0;
+    if (counted) mid_memset(stats, 0, (size_t)n * 4096, s); // on the stream: the histograms start from zero at every call
+    const long items = (long)(plane / (vec ? 4 : 1));
+    const int gx = mi_cdiv(items, TA_THREADS);
+    for (int r0 = 0; r0 < n; r0 += TA_ROWS) {
+        const int cnt = n - r0 < TA_ROWS ? n - r0 : TA_ROWS;
+        TaRows rw = {};
+        TaOps ops = {};
+        int active = 0;
+        for (int i = 0; i < cnt; i++) {
+            const mid_ta_row *r = rows_host + r0 + i;
+            rw.op[i] = ops.op[i] = (uint8_t)r->op;
+            active += r->op != MID_TA_IDENTITY;
+            if (r->op >= MID_TA_SHEAR_X && r->op <= MID_TA_ROTATE) for (int k = 0; k < 6; k++) rw.u[i][k] = r->A[k];
+            else if (r->op >= MID_TA_BRIGHTNESS && r->op <= MID_TA_SHARPNESS) { union { float f; int32_t i; } w; w.f = r->factor; rw.u[i][0] = w.i; }
+            else rw.u[i][0] = r->arg;
+        }
+        if (!active) continue; // identity rows only: nothing to do
+        const dim3 grid(gx < TA_MAX_BLOCKS_X ? gx : TA_MAX_BLOCKS_X, cnt), block(TA_THREADS);
+        float *const img = images + (size_t)r0 * image_size;
+        uint8_t *const stg = stage + (size_t)r0 * image_size;
+        uint32_t *const st = stats + (size_t)r0 * 1024;
+        const double bytes = 15.0 * (double)active * (double)plane; // algorithmic: 12 in and 3 out, then 3 in and 12 out per pixel
+        mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, bytes);
+        if (vec) hipLaunchKernelGGL((ta_stage_kernel<4>), grid, block, 0, (hipStream_t)s, img, stg, st, dim, ops);
+        else hipLaunchKernelGGL((ta_stage_kernel<1>), grid, block, 0, (hipStream_t)s, img, stg, st, dim, ops);
+        mi_prof_end((hipStream_t)s);
+        MI_LAUNCH_CHECK(vec ? "ta_stage_kernel<vec>" : "ta_stage_kernel<elem>");
+        mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, bytes);
+        if (vec) hipLaunchKernelGGL((ta_apply_kernel<4>), grid, block, 0, (hipStream_t)s, img, stg, st, dim, make_fastdiv((uint32_t)dim), rw);
+        else hipLaunchKernelGGL((ta_apply_kernel<1>), grid, block, 0, (hipStream_t)s, img, stg, st, dim, make_fastdiv((uint32_t)dim), rw);
+        mi_prof_end((hipStream_t)s);
+        MI_LAUNCH_CHECK(vec ? "ta_apply_kernel<vec>" : "ta_apply_kernel<elem>");
+    }
+    return 0;
+}
+/* [0] threads, [1] the cap on grid.x, [2] rows of a launch, [3] pixels a thread takes per turn on the 16-byte path */
+void mid_ta_geometry(size_t out[4]) { out[0] = TA_THREADS; out[1] = TA_MAX_BLOCKS_X; out[2] = TA_ROWS; out[3] = 4; }

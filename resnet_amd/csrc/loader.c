@@ -285,6 +285,98 @@ int mi_erase_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, i
     }
     return 0;
 }
+/* TrivialAugmentWide: the record of one (op, bin, sign) and the records of one step's rows (include/resnet_mi.h, "TrivialAugmentWide";
+ * tests/taref.py restates it with Python's math and round).  The two tables are torch.linspace(0, 0.99, 31) and torch.linspace(0, 32, 31)
+ * in float32, widened to double: torchvision's _augmentation_space(31) */
+static const double ta_mag_099[MI_TA_BINS] = {
+    0.0, 0.032999999821186066, 0.06599999964237213, 0.0989999994635582, 0.13199999928474426, 0.16499999165534973, 0.1979999989271164,
+    0.23100000619888306, 0.2639999985694885, 0.296999990940094, 0.32999998331069946, 0.3630000054836273, 0.3959999978542328,
+    0.42899999022483826, 0.4620000123977661, 0.4950000047683716, 0.527999997138977, 0.5609999895095825, 0.593999981880188,
+    0.6270000338554382, 0.6600000262260437, 0.6930000185966492, 0.7260000109672546, 0.7590000033378601, 0.7919999957084656,
+    0.824999988079071, 0.8580000400543213, 0.8910000324249268, 0.9240000247955322, 0.9570000171661377, 0.9900000095367432};
+static const double ta_mag_32[MI_TA_BINS] = {
+    0.0, 1.0666667222976685, 2.133333444595337, 3.200000286102295, 4.266666889190674, 5.333333492279053, 6.40000057220459,
+    7.466667175292969, 8.533333778381348, 9.600000381469727, 10.666666984558105, 11.733333587646484, 12.80000114440918,
+    13.866667747497559, 14.933334350585938, 15.999999046325684, 17.066665649414062, 18.133333206176758, 19.19999885559082,
+    20.266666412353516, 21.333332061767578, 22.399999618530273, 23.46666717529297, 24.53333282470703, 25.600000381469727,
+    26.66666603088379, 27.733333587646484, 28.799999237060547, 29.866666793823242, 30.933332443237305, 32.0};
+static const double TA_PI = 3.141592653589793;
+static int ta_fix(double v) { return (int)floor(v * 65536.0 + 0.5); } /* Pillow's FIX */
+/* Python's round(v, 15) for |v| <= 1: the exact value rounded half to even at 15 decimal places, then the nearest double */
+static double ta_round15(double v) {
+    char buf[40];
+    snprintf(buf, sizeof buf, "%.15f", v);
+    return strtod(buf, NULL);
+}
+static void ta_fixed(const double a[6], int A[6]) {
+    A[0] = ta_fix(a[0]); A[1] = ta_fix(a[1]); A[2] = ta_fix(a[2] + a[0] * 0.5 + a[1] * 0.5);
+    A[3] = ta_fix(a[3]); A[4] = ta_fix(a[4]); A[5] = ta_fix(a[5] + a[3] * 0.5 + a[4] * 0.5);
+}
+int mi_ta_row(int op, int bin, int neg, int dim, MiTaRow *out) {
+    const char *who = "mi_ta_row";
+    if (!out) { mi_record_host_error(who, "out is NULL"); return -1; }
+    if (op < 0 || op >= MI_TA_OPS) { mi_record_host_error(who, "op lies in [0, 14)"); return -1; }
+    if (bin < 0 || bin >= MI_TA_BINS) { mi_record_host_error(who, "bin lies in [0, 31)"); return -1; }
+    if (neg != 0 && neg != 1) { mi_record_host_error(who, "neg is 0 or 1"); return -1; }
+    if (dim < 1 || dim > 4096) { mi_record_host_error(who, "need 1 <= dim <= 4096"); return -1; }
+    const int is_signed = op >= MI_TA_SHEAR_X && op <= MI_TA_SHARPNESS;
+    double m = 0;
+    switch (op) {
+    case MI_TA_SHEAR_X: case MI_TA_SHEAR_Y: case MI_TA_BRIGHTNESS: case MI_TA_COLOR: case MI_TA_CONTRAST: case MI_TA_SHARPNESS: m = ta_mag_099[bin]; break;
+    case MI_TA_TRANSLATE_X: case MI_TA_TRANSLATE_Y: m = ta_mag_32[bin]; break;
+    case MI_TA_ROTATE: m = 4.5 * bin; break;
+    case MI_TA_POSTERIZE: m = 8 - (bin * 2 + 5) / 10; break; /* round(bin / 5): bin / 5 is never half an integer */
+    case MI_TA_SOLARIZE: m = 255.0 - 8.5 * bin; break;
+    default: break;
+    }
+    memset(out, 0, sizeof *out);
+    out->op = op; out->bin = bin; out->neg = is_signed ? neg : 0;
+    if (out->neg) m = -m;
+    out->magnitude = m;
+    double a[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    switch (op) {
+    case MI_TA_BRIGHTNESS: case MI_TA_COLOR: case MI_TA_CONTRAST: case MI_TA_SHARPNESS: out->factor = (float)(1.0 + m); break;
+    case MI_TA_POSTERIZE: out->arg = ~((1 << (8 - (int)m)) - 1) & 255; break;
+    case MI_TA_SOLARIZE: out->arg = (int)ceil(m); break;
+    case MI_TA_SHEAR_X: case MI_TA_SHEAR_Y: {
+        const double deg = atan(m) * (180.0 / TA_PI);   /* math.degrees */
+        const double t = tan(deg * (TA_PI / 180.0));    /* math.radians */
+        a[op == MI_TA_SHEAR_X ? 1 : 3] = t;
+        ta_fixed(a, out->A);
+        break;
+    }
+    case MI_TA_TRANSLATE_X: a[2] = -(double)(int)m; ta_fixed(a, out->A); break;
+    case MI_TA_TRANSLATE_Y: a[5] = -(double)(int)m; ta_fixed(a, out->A); break;
+    case MI_TA_ROTATE: {
+        double mod = fmod(m, 360.0); /* Python's %: the sign of the divisor */
+        if (mod != 0) { if (mod < 0) mod += 360.0; } else mod = 0.0;
+        const double r = -(mod * (TA_PI / 180.0)), c = dim / 2.0;
+        a[0] = ta_round15(cos(r)); a[1] = ta_round15(sin(r)); a[3] = ta_round15(-sin(r)); a[4] = ta_round15(cos(r));
+        a[2] = a[0] * -c + a[1] * -c + 0.0; a[2] += c;
+        a[5] = a[3] * -c + a[4] * -c + 0.0; a[5] += c;
+        ta_fixed(a, out->A);
+        break;
+    }
+    default: break;
+    }
+    return 0;
+}
+int mi_ta_plan(uint64_t seed, int epoch, int64_t step, int rank, int world, int n, int dim, MiTaRow *out) {
+    const char *who = "mi_ta_plan";
+    if (n < 0 || (n > 0 && !out)) { mi_record_host_error(who, "need n >= 0 and out"); return -1; }
+    if (dim < 1 || dim > 4096) { mi_record_host_error(who, "need 1 <= dim <= 4096"); return -1; }
+    if (world < 1 || rank < 0 || rank >= world) { mi_record_host_error(who, "need 0 <= rank < world"); return -1; }
+    const uint64_t s = mi_splitmix64_at(seed, (uint64_t)(int64_t)epoch);
+    const uint64_t k = mi_splitmix64_at(s, (uint64_t)step * (uint64_t)world + (uint64_t)rank); /* mi_mix_plan's step key */
+    const uint64_t a = mi_splitmix64_at(k, 2000);
+    for (int i = 0; i < n; i++) {
+        const uint64_t ki = mi_splitmix64_at(a, (uint64_t)i);
+        const int op = (int)(((mi_splitmix64_at(ki, 0) >> 32) * (uint64_t)MI_TA_OPS) >> 32);
+        const int bin = (int)(((mi_splitmix64_at(ki, 1) >> 32) * (uint64_t)MI_TA_BINS) >> 32);
+        if (mi_ta_row(op, bin, (int)(mi_splitmix64_at(ki, 2) >> 63), dim, out + i)) return -1;
+    }
+    return 0;
+}
 /* double-buffered H2D: while step t runs, batch t+1 of the resident shard goes pinned -> device on the copy stream
  * (the reference copies synchronously at the top of every step, resnet.cu:1315-1316) */
 void mi_batch_set_prefetch(Batch *b, int on) {
@@ -543,8 +635,9 @@ void load_new_batch(Train_ResNet *trainer, Class_Metadata *class_metadata, Batch
         memcpy(b->correct_classes_cpu, e->pool_labels_host + (size_t)j * N, (size_t)N * sizeof(int));
         e->pool_next = (j + 1) % e->pool_batches;
     }
-    /* random erasing, then mixup / CutMix (the per-sample transform in front of the collate step), every source: behind the load (or the
-     * prefetch swap) on the compute stream, drawn at the step the dump saves */
+    /* TrivialAugmentWide, random erasing, then mixup / CutMix (the per-sample transforms in front of the collate step), every source:
+     * behind the load (or the prefetch swap) on the compute stream, drawn at the step the dump saves */
+    if (e->status == 0) mi_trainer_ta_batch(trainer, b, e->rank, e->world);
     if (e->status == 0) mi_trainer_erase_batch(trainer, b, e->rank, e->world);
     if (e->status == 0) mi_trainer_mix_batch(trainer, b, e->rank, e->world);
     b->cur_batch_in_shard += 1;

@@ -352,6 +352,18 @@ int mid_erase_batch(mid_stream s, float *images, int n, size_t image_size, int d
                     const float *std, uint64_t noise_seed, int64_t first_row);
 int mid_erase_fill_ok(const char *who, int mode, const float *value, const float *std); /* 0 with the error recorded: unknown mode, a value or std not finite, a negative std */
 void mid_erase_geometry(size_t out[4]); /* [0] threads, [1] the cap on grid.x, [2] waves of a workgroup (a wave takes one row segment of a box), [3] rows of a launch */
+/* TrivialAugmentWide in place on fp32 NCHW images [n][3][dim][dim] (include/resnet_mi.h, "TrivialAugmentWide"): row i under rows_host[i]
+ * (host memory, read before the call returns; mid_ta_row is MiTaRow of resnet_mi.h, the op numbers MI_TA_* there), workspace
+ * mid_ta_workspace_bytes(n, dim) bytes of device memory, 16-byte aligned.  The records travel as kernel arguments, 128 rows a launch: a
+ * stage and an apply launch per 128 rows (none for 128 identity rows), in front of them one memset of the statistics on the stream when
+ * a row needs them.  -1: n outside [1, 65535], dim outside [1, 4096], image_size != 3 dim^2, a NULL pointer, misaligned images or
+ * workspace, an op or bin out of range */
+typedef struct { int op, bin, neg, arg; double magnitude; float factor; int A[6]; } mid_ta_row;
+enum { MID_TA_IDENTITY = 0, MID_TA_SHEAR_X, MID_TA_SHEAR_Y, MID_TA_TRANSLATE_X, MID_TA_TRANSLATE_Y, MID_TA_ROTATE, MID_TA_BRIGHTNESS, MID_TA_COLOR,
+       MID_TA_CONTRAST, MID_TA_SHARPNESS, MID_TA_POSTERIZE, MID_TA_SOLARIZE, MID_TA_AUTOCONTRAST, MID_TA_EQUALIZE, MID_TA_OPS = 14, MID_TA_BINS = 31 };
+size_t mid_ta_workspace_bytes(int n, int dim);
+int mid_trivial_augment(mid_stream s, float *images, int n, size_t image_size, int dim, const mid_ta_row *rows_host, void *workspace);
+void mid_ta_geometry(size_t out[4]); /* [0] threads, [1] the cap on grid.x, [2] rows of a launch, [3] pixels a thread takes per turn on the 16-byte path */
 /* splitmix64 counter streams on device (synthetic batches): uniform in [lo,hi) / labels mod n_classes */
 int mid_fill_uniform(mid_stream s, float *out, size_t n, uint64_t seed, uint64_t offset, float lo, float hi);
 /* test aids (kernels_misc.hip; callers serialise): `word` into every LDS word of every CU between two device synchronises, and a read-only

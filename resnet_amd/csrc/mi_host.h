@@ -239,6 +239,12 @@ typedef struct MiCtx {
     MiEraseFill erase_fill;
     uint64_t erase_seed;
     int *erase_last;
+    /* mi_trainer_set_trivial_augment (all 0 / NULL while it was never on): the records [batch] of the last load_new_batch in host memory
+     * with the number of rows they hold, and the device workspace of mi_op_trivial_augment for a whole batch */
+    int ta_on, ta_rows;
+    uint64_t ta_seed;
+    MiTaRow *ta_last;
+    void *ta_workspace;
     /* mi_trainer_track_running_stats (all NULL / 0 while off; none of it is tracked in allocs[]: it survives a rebuild of the
      * buffers): the arena [2][rs_channels] (running means, then running variances, units in the table's order at MiUnit.rs_off),
      * the per-unit table of bn_running_update_kernel on the device, the number of forward_pass updates so far; the eval pass's
@@ -324,6 +330,8 @@ void mi_dp_reduce_ready(Train_ResNet *t, size_t from_float_offset, int force);
 void mi_trainer_mix_batch(Train_ResNet *t, Batch *b, int rank, int world);
 /* trainer.c, in front of it while erasing is on: the boxes of this load and the erase launch on Batch.images, on the compute stream */
 void mi_trainer_erase_batch(Train_ResNet *t, Batch *b, int rank, int world);
+/* trainer.c, in front of that while TrivialAugmentWide is on: the records of this load and the launches on Batch.images, on the compute stream */
+void mi_trainer_ta_batch(Train_ResNet *t, Batch *b, int rank, int world);
 /* loader.c: e of mi_erase_plan (resnet_mi.h), the key of a step's rows and the noise seed the trainer passes */
 uint64_t mi_erase_key(uint64_t seed, int epoch, int64_t step, int rank, int world);
 /* trainer.c, for dump.c's restore: the whole averaged model from host arrays laid out as the two device arenas are (params: arena_floats

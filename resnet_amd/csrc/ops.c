@@ -260,6 +260,14 @@ int mi_op_erase_batch(float *images_nchw, int n, int image_size, int dim, const 
                                   fill_host->std, fill_host->noise_seed, first_row));
 }
 void mi_debug_erase_geometry(size_t out[4]) { mid_erase_geometry(out); }
+_Static_assert(sizeof(MiTaRow) == sizeof(mid_ta_row), "MiTaRow and mid_ta_row are one layout");
+size_t mi_ta_workspace_bytes(int n, int dim) { return mid_ta_workspace_bytes(n, dim); }
+int mi_op_trivial_augment(float *images_nchw, int n, int image_size, int dim, const MiTaRow *rows_host, void *workspace_dev) {
+    if (!rows_host || !workspace_dev) { mi_record_host_error("mi_op_trivial_augment", "rows_host / workspace_dev is NULL"); return -1; }
+    if (image_size < 1) { mi_record_host_error("mi_op_trivial_augment", "image_size = 3 dim^2"); return -1; }
+    return finish(mid_trivial_augment(mi_global()->compute, images_nchw, n, (size_t)image_size, dim, (const mid_ta_row *)rows_host, workspace_dev));
+}
+void mi_debug_ta_geometry(size_t out[4]) { mid_ta_geometry(out); }
 int mi_op_fill_uniform(float *out, size_t n, uint64_t seed, float lo, float hi) { return finish(mid_fill_uniform(mi_global()->compute, out, n, seed, 0, lo, hi)); }
 int mi_debug_lds_fill(uint32_t word) { return finish(mid_debug_lds_fill(word)); }
 int mi_debug_poison_lds(void) { return mi_debug_lds_fill(0xFFFFFFFFu); }

@@ -921,6 +921,37 @@ void mi_trainer_erase_batch(Train_ResNet *t, Batch *b, int rank, int world) {
     ck(mid_erase_batch(G.compute, b->images, n, (size_t)b->image_size, b->image_dim, c->erase_last, c->erase_fill.mode, c->erase_fill.value,
                        c->erase_fill.std, mi_erase_key(c->erase_seed, t->cur_epoch, t->cur_dump_id, rank, world), 0), "erase");
 }
+/* TrivialAugmentWide (resnet_mi.h, "TrivialAugmentWide") */
+int mi_trainer_set_trivial_augment(Train_ResNet *t, int on, uint64_t seed) {
+    MiCtx *c = ctx_of(t);
+    if (!on) { c->ta_on = 0; c->ta_rows = 0; return 0; }
+    const int dim = t->model->dims->input;
+    if (mi_ta_plan(seed, 0, 0, 0, 1, 0, dim, NULL)) return -1; /* the argument rule (dim) is the plan's */
+    if (!c->ta_last) c->ta_last = (MiTaRow *)calloc((size_t)t->batch_size, sizeof(MiTaRow));
+    if (!c->ta_last) { mi_record_host_error("mi_trainer_set_trivial_augment", "no memory for the records"); return -1; }
+    if (!c->ta_workspace) c->ta_workspace = mid_malloc(mid_ta_workspace_bytes(t->batch_size, dim));
+    if (!c->ta_workspace) { mi_record_host_error("mi_trainer_set_trivial_augment", "no device memory for the workspace"); return -1; }
+    c->ta_seed = seed;
+    c->ta_rows = 0;
+    c->ta_on = 1;
+    return 0;
+}
+int mi_trainer_last_trivial_augment(const Train_ResNet *t, MiTaRow *out) {
+    const MiCtx *c = ctx_of((Train_ResNet *)t);
+    if (!c->ta_on || !out) { mi_record_host_error("mi_trainer_last_trivial_augment", "TrivialAugmentWide is off (mi_trainer_set_trivial_augment)"); return -1; }
+    memcpy(out, c->ta_last, (size_t)c->ta_rows * sizeof(MiTaRow));
+    return c->ta_rows;
+}
+void mi_trainer_ta_batch(Train_ResNet *t, Batch *b, int rank, int world) {
+    MiCtx *c = ctx_of(t);
+    if (!c->ta_on) return;
+    const int n = b->n_images < t->batch_size ? b->n_images : t->batch_size;
+    c->ta_rows = 0;
+    if (b->image_dim != t->model->dims->input) { mi_record_host_error("mi_trainer_ta_batch", "the batch is not of the network's input size"); return; }
+    if (mi_ta_plan(c->ta_seed, t->cur_epoch, t->cur_dump_id, rank, world, n, b->image_dim, c->ta_last)) return;
+    c->ta_rows = n;
+    ck(mid_trivial_augment(G.compute, b->images, n, (size_t)b->image_size, b->image_dim, (const mid_ta_row *)c->ta_last, c->ta_workspace), "trivial augment");
+}
 /* the two records (last, total) a loss head keeps on the device */
 static int read_metrics(mid_loss_metrics *rec, MiLossMetrics *last, MiLossMetrics *total, int reset_total) {
     if (last) mid_memcpy_d2h(last, rec, sizeof *last, G.compute);
@@ -1761,6 +1792,7 @@ void destroy_trainer(Train_ResNet *t) {
     mi_optim_free(&c->optim);
     mid_free(c->mix_labels_b);
     free(c->erase_last);
+    free(c->ta_last); mid_free(c->ta_workspace);
     mid_free(c->rs_arena); mid_free(c->rs_tab_dev); mid_free(c->eval_row); mid_free(c->eval_rank); mid_free(c->eval_metrics);
     mid_free(c->ema_arena); mid_free(c->ema_rs);
     mid_free(c->acc_arena);

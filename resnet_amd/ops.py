@@ -279,6 +279,41 @@ class Ops:
         self.L.mi_debug_erase_geometry(out)
         return tuple(int(v) for v in out)
 
+    def ta_row(self, op, bin, neg, dim):
+        """mi_ta_row: the record of one operation, strength bin and sign on a dim x dim image, as a dict"""
+        r = B.MiTaRow()
+        self._chk(self.L.mi_ta_row(int(op), int(bin), int(neg), int(dim), C.byref(r)), "ta_row")
+        return r.as_dict()
+
+    def ta_plan(self, seed, epoch, step, rank, world, n, dim):
+        """mi_ta_plan: the records of one step's n rows, a list of dicts"""
+        rows = (B.MiTaRow * max(n, 1))()
+        self._chk(self.L.mi_ta_plan(int(seed) & (2 ** 64 - 1), int(epoch), int(step), int(rank), int(world), int(n), int(dim), rows), "ta_plan")
+        return [rows[i].as_dict() for i in range(n)]
+
+    def trivial_augment(self, images, rows, offset_floats=0, workspace=None, keep_workspace=False, n=None):
+        """mi_op_trivial_augment: fp32 images (n, 3, D, D) augmented in place on the device, row i under rows[i] (dicts as ta_row gives
+        them); returns the augmented batch.  offset_floats: as mix_batch.  workspace: a device buffer of an earlier call to run over again
+        (keep_workspace=True returns (batch, workspace)).  n: only the first n rows belong to the call, the rest of the buffer lies behind it"""
+        images = np.ascontiguousarray(images, np.float32)
+        D = images.shape[2]
+        n = images.shape[0] if n is None else int(n)
+        arr = B.ta_rows_struct(rows)
+        buf = np.zeros(offset_floats + images.size, np.float32)
+        buf[offset_floats:] = images.ravel()
+        d = self.dev(buf)
+        if workspace is None:
+            workspace = self.dev(np.full(int(self.L.mi_ta_workspace_bytes(n, D)), 0xA5, np.uint8))  # arbitrary contents
+        self._chk(self.L.mi_op_trivial_augment(d.ptr + 4 * offset_floats, n, 3 * D * D, D, arr, workspace.ptr), "trivial_augment")
+        out = d.get()[offset_floats:].reshape(images.shape)
+        return (out, workspace) if keep_workspace else out
+
+    def ta_geometry(self):
+        """(threads, cap on grid.x, rows of a launch, pixels a thread takes per turn on the 16-byte path) of the two kernels"""
+        out = (C.c_size_t * 4)()
+        self.L.mi_debug_ta_geometry(out)
+        return tuple(int(v) for v in out)
+
     def loss_head_mix(self, x, labels_a, labels_b, lam, smoothing=0.0, topk=5, total=None):
         """mi_op_loss_head_mix on logits x (N, L) with two labels per row and the weight lam: returns what loss_head returns"""
         N, L = x.shape

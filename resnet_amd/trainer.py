@@ -123,6 +123,21 @@ class Trainer:
             self._refused("mi_trainer_last_erase")
         return out[:rows]
 
+    # ---- TrivialAugmentWide (include/resnet_mi.h, "TrivialAugmentWide") ----
+    def set_trivial_augment(self, seed=0, on=True):
+        """TrivialAugmentWide on the device at every load_new_batch, in front of the erase and mix steps (torchvision's --auto-augment
+        ta_wide): per row one of 14 Pillow operations at one of 31 strengths, Pillow's bytes bit for bit"""
+        if self.L.mi_trainer_set_trivial_augment(self.t, 1 if on else 0, int(seed) & (2 ** 64 - 1)) != 0:
+            self._refused("mi_trainer_set_trivial_augment")
+
+    def last_trivial_augment(self):
+        """the records of the last load_new_batch: a list of dicts (op, bin, neg, arg, magnitude, factor, A)"""
+        out = (B.MiTaRow * self.batch)()
+        rows = self.L.mi_trainer_last_trivial_augment(self.t, out)
+        if rows < 0:
+            self._refused("mi_trainer_last_trivial_augment")
+        return [out[i].as_dict() for i in range(rows)]
+
     def track_running_stats(self, momentum=0.1, on=True):
         """keep torch.nn.BatchNorm2d's running statistics of every batch norm: one extra launch per forward(); after set_dtype, before
         the first forward()"""
