@@ -42,6 +42,12 @@
  *              gradient accumulation (mi_trainer_set_accumulation): one optimizer update per K iterations on the sum of their gradients
  *              times S (default 1: the sum, what a batch K times as large would give; 1/K: the mean over the micro-batches).  An
  *              iteration stays one micro-batch: the printout, --iters and --val-every count micro-batches, --ema-every counts updates
+ *   ./ResNetMI --optimizer sgd --momentum 0.9 --lr 0.5 --wd 0.00002 --norm-weight-decay 0 --clip-grad-norm 256
+ *              --optimizer adam (default) | sgd | lars (mi_trainer_set_optimizer; --momentum M, default 0.9).  --norm-weight-decay X (sgd):
+ *              BN gamma / beta decay with X in place of --wd (torchvision's flag).  --clip-grad-norm X: every applied update first scales
+ *              the gradient so that its global L2 norm is at most X (mi_trainer_set_clip_grad_norm), on the device; the gradient is a batch
+ *              SUM (times --accum-scale under --accum), so X is torchvision's value times the batch size.  Each epoch then ends with a
+ *              line of its clipped / total updates and the last gradient norm
  *   ./ResNetMI --labels-file id_to_label_mapping.txt --synsets-file id_to_synset_mapping.txt --counts-file id_to_img_count_mapping.txt
  *              the class metadata of resnet.cu:3236-3242: iterations per epoch = ceil(sum of the class counts / batch) (:3309)
  *              unless --iters says otherwise
@@ -150,6 +156,9 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; i++) if (!strcmp(argv[i], "--ema-warmup")) ema_warmup = 1;
     const int ACCUM = atoi(opt(argc, argv, "--accum", "1"));
     const float ACCUM_SCALE = (float)atof(opt(argc, argv, "--accum-scale", "1"));
+    const char *optimizer = opt(argc, argv, "--optimizer", "adam"), *norm_wd_arg = opt(argc, argv, "--norm-weight-decay", NULL);
+    const float MOMENTUM = (float)atof(opt(argc, argv, "--momentum", "0.9"));
+    const float CLIP_GRAD_NORM = (float)atof(opt(argc, argv, "--clip-grad-norm", "0"));
     const char *dump_root = opt(argc, argv, "--dump-root", NULL);
     const char *loss_log = opt(argc, argv, "--loss-log", "avg_loss_log.txt");
     const int resume_id = atoi(opt(argc, argv, "--resume", "-1"));           /* LOAD_FROM_DUMP_ID, resnet.cu:3299 */
@@ -185,6 +194,13 @@ int main(int argc, char **argv) {
     if (shards || shards_u8) mi_batch_set_prefetch(batch, 1);
     Train_ResNet *trainer = init_trainer(model, batch, BATCH_SIZE, LEARNING_RATE, WEIGHT_DECAY, 0.9f, 0.999f, EPS, N_EPOCHS, "my_custom");
     if (dump_root) mi_trainer_set_dump_root(trainer, dump_root); else mi_trainer_set_dump_every(trainer, 0);
+    if (strcmp(optimizer, "adam")) {
+        const int kind = !strcmp(optimizer, "sgd") ? MI_OPT_SGD : !strcmp(optimizer, "lars") ? MI_OPT_LARS : -1;
+        if (kind < 0) { fprintf(stderr, "--optimizer adam|sgd|lars\n"); return 1; }
+        if (mi_trainer_set_optimizer(trainer, kind, MOMENTUM, 0.001f)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    }
+    if (norm_wd_arg && mi_trainer_set_norm_weight_decay(trainer, (float)atof(norm_wd_arg))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+    if (CLIP_GRAD_NORM != 0 && mi_trainer_set_clip_grad_norm(trainer, CLIP_GRAD_NORM)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (loss_on_device && mi_trainer_set_loss(trainer, (float)atof(smoothing_arg ? smoothing_arg : "0"), TOPK,
                                               MI_LOSS_DEVICE | (device_loss ? MI_LOSS_NO_PRED_COPY : 0))) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
     if (mixing && mi_trainer_set_mix(trainer, MIXUP, CUTMIX, MIX_PROB, 0.5, mix_seed)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
@@ -214,6 +230,7 @@ int main(int argc, char **argv) {
     int cur_iter_in_epoch = (trainer->cur_dump_id + 1) % iterations_per_epoch;
     int stop = 0;
     long steps_done = 0;
+    MiClipRecord clip_before = {0};
     for (int epoch = trainer->cur_epoch; epoch < N_EPOCHS && !stop; epoch++) {
         float epoch_loss = 0, epoch_n_wrong = 0;
         for (int iter = cur_iter_in_epoch; iter < iterations_per_epoch; iter++) {
@@ -252,6 +269,14 @@ int main(int argc, char **argv) {
                 printf("Epoch: %d ----- Images: %lld, Avg. Loss: %.4f, Top-1 error: %.2f%%, Top-%d error: %.2f%%\n", epoch, (long long)total.rows,
                        total.loss_sum / (double)total.rows, 100.0 * (double)total.wrong_top1 / (double)total.rows, TOPK,
                        100.0 * (double)total.wrong_topk / (double)total.rows);
+        }
+        if (CLIP_GRAD_NORM != 0) { /* the record's counters run over the whole run: this epoch's share */
+            MiClipRecord clip;
+            if (mi_trainer_last_clip(trainer, &clip)) { fprintf(stderr, "%s\n", mi_last_error()); return 1; }
+            printf("Epoch: %d ----- Avg. Loss: %.4f, Clipped updates: %lld of %lld, last gradient norm: %.4f%s\n", epoch, epoch_loss / total_images_per_epoch,
+                   (long long)(clip.clipped - clip_before.clipped), (long long)(clip.updates - clip_before.updates), clip.norm,
+                   clip.nonfinite ? " (not finite: left unclipped)" : "");
+            clip_before = clip;
         }
         if (val_u8 && validate(trainer, val_u8, VAL_DIM_IN, VAL_RESIZE, TOPK, "epoch", ema_arg != NULL)) return 1;
         /* resnet.cu:3410-3421: per-epoch loss (a SUM over the epoch) and accuracy, rewind the data source */

@@ -451,7 +451,7 @@ void mi_trainer_set_nan_exit(Train_ResNet *t, int on);
  * out = sum / R), sums_out [R][2C] (the sums each replica's dx formula sees) or NULL.  Either pair may be NULL. */
 int mi_debug_bn_merge(int R, int C, float *means, float *vars, float *dgamma, float *dbeta, float *sums_out);
 /* The update rule of update_parameters.  MI_OPT_ADAM (default): the reference's Adam.  MI_OPT_SGD: torch.optim.SGD with momentum,
- * dampening 0, no Nesterov, weight decay on every tensor: d = g + wd w; b = mu b + d; w -= lr b.  MI_OPT_LARS (You et al. 2017, the
+ * dampening 0, no Nesterov, weight decay on every tensor (mi_trainer_set_norm_weight_decay gives BN gamma / beta their own): d = g + wd w; b = mu b + d; w -= lr b.  MI_OPT_LARS (You et al. 2017, the
  * MLPerf ResNet-50 form): convolution and FC weights b = mu b + lr trust (g + wd w); w -= b with trust = tau |w| / (|g| + wd |w|)
  * (1 where |w| or |g| is 0), the norms per tensor before any update; BN gamma / beta b = mu b + lr g; w -= b.  lr, wd = the trainer's
  * learning_rate / weight_decay, read at every update (a schedule writes learning_rate between steps).  b = the prev_means arena
@@ -657,13 +657,61 @@ void mi_debug_accum_geometry(size_t out[4]); /* as mi_debug_ema_geometry */
 int mi_trainer_set_accumulation(Train_ResNet *t, int k, float scale);
 int mi_trainer_accumulation(const Train_ResNet *t, int *k, int *pending);
 float *mi_debug_accum_arena(const Train_ResNet *t);
+/* ---------------- gradient clipping by the global L2 norm: torchvision's --clip-grad-norm on the device ----------------
+ * Off by default (max_norm 0); while off every launch, value and dumped file is what it was, and nothing is allocated before the first
+ * max_norm > 0.  While on, update_parameters runs three launches on the compute stream in front of the optimizer (kernels_optim.hip), over a
+ * chunk table that covers every tensor of the gradient arena and none of its padding, whatever the optimizer:
+ *   norm    sum g^2 per chunk of at most 8192 floats in double (a float's square is exact there)
+ *   coef    the partials summed by one wave in a fixed order; norm = sqrt(sq), coef = min(1, max_norm / (norm + 1e-6)) in double, rounded to
+ *           float once -- torch.nn.utils.clip_grad_norm_'s coefficient -- into a record in device memory; the host never sees it
+ *   scale   g = g * coef, one fp32 product per element, in place; where coef == 1.f no gradient word is read or written
+ * No atomics and no host synchronisation: the same gradient gives the same record and the same scaled bits.
+ * THE NON-FINITE RULE: where sq is NaN or Inf (a gradient element is), coef = 1, nonfinite = 1 and the gradient is left as it is; the
+ * optimizers' own guards and the NaN flag then report it exactly as without clipping.  This departs on purpose from
+ * torch.nn.utils.clip_grad_norm_, which would multiply every gradient by NaN.
+ * THE UNITS OF max_norm are those of the gradient the optimizer sees: a batch SUM (dlogits carries no 1/N), summed over the k micro-batches
+ * of an accumulation window times its scale, summed over the ranks under data parallel.  A recipe written for mean gradients multiplies its
+ * max_norm by the batch size, or folds with scale = 1 / (k batch).
+ * Order in update_parameters: accumulation fold, clip, optimizer, EMA.  Under accumulation the collecting calls do not touch the record; call
+ * k clips the folded gradient once.  LARS takes its per-tensor norms from the clipped gradient.  Data parallel: the norm is that of the
+ * all-reduced gradient, so with clipping on update_parameters waits for every bucket's event, clips the whole arena and runs the optimizer
+ * in one launch over it (the same bits as bucket by bucket) -- the overlap of the early buckets' updates with the late buckets' all-reduce
+ * is lost while clipping is on; with it off the bucket loop is untouched.
+ * mi_trainer_set_clip_grad_norm(t, max_norm): 0 turns it off; may be called between updates.  The first call with max_norm > 0 allocates the
+ * chunk table, the partials and the record (counted in mi_trainer_device_bytes; the record's counters start at 0).  -1, mi_last_error set,
+ * nothing changed: NaN, Inf or a negative value, a call inside an accumulation window (pending > 0) or between forward_pass and
+ * update_parameters.  Like the optimizer, the setting is not dumped.
+ * mi_trainer_last_clip: waits for the compute stream and copies the record of the last clipped update -- sq_norm and norm BEFORE the
+ * scaling (what torch returns), coef, nonfinite, and the running counters updates (clip passes) and clipped (those with coef < 1).  -1
+ * before the first max_norm > 0.
+ * mi_op_clip_grad_norm: the three kernels on their own over tensors [offsets_host[i], offsets_host[i + 1]) of the device array g of n
+ * floats (n_tensors + 1 offsets, multiples of 4 below 2^31, the last <= n: the rule of mi_op_momentum_update); *out (host, may be NULL): the
+ * record, counters from 0.  -1, mi_last_error set, nothing launched: g NULL or not 16-byte aligned, n == 0, bad offsets, a max_norm that
+ * is NaN, infinite or <= 0. */
+typedef struct { double sq_norm, norm; float coef; int nonfinite; int64_t updates, clipped; } MiClipRecord;
+int mi_trainer_set_clip_grad_norm(Train_ResNet *t, float max_norm);
+int mi_trainer_last_clip(Train_ResNet *t, MiClipRecord *out);
+int mi_op_clip_grad_norm(float *g, size_t n, const size_t *offsets_host, int n_tensors, float max_norm, MiClipRecord *out);
+/* for tools/bench_clip.py: the mean time in ms of one launch of the norm (pass 0), coefficient (1) or scale (2) kernel over reps launches,
+ * between HIP events on the compute stream; arguments as mi_op_clip_grad_norm, a scale pass multiplies g by coef reps + 3 times; < 0: refused */
+double mi_debug_clip_pass_ms(int pass, float *g, size_t n, const size_t *offsets_host, int n_tensors, float max_norm, int reps);
+/* torchvision's --norm-weight-decay for MI_OPT_SGD: the tensors that are no convolution or FC weight (BN gamma / beta) decay with wd_norm
+ * in place of the trainer's weight_decay -- torch.optim.SGD with two parameter groups.  Read at every update; until it is called gamma and
+ * beta decay with weight_decay, which gives the bits SGD always gave.  Call after mi_trainer_set_optimizer (which forgets it).  -1,
+ * mi_last_error set, nothing changed: the optimizer is Adam (the reference's rule stays) or LARS (which never decays them), a value that
+ * is NaN, infinite or negative.  Not dumped. */
+int mi_trainer_set_norm_weight_decay(Train_ResNet *t, float wd_norm);
 /* the SGD / LARS kernels on their own: p, g, b device arrays of n floats; tensor i starts at offsets_host[i] (n_tensors + 1 entries,
  * multiples of 4, the last <= n) and runs to the next offset; tensor_is_weight_host[i] 1: trust ratio and weight decay (LARS).
  * nan_flag_dev: device int or NULL.  sq_norms_out_host (optional, 2 n_tensors doubles): (|w|^2, |g|^2) per tensor before the update,
- * for SGD too.  Returns 0, or -1 (mi_last_error says why). */
+ * for SGD too.  Returns 0, or -1 (mi_last_error says why).  mi_op_momentum_update2: under MI_OPT_SGD the tensors with
+ * tensor_is_weight_host[i] == 0 decay with wd_norm (finite, >= 0) in place of wd; mi_op_momentum_update is it with wd_norm = wd. */
 int mi_op_momentum_update(int kind, float *p, float *g, float *b, size_t n, const size_t *offsets_host, int n_tensors,
                           const int *tensor_is_weight_host, float lr, float wd, float momentum, float trust_coef, int *nan_flag_dev,
                           double *sq_norms_out_host);
+int mi_op_momentum_update2(int kind, float *p, float *g, float *b, size_t n, const size_t *offsets_host, int n_tensors,
+                           const int *tensor_is_weight_host, float lr, float wd, float wd_norm, float momentum, float trust_coef,
+                           int *nan_flag_dev, double *sq_norms_out_host);
 /* the end-of-epoch bookkeeping of the reference's main() (resnet.cu:3410-3421) */
 void mi_trainer_end_epoch(Train_ResNet *t, float epoch_loss, float epoch_n_wrong, float total_images_per_epoch);
 /* host-only (no GPU needed): the gradient buckets the data-parallel path cuts for a network -- float offsets [from, to) into

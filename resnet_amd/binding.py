@@ -145,6 +145,14 @@ class MiLossMetrics(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class MiClipRecord(C.Structure):
+    _fields_ = [("sq_norm", C.c_double), ("norm", C.c_double), ("coef", C.c_float), ("nonfinite", C.c_int), ("updates", C.c_int64),
+                ("clipped", C.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 MI_SRC_SHARDS, MI_SRC_BUFFER, MI_SRC_SYNTHETIC, MI_SRC_HOST = 0, 1, 2, 3
 MI_SRC_SHARDS_U8 = 4
 MI_AUG_FIXED, MI_AUG_CENTER, MI_AUG_RANDOM, MI_AUG_RRC = 0, 1, 2, 3
@@ -295,6 +303,12 @@ PROTOTYPES = {
     "mi_trainer_accumulation": (_i, [_T, _ip, _ip]),
     "mi_debug_accum_arena": (_vp, [_T]),
     "mi_op_momentum_update": (_i, [_i, _vp, _vp, _vp, _sz, _vp, _i, _vp, _f, _f, _f, _f, _vp, _vp]),
+    "mi_op_momentum_update2": (_i, [_i, _vp, _vp, _vp, _sz, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
+    "mi_op_clip_grad_norm": (_i, [_vp, _sz, _vp, _i, _f, C.POINTER(MiClipRecord)]),
+    "mi_debug_clip_pass_ms": (C.c_double, [_i, _vp, _sz, _vp, _i, _f, _i]),
+    "mi_trainer_set_clip_grad_norm": (_i, [_T, _f]),
+    "mi_trainer_last_clip": (_i, [_T, C.POINTER(MiClipRecord)]),
+    "mi_trainer_set_norm_weight_decay": (_i, [_T, _f]),
     "mi_trainer_nan_location": (_i, [_T]),
     "mi_trainer_stem_dtype": (_i, [_T]),
     "mi_trainer_set_nan_exit": (None, [_T, _i]),

@@ -14,6 +14,10 @@
 // gradients are cleared; a non-finite result keeps w and b; LARS leaves a whole tensor untouched when its trust ratio is not
 // finite.  *nan_flag becomes the highest offending tensor index + 1 (atomicMax on an int).
 //
+// In front of them, where it is on, gradient clipping by the global L2 norm ("Gradient clipping") over a chunk table of its
+// own, whatever the optimizer: clip_norm_kernel, one double sum g^2 per chunk; clip_coef_kernel, one wave that sums them in a fixed order
+// and writes coef = min(1, max_norm / (norm + 1e-6)) into a record in device memory; clip_scale_kernel, g <- g coef where coef < 1.
+//
 // Behind them the two kernels of weight averaging ("Weight averaging"), which know no tensors: ema_update_kernel, e <- lerp(e,
 // p, w) over a whole arena, and exchange_kernel, which swaps two arenas word for word around an eval pass on the averaged model.  In the
 // same geometry grad_accum_kernel ("Gradient accumulation"): the gradient arenas of k micro-batches summed in a second arena
@@ -100,7 +104,8 @@ optim_trust_kernel(const double2 *__restrict__ part, const int *__restrict__ fir
     trust[t] = tr;
 }
 
-// KIND MID_OPT_SGD:  d = g + wd w;  b = mu b + d;  w = w - lr b                (torch.optim.SGD, dampening 0, no Nesterov)
+// KIND MID_OPT_SGD:  d = g + wd w;  b = mu b + d;  w = w - lr b                (torch.optim.SGD, dampening 0, no Nesterov; BN gamma /
+//                    beta: wd_norm in place of wd, a second parameter group)
 // KIND MID_OPT_LARS: b = mu b + (lr trust) (g + wd w);  w = w - b             (BN gamma / beta: trust 1, no weight decay)
 template <int KIND>
 __device__ __forceinline__ void opt_elem(float &w, float &gr, float &b, float s, float wdt, float lr, float mu, bool skip, bool &bad) {
@@ -119,7 +124,7 @@ __device__ __forceinline__ void opt_elem(float &w, float &gr, float &b, float s,
 template <int KIND>
 __global__ void __launch_bounds__(OPT_THREADS)
 optim_update_kernel(float *__restrict__ p, float *__restrict__ g, float *__restrict__ bm, const mid_chunk *__restrict__ chunks,
-                    int c0, const int *__restrict__ is_weight, const float *__restrict__ trust, float lr, float wd, float mu,
+                    int c0, const int *__restrict__ is_weight, const float *__restrict__ trust, float lr, float wd, float wd_norm, float mu,
                     int *__restrict__ nan_flag) {
     const mid_chunk ch = chunks[c0 + blockIdx.x];
     const int t = ch.tensor;
@@ -130,7 +135,7 @@ optim_update_kernel(float *__restrict__ p, float *__restrict__ g, float *__restr
         skip = !fin(tr);
         if (is_weight[t]) s = lr * tr;
         else wdt = 0.f;
-    }
+    } else if (!is_weight[t]) wdt = wd_norm;
     bool bad = skip;
     float *pw = p + ch.start, *pg = g + ch.start, *pb = bm + ch.start;
     const int n4 = ch.len >> 2;
@@ -167,6 +172,93 @@ optim_update_kernel(float *__restrict__ p, float *__restrict__ g, float *__restr
         pw[i] = w; pg[i] = q; pb[i] = b;
     }
     if (bad && nan_flag) atomicMax(nan_flag, t + 1);
+}
+
+// ---- gradient clipping by the global L2 norm ("Gradient clipping"): three launches over a chunk table that covers every tensor
+// of the gradient arena and none of its padding.  No atomics: the same gradient gives the same record and the same scaled bits ----
+// sum g^2 of one chunk in double (a float's square is exact there); reads g only
+__global__ void __launch_bounds__(OPT_THREADS)
+clip_norm_kernel(const float *__restrict__ g, const mid_chunk *__restrict__ chunks, double *__restrict__ part) {
+    const mid_chunk ch = chunks[blockIdx.x];
+    const float *src = g + ch.start;
+    const int n4 = ch.len >> 2;
+    double acc = 0.0;
+    if (n4 == MID_OPT_CHUNK / 4) { // a whole chunk: every load in flight before the first product
+        constexpr int K = MID_OPT_CHUNK / 4 / OPT_THREADS;
+        float4 v[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) v[k] = ((const float4 *)src)[threadIdx.x + k * OPT_THREADS];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            acc = fma((double)v[k].x, (double)v[k].x, acc); acc = fma((double)v[k].y, (double)v[k].y, acc);
+            acc = fma((double)v[k].z, (double)v[k].z, acc); acc = fma((double)v[k].w, (double)v[k].w, acc);
+        }
+    } else {
+        for (int i = threadIdx.x; i < n4; i += OPT_THREADS) {
+            const float4 v = ((const float4 *)src)[i];
+            acc = fma((double)v.x, (double)v.x, acc); acc = fma((double)v.y, (double)v.y, acc);
+            acc = fma((double)v.z, (double)v.z, acc); acc = fma((double)v.w, (double)v.w, acc);
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < ch.len; i += OPT_THREADS) acc = fma((double)src[i], (double)src[i], acc);
+    }
+    acc = wave_sum_d(acc);
+    __shared__ double wave_acc[OPT_THREADS / 64];
+    if ((threadIdx.x & 63) == 0) wave_acc[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        for (int k = 0; k < OPT_THREADS / 64; k++) total += wave_acc[k];
+        part[blockIdx.x] = total;
+    }
+}
+
+// one wave: lane l sums partials l, l + 64, ... in order (ResNet-50: 5910 partials, 93 turns), then the butterfly; lane 0 writes the
+// record.  A sum that is not finite leaves the gradient to the optimizers' own guards: coef 1, nonfinite 1 (torch.nn.utils.clip_grad_norm_
+// would multiply every gradient by NaN)
+__global__ void __launch_bounds__(64)
+clip_coef_kernel(const double *__restrict__ part, int n_chunks, float max_norm, mid_clip_record *__restrict__ rec) {
+    double sq = 0.0;
+    for (int c = threadIdx.x; c < n_chunks; c += 64) sq += part[c];
+    sq = wave_sum_d(sq);
+    if (threadIdx.x) return;
+    const bool bad = isnan(sq) || isinf(sq);
+    const double norm = sqrt(sq);
+    float coef = 1.f;
+    if (!bad) {
+        const double r = (double)max_norm / (norm + 1e-6);
+        if (r < 1.0) coef = (float)r; // rounded once; a ratio within half an ulp of 1 rounds to 1.f: not clipped
+    }
+    rec->sq_norm = sq; rec->norm = norm; rec->coef = coef; rec->nonfinite = bad;
+    rec->updates += 1;
+    if (coef < 1.f) rec->clipped += 1;
+}
+
+// g <- g coef, one fp32 product per element; coef == 1: no gradient word is read or written
+__global__ void __launch_bounds__(OPT_THREADS)
+clip_scale_kernel(float *__restrict__ g, const mid_chunk *__restrict__ chunks, const mid_clip_record *__restrict__ rec) {
+    const float coef = rec->coef;
+    if (coef == 1.0f) return;
+    const mid_chunk ch = chunks[blockIdx.x];
+    float *dst = g + ch.start;
+    const int n4 = ch.len >> 2;
+    if (n4 == MID_OPT_CHUNK / 4) { // a whole chunk: every load in flight before the first store
+        constexpr int K = MID_OPT_CHUNK / 4 / OPT_THREADS;
+        float4 v[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) v[k] = ((const float4 *)dst)[threadIdx.x + k * OPT_THREADS];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            v[k].x *= coef; v[k].y *= coef; v[k].z *= coef; v[k].w *= coef;
+            ((float4 *)dst)[threadIdx.x + k * OPT_THREADS] = v[k];
+        }
+    } else {
+        for (int i = threadIdx.x; i < n4; i += OPT_THREADS) {
+            float4 v = ((const float4 *)dst)[i];
+            v.x *= coef; v.y *= coef; v.z *= coef; v.w *= coef;
+            ((float4 *)dst)[i] = v;
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < ch.len; i += OPT_THREADS) dst[i] *= coef;
+    }
 }
 
 // ---- weight averaging: the EMA of an arena and the exchange of two arenas.  Pure streaming, no tensor table: a workgroup's turn is
@@ -377,6 +469,29 @@ int mid_grad_accumulate(mid_stream s, float *acc, float *g, size_t n, int mode, 
     MI_LAUNCH_CHECK(names[mode][vec]);
     return 0;
 }
+int mid_clip_norm(mid_stream s, const float *g, const mid_chunk *chunks, int n_chunks, double *part) {
+    if (n_chunks < 1) return 0;
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 0); // (the bytes are the caller's to count: the launcher does not know the chunks' lengths)
+    hipLaunchKernelGGL(clip_norm_kernel, dim3(n_chunks), dim3(OPT_THREADS), 0, (hipStream_t)s, g, chunks, part);
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK("clip_norm_kernel");
+    return 0;
+}
+int mid_clip_coef(mid_stream s, const double *part, int n_chunks, float max_norm, mid_clip_record *rec) {
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 8.0 * n_chunks);
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, part, n_chunks, max_norm, rec);
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK("clip_coef_kernel");
+    return 0;
+}
+int mid_clip_scale(mid_stream s, float *g, const mid_chunk *chunks, int n_chunks, const mid_clip_record *rec) {
+    if (n_chunks < 1) return 0;
+    mi_prof_begin((hipStream_t)s, MI_FAM_OTHER, 0, 0);
+    hipLaunchKernelGGL(clip_scale_kernel, dim3(n_chunks), dim3(OPT_THREADS), 0, (hipStream_t)s, g, chunks, rec);
+    mi_prof_end((hipStream_t)s);
+    MI_LAUNCH_CHECK("clip_scale_kernel");
+    return 0;
+}
 int mid_optim_norms(mid_stream s, const float *p, const float *g, const mid_chunk *chunks, int c0, int c1, double *part) {
     if (c1 <= c0) return 0;
     hipLaunchKernelGGL(optim_norm_kernel, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, chunks, c0, (double2 *)part);
@@ -392,14 +507,14 @@ int mid_optim_trust(mid_stream s, const double *part, const int *first_chunk, co
     return 0;
 }
 int mid_optim_update(mid_stream s, int kind, float *p, float *g, float *b, const mid_chunk *chunks, int c0, int c1, const int *is_weight,
-                     const float *trust, float lr, float wd, float momentum, int *nan_flag) {
+                     const float *trust, float lr, float wd, float wd_norm, float momentum, int *nan_flag) {
     if (c1 <= c0) return 0;
     if (kind == MID_OPT_SGD)
         hipLaunchKernelGGL(optim_update_kernel<MID_OPT_SGD>, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, b, chunks, c0,
-                           is_weight, trust, lr, wd, momentum, nan_flag);
+                           is_weight, trust, lr, wd, wd_norm, momentum, nan_flag);
     else if (kind == MID_OPT_LARS)
         hipLaunchKernelGGL(optim_update_kernel<MID_OPT_LARS>, dim3(c1 - c0), dim3(OPT_THREADS), 0, (hipStream_t)s, p, g, b, chunks, c0,
-                           is_weight, trust, lr, wd, momentum, nan_flag);
+                           is_weight, trust, lr, wd, wd_norm, momentum, nan_flag);
     else { mi_record_error("mid_optim_update", "unknown optimizer kind"); return -1; }
     MI_LAUNCH_CHECK("optim_update_kernel");
     return 0;

@@ -302,7 +302,8 @@ int mid_adam(mid_stream s, float *p, float *g, float *m, float *v, size_t n, flo
  * never cross a tensor (start: float offset into the arena, a multiple of 4); every pass runs one workgroup per chunk of
  * [c0, c1).  norms: double2 (sum w^2, sum g^2) per chunk into part[2 * chunk].  trust: for tensors [t0, t1) (first_chunk:
  * n_tensors + 1 entries) the partials summed in a fixed order into sq[2 * t] and the LARS trust ratio into trust[t] (NaN: a norm
- * is not finite).  update: the rule of `kind` (MID_OPT_SGD ignores is_weight / trust); *nan_flag = highest offending tensor + 1 */
+ * is not finite).  update: the rule of `kind` (MID_OPT_SGD ignores trust and decays the tensors with is_weight 0 by wd_norm, which
+ * MID_OPT_LARS ignores); *nan_flag = highest offending tensor + 1 */
 enum { MID_OPT_ADAM = 0, MID_OPT_SGD = 1, MID_OPT_LARS = 2 };
 #define MID_OPT_CHUNK 8192
 typedef struct { int tensor, start, len, pad; } mid_chunk;
@@ -310,7 +311,16 @@ int mid_optim_norms(mid_stream s, const float *p, const float *g, const mid_chun
 int mid_optim_trust(mid_stream s, const double *part, const int *first_chunk, const int *is_weight, int t0, int t1, float trust_coef,
                     float wd, double *sq, float *trust);
 int mid_optim_update(mid_stream s, int kind, float *p, float *g, float *b, const mid_chunk *chunks, int c0, int c1, const int *is_weight,
-                     const float *trust, float lr, float wd, float momentum, int *nan_flag);
+                     const float *trust, float lr, float wd, float wd_norm, float momentum, int *nan_flag);
+/* gradient clipping by the global L2 norm (kernels_optim.hip), over a chunk table of n_chunks chunks that covers the tensors of g and none
+ * of the padding between them.  norm: one workgroup per chunk, sum g^2 in double into part[chunk].  coef: one wave sums the partials in a
+ * fixed order and writes the record (MiClipRecord of resnet_mi.h, device memory): coef = min(1, max_norm / (sqrt(sq) + 1e-6)) computed in
+ * double and rounded to float once; a sum that is not finite gives coef 1 and nonfinite 1; updates goes up by one, clipped where coef < 1.
+ * scale: g[i] = g[i] * coef in fp32 where the record's coef is not 1.f -- then no word of g is read or written.  No atomics */
+typedef struct { double sq_norm, norm; float coef; int nonfinite; int64_t updates, clipped; } mid_clip_record;
+int mid_clip_norm(mid_stream s, const float *g, const mid_chunk *chunks, int n_chunks, double *part);
+int mid_clip_coef(mid_stream s, const double *part, int n_chunks, float max_norm, mid_clip_record *rec);
+int mid_clip_scale(mid_stream s, float *g, const mid_chunk *chunks, int n_chunks, const mid_clip_record *rec);
 /* weight averaging (kernels_optim.hip).  ema[i] = lerp(ema[i], p[i], w), torch.lerp's float32 bits: d = p - e rounded, then fmaf(w, d, e)
  * for w < 0.5f and fmaf(-(1.f - w), d, p) otherwise; a result that is not finite keeps e.  exchange: a[i] <-> b[i] as 32-bit words.  Both
  * pointers 16-byte aligned: 16-byte accesses; otherwise element-wise.  -1, mid_last_error set, nothing launched: a NULL pointer, a pointer

@@ -181,8 +181,22 @@ int mi_optim_init(MiOptim *o, int kind, float momentum, float trust_coef, const 
 void mi_optim_free(MiOptim *o);
 /* one update of the tensors whose start lies in [from, to) (floats into the arena), stream-ordered; want_norms: SGD too runs the
  * norm pass (sq_dev filled) */
-int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, size_t from, size_t to, float lr, float wd,
+int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, size_t from, size_t to, float lr, float wd, float wd_norm,
                   int *nan_flag, int want_norms);
+/* gradient clipping by the global L2 norm over a parameter-shaped arena (kernels_optim.hip): a chunk table of its own -- cut as
+ * MiOptim's is, whatever the optimizer -- one double partial per chunk and the record, all in device memory */
+typedef struct {
+    int n_chunks;
+    mid_chunk *chunks_dev;
+    double *part_dev;
+    mid_clip_record *rec_dev;    /* zeroed when built: the counters run from there */
+    size_t bytes;                /* of the three allocations */
+} MiClip;
+/* off / sizes / n as mi_optim_init.  Returns 0, or -1 with mi_last_error set (bad offsets: before any device work) */
+int mi_clip_init(MiClip *k, const char *who, const size_t *off, const int *sizes, int n);
+void mi_clip_free(MiClip *k);
+/* the three launches on s: norm, coefficient, scale */
+int mi_clip_run(const MiClip *k, mid_stream s, float *g, float max_norm);
 
 typedef struct MiCtx {
     MiLayerWs lw;
@@ -220,6 +234,11 @@ typedef struct MiCtx {
     int params_dirty;            /* update_parameters ran since the last weight re-layout */
     MiOptim optim;               /* mi_trainer_set_optimizer: SGD / LARS instead of Adam (kind MI_OPT_ADAM: nothing built) */
     int n_updates;               /* update_parameters calls so far (the optimizer is chosen before the first) */
+    /* mi_trainer_set_clip_grad_norm (0: off; the table is built at the first value > 0 and is not tracked in allocs[]) and
+     * mi_trainer_set_norm_weight_decay (wd_norm_set 0: BN gamma / beta decay with weight_decay, as every tensor does) */
+    float clip_max_norm;
+    MiClip clip;
+    float wd_norm; int wd_norm_set;
     /* mi_trainer_set_loss: the head of forward_pass (MI_LOSS_* flags; 0: the reference's soft-max, host loss, ce_deriv), and for
      * MI_LOSS_DEVICE the per-row outputs [batch] and the two records (last, total) the loss head writes */
     float loss_smoothing; int loss_topk, loss_flags;

@@ -5,6 +5,8 @@
  * kernel on its own.  The convolution operators plan one layer with their routes forced and run it
  * through the runners the trainer runs its table through (layer.c).
  */
+#include <math.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 #include "mi_host.h"
@@ -197,10 +199,11 @@ int mi_op_adam(float *p, const float *g, float *m, float *v, size_t n, float lr,
                float cur_b2, float eps, int *nan_flag_dev) {
     return finish(mid_adam(mi_global()->compute, p, (float *)g, m, v, n, lr, wd, b1, b2, cur_b1, cur_b2, eps, nan_flag_dev, 0, NULL, 0, 0));
 }
-int mi_op_momentum_update(int kind, float *p, float *g, float *b, size_t n, const size_t *offsets_host, int n_tensors,
-                          const int *tensor_is_weight_host, float lr, float wd, float momentum, float trust_coef, int *nan_flag_dev,
-                          double *sq_norms_out_host) {
+int mi_op_momentum_update2(int kind, float *p, float *g, float *b, size_t n, const size_t *offsets_host, int n_tensors,
+                           const int *tensor_is_weight_host, float lr, float wd, float wd_norm, float momentum, float trust_coef, int *nan_flag_dev,
+                           double *sq_norms_out_host) {
     if (kind != MI_OPT_SGD && kind != MI_OPT_LARS) { mi_record_host_error("mi_op_momentum_update", "kind is MI_OPT_SGD or MI_OPT_LARS"); return -1; }
+    if (!(wd_norm >= 0.f) || isinf(wd_norm)) { mi_record_host_error("mi_op_momentum_update", "wd_norm is finite and >= 0"); return -1; }
     if (n_tensors < 1 || offsets_host[n_tensors] > n) { mi_record_host_error("mi_op_momentum_update", "tensors beyond the n floats"); return -1; }
     int *sizes = (int *)malloc(sizeof(int) * (size_t)n_tensors);
     for (int i = 0; i < n_tensors; i++) {
@@ -212,13 +215,78 @@ int mi_op_momentum_update(int kind, float *p, float *g, float *b, size_t n, cons
     free(sizes);
     if (rc) return -1;
     mid_stream s = mi_global()->compute;
-    rc = finish(mi_optim_step(&o, s, p, g, b, 0, offsets_host[n_tensors], lr, wd, nan_flag_dev, sq_norms_out_host != NULL));
+    rc = finish(mi_optim_step(&o, s, p, g, b, 0, offsets_host[n_tensors], lr, wd, wd_norm, nan_flag_dev, sq_norms_out_host != NULL));
     if (!rc && sq_norms_out_host) {
         mid_memcpy_d2h(sq_norms_out_host, o.sq_dev, 2 * sizeof(double) * (size_t)n_tensors, s);
         rc = finish(0);
     }
     mi_optim_free(&o);
     return rc;
+}
+int mi_op_momentum_update(int kind, float *p, float *g, float *b, size_t n, const size_t *offsets_host, int n_tensors,
+                          const int *tensor_is_weight_host, float lr, float wd, float momentum, float trust_coef, int *nan_flag_dev,
+                          double *sq_norms_out_host) {
+    return mi_op_momentum_update2(kind, p, g, b, n, offsets_host, n_tensors, tensor_is_weight_host, lr, wd, wd, momentum, trust_coef, nan_flag_dev,
+                                  sq_norms_out_host);
+}
+_Static_assert(sizeof(MiClipRecord) == sizeof(mid_clip_record), "one record, declared on both sides of mi_device.h");
+/* gradient clipping (resnet_mi.h): the three kernels on their own.  Every refusal comes before any device work */
+int mi_op_clip_grad_norm(float *g, size_t n, const size_t *offsets_host, int n_tensors, float max_norm, MiClipRecord *out) {
+    const char *who = "mi_op_clip_grad_norm";
+    if (!g || ((uintptr_t)g & 15) != 0) { mi_record_host_error(who, "g is a 16-byte aligned device pointer"); return -1; }
+    if (n == 0) { mi_record_host_error(who, "n is at least 1"); return -1; }
+    if (!(max_norm > 0.f) || isinf(max_norm)) { mi_record_host_error(who, "max_norm is finite and > 0"); return -1; }
+    if (!offsets_host || n_tensors < 1 || offsets_host[n_tensors] > n) { mi_record_host_error(who, "tensors beyond the n floats"); return -1; }
+    int *sizes = (int *)malloc(sizeof(int) * (size_t)n_tensors);
+    for (int i = 0; i < n_tensors; i++) {
+        const size_t len = offsets_host[i + 1] >= offsets_host[i] ? offsets_host[i + 1] - offsets_host[i] : 0;
+        sizes[i] = len > (size_t)INT32_MAX || offsets_host[i + 1] < offsets_host[i] ? -1 : (int)len; /* descending or oversized: refused by the chunk cutting */
+    }
+    MiClip k;
+    int rc = mi_clip_init(&k, who, offsets_host, sizes, n_tensors);
+    free(sizes);
+    if (rc) return -1;
+    mid_stream s = mi_global()->compute;
+    rc = finish(mi_clip_run(&k, s, g, max_norm));
+    if (!rc && out) {
+        mid_memcpy_d2h(out, k.rec_dev, sizeof *out, s);
+        rc = finish(0);
+    }
+    mi_clip_free(&k);
+    return rc;
+}
+/* tools/bench_clip.py: the mean time in ms of one launch of the norm (pass 0), coefficient (1) or scale (2) kernel over `reps` launches
+ * behind 3 unmeasured ones, each between HIP events on the compute stream (mi_prof_*, which it switches off again); the record the scale
+ * kernel reads comes from one norm + coefficient pass in front.  Arguments as mi_op_clip_grad_norm; < 0: refused or failed */
+double mi_debug_clip_pass_ms(int pass, float *g, size_t n, const size_t *offsets_host, int n_tensors, float max_norm, int reps) {
+    const char *who = "mi_debug_clip_pass_ms";
+    if (pass < 0 || pass > 2 || reps < 1) { mi_record_host_error(who, "pass is 0, 1 or 2 and reps >= 1"); return -1.0; }
+    if (!g || ((uintptr_t)g & 15) != 0 || n == 0 || !offsets_host || n_tensors < 1 || offsets_host[n_tensors] > n || !(max_norm > 0.f) || isinf(max_norm)) {
+        mi_record_host_error(who, "arguments as mi_op_clip_grad_norm");
+        return -1.0;
+    }
+    int *sizes = (int *)malloc(sizeof(int) * (size_t)n_tensors);
+    for (int i = 0; i < n_tensors; i++) {
+        const size_t len = offsets_host[i + 1] >= offsets_host[i] ? offsets_host[i + 1] - offsets_host[i] : 0;
+        sizes[i] = len > (size_t)INT32_MAX || offsets_host[i + 1] < offsets_host[i] ? -1 : (int)len;
+    }
+    MiClip k;
+    int rc = mi_clip_init(&k, who, offsets_host, sizes, n_tensors);
+    free(sizes);
+    if (rc) return -1.0;
+    mid_stream s = mi_global()->compute;
+    rc = mid_clip_norm(s, g, k.chunks_dev, k.n_chunks, k.part_dev) || mid_clip_coef(s, k.part_dev, k.n_chunks, max_norm, k.rec_dev);
+    double ms = 0.0;
+    for (int i = -3; i < reps && !rc; i++) {
+        if (i == 0) { mid_stream_sync(s); mid_prof_enable(1 << 4); mid_prof_reset(); } /* family 4: other */
+        rc = pass == 0 ? mid_clip_norm(s, g, k.chunks_dev, k.n_chunks, k.part_dev)
+           : pass == 1 ? mid_clip_coef(s, k.part_dev, k.n_chunks, max_norm, k.rec_dev) : mid_clip_scale(s, g, k.chunks_dev, k.n_chunks, k.rec_dev);
+    }
+    rc = finish(rc);
+    mid_prof_get(4, NULL, &ms, NULL, NULL);
+    mid_prof_enable(0);
+    mi_clip_free(&k);
+    return rc ? -1.0 : ms / reps;
 }
 /* weight averaging (resnet_mi.h): the weight of update k, host only; the two kernels on their own (the launchers refuse what the header lists) */
 float mi_ema_weight(double decay, int warmup, int64_t k) {

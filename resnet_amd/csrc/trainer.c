@@ -659,7 +659,7 @@ size_t mi_trainer_device_bytes(const Train_ResNet *t) {
     const MiCtx *c = (MiCtx *)t->backend_ctx;
     const size_t ema = c->ema_arena ? (c->arena_floats + 2 * (size_t)c->rs_channels) * sizeof(float) : 0; /* mi_trainer_set_ema's two arenas */
     const size_t acc = c->acc_arena ? c->arena_floats * sizeof(float) : 0; /* mi_trainer_set_accumulation's arena */
-    return c->dev_bytes + c->arena_floats * sizeof(float) + ema + acc; /* + the parameter arena (owned by the model) */
+    return c->dev_bytes + c->arena_floats * sizeof(float) + ema + acc + c->clip.bytes; /* + the parameter arena (owned by the model); + mi_trainer_set_clip_grad_norm's table */
 }
 void mi_trainer_set_dump_every(Train_ResNet *t, int every) { ctx_of(t)->dump_every = every; }
 void mi_trainer_set_overlap(Train_ResNet *t, int mode) {
@@ -1524,30 +1524,25 @@ void mi_dp_reduce_ready(Train_ResNet *t, size_t from, int force) {
     c->dp_pending = 1;
 }
 
-/* ---- momentum SGD / LARS (kernels_optim.hip) ---- */
-int mi_optim_init(MiOptim *o, int kind, float momentum, float trust_coef, const size_t *off, const int *sizes, const int *is_weight, int n) {
-    memset(o, 0, sizeof *o);
-    o->kind = kind; o->momentum = momentum; o->trust_coef = trust_coef;
-    if (kind == MI_OPT_ADAM) return 0;
-    if (kind != MI_OPT_SGD && kind != MI_OPT_LARS) { mi_record_host_error("mi_optim_init", "unknown optimizer kind"); return -1; }
-    if (n < 1) { mi_record_host_error("mi_optim_init", "no tensors"); return -1; }
+/* ---- momentum SGD / LARS, gradient clipping (kernels_optim.hip) ---- */
+/* The chunk table of n tensors (tensor i: sizes[i] floats at float offset off[i], off holds n + 1 entries): chunks of at most
+ * MID_OPT_CHUNK floats that never cross a tensor, so no padding word between tensors is in one.  first_chunk: n + 1 entries, the
+ * last the number of chunks.  Returns the table (malloc; one unused entry where there is no chunk), or NULL with mi_last_error set
+ * under `who`: host arithmetic only */
+static mid_chunk *cut_chunks(const char *who, const size_t *off, const int *sizes, int n, int *first_chunk) {
+    if (n < 1) { mi_record_host_error(who, "no tensors"); return NULL; }
     size_t n_chunks = 0;
     for (int i = 0; i < n; i++) {
         if (off[i] % 4 || off[i + 1] < off[i] + (size_t)sizes[i] || sizes[i] < 0 || off[i] + (size_t)sizes[i] > (size_t)INT32_MAX) {
-            mi_record_host_error("mi_optim_init", "tensor offsets must ascend in multiples of 4 floats below 2^31, each tensor within its gap");
-            return -1;
+            mi_record_host_error(who, "tensor offsets must ascend in multiples of 4 floats below 2^31, each tensor within its gap");
+            return NULL;
         }
         n_chunks += ((size_t)sizes[i] + MID_OPT_CHUNK - 1) / MID_OPT_CHUNK;
     }
     mid_chunk *ch = (mid_chunk *)malloc(sizeof(mid_chunk) * (n_chunks ? n_chunks : 1));
-    int *isw = (int *)malloc(sizeof(int) * (size_t)n);
-    o->off = (size_t *)malloc(sizeof(size_t) * (size_t)(n + 1));
-    o->first_chunk = (int *)malloc(sizeof(int) * (size_t)(n + 1));
     int k = 0;
     for (int i = 0; i < n; i++) {
-        o->off[i] = off[i];
-        o->first_chunk[i] = k;
-        isw[i] = is_weight[i] != 0;
+        first_chunk[i] = k;
         for (int s0 = 0; s0 < sizes[i]; s0 += MID_OPT_CHUNK) {
             ch[k].tensor = i; ch[k].start = (int)(off[i] + (size_t)s0);
             ch[k].len = sizes[i] - s0 < MID_OPT_CHUNK ? sizes[i] - s0 : MID_OPT_CHUNK;
@@ -1555,8 +1550,61 @@ int mi_optim_init(MiOptim *o, int kind, float momentum, float trust_coef, const 
             k++;
         }
     }
+    first_chunk[n] = k;
+    return ch;
+}
+
+int mi_clip_init(MiClip *k, const char *who, const size_t *off, const int *sizes, int n) {
+    memset(k, 0, sizeof *k);
+    int *first = (int *)malloc(sizeof(int) * (size_t)(n > 0 ? n + 1 : 1));
+    mid_chunk *ch = cut_chunks(who, off, sizes, n, first);
+    if (!ch) { free(first); return -1; }
+    const size_t nc = (size_t)first[n];
+    free(first);
+    k->n_chunks = (int)nc;
+    const size_t bytes[3] = {sizeof(mid_chunk) * (nc ? nc : 1), sizeof(double) * (nc ? nc : 1), sizeof(mid_clip_record)};
+    k->chunks_dev = (mid_chunk *)mid_malloc(bytes[0]);
+    k->part_dev = (double *)mid_malloc(bytes[1]);
+    k->rec_dev = (mid_clip_record *)mid_malloc(bytes[2]);
+    k->bytes = bytes[0] + bytes[1] + bytes[2];
+    int rc = 0;
+    if (!k->chunks_dev || !k->part_dev || !k->rec_dev) { mi_record_host_error(who, "device allocation failed"); rc = -1; }
+    else {
+        MiGlobal *g = mi_global();
+        if (nc) mid_memcpy_h2d(k->chunks_dev, ch, sizeof(mid_chunk) * nc, g->compute);
+        mid_memset(k->rec_dev, 0, sizeof(mid_clip_record), g->compute);
+        mid_stream_sync(g->compute);
+    }
+    free(ch);
+    if (rc) mi_clip_free(k);
+    return rc;
+}
+void mi_clip_free(MiClip *k) {
+    mid_free(k->chunks_dev); mid_free(k->part_dev); mid_free(k->rec_dev);
+    memset(k, 0, sizeof *k);
+}
+int mi_clip_run(const MiClip *k, mid_stream s, float *g, float max_norm) {
+    if (mid_clip_norm(s, g, k->chunks_dev, k->n_chunks, k->part_dev)) return -1;
+    if (mid_clip_coef(s, k->part_dev, k->n_chunks, max_norm, k->rec_dev)) return -1;
+    return mid_clip_scale(s, g, k->chunks_dev, k->n_chunks, k->rec_dev);
+}
+
+int mi_optim_init(MiOptim *o, int kind, float momentum, float trust_coef, const size_t *off, const int *sizes, const int *is_weight, int n) {
+    memset(o, 0, sizeof *o);
+    o->kind = kind; o->momentum = momentum; o->trust_coef = trust_coef;
+    if (kind == MI_OPT_ADAM) return 0;
+    if (kind != MI_OPT_SGD && kind != MI_OPT_LARS) { mi_record_host_error("mi_optim_init", "unknown optimizer kind"); return -1; }
+    o->first_chunk = (int *)malloc(sizeof(int) * (size_t)(n > 0 ? n + 1 : 1));
+    mid_chunk *ch = cut_chunks("mi_optim_init", off, sizes, n, o->first_chunk);
+    if (!ch) { free(o->first_chunk); o->first_chunk = NULL; return -1; }
+    int *isw = (int *)malloc(sizeof(int) * (size_t)n);
+    o->off = (size_t *)malloc(sizeof(size_t) * (size_t)(n + 1));
+    for (int i = 0; i < n; i++) {
+        o->off[i] = off[i];
+        isw[i] = is_weight[i] != 0;
+    }
     o->off[n] = off[n];
-    o->first_chunk[n] = k;
+    const int k = o->first_chunk[n];
     o->n_tensors = n; o->n_chunks = k;
     o->chunks_dev = (mid_chunk *)mid_malloc(sizeof(mid_chunk) * (size_t)(k ? k : 1));
     o->first_chunk_dev = (int *)mid_malloc(sizeof(int) * (size_t)(n + 1));
@@ -1593,7 +1641,7 @@ static int optim_tensor_at(const MiOptim *o, size_t pos) {
     }
     return lo;
 }
-int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, size_t from, size_t to, float lr, float wd,
+int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, size_t from, size_t to, float lr, float wd, float wd_norm,
                   int *nan_flag, int want_norms) {
     const int t0 = optim_tensor_at(o, from), t1 = optim_tensor_at(o, to);
     const int c0 = o->first_chunk[t0], c1 = o->first_chunk[t1];
@@ -1601,7 +1649,7 @@ int mi_optim_step(const MiOptim *o, mid_stream s, float *p, float *g, float *b, 
         if (mid_optim_norms(s, p, g, o->chunks_dev, c0, c1, o->part_dev)) return -1;
         if (mid_optim_trust(s, o->part_dev, o->first_chunk_dev, o->is_weight_dev, t0, t1, o->trust_coef, wd, o->sq_dev, o->trust_dev)) return -1;
     }
-    return mid_optim_update(s, o->kind, p, g, b, o->chunks_dev, c0, c1, o->is_weight_dev, o->trust_dev, lr, wd, o->momentum, nan_flag);
+    return mid_optim_update(s, o->kind, p, g, b, o->chunks_dev, c0, c1, o->is_weight_dev, o->trust_dev, lr, wd, wd_norm, o->momentum, nan_flag);
 }
 
 /* momentum SGD or LARS instead of Adam; before the first update_parameters (later, the momentum arena would hold Adam moments) */
@@ -1626,9 +1674,43 @@ int mi_trainer_set_optimizer(Train_ResNet *t, int kind, float momentum, float tr
     if (rc) return -1;
     mi_optim_free(&c->optim);
     c->optim = o;
+    c->wd_norm_set = 0; /* the second decay group is a setting of the SGD it was made under */
     return 0;
 }
 int mi_trainer_get_optimizer(const Train_ResNet *t) { return ((const MiCtx *)t->backend_ctx)->optim.kind; }
+int mi_trainer_set_norm_weight_decay(Train_ResNet *t, float wd_norm) {
+    MiCtx *c = ctx_of(t);
+    const char *who = "mi_trainer_set_norm_weight_decay";
+    if (c->optim.kind != MI_OPT_SGD) { mi_record_host_error(who, "MI_OPT_SGD only (Adam keeps the reference's rule, LARS never decays gamma / beta)"); return -1; }
+    if (!(wd_norm >= 0.f) || isinf(wd_norm)) { mi_record_host_error(who, "wd_norm is finite and >= 0"); return -1; }
+    c->wd_norm = wd_norm; c->wd_norm_set = 1;
+    return 0;
+}
+
+/* Gradient clipping (resnet_mi.h): update_parameters scales the gradient the optimizer is about to see so that its global L2 norm is at
+ * most max_norm -- three launches on the compute stream, the coefficient stays on the device */
+int mi_trainer_set_clip_grad_norm(Train_ResNet *t, float max_norm) {
+    MiCtx *c = ctx_of(t);
+    const char *who = "mi_trainer_set_clip_grad_norm";
+    if (!(max_norm >= 0.f) || isinf(max_norm)) { mi_record_host_error(who, "max_norm is finite and >= 0 (0: off)"); return -1; }
+    if (c->acc_pending > 0) { mi_record_host_error(who, "a window is open: micro-batches are pending"); return -1; }
+    if (c->acc_in_step) { mi_record_host_error(who, "not between forward_pass and update_parameters"); return -1; }
+    if (max_norm > 0.f && !c->clip.rec_dev) { /* the first time: the chunk table of the gradient arena, the partials and the record */
+        const Params *p = t->model->params;
+        MiClip k;
+        if (mi_clip_init(&k, who, c->loc_off, p->sizes, p->n_locations)) return -1;
+        c->clip = k;
+    }
+    c->clip_max_norm = max_norm;
+    return 0;
+}
+int mi_trainer_last_clip(Train_ResNet *t, MiClipRecord *out) {
+    MiCtx *c = ctx_of(t);
+    if (!c->clip.rec_dev || !out) { mi_record_host_error("mi_trainer_last_clip", !out ? "out is NULL" : "clipping was never on"); return -1; }
+    mid_memcpy_d2h(out, c->clip.rec_dev, sizeof *out, G.compute);
+    mid_stream_sync(G.compute);
+    return mid_last_error()[0] ? -1 : 0;
+}
 
 /* resnet.cu:2910-2987.  No host synchronisation in here: the NaN / Inf flag is copied back asynchronously and read at the
  * next synchronisation point (forward_pass's pred copy), and with a communicator Adam runs bucket by bucket, each launch
@@ -1662,13 +1744,23 @@ void update_parameters(Train_ResNet *t) {
         if (!c->acc_folded) ck(mid_grad_accumulate(G.compute, c->acc_arena, c->g_arena, c->arena_floats, MID_ACC_FOLD, c->acc_scale), "gradient fold");
         c->acc_folded = 0; c->acc_pending = 0;
     }
+    const float wd_norm = c->wd_norm_set ? c->wd_norm : t->weight_decay;
+    if (c->clip_max_norm > 0.f) {
+        /* the global norm is that of the whole all-reduced gradient: every bucket first, then one update over the arena (the overlap of
+         * the early buckets' updates with the late buckets' all-reduce is the price) */
+        if (c->dp_pending) {
+            for (int b = 0; b < c->n_buckets; b++) mid_stream_wait_event(G.compute, c->bk_ev[b]);
+            c->dp_pending = 0; c->n_buckets = 0;
+        }
+        ck(mi_clip_run(&c->clip, G.compute, c->g_arena, c->clip_max_norm), "gradient clipping");
+    }
     if (c->dp_pending && c->n_buckets > 0) {
         for (int b = 0; b < c->n_buckets; b++) {
             mid_stream_wait_event(G.compute, c->bk_ev[b]);
             const size_t o = c->bk_from[b], n = c->bk_to[b] - c->bk_from[b];
             if (c->optim.kind != MI_OPT_ADAM)
                 ck(mi_optim_step(&c->optim, G.compute, p_arena, c->g_arena, c->m_arena, o, o + n, t->learning_rate, t->weight_decay,
-                                 c->nan_flag_dev, 0), c->optim.kind == MI_OPT_SGD ? "SGD" : "LARS");
+                                 wd_norm, c->nan_flag_dev, 0), c->optim.kind == MI_OPT_SGD ? "SGD" : "LARS");
             else
                 ck(mid_adam(G.compute, p_arena + o, c->g_arena + o, c->m_arena + o, c->v_arena + o, n, t->learning_rate, t->weight_decay,
                             t->base_mean_decay, t->base_var_decay, cur_b1, cur_b2, t->eps, c->nan_flag_dev, 1, c->loc_off_dev, c->n_loc, o), "Adam");
@@ -1678,7 +1770,7 @@ void update_parameters(Train_ResNet *t) {
         /* one launch over the whole arena (LARS: norm pass, trust ratios, update); it also clears the gradients (:2972-2978) */
         if (c->optim.kind != MI_OPT_ADAM)
             ck(mi_optim_step(&c->optim, G.compute, p_arena, c->g_arena, c->m_arena, 0, c->arena_floats, t->learning_rate, t->weight_decay,
-                             c->nan_flag_dev, 0), c->optim.kind == MI_OPT_SGD ? "SGD" : "LARS");
+                             wd_norm, c->nan_flag_dev, 0), c->optim.kind == MI_OPT_SGD ? "SGD" : "LARS");
         else ck(mid_adam(G.compute, p_arena, c->g_arena, c->m_arena, c->v_arena, c->arena_floats, t->learning_rate, t->weight_decay,
                     t->base_mean_decay, t->base_var_decay, cur_b1, cur_b2, t->eps, c->nan_flag_dev, 1, c->loc_off_dev, c->n_loc, 0), "Adam");
     }
@@ -1790,6 +1882,7 @@ void destroy_trainer(Train_ResNet *t) {
     free(t->model->dims); free(t->model);
     free(t->loss_per_epoch); free(t->accuracy_per_epoch);
     mi_optim_free(&c->optim);
+    mi_clip_free(&c->clip);
     mid_free(c->mix_labels_b);
     free(c->erase_last);
     free(c->ta_last); mid_free(c->ta_workspace);

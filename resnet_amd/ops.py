@@ -407,8 +407,17 @@ class Ops:
         self._chk(self.L.mi_op_adam(dp.ptr, dg.ptr, dm.ptr, dv.ptr, p.size, lr, wd, b1, b2, cur_b1, cur_b2, eps, flag.ptr), "adam")
         return dp.get(), dm.get(), dv.get(), int(flag.get()[0])
 
-    def momentum_update(self, kind, p, g, b, offsets, is_weight, lr, wd, momentum, trust=0.001):
+    def clip_grad_norm(self, g, offsets, max_norm):
+        """mi_op_clip_grad_norm on a float32 array: tensor i = [offsets[i], offsets[i + 1]).  Returns (g, the record as a dict)"""
+        dg = self.dev(np.ascontiguousarray(g, np.float32).ravel())
+        off = np.ascontiguousarray(offsets, np.uint64)
+        r = B.MiClipRecord()
+        self._chk(self.L.mi_op_clip_grad_norm(dg.ptr, int(np.size(g)), off.ctypes.data, len(off) - 1, float(max_norm), C.byref(r)), "clip_grad_norm")
+        return dg.get(), r.as_dict()
+
+    def momentum_update(self, kind, p, g, b, offsets, is_weight, lr, wd, momentum, trust=0.001, wd_norm=None):
         """mi_op_momentum_update over one arena: p, g, b float32 arrays of the same length, tensor i = [offsets[i], offsets[i + 1]).
+        wd_norm (SGD): the decay of the tensors with is_weight 0, None: wd (mi_op_momentum_update2).
         Returns (p, g, b, NaN flag, squared norms [n_tensors, 2] as (|w|^2, |g|^2) before the update)"""
         dp, dg, db = (self.dev(np.ascontiguousarray(a, np.float32)) for a in (p, g, b))
         flag = self.dev(np.zeros(1, np.int32))
@@ -417,8 +426,12 @@ class Ops:
         n_t = len(off) - 1
         assert isw.size == n_t and C.sizeof(C.c_size_t) == 8
         sq = np.zeros((n_t, 2), np.float64)
-        self._chk(self.L.mi_op_momentum_update(int(kind), dp.ptr, dg.ptr, db.ptr, p.size, off.ctypes.data, n_t, isw.ctypes.data, lr, wd,
-                                               momentum, trust, flag.ptr, sq.ctypes.data), "momentum_update")
+        if wd_norm is None:
+            self._chk(self.L.mi_op_momentum_update(int(kind), dp.ptr, dg.ptr, db.ptr, p.size, off.ctypes.data, n_t, isw.ctypes.data, lr, wd,
+                                                   momentum, trust, flag.ptr, sq.ctypes.data), "momentum_update")
+        else:
+            self._chk(self.L.mi_op_momentum_update2(int(kind), dp.ptr, dg.ptr, db.ptr, p.size, off.ctypes.data, n_t, isw.ctypes.data, lr, wd,
+                                                    float(wd_norm), momentum, trust, flag.ptr, sq.ctypes.data), "momentum_update2")
         return dp.get(), dg.get(), db.get(), int(flag.get()[0]), sq
 
     def nhwc_to_nchw(self, x):

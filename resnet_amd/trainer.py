@@ -287,6 +287,26 @@ class Trainer:
             self._refused("mi_trainer_accumulation")
         return k.value, pending.value
 
+    # ---- gradient clipping, norm weight decay (include/resnet_mi.h, "gradient clipping") ----
+    def set_clip_grad_norm(self, max_norm):
+        """clip the gradient the optimizer sees to a global L2 norm of max_norm at every applied update(), on the device (torchvision's
+        --clip-grad-norm; the gradient is a batch sum); 0: off.  Between updates only"""
+        if self.L.mi_trainer_set_clip_grad_norm(self.t, float(max_norm)) != 0:
+            self._refused("mi_trainer_set_clip_grad_norm")
+
+    def last_clip(self):
+        """the record of the last clipped update as a dict: sq_norm, norm (before scaling: what torch's clip_grad_norm_ returns), coef,
+        nonfinite, and the running counters updates and clipped"""
+        r = B.MiClipRecord()
+        if self.L.mi_trainer_last_clip(self.t, C.byref(r)) != 0:
+            self._refused("mi_trainer_last_clip")
+        return r.as_dict()
+
+    def set_norm_weight_decay(self, wd):
+        """SGD only: BN gamma / beta decay with wd in place of the trainer's weight decay (torchvision's --norm-weight-decay)"""
+        if self.L.mi_trainer_set_norm_weight_decay(self.t, float(wd)) != 0:
+            self._refused("mi_trainer_set_norm_weight_decay")
+
     def set_lr(self, lr):
         """learning_rate for the next update_parameters and on (read at every update)"""
         self.t.contents.learning_rate = lr
